@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """MPPI solve-steps/sec on MI355X (BASELINE.json metric) -- one JSON line on stdout.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment launches the N ranks itself (one process per GPU under
@@ -17,16 +17,24 @@ variant).  Inputs (map, goal, state, mean) are resident in HBM bef
 rank plans its own map seed (instance sharding, no data-path collective); RCCL carries only the barrier around the timed
 region and the final gather of the per-rank times.
 
-Timing: exactly K steps bracketed by barrier + synchronize, max over ranks -- repeated (`repeats`) so that a K of 20 is not
-a 0.3 ms sample; `ms_per_step` / `value` are the MEDIAN repeat, the min is reported beside it.  Per rank and repeat: barrier,
-synchronize, clock, the K steps, synchronize, clock, barrier.  The closing barrier sits BEHIND the second clock reading: the
-job time of a repeat is the maximum over the ranks of intervals that start together, which is what a barrier in front of the
-clock would yield -- minus the collective's own latency (an RCCL barrier is ~130 us here, more than half of a 20-step region).
+Timing: exactly K steps bracketed by barrier + synchronize, max over ranks: ONE timed region (`repeats` is 1), so `--steps`
+is the number of timed solves.  Per rank: barrier, synchronize, clock, the K steps, synchronize, clock, barrier.  The closing
+barrier sits BEHIND the second clock reading: the job time is the maximum over the ranks of intervals that start together,
+which is what a barrier in front of the clock would yield -- minus the collective's own latency (an RCCL barrier is ~130 us
+here, more than half of a 20-step region).  In front of the region, untimed: the warm-up (W solves) and the settle probes
+(3 x 100 solves) on the same handle, always the same number of solves, so the K timed solves continue the same chain whatever
+the probes found.
+
+--dump-outputs DIR (c2 only): after the timed region, rank 0 writes what the timed path's LAST solve hands its caller as
+float32 .npy files -- optimal_action_seq (T,2), optimal_state_seq (T+1,3), weights (K,), costs (K,), state_seq_batch
+(K,T+1,3), previous_action_seq (T,2), under 1 MB in all.  The inputs (map seed, state, goal, Philox seed or the seeded
+injected ring) and the number of solves in front of the last one follow from the arguments alone, so two runs with the same
+arguments write the same files and two builds of the project can be compared output for output.
 
 Extra objects on the line:
   roofline      dominant kernel (rollout) against the HBM roofline: algorithmic bytes per launch over the kernel's mean
                 launch-to-launch duration, from a HIP event pair on the launch stream around the same K launches on the same
-                handle right after the timed repeats (the timed region itself holds nothing but the solves)
+                handle right after the timed region (the timed region itself holds nothing but the solves)
   no_overlap    the headline with every launch on one stream: the configuration whose per-kernel duration rocprofv3 reports
                 directly (by default consecutive dependent solves overlap on two streams, bn_mppi_solve_n_async)
   cpu_baseline  the PyTorch-CPU port of the reference (oracle/torch_port.py) timed on this host (N = 1 only)
@@ -52,7 +60,8 @@ sys.path.insert(0, ROOT)
 
 G, K, T, RES = 256, 1024, 50, 0.5
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E datasheet peak (MI355X_MICROARCH.md)
-MIN_TIMED_STEPS = 2000         # repeats = ceil(MIN_TIMED_STEPS / steps)
+ROOFLINE_EVENT_STEPS = 2000    # the roofline's HIP-event regions after the timed one: ceil(this / steps) of them, at most 20
+SETTLE_PROBES, SETTLE_PROBE_STEPS = 3, 100
 
 
 def parse():
@@ -76,6 +85,8 @@ def parse():
                          "512x512 solve sharded by rollouts over the ranks (RCCL all-gather of the softmin partials per solve)")
     ap.add_argument("--rehearse", action="store_true",
                     help="launcher check without a GPU: spawn the ranks, rendezvous, gather, print who took part; no planning")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the timed path's last solve to DIR/<name>.npy (float32; c2 only)")
     return ap.parse_args()
 
 
@@ -159,6 +170,10 @@ def main():
     a = parse()
     if a.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if a.steps < 1 or a.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    if a.dump_outputs is not None and a.workload != "c2":
+        raise SystemExit("--dump-outputs writes the outputs of the headline workload (c2)")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(spawn_ranks(a))
     # Exactly ONE line on stdout: libraries that write to file descriptor 1 themselves (RCCL prints a version banner there when a
@@ -266,12 +281,15 @@ def main():
     def settle(make, state_dev, eps_ring, kind, warmup, tries=3):
         """Untimed: build the planner, run the warm-up steps, and make sure the queue is not in the rare slow-dispatch
         state seen on some boxes (milliseconds between back-to-back launches): if a 100-step probe is >5x slower than the
-        best probe seen, rebuild the handle and try again."""
+        best probe seen, rebuild the handle and try again.  Every handle returned has run the same solves (warm-up + probes)."""
+        def warm(pl):
+            timed_solves(pl, state_dev, eps_ring, kind, max(warmup, 1), torch.cuda.synchronize)
+            return [timed_solves(pl, state_dev, eps_ring, kind, SETTLE_PROBE_STEPS, torch.cuda.synchronize)[0] / SETTLE_PROBE_STEPS
+                    for _ in range(SETTLE_PROBES)]
         best = None
         for _ in range(tries):
             pl = make()
-            timed_solves(pl, state_dev, eps_ring, kind, max(warmup, 1), torch.cuda.synchronize)
-            probes = [timed_solves(pl, state_dev, eps_ring, kind, 100, torch.cuda.synchronize)[0] / 100 for _ in range(3)]
+            probes = warm(pl)
             p = min(probes)
             if os.environ.get("BENCH_DEBUG"):
                 print(f"[settle] probes us/step: {[round(x * 1e6, 2) for x in probes]}", file=sys.stderr)
@@ -279,13 +297,18 @@ def main():
             if p <= 5 * best and p < 2e-3:
                 return pl
             pl.close()
-        return make()
+        pl = make()
+        warm(pl)
+        return pl
 
-    def repeated(pl, state_dev, eps_ring, kind, steps, sync_, repeats):
-        """The contract's timed region, `repeats` times: nothing inside it but the K solves and the last tail.  The kernel's
-        launch-to-launch time comes from the same handle right afterwards: the same K launches between two HIP events."""
-        walls = [timed_solves(pl, state_dev, eps_ring, kind, steps, sync_, events=False)[0] for _ in range(repeats)]
-        evs = [timed_solves(pl, state_dev, eps_ring, kind, steps, torch.cuda.synchronize)[1] for _ in range(min(repeats, 20))]
+    def timed_region(pl, state_dev, eps_ring, kind, steps, sync_, n_events, dump=None):
+        """The contract's timed region, once: nothing inside it but the K solves and the last tail (`dump` reads the outputs of
+        the last solve right behind it).  The kernel's launch-to-launch time comes from the same handle afterwards: the same K
+        launches between two HIP events, `n_events` times."""
+        walls = [timed_solves(pl, state_dev, eps_ring, kind, steps, sync_, events=False)[0]]
+        if dump is not None:
+            dump(pl)
+        evs = [timed_solves(pl, state_dev, eps_ring, kind, steps, torch.cuda.synchronize)[1] for _ in range(n_events)]
         return walls, evs
 
     inst = synth.make_instance(G, seed=rank, resolution=RES)       # independent map seed per rank
@@ -304,10 +327,12 @@ def main():
     if extras and not a.no_batched:
         batched_insts = [synth.make_instance(G, seed=s, resolution=RES, jitter=True) for s in range(a.batched_instances)]
 
-    # ---- headline: dependent solves of one instance per GPU, K steps x `repeats` ------------------------------
-    repeats = max(1, min(200, -(-MIN_TIMED_STEPS // max(a.steps, 1))))
+    # ---- headline: K dependent solves of one instance per GPU, one timed region ------------------------------
+    repeats = 1
+    n_events = max(1, min(20, -(-ROOFLINE_EVENT_STEPS // a.steps)))
+    dump = (lambda pl_: dump_outputs(a.dump_outputs, pl_)) if (a.dump_outputs is not None and rank == 0) else None
     pl = settle(lambda: make_planner(inst), state_dev, eps_ring, kind, a.warmup)
-    walls, evs = repeated(pl, state_dev, eps_ring, kind, a.steps, sync, repeats)
+    walls, evs = timed_region(pl, state_dev, eps_ring, kind, a.steps, sync, n_events, dump)
     alg_bytes = pl.algorithmic_bytes(injected_noise=injected)
     sustained = None
     if rank == 0 and world == 1 and a.steps < 1000:      # the steady-state figure next to a short contract run
@@ -328,7 +353,7 @@ def main():
 
     out = None
     if rank == 0:
-        kernel_ms = statistics.median(evs) / a.steps               # same handle, the same K launches, right after the timed repeats
+        kernel_ms = statistics.median(evs) / a.steps               # same handle, the same K launches, right after the timed region
         achieved = alg_bytes / (kernel_ms * 1e-3) / 1e9
         traffic, traffic_src = None, None
         tpath = os.path.join(ROOT, "profiles", "traffic.json")     # PMC-derived HBM bytes per launch, see profiles/README.md
@@ -374,7 +399,7 @@ def main():
                                    "every launch also carries the previous solve's merge + tail workgroup)",
                          "kernel_ms": kernel_ms,
                          "kernel_ms_source": "HIP event pair on the launch stream around the same K launches on the same handle, right after "
-                                             "the timed repeats (median; launch-to-launch mean).  With overlapped launches (default) two kernels "
+                                             "the timed region (median; launch-to-launch mean).  With overlapped launches (default) two kernels "
                                              "are in flight and each one's own duration, as rocprofv3 lists it, includes its wait for the "
                                              "predecessor's partials (about twice this figure); `no_overlap` below is the one-stream "
                                              "configuration whose per-kernel duration rocprofv3 reports directly",
@@ -635,6 +660,25 @@ def main():
         emit(out)
 
 
+def dump_outputs(out_dir, pl):
+    """--dump-outputs: the outputs of the planner's latest solve, as a caller of the timed path receives them (the U* | X* block
+    of the tail, weights, per-rollout costs, the trajectory batch, the warm start of the next solve), one float32 .npy each."""
+    import numpy as np
+    import torch
+    from benchnav_amd import _capi
+    from benchnav_amd.mppi import _DevArray
+    pl.sync()                                            # the last solve's tail is written and the handle's stream is idle
+    n = pl.T * 2 + (pl.T + 1) * 3
+    ptr, nbytes = pl.device_buffer(_capi.BN_BUF_USTAR_XSTAR)
+    assert pl.B == 1 and nbytes == n * 4, (pl.B, nbytes)
+    blk = torch.as_tensor(_DevArray(ptr, (n,)), device="cuda").cpu().numpy()
+    outs = {"optimal_action_seq": blk[:2 * pl.T].reshape(pl.T, 2), "optimal_state_seq": blk[2 * pl.T:].reshape(pl.T + 1, 3),
+            "weights": pl.weights(), "costs": pl.costs(), "state_seq_batch": pl.states(), "previous_action_seq": pl.get_mean()}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in outs.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float32))
+
+
 def dropin_forward(inst, dev, n_steps):
     """The path a BenchNav user gets after changing the import: `benchnav_amd.MPPI(...)` built from reference-shaped `dynamics` /
     `objectives` objects and driven as the reference's loop drives it (test/test_mppi.py:174-181) -- one `forward(state)` per control
@@ -741,7 +785,7 @@ def run_workload(a, which, steps, rank, world, dev, dist, coll_dev, sync, stream
     import torch
     from benchnav_amd import NativeMPPI, synth
     from benchnav_amd.sharding import ShardedMPPI, gather_times, shard_instances
-    repeats = max(1, min(50, -(-400 // max(steps, 1))))
+    repeats = 1                                          # one timed region of exactly `steps` steps
     names = [None] * world
     me = f"rank {rank}: cuda:{dev} {torch.cuda.get_device_name(dev)}"
     if dist is not None:

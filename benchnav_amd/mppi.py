@@ -285,7 +285,7 @@ class MPPI(nn.Module):
     # -- reference attributes --------------------------------------------------------
     @property
     def _previous_action_seq(self) -> torch.Tensor:
-        self._unordered and self.order_outputs()
+        self._host_loop and self._outputs_in_use()
         return self._buf_mean
 
     @_previous_action_seq.setter
@@ -297,7 +297,7 @@ class MPPI(nn.Module):
     def _state_seq_batch(self) -> torch.Tensor:
         """(K, T+1, 3): a view of the planner-native (T+1, 3, K) buffer (no copy); in lean mode the rows are re-rolled
         on first access after a forward() (bit-identical to what a full-API solve stores)."""
-        self._unordered and self.order_outputs()
+        self._host_loop and self._outputs_in_use()
         if self._lean:
             if self._cs.rolled is None:
                 self._cs.rolled = self._reroll(None, self._num_samples)
@@ -305,6 +305,14 @@ class MPPI(nn.Module):
         if self._host_loop and self._lib.bn_mppi_states_buffer_index(self._h) == 1:
             return self._buf_X_alt.permute(2, 0, 1)
         return self._buf_X.permute(2, 0, 1)
+
+    def _outputs_in_use(self) -> None:
+        """host_loop: the caller is about to use one of the planner's own buffers (weights, costs, trajectory / control batch, mean) on
+        torch's stream.  The launch that waits for the next state writes them as soon as the next forward() posts that state -- it is
+        paced by the host's store, not by the stream, so reads still queued there would see the next solve's values.  It is cancelled
+        here (bn_mppi_flush, which also orders the stream behind the latest solve): the next forward() enqueues its solve on the stream,
+        behind those reads, and prelaunches the one after it again.  Same results; forward() + first_action() alone keep their pace."""
+        _capi.check(self._lib.bn_mppi_flush(self._handle))
 
     def order_outputs(self) -> None:
         """host_loop="actions": order torch's stream behind the latest solve -- before torch work that consumes the tensors forward()
@@ -324,19 +332,19 @@ class MPPI(nn.Module):
 
     @property
     def _weights(self) -> torch.Tensor:
-        self._unordered and self.order_outputs()
+        self._host_loop and self._outputs_in_use()
         return self._buf_w
 
     @property
     def _costs(self) -> torch.Tensor:
-        self._unordered and self.order_outputs()
+        self._host_loop and self._outputs_in_use()
         return self._buf_cost
 
     @property
     def _perturbed_action_seqs(self) -> torch.Tensor:
         if self._buf_U is None:
             raise AttributeError("_perturbed_action_seqs is not stored (store_controls=False)")
-        self._unordered and self.order_outputs()
+        self._host_loop and self._outputs_in_use()
         if self._host_loop and self._lib.bn_mppi_states_buffer_index(self._h) == 1:
             return self._buf_U_alt.permute(2, 0, 1)
         return self._buf_U.permute(2, 0, 1)

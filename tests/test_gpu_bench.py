@@ -23,7 +23,7 @@ def _bench(args, env_extra=None):
 
 def test_single_rank_line():
     out = _bench(["--steps", "20", "--warmup", "5", "--no-extras", "--no-cpu-baseline"])
-    assert out["n_gpus"] == 1 and out["world_size"] == 1 and out["steps"] == 20 and out["repeats"] == 100
+    assert out["n_gpus"] == 1 and out["world_size"] == 1 and out["steps"] == 20 and out["repeats"] == 1
     assert out["ms_per_step_min"] <= out["ms_per_step"] <= out["ms_per_step_max"]
     rf = out["roofline"]
     # the launch-to-launch time (HIP event pair around the same K launches, two extra packets in a 0.2 ms window) against the
@@ -32,6 +32,42 @@ def test_single_rank_line():
     assert abs(rf["frac"] - rf["achieved"] / rf["peak"]) < 1e-12 and rf["peak_measured_copy"] > 1000.0
     assert out["value"] > 20000 and out["unit"] == "solves/s" and out["host_cpu"]["logical_cpus"] >= 1
     assert out["sustained"]["value"] > 20000
+
+
+def test_dump_outputs_are_the_last_timed_solves_and_repeat_exactly(tmp_path):
+    """--dump-outputs DIR: the outputs of the timed path's last solve, float32 .npy.  The same arguments write the same files; one
+    more timed step writes the next solve's; and they are the outputs of solve W + 300 + K of one chain on a fresh handle (warm-up,
+    the three 100-step settle probes, the K timed steps) -- `--steps` is the number of timed solves."""
+    import numpy as np
+    import torch
+    from benchnav_amd import NativeMPPI, _capi, synth
+    from benchnav_amd.mppi import _DevArray
+    base = ["--warmup", "5", "--no-extras", "--no-cpu-baseline", "--dump-outputs"]
+    runs = {}
+    for tag, steps in (("a", 20), ("b", 20), ("c", 21)):
+        out = _bench(["--steps", str(steps)] + base + [str(tmp_path / tag)])
+        assert out["steps"] == steps and out["repeats"] == 1
+        runs[tag] = {f.stem: np.load(f) for f in sorted((tmp_path / tag).glob("*.npy"))}
+    K, T, G = 1024, 50, 256
+    shapes = {"optimal_action_seq": (T, 2), "optimal_state_seq": (T + 1, 3), "weights": (K,), "costs": (K,),
+              "state_seq_batch": (K, T + 1, 3), "previous_action_seq": (T, 2)}
+    assert {k: v.shape for k, v in runs["a"].items()} == shapes
+    assert sum(f.stat().st_size for f in (tmp_path / "a").glob("*.npy")) < 64 << 20
+    for name, arr in runs["a"].items():
+        assert arr.dtype == np.float32 and np.isfinite(arr).all(), name
+        assert np.array_equal(arr, runs["b"][name]), name
+    assert not np.array_equal(runs["a"]["weights"], runs["c"]["weights"])
+    inst = synth.make_instance(G, seed=0, resolution=0.5)
+    st = inst.start.cuda()
+    with NativeMPPI(horizon=T, num_samples=K, grid_size=G, resolution=0.5, stream=torch.cuda.current_stream().cuda_stream) as pl:
+        pl.set_map(inst.risk.numpy()); pl.set_goal(inst.goal.numpy())
+        pl.solve_n_async_device(5 + 300 + 20, st.data_ptr())
+        pl.sync()
+        blk = torch.as_tensor(_DevArray(pl.device_buffer(_capi.BN_BUF_USTAR_XSTAR)[0], (T * 2 + (T + 1) * 3,)), device="cuda").cpu().numpy()
+        want = {"optimal_action_seq": blk[:2 * T].reshape(T, 2), "optimal_state_seq": blk[2 * T:].reshape(T + 1, 3), "weights": pl.weights(),
+                "costs": pl.costs(), "state_seq_batch": pl.states(), "previous_action_seq": pl.get_mean()}
+    for name, arr in want.items():
+        assert np.array_equal(arr, runs["a"][name]), name
 
 
 def test_the_line_carries_the_reference_boundarys_own_figure():

@@ -138,7 +138,9 @@ def test_a_launch_that_gave_up_waiting_is_replaced(unchecked):
 
 def test_drop_in_class_host_loop():
     """MPPI(host_loop=True, noise="philox") driven like the reference's loop: forward(cpu_state), first_action(), the outputs used on
-    torch's stream while the next launch already waits (they are ordered behind the solve's own launch), get_top_samples in between."""
+    torch's stream while the next launch already waits (they are ordered behind the solve's own launch), get_top_samples in between.
+    The planner's own attributes (weights, trajectory and control batches) are read on torch's stream too: reading one cancels the
+    launch that waits for the next state, so the next solve cannot overwrite them before those reads have run."""
     import torch
     from helpers import load_case, mppi_for_fixture
     fx = load_case("c2")
