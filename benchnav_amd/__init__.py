@@ -2,6 +2,7 @@
 
     from benchnav_amd import MPPI          # drop-in for src/planners/local_planners/mppi.py:MPPI
     from benchnav_amd import NativeMPPI    # numpy-level wrapper of the C ABI, B instances per call
+    from benchnav_amd import AStar         # drop-in for src/planners/global_planners/search_based/astar.py:AStar
     from benchnav_amd import BatchedPlanetaryEnv   # reset / step / collision_check of PlanetaryEnv for B environments on the GPU
 """
 from .native import NativeMPPI  # noqa: F401
@@ -14,6 +15,9 @@ def __getattr__(name):
     if name == "DWA":
         from .dwa import DWA
         return DWA
+    if name == "AStar":
+        from .astar import AStar
+        return AStar
     if name == "BatchedPlanetaryEnv":
         from .env import BatchedPlanetaryEnv
         return BatchedPlanetaryEnv

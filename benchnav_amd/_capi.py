@@ -114,6 +114,16 @@ SYMBOLS = {
     "bn_risk_map_infer": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int32, C.c_int, C.c_float,
                                     C.c_int32, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_int]),
     "bn_risk_last_error": (C.c_char_p, []),
+    "bn_astar_create": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_H)]),
+    "bn_astar_destroy": (None, [_H]),
+    "bn_astar_set_map": (C.c_int, [_H, C.c_int32, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_double]),
+    "bn_astar_set_goal": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32]),
+    "bn_astar_solve_async": (C.c_int, [_H, C.c_void_p]),
+    "bn_astar_sync": (C.c_int, [_H]),
+    "bn_astar_kernel_ms": (C.c_int, [_H, _FP]),
+    "bn_astar_path": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32]),
+    "bn_astar_buffers": (C.c_int, [_H, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "bn_astar_last_error": (C.c_char_p, []),
     "bn_device_math_eval": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "bn_last_error": (C.c_char_p, []),
     "bn_mppi_abi_version": (C.c_int, []),

@@ -1,0 +1,121 @@
+"""MI355X-native A* global planner with the reference's Python interface.
+
+Mirror of `AStar(nn.Module)` in the reference's src/planners/global_planners/search_based/astar.py (constructor :33-71,
+forward :73-122).  The reference searches from the new start on every forward() call; the goal and the maps are fixed at
+construction and the edge weight is symmetric, so here the constructor enqueues ONE goal-rooted shortest-path solve on the
+GPU (csrc/astar_kernels.hip: the cost-to-go field and a one-byte next-hop map, copied to pinned host memory), and forward()
+walks the next-hop map on the host from the start cell: O(path length), no GPU round trip.
+
+It returns A shortest path (first minimiser in the reference's direction order among equal-cost hops); the reference returns
+one too where its search is exact, and otherwise a costlier one ("AStar").
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+from . import _capi
+
+
+class _DevArray:
+    """Library-owned device memory exposed to torch through __cuda_array_interface__."""
+
+    def __init__(self, ptr: int, shape, typestr="<f4"):
+        self.__cuda_array_interface__ = {"shape": tuple(int(v) for v in shape), "typestr": typestr, "data": (int(ptr), False),
+                                         "version": 2, "strides": None}
+
+
+class AStar(nn.Module):
+    def __init__(self, grid_map, goal_pos: torch.Tensor, dynamics, stuck_threshold: float, device: Optional[str] = None) -> None:
+        super().__init__()
+        heights = grid_map.tensors["heights"].detach()                            # astar.py:53-58
+        risks = dynamics._traversability_model._risks.detach()
+        self.resolution = grid_map.resolution
+        self.x_limits = grid_map.x_limits
+        self.y_limits = grid_map.y_limits
+        self._stuck_threshold = stuck_threshold
+        self.device = device if device is not None else "cuda" if torch.cuda.is_available() else "cpu"
+        assert risks.shape == heights.shape, "Traversability and height maps must have the same shape."
+        self._h, self._w = heights.shape
+        self._goal_node = self._pos_to_index(goal_pos)                             # astar.py:71
+        if not torch.cuda.is_available():
+            raise RuntimeError("benchnav_amd.AStar needs an MI355X (gfx950) device; there is no CPU fallback")
+        dev = torch.device(self.device)
+        self._dev = dev if dev.type == "cuda" and dev.index is not None else torch.device("cuda", torch.cuda.current_device())
+        heights = heights.to(torch.float32).contiguous()
+        risks = risks.to(torch.float32).contiguous()
+        # the goal checks of forward() (astar.py:88-94), decided once: the goal never changes
+        gx, gy = self._goal_node
+        self._goal_in_bounds = self._is_within_bounds(self._goal_node)
+        self._goal_collision = self._goal_in_bounds and bool(risks[gy, gx].item() <= np.float32(stuck_threshold))
+        self._lib = _capi.load()
+        h = C.c_void_p()
+        self._check(self._lib.bn_astar_create(self._dev.index, self._h, self._w, 1, C.byref(h)))
+        self._handle = h
+        on_dev = heights.is_cuda and risks.is_cuda and heights.device == self._dev and risks.device == self._dev
+        if on_dev:
+            where, hp, rp = _capi.BN_MEM_DEVICE, heights.data_ptr(), risks.data_ptr()
+        else:
+            hn, rn = heights.cpu().numpy(), risks.cpu().numpy()      # alive until set_map returns (it copies synchronously)
+            where, hp, rp = _capi.BN_MEM_HOST, hn.ctypes.data, rn.ctypes.data
+        self._check(self._lib.bn_astar_set_map(self._handle, 0, hp, rp, where, float(stuck_threshold), float(self.resolution)))
+        self._check(self._lib.bn_astar_set_goal(self._handle, 0, gx, gy))
+        self._check(self._lib.bn_astar_solve_async(self._handle, C.c_void_p(torch.cuda.current_stream(self._dev).cuda_stream)))
+        self._buf = np.empty((self._h * self._w, 2), np.int32)
+
+    def forward(self, state: torch.Tensor) -> Optional[torch.Tensor]:
+        state = state[:2] if state.shape[0] == 3 else state                        # astar.py:84
+        if state.is_cuda:
+            state = state.detach().cpu()                                           # one read; the index arithmetic below is IEEE f32
+        start_node = self._pos_to_index(state)
+        if not self._is_within_bounds(start_node) or not self._goal_in_bounds:     # astar.py:88-92
+            raise ValueError("Start or goal position is out of bounds.")
+        if self._goal_collision:                                                   # astar.py:93-94
+            raise ValueError("Goal position is not traversable.")
+        n = self._lib.bn_astar_path(self._handle, 0, start_node[0], start_node[1],
+                                    self._buf.ctypes.data_as(C.POINTER(C.c_int32)), self._buf.shape[0])
+        if n < 0:
+            self._check(n)
+        if n == 0:
+            return None                                                            # astar.py:122
+        nodes = torch.from_numpy(self._buf[:n].astype(np.int64))
+        return nodes.to(self.device) * self.resolution                             # _reconstruct_path, astar.py:213
+
+    def field(self):
+        """(D, next) of the solve as device tensors: D (H, W) float32, +inf where the goal is not reached and on collision
+        cells; next (H, W) uint8, a direction index of astar.py:154-163, 8 at the goal, 255 where the goal is unreachable."""
+        self._check(self._lib.bn_astar_sync(self._handle))
+        d, nx = C.c_void_p(), C.c_void_p()
+        self._check(self._lib.bn_astar_buffers(self._handle, 0, C.byref(d), C.byref(nx)))
+        D = torch.as_tensor(_DevArray(d.value, (self._h, self._w)), device=self._dev).clone()
+        n = torch.as_tensor(_DevArray(nx.value, (self._h, self._w), typestr="|u1"), device=self._dev).clone()
+        return D, n
+
+    def _pos_to_index(self, pos: torch.Tensor) -> tuple[int, int]:               # astar.py:215-228
+        return (
+            int((pos[0] - self.x_limits[0]) / self.resolution),
+            int((pos[1] - self.y_limits[0]) / self.resolution),
+        )
+
+    def _is_within_bounds(self, node: tuple[int, int]) -> bool:                   # astar.py:169-180
+        return 0 <= node[0] < self._w and 0 <= node[1] < self._h
+
+    def _check(self, code):
+        if code < 0:
+            raise _capi.BenchnavError(code, self._lib.bn_astar_last_error().decode("utf-8", "replace"))
+
+    def close(self):
+        h = getattr(self, "_handle", None)
+        if h is not None and h.value:
+            self._lib.bn_astar_destroy(h)
+            self._handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -1,0 +1,548 @@
+// astar_kernels.hip -- the A* global planner as one goal-rooted shortest-path solve per (map, goal).
+//
+// Replaces AStar.forward (reference src/planners/global_planners/search_based/astar.py:73-122), a host best-first search run
+// anew on every control step.  Every call searches toward the SAME goal on the SAME maps (the constructor fixes both,
+// astar.py:55-71) and the edge weight is symmetric, so one cost-to-go field rooted at the goal serves every start:
+//   D[goal] = 0,  D[n] = min over edges n->m of fl32(w(n,m) + D[m])            (n, m not in collision)
+//   next[n] = first minimiser of fl32(w(n,m) + D[m]) in the reference's direction order (every cell, collision cells too)
+// and AStar.forward becomes an O(path length) pointer walk over `next` on the host (bn_astar_path).
+//
+// Graph (astar.py): cells (ix, iy), arrays indexed [iy, ix] (_get_value :230-241); an edge a->b for each of the 8 neighbours b
+// in bounds that is not a collision (_get_neighbors :142-167); collision = risk[iy, ix] <= stuck_threshold (_is_collision
+// :182-192; NaN risk is traversable); weight (_distance :124-140, NumPy 2 scalar arithmetic)
+//   w = sqrt_f32( f32(dx^2 + dy^2) + f32(dz * dz) ),  dx, dy = |d index| * resolution in double,  dz = |h_a - h_b| in f32.
+//
+// fl32(w + d) is monotone in d and w > 0, so fair relaxation in ANY order reaches the same fixpoint as a Dijkstra in the same
+// arithmetic: the field is bit-exact and bit-identical run to run although workgroups race.
+//
+// Kernel: a persistent tile worklist.  Each map is cut into 32x32 tiles with one dirty flag each.  A workgroup claims a dirty
+// tile (atomic exchange 1 -> 0), reads it and its 1-cell halo, relaxes it in LDS to its local fixpoint, publishes the improved
+// cells with device-scope atomicMin (D >= 0, so the float order is the unsigned order), and re-flags every neighbouring tile
+// whose halo holds an improved border cell.  `pending` counts dirty flags plus tiles in flight: the workers exit when it is 0.
+// No co-residency is assumed (a workgroup that starts after the work is done exits at once), and every wait is bounded by
+// a wall-clock deadline that reports through the error word.
+#include "../../include/benchnav_mppi.h"
+#include "bn_device_math.h"
+
+#include <hip/hip_runtime.h>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <vector>
+
+namespace bn {
+namespace {
+
+constexpr int kTile = 32;                    // tile edge (cells)
+constexpr int kHalo = kTile + 2;             // with the 1-cell halo
+constexpr int kThreads = 256;                // 4 cells per thread: column tid % 32, rows tid / 32 + 8 k
+constexpr int kCellsPerThread = kTile * kTile / kThreads;
+constexpr int kMaxLocalIters = 4 * kHalo * kHalo;   // in-place relaxation of 1024 cells converges in <= 1024 sweeps
+constexpr uint8_t kNextGoal = 8, kNextNone = 255;
+// error word bits
+constexpr int kErrDeadline = 1, kErrLocal = 2;
+
+// the reference's direction order (astar.py:154-163), as (dx, dy) on (ix, iy)
+__constant__ int8_t c_dx[8] = {-1, 1, 0, 0, -1, -1, 1, 1};
+__constant__ int8_t c_dy[8] = {0, 0, -1, 1, -1, 1, -1, 1};
+constexpr int8_t h_dx[8] = {-1, 1, 0, 0, -1, -1, 1, 1};
+constexpr int8_t h_dy[8] = {0, 0, -1, 1, -1, 1, -1, 1};
+
+struct InstParams {
+    int32_t gx, gy;          // goal cell; gx < 0: no goal (the field stays +inf everywhere)
+    float thr;               // stuck threshold: collision = risk <= thr
+    int32_t pad;
+};
+
+struct FieldArgs {
+    const float *heights;    // (B, H, W)
+    const float *risk;       // (B, H, W)
+    const InstParams *inst;  // (B)
+    float *D;                // (B, H, W) cost-to-go, +inf where not reached
+    uint8_t *next;           // (B, H, W)
+    int32_t *flags;          // (B, TY, TX) dirty flags
+    int32_t *ctl;            // [0] pending, [1] error word
+    int H, W, B, TX, TY;
+    float p_axis, p_diag;    // f32(res^2), f32(res^2 + res^2): the planar terms, rounded once from double
+    uint64_t deadline_ticks; // wall-clock bound of the field kernel
+};
+
+__device__ __forceinline__ bool is_free(float r, float thr) { return !(r <= thr); }
+
+__device__ __forceinline__ float edge_w(float p, float ha, float hb)
+{
+    const float dz = fabsf(ha - hb);
+    return sqrt_cr(p + dz * dz);             // -ffp-contract=off: a rounded product, then a rounded sum
+}
+
+__device__ __forceinline__ uint32_t atomic_read_u32(uint32_t *p)
+{
+    return __hip_atomic_fetch_or(p, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // served where the atomics are
+}
+__device__ __forceinline__ int32_t atomic_read_i32(int32_t *p)
+{
+    return __hip_atomic_fetch_or(p, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// D = +inf, D[goal] = 0 and the goal's tile flagged where the goal is in bounds and free
+__global__ __launch_bounds__(256) void astar_init_kernel(FieldArgs a)
+{
+    const size_t cells = (size_t)a.H * a.W;
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= cells * a.B) return;
+    const int b = (int)(i / cells);
+    const int c = (int)(i - (size_t)b * cells);
+    const int ix = c % a.W, iy = c / a.W;
+    const InstParams p = a.inst[b];
+    const bool goal = p.gx == ix && p.gy == iy && is_free(a.risk[i], p.thr);
+    a.D[i] = goal ? 0.0f : INFINITY;
+    if (goal) {
+        a.flags[(size_t)b * a.TX * a.TY + (iy / kTile) * a.TX + ix / kTile] = 1;
+        atomicAdd(&a.ctl[0], 1);
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void astar_field_kernel(FieldArgs a)
+{
+    __shared__ float s_D[kHalo * kHalo];
+    __shared__ float s_h[kHalo * kHalo];
+    __shared__ uint8_t s_free[kHalo * kHalo];
+    __shared__ int s_pick, s_cmd, s_mask;
+
+    const int tid = threadIdx.x;
+    const int NT = a.B * a.TX * a.TY;
+    const int tiles_per_inst = a.TX * a.TY;
+    const uint64_t t0 = wall_clock64();
+    int window = (int)(((uint64_t)blockIdx.x * kThreads) % (uint64_t)NT);
+    const int scan = NT < kThreads ? NT : kThreads;
+
+    for (;;) {
+        // ---- find and claim one dirty tile ------------------------------------------------------------------------------
+        if (tid == 0) s_pick = 0x7fffffff;
+        __syncthreads();
+        if (tid < scan) {
+            int t = window + tid;
+            if (t >= NT) t -= NT;
+            if (atomic_read_i32(&a.flags[t])) atomicMin(&s_pick, t);
+        }
+        __syncthreads();
+        if (tid == 0) {
+            int cmd = -1;                                  // -1: nothing claimed, -2: exit
+            if (s_pick != 0x7fffffff &&
+                __hip_atomic_exchange(&a.flags[s_pick], 0, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == 1) {
+                cmd = s_pick;
+            } else {
+                if (atomic_read_i32(&a.ctl[0]) == 0 || atomic_read_i32(&a.ctl[1]) != 0) cmd = -2;
+                else if (wall_clock64() - t0 > a.deadline_ticks) {
+                    atomicOr(&a.ctl[1], kErrDeadline);
+                    cmd = -2;
+                }
+            }
+            s_cmd = cmd;
+            s_mask = 0;
+        }
+        __syncthreads();
+        const int tile = s_cmd;
+        if (tile == -2) return;
+        if (tile == -1) {
+            window += scan;
+            if (window >= NT) window -= NT;
+            __builtin_amdgcn_s_sleep(8);
+            continue;
+        }
+
+        // ---- load the tile and its halo -------------------------------------------------------------------------------
+        const int b = tile / tiles_per_inst;
+        const int tr = tile - b * tiles_per_inst;
+        const int ty = tr / a.TX, tx = tr - ty * a.TX;
+        const int x0 = tx * kTile - 1, y0 = ty * kTile - 1;       // global cell of halo (0, 0)
+        const size_t base = (size_t)b * a.H * a.W;
+        const float thr = a.inst[b].thr;
+        for (int j = tid; j < kHalo * kHalo; j += kThreads) {
+            const int hx = j % kHalo, hy = j / kHalo;
+            const int gx = x0 + hx, gy = y0 + hy;
+            float d = INFINITY, h = 0.0f;
+            uint8_t f = 0;
+            if (gx >= 0 && gx < a.W && gy >= 0 && gy < a.H) {
+                const size_t g = base + (size_t)gy * a.W + gx;
+                h = a.heights[g];
+                f = is_free(a.risk[g], thr) ? 1 : 0;
+                if (f) d = __uint_as_float(atomic_read_u32(reinterpret_cast<uint32_t *>(a.D + g)));
+            }
+            s_D[j] = d; s_h[j] = h; s_free[j] = f;
+        }
+        __syncthreads();
+
+        // per-cell edge weights, +inf to a neighbour that is out of bounds or in collision
+        const int cx = tid % kTile;
+        float w[kCellsPerThread][8];
+        float d0[kCellsPerThread];
+        bool active[kCellsPerThread];
+#pragma unroll
+        for (int k = 0; k < kCellsPerThread; ++k) {
+            const int cy = tid / kTile + 8 * k;
+            const int hj = (cy + 1) * kHalo + cx + 1;
+            active[k] = s_free[hj] != 0;            // a collision cell has no incoming edge: it never gets a value
+            d0[k] = s_D[hj];
+            const float hc = s_h[hj];
+#pragma unroll
+            for (int d = 0; d < 8; ++d) {
+                const int nj = hj + c_dy[d] * kHalo + c_dx[d];
+                w[k][d] = s_free[nj] ? edge_w(d < 4 ? a.p_axis : a.p_diag, hc, s_h[nj]) : INFINITY;
+            }
+        }
+
+        // ---- relax to the tile's local fixpoint (in place: values only fall, each one a realised path cost) -----------
+        int iters = 0;
+        for (;;) {
+            int changed = 0;
+#pragma unroll
+            for (int k = 0; k < kCellsPerThread; ++k) {
+                if (!active[k]) continue;
+                const int hj = (tid / kTile + 8 * k + 1) * kHalo + cx + 1;
+                float best = s_D[hj];
+#pragma unroll
+                for (int d = 0; d < 8; ++d) {
+                    const float cand = w[k][d] + s_D[hj + c_dy[d] * kHalo + c_dx[d]];
+                    if (cand < best) best = cand;
+                }
+                if (best < s_D[hj]) { s_D[hj] = best; changed = 1; }
+            }
+            if (!__syncthreads_or(changed)) break;
+            if (++iters > kMaxLocalIters) {
+                if (tid == 0) atomicOr(&a.ctl[1], kErrLocal);
+                break;
+            }
+        }
+
+        // ---- publish improved cells; collect the neighbouring tiles whose halo changed ----------------------------------
+        int mask = 0;
+#pragma unroll
+        for (int k = 0; k < kCellsPerThread; ++k) {
+            const int cy = tid / kTile + 8 * k;
+            const int hj = (cy + 1) * kHalo + cx + 1;
+            const float v = s_D[hj];
+            const int gx = x0 + 1 + cx, gy = y0 + 1 + cy;
+            if (!active[k] || !(v < d0[k]) || gx >= a.W || gy >= a.H) continue;
+            const uint32_t vb = __float_as_uint(v);
+            const uint32_t old = __hip_atomic_fetch_min(reinterpret_cast<uint32_t *>(a.D + base + (size_t)gy * a.W + gx), vb,
+                                                        __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (vb < old) {
+                const int ex = cx == 0 ? -1 : (cx == kTile - 1 ? 1 : 0);
+                const int ey = cy == 0 ? -1 : (cy == kTile - 1 ? 1 : 0);
+                if (ex) mask |= 1 << ((0 + 1) * 3 + ex + 1);
+                if (ey) mask |= 1 << ((ey + 1) * 3 + 0 + 1);
+                if (ex && ey) mask |= 1 << ((ey + 1) * 3 + ex + 1);
+            }
+        }
+        if (mask) atomicOr(&s_mask, mask);
+        __syncthreads();
+        if (tid == 0) {
+            // every published atomicMin above has returned; the release orders them before the flags
+            const int m = s_mask;
+            for (int e = 0; e < 9; ++e) {
+                if (!(m >> e & 1)) continue;
+                const int ntx = tx + e % 3 - 1, nty = ty + e / 3 - 1;
+                if (ntx < 0 || ntx >= a.TX || nty < 0 || nty >= a.TY) continue;
+                const int nt = b * tiles_per_inst + nty * a.TX + ntx;
+                if (__hip_atomic_exchange(&a.flags[nt], 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == 0)
+                    __hip_atomic_fetch_add(&a.ctl[0], 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            __hip_atomic_fetch_add(&a.ctl[0], -1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);   // this tile is done
+        }
+        __syncthreads();
+    }
+}
+
+// next[n]: first minimiser of fl32(w(n, m) + D[m]) over the 8 neighbours in direction order; D is +inf on collision cells,
+// so they are never chosen.  kNextGoal at the goal, kNextNone where no candidate is finite.
+__global__ __launch_bounds__(256) void astar_next_kernel(FieldArgs a)
+{
+    const size_t cells = (size_t)a.H * a.W;
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= cells * a.B) return;
+    const int b = (int)(i / cells);
+    const int c = (int)(i - (size_t)b * cells);
+    const int ix = c % a.W, iy = c / a.W;
+    const InstParams p = a.inst[b];
+    if (p.gx == ix && p.gy == iy && a.D[i] == 0.0f) { a.next[i] = kNextGoal; return; }
+    const float hc = a.heights[i];
+    float best = INFINITY;
+    uint8_t arg = kNextNone;
+#pragma unroll
+    for (int d = 0; d < 8; ++d) {
+        const int nx = ix + c_dx[d], ny = iy + c_dy[d];
+        if (nx < 0 || nx >= a.W || ny < 0 || ny >= a.H) continue;
+        const size_t j = (size_t)b * cells + (size_t)ny * a.W + nx;
+        const float cand = edge_w(d < 4 ? a.p_axis : a.p_diag, hc, a.heights[j]) + a.D[j];
+        if (cand < best) { best = cand; arg = (uint8_t)d; }
+    }
+    a.next[i] = arg;
+}
+
+thread_local std::string g_astar_error;
+
+}  // namespace
+}  // namespace bn
+
+struct bn_astar {
+    int device = 0, H = 0, W = 0, B = 0, TX = 0, TY = 0;
+    double resolution = -1.0;                  // planar terms are set with the first map
+    float p_axis = 0.0f, p_diag = 0.0f;
+    float *heights = nullptr, *risk = nullptr, *D = nullptr;
+    uint8_t *next = nullptr;
+    int32_t *flags = nullptr, *ctl = nullptr;
+    bn::InstParams *inst_dev = nullptr;
+    std::vector<bn::InstParams> inst;           // host mirror, uploaded by every solve
+    std::vector<uint8_t> have_map;
+    bn::InstParams *inst_pinned = nullptr;
+    uint8_t *next_host = nullptr;               // pinned copy of `next`, refreshed by every solve
+    int32_t *ctl_host = nullptr;
+    hipEvent_t ev_start = nullptr, ev_kernels = nullptr, ev_done = nullptr;
+    bool solved = false, pending_check = false;
+    uint64_t deadline_ticks = 0;
+};
+
+namespace {
+
+int astar_fail(int code, const std::string &msg)
+{
+    bn::g_astar_error = msg;
+    return code;
+}
+
+struct DeviceGuard {
+    int prev = -1; bool changed = false, ok = true;
+    explicit DeviceGuard(int want) { if (hipGetDevice(&prev) != hipSuccess) { ok = false; return; }
+                                     if (prev != want) { ok = hipSetDevice(want) == hipSuccess; changed = ok; } }
+    ~DeviceGuard() { if (changed) (void)hipSetDevice(prev); }
+};
+
+#define ASTAR_HIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return astar_fail(BN_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); } while (0)
+
+// waits for the last solve, copies nothing: the pinned `next` and error word are already on the host
+int astar_wait(bn_astar_t *h)
+{
+    if (!h->solved) return astar_fail(BN_ERR_STATE, "no solve has been enqueued");
+    if (h->pending_check) {
+        ASTAR_HIP(hipEventSynchronize(h->ev_done));
+        h->pending_check = false;
+    }
+    if (h->ctl_host[1] != 0)
+        return astar_fail(BN_ERR_STATE, std::string("field solve failed: ") +
+                                        ((h->ctl_host[1] & bn::kErrDeadline) ? "deadline exceeded " : "") +
+                                        ((h->ctl_host[1] & bn::kErrLocal) ? "tile relaxation did not converge" : ""));
+    return BN_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+const char *bn_astar_last_error(void) { return bn::g_astar_error.c_str(); }
+
+/* astar.py:33-71 (the constructor's buffers): B instances of one H x W shape on `device_id`. */
+int bn_astar_create(int32_t device_id, int32_t H, int32_t W, int32_t B, bn_astar_t **out)
+{
+    if (!out) return astar_fail(BN_ERR_INVALID, "null handle pointer");
+    *out = nullptr;
+    if (H < 1 || W < 1 || B < 1 || (int64_t)H * W > (1 << 26) || (int64_t)H * W * B > ((int64_t)1 << 31))
+        return astar_fail(BN_ERR_INVALID, "H, W, B must be >= 1 and the field must fit 2^31 cells");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return astar_fail(BN_ERR_NO_DEVICE, "no HIP device visible: no CPU fallback");
+    if (device_id < 0 || device_id >= ndev) return astar_fail(BN_ERR_INVALID, "device_id out of range");
+    DeviceGuard guard(device_id);
+    if (!guard.ok) return astar_fail(BN_ERR_HIP, "hipSetDevice failed");
+    auto *h = new bn_astar_t();
+    h->device = device_id; h->H = H; h->W = W; h->B = B;
+    h->TX = (W + bn::kTile - 1) / bn::kTile;
+    h->TY = (H + bn::kTile - 1) / bn::kTile;
+    const size_t cells = (size_t)H * W * B;
+    h->inst.assign(B, bn::InstParams{-1, -1, 0.0f, 0});
+    h->have_map.assign(B, 0);
+    int clock_khz = 0;
+    auto bad = [&](hipError_t e, const char *what) {
+        if (e == hipSuccess) return false;
+        astar_fail(BN_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+        return true;
+    };
+    if (bad(hipMalloc((void **)&h->heights, cells * 4), "hipMalloc heights") ||
+        bad(hipMalloc((void **)&h->risk, cells * 4), "hipMalloc risk") ||
+        bad(hipMalloc((void **)&h->D, cells * 4), "hipMalloc D") ||
+        bad(hipMalloc((void **)&h->next, cells), "hipMalloc next") ||
+        bad(hipMalloc((void **)&h->flags, (size_t)B * h->TX * h->TY * 4), "hipMalloc flags") ||
+        bad(hipMalloc((void **)&h->ctl, 4 * 4), "hipMalloc ctl") ||
+        bad(hipMalloc((void **)&h->inst_dev, sizeof(bn::InstParams) * B), "hipMalloc inst") ||
+        bad(hipHostMalloc((void **)&h->inst_pinned, sizeof(bn::InstParams) * B, hipHostMallocDefault), "hipHostMalloc inst") ||
+        bad(hipHostMalloc((void **)&h->next_host, cells, hipHostMallocDefault), "hipHostMalloc next") ||
+        bad(hipHostMalloc((void **)&h->ctl_host, 4 * 4, hipHostMallocDefault), "hipHostMalloc ctl") ||
+        bad(hipEventCreate(&h->ev_start), "hipEventCreate") || bad(hipEventCreate(&h->ev_kernels), "hipEventCreate") ||
+        bad(hipEventCreate(&h->ev_done), "hipEventCreate") ||
+        bad(hipDeviceGetAttribute(&clock_khz, hipDeviceAttributeWallClockRate, device_id), "wall clock rate") ||
+        bad(hipMemset(h->heights, 0, cells * 4), "hipMemset") || bad(hipMemset(h->risk, 0, cells * 4), "hipMemset")) {
+        std::string keep = bn::g_astar_error;
+        bn_astar_destroy(h);
+        bn::g_astar_error = keep;
+        return BN_ERR_HIP;
+    }
+    std::memset(h->ctl_host, 0, 16);
+    h->deadline_ticks = (uint64_t)(clock_khz > 0 ? clock_khz : 100000) * 1000ull * 5ull;    // 5 s
+    *out = h;
+    return BN_OK;
+}
+
+void bn_astar_destroy(bn_astar_t *h)
+{
+    if (!h) return;
+    DeviceGuard guard(h->device);
+    if (h->pending_check) (void)hipEventSynchronize(h->ev_done);
+    for (void *p : {(void *)h->heights, (void *)h->risk, (void *)h->D, (void *)h->next, (void *)h->flags, (void *)h->ctl, (void *)h->inst_dev})
+        if (p) (void)hipFree(p);
+    for (void *p : {(void *)h->inst_pinned, (void *)h->next_host, (void *)h->ctl_host})
+        if (p) (void)hipHostFree(p);
+    for (hipEvent_t e : {h->ev_start, h->ev_kernels, h->ev_done})
+        if (e) (void)hipEventDestroy(e);
+    delete h;
+}
+
+/* astar.py:53-58: heights = grid_map.tensors["heights"], travs = _traversability_model._risks, _stuck_threshold, resolution.
+ * Both maps are (H, W) row-major, indexed [iy, ix]; `where` says where they live.  Device-resident maps are copied after a
+ * device synchronisation (the producer's stream is finished first).  Every instance must use the same resolution. */
+int bn_astar_set_map(bn_astar_t *h, int32_t inst, const float *heights, const float *risks, bn_mem_kind where,
+                     float stuck_threshold, double resolution)
+{
+    if (!h || !heights || !risks) return astar_fail(BN_ERR_INVALID, "null argument");
+    if (inst < 0 || inst >= h->B) return astar_fail(BN_ERR_INVALID, "instance out of range");
+    if (!(resolution > 0.0) || !std::isfinite(resolution)) return astar_fail(BN_ERR_INVALID, "resolution must be finite and > 0");
+    if (h->resolution > 0.0 && resolution != h->resolution) return astar_fail(BN_ERR_INVALID, "every instance must share one resolution");
+    if (where != BN_MEM_HOST && where != BN_MEM_DEVICE) return astar_fail(BN_ERR_INVALID, "unknown memory kind");
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return astar_fail(BN_ERR_HIP, "hipSetDevice failed");
+    if (h->pending_check) { ASTAR_HIP(hipEventSynchronize(h->ev_done)); h->pending_check = false; }
+    const size_t cells = (size_t)h->H * h->W, off = cells * inst;
+    if (where == BN_MEM_DEVICE) ASTAR_HIP(hipDeviceSynchronize());
+    const hipMemcpyKind kind = where == BN_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
+    ASTAR_HIP(hipMemcpy(h->heights + off, heights, cells * 4, kind));
+    ASTAR_HIP(hipMemcpy(h->risk + off, risks, cells * 4, kind));
+    // _distance (:134-140): dx = |di| * resolution and dy likewise are Python floats, dx**2 + dy**2 a double, rounded to f32 once
+    // when the f32 dz**2 is added
+    h->resolution = resolution;
+    h->p_axis = (float)(resolution * resolution + 0.0);
+    h->p_diag = (float)(resolution * resolution + resolution * resolution);
+    h->inst[inst].thr = stuck_threshold;
+    h->have_map[inst] = 1;
+    return BN_OK;
+}
+
+/* astar.py:71 (_goal_node = _pos_to_index(goal_pos)): the goal cell of instance `inst`.  An out-of-bounds or collision goal is
+ * accepted (the reference raises only in forward(), :88-94): its field is +inf everywhere and every path is "none". */
+int bn_astar_set_goal(bn_astar_t *h, int32_t inst, int32_t ix, int32_t iy)
+{
+    if (!h) return astar_fail(BN_ERR_INVALID, "null handle");
+    if (inst < 0 || inst >= h->B) return astar_fail(BN_ERR_INVALID, "instance out of range");
+    const bool in = ix >= 0 && ix < h->W && iy >= 0 && iy < h->H;
+    h->inst[inst].gx = in ? ix : -1;
+    h->inst[inst].gy = in ? iy : -1;
+    return BN_OK;
+}
+
+/* astar.py:96-122 (the search), done once per (map, goal) for all B instances: the cost-to-go field D and the next-hop map,
+ * then an async copy of `next` to pinned host memory.  Enqueued on `stream`; bn_astar_path / bn_astar_sync wait for it. */
+int bn_astar_solve_async(bn_astar_t *h, void *stream)
+{
+    if (!h) return astar_fail(BN_ERR_INVALID, "null handle");
+    for (int b = 0; b < h->B; ++b)
+        if (!h->have_map[b]) return astar_fail(BN_ERR_STATE, "instance " + std::to_string(b) + " has no map");
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return astar_fail(BN_ERR_HIP, "hipSetDevice failed");
+    if (h->pending_check) { ASTAR_HIP(hipEventSynchronize(h->ev_done)); h->pending_check = false; }   // pinned buffers are reused
+    hipStream_t s = (hipStream_t)stream;
+    const size_t cells = (size_t)h->H * h->W * h->B;
+    const int NT = h->B * h->TX * h->TY;
+    std::memcpy(h->inst_pinned, h->inst.data(), sizeof(bn::InstParams) * h->B);
+    bn::FieldArgs a{h->heights, h->risk, h->inst_dev, h->D, h->next, h->flags, h->ctl,
+                    h->H, h->W, h->B, h->TX, h->TY, h->p_axis, h->p_diag, h->deadline_ticks};
+    ASTAR_HIP(hipEventRecord(h->ev_start, s));
+    ASTAR_HIP(hipMemcpyAsync(h->inst_dev, h->inst_pinned, sizeof(bn::InstParams) * h->B, hipMemcpyHostToDevice, s));
+    ASTAR_HIP(hipMemsetAsync(h->flags, 0, (size_t)NT * 4, s));
+    ASTAR_HIP(hipMemsetAsync(h->ctl, 0, 16, s));
+    const int blocks = (int)((cells + 255) / 256);
+    bn::astar_init_kernel<<<blocks, 256, 0, s>>>(a);
+    ASTAR_HIP(hipGetLastError());
+    int cus = 256;
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device);
+    const int workers = NT < cus ? NT : cus;          // residency is not required; more workers than tiles would only scan
+    bn::astar_field_kernel<<<workers, bn::kThreads, 0, s>>>(a);
+    ASTAR_HIP(hipGetLastError());
+    bn::astar_next_kernel<<<blocks, 256, 0, s>>>(a);
+    ASTAR_HIP(hipGetLastError());
+    ASTAR_HIP(hipEventRecord(h->ev_kernels, s));
+    ASTAR_HIP(hipMemcpyAsync(h->next_host, h->next, cells, hipMemcpyDeviceToHost, s));
+    ASTAR_HIP(hipMemcpyAsync(h->ctl_host, h->ctl, 16, hipMemcpyDeviceToHost, s));
+    ASTAR_HIP(hipEventRecord(h->ev_done, s));
+    h->solved = true;
+    h->pending_check = true;
+    return BN_OK;
+}
+
+/* Waits for the last solve and reports a kernel-side failure (the field kernel's bounded waits). */
+int bn_astar_sync(bn_astar_t *h)
+{
+    if (!h) return astar_fail(BN_ERR_INVALID, "null handle");
+    DeviceGuard guard(h->device);
+    return astar_wait(h);
+}
+
+/* Device time of the last solve's kernels (init, field, next), in ms: for the rate tool. */
+int bn_astar_kernel_ms(bn_astar_t *h, float *ms)
+{
+    if (!h || !ms) return astar_fail(BN_ERR_INVALID, "null argument");
+    DeviceGuard guard(h->device);
+    int rc = astar_wait(h);
+    if (rc != BN_OK) return rc;
+    ASTAR_HIP(hipEventElapsedTime(ms, h->ev_start, h->ev_kernels));
+    return BN_OK;
+}
+
+/* astar.py:73-122 + _reconstruct_path :194-213 for the start cell (ix, iy): walks `next` on the host from the start to the
+ * goal and writes the nodes (ix, iy) start first into out_xy (2 * max_len int32).  Returns the node count (the full count,
+ * even where it exceeds max_len: only max_len nodes are written), 0 where the goal is unreachable (the reference's None),
+ * BN_ERR_INVALID for a start out of bounds. */
+int bn_astar_path(bn_astar_t *h, int32_t inst, int32_t ix, int32_t iy, int32_t *out_xy, int32_t max_len)
+{
+    if (!h) return astar_fail(BN_ERR_INVALID, "null handle");
+    if (inst < 0 || inst >= h->B) return astar_fail(BN_ERR_INVALID, "instance out of range");
+    if (ix < 0 || ix >= h->W || iy < 0 || iy >= h->H) return astar_fail(BN_ERR_INVALID, "start out of bounds");
+    if (max_len > 0 && !out_xy) return astar_fail(BN_ERR_INVALID, "null output");
+    DeviceGuard guard(h->device);
+    int rc = astar_wait(h);
+    if (rc != BN_OK) return rc;
+    const uint8_t *nx = h->next_host + (size_t)h->H * h->W * inst;
+    const int64_t bound = (int64_t)h->H * h->W;       // D strictly falls along next: no node repeats
+    int32_t n = 0;
+    for (int64_t step = 0; step < bound; ++step) {
+        if (n < max_len) { out_xy[2 * n] = ix; out_xy[2 * n + 1] = iy; }
+        ++n;
+        const uint8_t c = nx[(size_t)iy * h->W + ix];
+        if (c == bn::kNextGoal) return n;
+        if (c >= 8) return 0;
+        ix += bn::h_dx[c];
+        iy += bn::h_dy[c];
+    }
+    return astar_fail(BN_ERR_STATE, "next-hop walk exceeded H*W nodes");
+}
+
+/* Test hook: the device buffers of instance `inst` -- D (H*W float32) and next (H*W uint8: 0-7 a direction of astar.py:154-163,
+ * 8 the goal, 255 unreachable).  Valid after bn_astar_sync. */
+int bn_astar_buffers(bn_astar_t *h, int32_t inst, void **D_dev, void **next_dev)
+{
+    if (!h || !D_dev || !next_dev) return astar_fail(BN_ERR_INVALID, "null argument");
+    if (inst < 0 || inst >= h->B) return astar_fail(BN_ERR_INVALID, "instance out of range");
+    const size_t off = (size_t)h->H * h->W * inst;
+    *D_dev = h->D + off;
+    *next_dev = h->next + off;
+    return BN_OK;
+}
+
+}  // extern "C"

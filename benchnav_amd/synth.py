@@ -95,3 +95,29 @@ def torch_cpu_noise(seed: int, K: int, T: int, n_solves: int) -> torch.Tensor:
     g = torch.Generator().manual_seed(seed)
     torch.empty(K, T, 2).normal_(generator=g)
     return torch.stack([torch.empty(K, T, 2).normal_(generator=g) for _ in range(n_solves)])
+
+
+def smooth_height_map(height: int, width: int, seed: int = 0, coarse: int = 16, amplitude: float = 2.0) -> torch.Tensor:
+    """Bicubic-upsampled uniform noise scaled to [0, amplitude] metres (float32 [H, W]): a terrain for the A* planner's dz."""
+    g = torch.Generator().manual_seed(seed + 104729)
+    base = torch.rand(1, 1, max(2, height // coarse), max(2, width // coarse), generator=g)
+    up = F.interpolate(base, size=(height, width), mode="bicubic", align_corners=False)[0, 0]
+    up = (up - up.min()) / (up.max() - up.min())
+    return (up * amplitude).to(torch.float32).contiguous()
+
+
+def iid_height_map(height: int, width: int, seed: int = 0, amplitude: float = 0.5) -> torch.Tensor:
+    """Cell-wise independent heights in [0, amplitude) (float32 [H, W])."""
+    g = torch.Generator().manual_seed(seed + 130363)
+    return (torch.rand(height, width, generator=g) * amplitude).to(torch.float32)
+
+
+def serpentine_risk_map(height: int, width: int, period: int = 4, free: float = 0.9, blocked: float = 0.0) -> torch.Tensor:
+    """A serpentine maze (float32 [H, W]): every `period`-th row is a wall with one gap, alternately at its right and left end,
+    so the only route from the top to the bottom sweeps every corridor.  Walls hold `blocked` (a collision under the A*
+    planner's `risk <= stuck_threshold` reading), corridors `free`."""
+    r = torch.full((height, width), free, dtype=torch.float32)
+    for k, y in enumerate(range(period - 1, height - 1, period)):
+        r[y, :] = blocked
+        r[y, width - 1 if k % 2 == 0 else 0] = free
+    return r

@@ -492,6 +492,36 @@ int bn_risk_map_infer(int32_t device_id, void *stream, const float *mean, const 
                       const float *z, bn_mem_kind where_z, uint64_t seed, float *out, bn_mem_kind where_out);
 const char *bn_risk_last_error(void);
 
+/*
+ * AStar (src/planners/global_planners/search_based/astar.py), the A* global planner, as one goal-rooted shortest-path solve
+ * per (map, goal) on the GPU: the cost-to-go field D and a one-byte next-hop map for B instances of one H x W shape, then
+ * O(path length) host walks per start (csrc/astar_kernels.hip).  Graph and arithmetic are astar.py's: 8-connected cells
+ * (ix, iy) indexed [iy, ix], edges into cells with risk > stuck_threshold (NaN risk too), weight
+ * sqrt_f32(f32(dx^2 + dy^2) + dz * dz).  Errors: bn_astar_last_error().
+ */
+typedef struct bn_astar bn_astar_t;
+/* astar.py:33-71 (constructor buffers). */
+int bn_astar_create(int32_t device_id, int32_t H, int32_t W, int32_t B, bn_astar_t **out);
+void bn_astar_destroy(bn_astar_t *h);
+/* astar.py:53-58: heights and risks (H, W), the stuck threshold and the map resolution (shared by every instance). */
+int bn_astar_set_map(bn_astar_t *h, int32_t inst, const float *heights, const float *risks, bn_mem_kind where,
+                     float stuck_threshold, double resolution);
+/* astar.py:71: the goal cell; an out-of-bounds or collision goal is accepted (every path is then none, 0). */
+int bn_astar_set_goal(bn_astar_t *h, int32_t inst, int32_t ix, int32_t iy);
+/* astar.py:96-122 for every start at once: field + next-hop map on `stream`, then an async copy of next to pinned memory. */
+int bn_astar_solve_async(bn_astar_t *h, void *stream);
+/* Waits for the last solve; BN_ERR_STATE if its kernel reported a failure. */
+int bn_astar_sync(bn_astar_t *h);
+/* Device time of the last solve's kernels in ms. */
+int bn_astar_kernel_ms(bn_astar_t *h, float *ms);
+/* astar.py:73-122 + _reconstruct_path :194-213: nodes (ix, iy) from the start to the goal into out_xy (2 * max_len int32).
+ * Returns the node count, 0 if the goal is unreachable (None), BN_ERR_INVALID for a start out of bounds. */
+int bn_astar_path(bn_astar_t *h, int32_t inst, int32_t ix, int32_t iy, int32_t *out_xy, int32_t max_len);
+/* Test hook: device pointers of instance inst's D (H*W float32) and next (H*W uint8: 0-7 direction in astar.py:154-163
+ * order, 8 goal, 255 unreachable). */
+int bn_astar_buffers(bn_astar_t *h, int32_t inst, void **D_dev, void **next_dev);
+const char *bn_astar_last_error(void);
+
 /* Test hook: the library's device arithmetic (DESIGN.md "Arithmetic spec") applied elementwise to n device floats:
  * fn 0 = correctly rounded sqrt, 1 / 2 = sin / cos of the spec, 3 = heading wrap (theta + pi) % 2pi - pi with
  * torch.remainder semantics (robot_model.py:90), 4 = its in-loop form, 5 = the sqrt for zero / normal finite arguments.  Lets the tests compare the kernels' building
