@@ -85,7 +85,9 @@ __device__ __forceinline__ int32_t atomic_read_i32(int32_t *p)
     return __hip_atomic_fetch_or(p, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// D = +inf, D[goal] = 0 and the goal's tile flagged where the goal is in bounds and free
+// D = +inf, D[goal] = 0 where the goal is in bounds and free, and every tile whose halo holds the goal flagged: its own tile
+// and, for a goal on a tile border, the neighbouring tiles across it.  The field kernel never publishes the goal (its value
+// starts at 0 and cannot fall), so a goal whose only free neighbours lie in another tile is seen there through this flag alone.
 __global__ __launch_bounds__(256) void astar_init_kernel(FieldArgs a)
 {
     const size_t cells = (size_t)a.H * a.W;
@@ -98,8 +100,16 @@ __global__ __launch_bounds__(256) void astar_init_kernel(FieldArgs a)
     const bool goal = p.gx == ix && p.gy == iy && is_free(a.risk[i], p.thr);
     a.D[i] = goal ? 0.0f : INFINITY;
     if (goal) {
-        a.flags[(size_t)b * a.TX * a.TY + (iy / kTile) * a.TX + ix / kTile] = 1;
-        atomicAdd(&a.ctl[0], 1);
+        const int tx = ix / kTile, ty = iy / kTile, cx = ix % kTile, cy = iy % kTile;
+        const int x_lo = cx == 0 ? -1 : 0, x_hi = cx == kTile - 1 ? 1 : 0;
+        const int y_lo = cy == 0 ? -1 : 0, y_hi = cy == kTile - 1 ? 1 : 0;
+        for (int ey = y_lo; ey <= y_hi; ++ey)
+            for (int ex = x_lo; ex <= x_hi; ++ex) {
+                const int ntx = tx + ex, nty = ty + ey;
+                if (ntx < 0 || ntx >= a.TX || nty < 0 || nty >= a.TY) continue;
+                a.flags[(size_t)b * a.TX * a.TY + nty * a.TX + ntx] = 1;
+                atomicAdd(&a.ctl[0], 1);
+            }
     }
 }
 

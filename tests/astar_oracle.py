@@ -182,6 +182,133 @@ def check_path(path, start, goal, free) -> str:
     return ""
 
 
+# ---- independent checks: a float64 shortest path, an oracle-free fixpoint certificate, hop counts ------------------------
+def field_f64(heights, risk, threshold, resolution, goal) -> np.ndarray:
+    """D (H, W) float64 by scipy's Dijkstra over the same graph, built afresh in float64 (no code shared with `weights`):
+    an edge n -> m between 8-neighbours that are both in bounds and free (risk > threshold, NaN free), of weight
+    sqrt((dx res)^2 + (dy res)^2 + (h_n - h_m)^2) from the float32 heights.  +inf where the goal is not reached, on collision
+    cells, and everywhere when the goal is out of bounds or in collision.  Finite heights only."""
+    from scipy.sparse import coo_matrix
+    from scipy.sparse.csgraph import dijkstra
+    h = np.asarray(heights, np.float32).astype(np.float64)
+    r = np.asarray(risk, np.float32)
+    free = ~(r <= np.float32(threshold))
+    H, W = h.shape
+    out = np.full((H, W), np.inf)
+    gx, gy = goal
+    if not (0 <= gx < W and 0 <= gy < H and free[gy, gx]):
+        return out
+    iy, ix = np.mgrid[0:H, 0:W]
+    rows, cols, vals = [], [], []
+    for ddx in (-1, 0, 1):
+        for ddy in (-1, 0, 1):
+            if ddx == 0 and ddy == 0:
+                continue
+            jx, jy = ix + ddx, iy + ddy
+            ok = (jx >= 0) & (jx < W) & (jy >= 0) & (jy < H)
+            ok[ok] &= free[iy[ok], ix[ok]] & free[jy[ok], jx[ok]]
+            a, b = iy[ok] * W + ix[ok], jy[ok] * W + jx[ok]
+            dz = h.ravel()[a] - h.ravel()[b]
+            rows.append(a)
+            cols.append(b)
+            vals.append(np.sqrt((ddx * float(resolution)) ** 2 + (ddy * float(resolution)) ** 2 + dz * dz))
+    g = coo_matrix((np.concatenate(vals), (np.concatenate(rows), np.concatenate(cols))), shape=(H * W, H * W)).tocsr()
+    # the graph is symmetric, so the distances from the goal are the costs to it
+    return dijkstra(g, directed=True, indices=gy * W + gx).reshape(H, W)
+
+
+def certify_field(heights, risk, threshold, resolution, goal, D) -> str:
+    """'' when D is THE float32 field of (map, goal), else what is wrong.  Oracle-free: one vectorised pass computes
+    best[n] = min over in-bounds m of fl32(w(n, m) + D[m]) (D read as +inf on collision cells; `c < best` selects, so a NaN
+    weight is no edge), then +inf on collision cells and 0 at an in-bounds free goal, and requires best == D bit for bit.
+
+    Why a fixpoint is the field: let D* be the Dijkstra field, the least realised f32 path cost from every cell.  (a) D <= D*:
+    along D*'s shortest-path tree in increasing D*, D[n] <= fl32(w + D[m]) <= fl32(w + D*[m]) = D*[n], since fl32(w + d) is
+    monotone in d.  (b) D >= D*: when w > 0 is never absorbed (fl32(w + d) > d for every finite d used), D strictly falls
+    along the minimising neighbour, so from a finite D[n] that chain cannot repeat a cell and ends at the goal, and D[n] is
+    the realised cost of that path, hence >= D*[n].  So the fixpoint is unique and equals D*.  With absorption (costs near
+    2^24 x an edge weight, `plateau` in astar_maps.py) step (b) fails and a fixpoint lower than D* could pass."""
+    D = np.asarray(D, np.float32)
+    free = free_mask(risk, threshold)
+    H, W = free.shape
+    if D.shape != (H, W):
+        return f"shape {D.shape}, expected {(H, W)}"
+    Dm = np.where(free, D, np.float32(np.inf))
+    h = np.asarray(heights, np.float32)
+    r = float(resolution)
+    best = np.full((H, W), np.inf, np.float32)
+    for dx, dy in DIRS:
+        p = np.float32(r * r + 0.0) if dx == 0 or dy == 0 else np.float32(r * r + r * r)
+        ys, yd = slice(max(0, -dy), H - max(0, dy)), slice(max(0, dy), H - max(0, -dy))
+        xs, xd = slice(max(0, -dx), W - max(0, dx)), slice(max(0, dx), W - max(0, -dx))
+        with np.errstate(invalid="ignore"):
+            dz = np.abs(h[ys, xs] - h[yd, xd])
+            c = np.sqrt(p + dz * dz) + Dm[yd, xd]
+            sub = best[ys, xs]
+            best[ys, xs] = np.where(c < sub, c, sub)
+    best[~free] = np.inf
+    gx, gy = goal
+    if 0 <= gx < W and 0 <= gy < H and free[gy, gx]:
+        best[gy, gx] = 0.0
+    else:
+        best[:] = np.inf
+    bad = best.view(np.uint32) != D.view(np.uint32)
+    if bad.any():
+        y, x = np.argwhere(bad)[0]
+        return f"{int(bad.sum())} cells are not the fixpoint, first ({x}, {y}): D {D[y, x]!r}, min over neighbours {best[y, x]!r}"
+    return ""
+
+
+def hop_counts(nxt) -> np.ndarray:
+    """(H, W) int64: the number of hops along `nxt` from every cell to NEXT_GOAL (0 at the goal), -1 where the walk ends at
+    NEXT_NONE.  Pointer doubling, ceil(log2(H W)) + 1 rounds.  Raises on a cycle, a hop off the map or an unknown code."""
+    nxt = np.asarray(nxt, np.uint8)
+    H, W = nxt.shape
+    n = H * W
+    code = nxt.ravel().astype(np.int64)
+    if ((code > NEXT_GOAL) & (code != NEXT_NONE)).any():
+        raise ValueError(f"unknown next-hop code {sorted(set(code[(code > NEXT_GOAL) & (code != NEXT_NONE)].tolist()))}")
+    idx = np.arange(n)
+    step = code < 8
+    ddx = np.array([d[0] for d in DIRS] + [0], np.int64)[np.minimum(code, 8)]
+    ddy = np.array([d[1] for d in DIRS] + [0], np.int64)[np.minimum(code, 8)]
+    x, y = idx % W + ddx, idx // W + ddy
+    off = step & ((x < 0) | (x >= W) | (y < 0) | (y >= H))
+    if off.any():
+        raise ValueError(f"next of cell {int(idx[off][0] % W), int(idx[off][0] // W)} points off the map")
+    jump = np.where(step, y * W + x, idx)
+    hops = step.astype(np.int64)
+    for _ in range(int(np.ceil(np.log2(max(n, 1)))) + 1):
+        hops = hops + hops[jump]
+        jump = jump[jump]
+    if step[jump].any():
+        c = int(idx[step[jump]][0])
+        raise RuntimeError(f"next-hop cycle reached from cell {(c % W, c // W)}")
+    return np.where(code[jump] == NEXT_GOAL, hops, -1).reshape(H, W)
+
+
+def check_f64(heights, risk, threshold, resolution, goal, D, nxt) -> str:
+    """'' when the float32 field D (and its next-hop map) agrees with field_f64: the same finite cells, every free cell's walk
+    ends at the goal exactly where D is finite, and |D - D64| <= (hops + 1) 2^-22 D64 per cell, hops counted along `nxt`
+    (each hop rounds its weight and its sum in float32: a few 2^-24 relative)."""
+    D = np.asarray(D, np.float32)
+    D64 = field_f64(heights, risk, threshold, resolution, goal)
+    fin = np.isfinite(D)
+    if not np.array_equal(fin, np.isfinite(D64)):
+        y, x = np.argwhere(fin != np.isfinite(D64))[0]
+        return f"finite cells differ, first ({x}, {y}): D {D[y, x]!r}, float64 {D64[y, x]!r}"
+    hops = hop_counts(nxt)
+    free = free_mask(risk, threshold)           # a collision cell has D = +inf but a next hop: a start may be in collision
+    if not np.array_equal((hops >= 0)[free], fin[free]):
+        return "the next-hop walks do not end at the goal exactly where D is finite"
+    err = np.abs(D[fin].astype(np.float64) - D64[fin])
+    tol = (hops[fin] + 1) * 2.0 ** -22 * D64[fin]
+    if (err > tol).any():
+        j = np.argmax(err - tol)
+        return f"{int((err > tol).sum())} cells beyond tolerance, worst {err[j]!r} > {tol[j]!r}"
+    return ""
+
+
 # ---- tests/golden/astar.npz (tests/golden/make_golden_astar.py) ---------------------------------------------------------
 def load_fixtures(path):
     """{name: dict(heights, risk, thr, res, x0, y0, goal_pos, starts, status, messages, paths)}; status 0 path, 1 None, 2 ValueError."""
