@@ -125,6 +125,7 @@ SYMBOLS = {
     "bn_astar_buffers": (C.c_int, [_H, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "bn_astar_last_error": (C.c_char_p, []),
     "bn_device_math_eval": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "bn_device_rng_eval": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "bn_last_error": (C.c_char_p, []),
     "bn_mppi_abi_version": (C.c_int, []),
 }

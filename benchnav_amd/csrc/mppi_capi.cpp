@@ -2708,7 +2708,7 @@ int bn_mppi_get_slip_noise(bn_mppi_t *h, int32_t instance, uint64_t solve_index,
     const size_t K = h->p.K, T = h->p.T, nt = K * T, nc = K * (T + 1);
     if (int rc = ensure_scratch(h, (nt + nc + T) * 4)) return rc;
     float *zt = h->d_scratch, *zc = zt + nt, *zo = zc + nc;
-    BN_HIP(bn::launch_philox_slip(zt, zc, zo, h->p.seed, solve_index, instance, (int)K, (int)T, h->stream));
+    BN_HIP(bn::launch_philox_slip(zt, zc, zo, h->p.seed, solve_index, instance, (int)K, (int)T, h->p.k0, h->stream));
     BN_HIP(hipMemcpyAsync(zt_host, zt, nt * 4, hipMemcpyDeviceToHost, h->stream));
     BN_HIP(hipMemcpyAsync(zc_host, zc, nc * 4, hipMemcpyDeviceToHost, h->stream));
     BN_HIP(hipMemcpyAsync(zo_host, zo, T * 4, hipMemcpyDeviceToHost, h->stream));
@@ -2873,6 +2873,14 @@ int bn_device_math_eval(int32_t fn, const float *in_device, float *out_device, i
     if (fn < 0 || fn > 5 || !in_device || !out_device || n < 0) return fail(BN_ERR_INVALID, "bad argument");
     if (n == 0) return BN_OK;
     BN_HIP(bn::launch_math_eval(fn, in_device, out_device, (size_t)n, (hipStream_t)stream));
+    return BN_OK;
+}
+
+int bn_device_rng_eval(int32_t fn, const uint32_t *in_device, uint32_t *out_device, int64_t n, void *stream)
+{
+    if (fn < 0 || fn > 2 || !in_device || !out_device || n < 0) return fail(BN_ERR_INVALID, "bad argument");
+    if (n == 0) return BN_OK;
+    BN_HIP(bn::launch_rng_eval(fn, in_device, out_device, (size_t)n, (hipStream_t)stream));
     return BN_OK;
 }
 

@@ -205,12 +205,13 @@ hipError_t launch_echo64(const unsigned long long *src, unsigned long long *dst,
 hipError_t launch_stamp(int *word, int value, hipStream_t s);      // one thread: *word = value (system scope) -- a marker in a queue, for the host
 hipError_t launch_quotient_check(float res, float inv_res, float d_max, unsigned long long *bad, hipStream_t s);
 hipError_t launch_math_eval(int fn, const float *in, float *out, size_t n, hipStream_t s);   // 0 sqrt, 1 sin, 2 cos, 3 wrap, 4 wrap_near
+hipError_t launch_rng_eval(int fn, const uint32_t *in, uint32_t *out, size_t n, hipStream_t s);   // 0 philox4x32<10>, 1 <kStreamRounds>, 2 box_muller
 
 // layout conversion helpers (planner-native k-fastest <-> reference k-major)
 hipError_t launch_states_to_reference(const float *X_soa, float *X_aos, int K, int Kp, int T1, hipStream_t s);   // (T1,3,Kp)->(K,T1,3)
 hipError_t launch_controls_to_reference(const float *U_soa, float *U_aos, int K, int Kp, int T, hipStream_t s);  // (T,2,Kp)->(K,T,2)
 hipError_t launch_gather_states(const float *X_soa, const int *idx, float *out, int n, int Kp, int T1, hipStream_t s);
-hipError_t launch_philox_slip(float *zt, float *zc, float *zo, uint64_t seed, uint64_t solve, int b, int K, int T, hipStream_t s);   // (K,T), (K,T+1), (T)
+hipError_t launch_philox_slip(float *zt, float *zc, float *zo, uint64_t seed, uint64_t solve, int b, int K, int T, int k0, hipStream_t s);   // (K,T), (K,T+1), (T)
 hipError_t launch_philox_noise(float *eps_kt2, uint64_t seed, uint64_t solve, int b, int K, int T, int k0, hipStream_t s);
 
 }  // namespace bn

@@ -370,6 +370,26 @@ __global__ void math_eval_kernel(int fn, const float *__restrict__ in, float *__
     }
 }
 
+// ---- the library's generator on caller-supplied words (test hook: bn_device_rng_eval) ----
+// fn 0 / 1: record i = 6 words (counter c0..c3, key k0, k1) -> philox4x32<10> / philox4x32<kStreamRounds>, 4 words;
+// fn 2: record i = 2 words (a, b) -> box_muller(a, b), 2 floats as bits.  The inline functions every stream is built from.
+__global__ void rng_eval_kernel(int fn, const uint32_t *__restrict__ in, uint32_t *__restrict__ out, size_t n)
+{
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        if (fn == 2) {
+            float z0, z1;
+            box_muller(in[2 * i], in[2 * i + 1], z0, z1);
+            out[2 * i] = __float_as_uint(z0);
+            out[2 * i + 1] = __float_as_uint(z1);
+            continue;
+        }
+        const uint32_t *r = in + 6 * i;
+        const u32x4 c = {r[0], r[1], r[2], r[3]};
+        const u32x4 q = fn == 0 ? philox4x32<10>(c, r[4], r[5]) : philox4x32<kStreamRounds>(c, r[4], r[5]);
+        out[4 * i] = q.x; out[4 * i + 1] = q.y; out[4 * i + 2] = q.z; out[4 * i + 3] = q.w;
+    }
+}
+
 // ---- layout helpers -----------------------------------------------------------
 __global__ void soa_to_aos_kernel(const float *__restrict__ in, float *__restrict__ out, int K, int Kp, int R)
 {   // in (R, Kp pitch) -> out (K, R)
@@ -665,6 +685,12 @@ hipError_t launch_stamp(int *word, int value, hipStream_t s)
 hipError_t launch_math_eval(int fn, const float *in, float *out, size_t n, hipStream_t s)
 {
     math_eval_kernel<<<grid_for(n), 256, 0, s>>>(fn, in, out, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_rng_eval(int fn, const uint32_t *in, uint32_t *out, size_t n, hipStream_t s)
+{
+    rng_eval_kernel<<<grid_for(n), 256, 0, s>>>(fn, in, out, n);
     return hipGetLastError();
 }
 

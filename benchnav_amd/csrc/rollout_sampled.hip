@@ -288,16 +288,17 @@ __global__ __launch_bounds__(64) void rollout_sampled_global_kernel(const SolveP
     if (lane == 0) { part[0] = zmax; part[1] = esum; }
 }
 
-// The slip draws of one solve, exactly the stream the sampled kernels consume: zt (K,T), zc (K,T+1), zo (T).
+// The slip draws of one solve, exactly the stream the sampled kernels consume: zt (K,T), zc (K,T+1), zo (T).  Row k is keyed by
+// rollout k + k0, as in the kernels (bn_mppi_set_rollout_offset); the optimal rollout's key 0xffffffff takes no offset.
 __global__ void philox_slip_kernel(float *__restrict__ zt, float *__restrict__ zc, float *__restrict__ zo, uint64_t seed,
-                                   uint64_t solve, int b, int K, int T)
+                                   uint64_t solve, int b, int K, int T, int k0)
 {
     const int nS = ((T + 2) & ~1) >> 1;
     const size_t tot = (size_t)K * nS;
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < tot; i += (size_t)gridDim.x * blockDim.x) {
         const int k = (int)(i / nS), j = (int)(i - (size_t)k * nS);
         float z[4];
-        philox_slip_block(seed, solve, (uint32_t)b, (uint32_t)k, (uint32_t)j, z);
+        philox_slip_block(seed, solve, (uint32_t)b, (uint32_t)(k + k0), (uint32_t)j, z);
         for (int s = 0; s < 2; ++s) {
             const int r = 2 * j + s;
             if (r < T) zt[(size_t)k * T + r] = z[s];
@@ -378,9 +379,9 @@ hipError_t launch_rollout_sampled(const SolveParams &p, EpsMode mode, hipStream_
     }
 }
 
-hipError_t launch_philox_slip(float *zt, float *zc, float *zo, uint64_t seed, uint64_t solve, int b, int K, int T, hipStream_t s)
+hipError_t launch_philox_slip(float *zt, float *zc, float *zo, uint64_t seed, uint64_t solve, int b, int K, int T, int k0, hipStream_t s)
 {
-    philox_slip_kernel<<<grid_for((size_t)K * (T / 2 + 1)), 256, 0, s>>>(zt, zc, zo, seed, solve, b, K, T);
+    philox_slip_kernel<<<grid_for((size_t)K * (T / 2 + 1)), 256, 0, s>>>(zt, zc, zo, seed, solve, b, K, T, k0);
     return hipGetLastError();
 }
 

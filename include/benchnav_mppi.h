@@ -420,9 +420,25 @@ int bn_mppi_get_weights(bn_mppi_t *h, int32_t instance, float *out_host);
 int bn_mppi_get_costs(bn_mppi_t *h, int32_t instance, float *out_host);
 int bn_mppi_get_states(bn_mppi_t *h, int32_t instance, float *out_host);
 int bn_mppi_get_controls(bn_mppi_t *h, int32_t instance, float *out_host);
+/* The library's noise streams (BN_NOISE_PHILOX).  Each 128-bit block is Philox4x32-R (Random123 constants) of a counter
+ * {c0, c1, c2, c3} under a key {k0, k1}; its words (x, y) and (z, w) become two normals each by Box-Muller:
+ * u1 = fl(a) 2^-32 + 2^-33 in (0, 1], u2 = fl(b) 2^-32 revolutions, (z0, z1) = sqrt(-2 ln u1) (cos, sin)(2 pi u2) (a >= 0xffffff80
+ * gives u1 = 1, so z = 0; a = 0 gives the largest radius, sqrt(66 ln 2) = 6.7637).  k is the global rollout index (k + the
+ * rollout offset of bn_mppi_set_rollout_offset), b the instance, s the solve index, seed the config's seed:
+ *   control noise  R = 8   {k, t/2, lo(s) ^ (b << 20), hi(s) ^ (b >> 12)}   key (lo(seed), hi(seed))
+ *                  block (k, p) holds the (v, omega) noise of steps 2p and 2p + 1; the second half is dropped for odd T
+ *   slip draws     R = 8   the same counter with t/2 -> j                     key (lo(seed) ^ 0x534c4950, hi(seed))
+ *                  block (k, j): transit draws of steps 2j, 2j + 1 (x, y), cost draws of slots 2j, 2j + 1 (z, w); the optimal
+ *                  rollout uses k = 0xffffffff (no offset), its block j holds the transit draws of steps 4j .. 4j + 3
+ *   risk map       R = 10  {cell, i4, 0x5249534b, 0}                         key (lo(seed), hi(seed)): sample 4 i4 + s of cell
+ *   env step       R = 10  {b, lo(step), hi(step), 0x454e5631}               key env seed: z = the cosine of words (x, y)
+ *   collision      R = 10  {lo(i), hi(i), lo(draw), 0x434f4c4c ^ hi(draw)}   key env seed: i = b N + n, z = the cosine of (x, y)
+ * The instance enters the counter by xor: instance b at solve s draws exactly what instance b' draws at solve s ^ ((b ^ b') << 20).
+ * Within 2^20 consecutive solves of one handle no two instances share a block; an instance never repeats one.
+ * bn_mppi_get_philox_noise regenerates the control noise of solve `solve_index` (K,T,2) with the kernels' own functions. */
 int bn_mppi_get_philox_noise(bn_mppi_t *h, int32_t instance, uint64_t solve_index, float *out_host);
 /* Sampled-slip mode: regenerate the library's slip draws of solve `solve_index` in the oracle's layout:
- * transit (K,T), cost (K,T+1), optimal rollout (T). */
+ * transit (K,T), cost (K,T+1), optimal rollout (T); rows keyed by rollout k + the rollout offset, as the solve drew them. */
 int bn_mppi_get_slip_noise(bn_mppi_t *h, int32_t instance, uint64_t solve_index, float *zt_host, float *zc_host, float *zo_host);
 
 /* MPPI.get_top_samples(n), mppi.py:221-240: the n highest-weight rollouts, sorted
@@ -527,6 +543,10 @@ const char *bn_astar_last_error(void);
  * torch.remainder semantics (robot_model.py:90), 4 = its in-loop form, 5 = the sqrt for zero / normal finite arguments.  Lets the tests compare the kernels' building
  * blocks with the oracle's one value at a time. */
 int bn_device_math_eval(int32_t fn, const float *in_device, float *out_device, int64_t n, void *stream);
+/* Test hook: the generator every noise stream is built from, on n caller-supplied device records (uint32 words):
+ * fn 0 = Philox4x32-10, 1 = Philox4x32 with the per-rollout streams' eight rounds: record 6 words (c0, c1, c2, c3, k0, k1)
+ * -> 4 words; fn 2 = Box-Muller: record 2 words (a, b) -> 2 floats (z0, z1) as bits.  The kernels' own inline functions. */
+int bn_device_rng_eval(int32_t fn, const uint32_t *in_device, uint32_t *out_device, int64_t n, void *stream);
 
 const char *bn_last_error(void);
 int bn_mppi_abi_version(void);
