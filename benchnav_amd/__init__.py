@@ -4,6 +4,7 @@
     from benchnav_amd import NativeMPPI    # numpy-level wrapper of the C ABI, B instances per call
     from benchnav_amd import AStar         # drop-in for src/planners/global_planners/search_based/astar.py:AStar
     from benchnav_amd import BatchedPlanetaryEnv   # reset / step / collision_check of PlanetaryEnv for B environments on the GPU
+    from benchnav_amd import AStarDWALoop  # test_astar_dwa.py's A* + DWA loop on the device, B rovers per launch
 """
 from .native import NativeMPPI  # noqa: F401
 
@@ -21,4 +22,7 @@ def __getattr__(name):
     if name == "BatchedPlanetaryEnv":
         from .env import BatchedPlanetaryEnv
         return BatchedPlanetaryEnv
+    if name == "AStarDWALoop":
+        from .astar_dwa import AStarDWALoop
+        return AStarDWALoop
     raise AttributeError(name)

@@ -23,6 +23,7 @@
 // a wall-clock deadline that reports through the error word.
 #include "../../include/benchnav_mppi.h"
 #include "bn_device_math.h"
+#include "astar_view.h"
 
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -49,11 +50,7 @@ __constant__ int8_t c_dy[8] = {0, 0, -1, 1, -1, 1, -1, 1};
 constexpr int8_t h_dx[8] = {-1, 1, 0, 0, -1, -1, 1, 1};
 constexpr int8_t h_dy[8] = {0, 0, -1, 1, -1, 1, -1, 1};
 
-struct InstParams {
-    int32_t gx, gy;          // goal cell; gx < 0: no goal (the field stays +inf everywhere)
-    float thr;               // stuck threshold: collision = risk <= thr
-    int32_t pad;
-};
+using InstParams = AStarInst;   // goal cell (gx < 0: no goal, the field stays +inf everywhere), stuck threshold
 
 struct FieldArgs {
     const float *heights;    // (B, H, W)
@@ -310,7 +307,8 @@ struct bn_astar {
     uint8_t *next_host = nullptr;               // pinned copy of `next`, refreshed by every solve
     int32_t *ctl_host = nullptr;
     hipEvent_t ev_start = nullptr, ev_kernels = nullptr, ev_done = nullptr;
-    bool solved = false, pending_check = false;
+    hipEvent_t ev_reader = nullptr;             // behind the latest fused episode that reads the buffers (bn::astar_add_reader)
+    bool solved = false, pending_check = false, reader_pending = false;
     uint64_t deadline_ticks = 0;
 };
 
@@ -330,6 +328,14 @@ struct DeviceGuard {
 };
 
 #define ASTAR_HIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return astar_fail(BN_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); } while (0)
+
+// an enqueued episode still reads the buffers: wait for it before they are rewritten or freed
+void wait_readers(bn_astar_t *h)
+{
+    if (!h->reader_pending) return;
+    (void)hipEventSynchronize(h->ev_reader);
+    h->reader_pending = false;
+}
 
 // waits for the last solve, copies nothing: the pinned `next` and error word are already on the host
 int astar_wait(bn_astar_t *h)
@@ -407,11 +413,12 @@ void bn_astar_destroy(bn_astar_t *h)
     if (!h) return;
     DeviceGuard guard(h->device);
     if (h->pending_check) (void)hipEventSynchronize(h->ev_done);
+    wait_readers(h);
     for (void *p : {(void *)h->heights, (void *)h->risk, (void *)h->D, (void *)h->next, (void *)h->flags, (void *)h->ctl, (void *)h->inst_dev})
         if (p) (void)hipFree(p);
     for (void *p : {(void *)h->inst_pinned, (void *)h->next_host, (void *)h->ctl_host})
         if (p) (void)hipHostFree(p);
-    for (hipEvent_t e : {h->ev_start, h->ev_kernels, h->ev_done})
+    for (hipEvent_t e : {h->ev_start, h->ev_kernels, h->ev_done, h->ev_reader})
         if (e) (void)hipEventDestroy(e);
     delete h;
 }
@@ -430,6 +437,7 @@ int bn_astar_set_map(bn_astar_t *h, int32_t inst, const float *heights, const fl
     DeviceGuard guard(h->device);
     if (!guard.ok) return astar_fail(BN_ERR_HIP, "hipSetDevice failed");
     if (h->pending_check) { ASTAR_HIP(hipEventSynchronize(h->ev_done)); h->pending_check = false; }
+    wait_readers(h);
     const size_t cells = (size_t)h->H * h->W, off = cells * inst;
     if (where == BN_MEM_DEVICE) ASTAR_HIP(hipDeviceSynchronize());
     const hipMemcpyKind kind = where == BN_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
@@ -467,6 +475,7 @@ int bn_astar_solve_async(bn_astar_t *h, void *stream)
     DeviceGuard guard(h->device);
     if (!guard.ok) return astar_fail(BN_ERR_HIP, "hipSetDevice failed");
     if (h->pending_check) { ASTAR_HIP(hipEventSynchronize(h->ev_done)); h->pending_check = false; }   // pinned buffers are reused
+    wait_readers(h);
     hipStream_t s = (hipStream_t)stream;
     const size_t cells = (size_t)h->H * h->W * h->B;
     const int NT = h->B * h->TX * h->TY;
@@ -556,3 +565,24 @@ int bn_astar_buffers(bn_astar_t *h, int32_t inst, void **D_dev, void **next_dev)
 }
 
 }  // extern "C"
+
+namespace bn {
+
+int astar_view(bn_astar_t *h, AStarView *v)
+{
+    if (!h || !v) return astar_fail(BN_ERR_INVALID, "null argument");
+    if (!h->solved) return astar_fail(BN_ERR_STATE, "no A* solve has been enqueued");
+    *v = AStarView{h->device, h->H, h->W, h->B, h->next, h->risk, h->inst_dev, h->ctl + 1, h->ev_kernels};
+    return BN_OK;
+}
+
+int astar_add_reader(bn_astar_t *h, hipStream_t s)
+{
+    DeviceGuard guard(h->device);
+    if (!h->ev_reader) ASTAR_HIP(hipEventCreateWithFlags(&h->ev_reader, hipEventDisableTiming));
+    ASTAR_HIP(hipEventRecord(h->ev_reader, s));
+    h->reader_pending = true;
+    return BN_OK;
+}
+
+}  // namespace bn

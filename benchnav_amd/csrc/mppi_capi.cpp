@@ -5,6 +5,7 @@
 // fallback: creation fails without a gfx950 device.
 #include "../../include/benchnav_mppi.h"
 #include "mppi_kernels.h"
+#include "astar_dwa.h"
 
 #include <algorithm>
 #include <atomic>
@@ -277,6 +278,12 @@ struct bn_mppi {
     int ep_len = 0;              // steps enqueued in the current episode
     const float *ep_z = nullptr; // (n_steps, B) device slip draws of the current episode, or nullptr
     bool in_episode = false;
+    // fused A* + DWA episode (bn_astar_dwa_episode_async)
+    int32_t *d_ad_i = nullptr;   // (B) root cell | (B) status | (B) status step | (B) done step | error word
+    float *d_ad_state = nullptr; // (B, 3) the environment states the episode advances
+    float *d_ad_log = nullptr;   // (n+1, B, 3) states | (n, B) rewards | (n, B, 2) actions | (n, B, 2) sub-goals
+    int ad_cap = 0, ad_len = 0;  // steps the log holds / the latest call ran
+    uint64_t ad_step = 0;        // episode steps since bn_astar_dwa_reset
     size_t scratch_bytes = 0, eps_bytes = 0, idx_count = 0;
     float *h_pinned = nullptr;   // pinned staging for (B,3) states
     // profiling
@@ -1148,7 +1155,7 @@ void bn_mppi_destroy(bn_mppi_t *h)
                     h->d_w, h->d_ustar /* d_xstar lives in the same block */, h->d_stats, h->d_scratch, h->d_idx, h->d_lat_mean, h->d_lat_std,
                     h->d_ep_states, h->d_ep_reward, h->d_env_state, h->d_ep_done, h->d_ep_action, h->d_slip_std,
                     h->d_ustar2[0], h->d_ustar2[1], h->d_ustar2[2], h->d_ustar2[3], h->d_stats2[0], h->d_stats2[1], h->d_stats2[2], h->d_stats2[3],
-                    h->d_ticket, h->d_gpart, h->d_mean_used};
+                    h->d_ticket, h->d_gpart, h->d_mean_used, h->d_ad_i, h->d_ad_state, h->d_ad_log};
     static_assert(kSlots == 4, "the list above names the four slots");
     for (void *b : bufs)
         if (b) (void)hipFree(b);
@@ -2449,6 +2456,130 @@ int bn_mppi_dwa_candidates(bn_mppi_t *h, int32_t num_actions, const float **acti
     if (!h->d_scratch) return fail(BN_ERR_STATE, "no DWA solve has run");
     if (actions_device) *actions_device = h->d_scratch;                                                    // (B, num_actions, 2)
     if (stage_goal_device) *stage_goal_device = h->d_scratch + (size_t)h->p.B * num_actions * 2;            // (B, 2)
+    return BN_OK;
+}
+
+// ---- the A* + DWA closed loop (astar_dwa.hip) ----
+
+// root cells -1, statuses BN_AD_OK, status / done steps -1, error word 0 (allocates on first use)
+static int astar_dwa_clear(bn_mppi *h)
+{
+    const size_t B = h->p.B;
+    if (!h->d_ad_i) {
+        BN_HIP(hipMalloc((void **)&h->d_ad_i, (4 * B + 1) * sizeof(int32_t)));
+        BN_HIP(hipMalloc((void **)&h->d_ad_state, B * 3 * sizeof(float)));
+    }
+    BN_HIP(hipMemsetAsync(h->d_ad_i, 0xff, B * sizeof(int32_t), h->stream));
+    BN_HIP(hipMemsetAsync(h->d_ad_i + B, 0, B * sizeof(int32_t), h->stream));
+    BN_HIP(hipMemsetAsync(h->d_ad_i + 2 * B, 0xff, 2 * B * sizeof(int32_t), h->stream));
+    BN_HIP(hipMemsetAsync(h->d_ad_i + 4 * B, 0, sizeof(int32_t), h->stream));
+    h->ad_step = 0;
+    return BN_OK;
+}
+
+int bn_astar_dwa_reset(bn_mppi_t *h)
+{
+    if (!h) return fail(BN_ERR_INVALID, "null handle");
+    BN_BIND(h);
+    if (int rc = settle_point(h)) return rc;
+    return astar_dwa_clear(h);
+}
+
+int bn_astar_dwa_set_root(bn_mppi_t *h, int32_t instance, int32_t ix, int32_t iy)
+{
+    if (!h) return fail(BN_ERR_INVALID, "null handle");
+    if (instance < 0 || instance >= h->p.B) return fail(BN_ERR_INVALID, "instance out of range");
+    if (ix >= 0 && (ix >= h->p.G || iy < 0 || iy >= h->p.G)) return fail(BN_ERR_INVALID, "root cell out of bounds");
+    BN_BIND(h);
+    if (int rc = settle_point(h)) return rc;
+    if (!h->d_ad_i)
+        if (int rc = astar_dwa_clear(h)) return rc;
+    const int32_t cell = ix < 0 ? -1 : iy * h->p.G + ix;
+    BN_HIP(hipStreamSynchronize(h->stream));
+    BN_HIP(hipMemcpy(h->d_ad_i + instance, &cell, sizeof(int32_t), hipMemcpyHostToDevice));
+    return BN_OK;
+}
+
+int bn_astar_dwa_episode_async(bn_mppi_t *h, bn_astar_t *a, int32_t n_steps, const float *states0, bn_mem_kind where,
+                               float *prev_action_device, const float a_lim[2], float dwa_delta_t, int32_t num_lin_vel,
+                               int32_t num_ang_vel, float lookahead, const float *z_device)
+{
+    if (!h || !a || !states0 || !prev_action_device || !a_lim) return fail(BN_ERR_INVALID, "null argument");
+    if (n_steps < 1) return fail(BN_ERR_INVALID, "n_steps must be >= 1");
+    const int64_t NA = (int64_t)num_lin_vel * num_ang_vel;
+    if (num_lin_vel < 1 || num_ang_vel < 1 || NA > 1024) return fail(BN_ERR_INVALID, "num_lin_vel * num_ang_vel must be in [1, 1024]");
+    if (where != BN_MEM_HOST && where != BN_MEM_DEVICE) return fail(BN_ERR_INVALID, "unknown memory kind");
+    if (!h->env_attached) return fail(BN_ERR_STATE, "bn_mppi_env_attach must precede bn_astar_dwa_episode_async");
+    if (!h->map_set || !h->goal_set) return fail(BN_ERR_STATE, "set_map and set_goal must precede bn_astar_dwa_episode_async");
+    bn::AStarView v;
+    if (bn::astar_view(a, &v) != BN_OK) return fail(BN_ERR_STATE, "the A* handle has no solve: bn_astar_solve_async must precede the episode");
+    if (v.device != h->cfg.device_id) return fail(BN_ERR_INVALID, "the A* handle is on device %d, the planner on device %d", v.device, h->cfg.device_id);
+    if (v.B != h->p.B) return fail(BN_ERR_INVALID, "the A* handle has %d instances, the planner %d", v.B, h->p.B);
+    if (v.H != h->p.G || v.W != h->p.G) return fail(BN_ERR_INVALID, "the A* maps are %d x %d, the planner's grid is %d x %d", v.H, v.W, h->p.G, h->p.G);
+    BN_BIND(h);
+    if (int rc = settle_point(h)) return rc;
+    if (int rc = flush_tail(h)) return rc;
+    if (int rc = guard_foreign_overlap(h)) return rc;
+    const size_t B = h->p.B, n = (size_t)n_steps;
+    if (!h->d_ad_i)
+        if (int rc = astar_dwa_clear(h)) return rc;
+    if (n_steps > h->ad_cap) {
+        BN_HIP(hipStreamSynchronize(h->stream));       // the log of the previous call may still be written
+        if (h->d_ad_log) BN_HIP(hipFree(h->d_ad_log));
+        h->d_ad_log = nullptr;
+        BN_HIP(hipMalloc((void **)&h->d_ad_log, ((n + 1) * 3 + n * 5) * B * sizeof(float)));
+        h->ad_cap = n_steps;
+    }
+    const hipMemcpyKind kind = where == BN_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    BN_HIP(hipMemcpyAsync(h->d_ad_state, states0, B * 3 * sizeof(float), kind, h->stream));
+    if (where == BN_MEM_HOST) BN_HIP(hipStreamSynchronize(h->stream));   // (pageable source: one upload, before the loop)
+    BN_HIP(hipStreamWaitEvent(h->stream, v.solved, 0));                 // behind a's latest solve, without the host
+    float *lg = h->d_ad_log;
+    const size_t cap = (size_t)h->ad_cap;                                 // the log's layout is by capacity (bn_astar_dwa_episode_log)
+    bn::AstarDwaArgs x{};
+    x.next = v.next; x.arisk = v.risk; x.ainst = v.inst; x.aerr = v.err; x.H = v.H; x.W = v.W;
+    x.state = h->d_ad_state; x.prev = prev_action_device;
+    x.root = h->d_ad_i; x.status = h->d_ad_i + B; x.status_step = h->d_ad_i + 2 * B; x.done = h->d_ad_i + 3 * B; x.err = h->d_ad_i + 4 * B;
+    x.log_states = lg; x.log_reward = lg + (cap + 1) * B * 3; x.log_action = x.log_reward + cap * B; x.log_subgoal = x.log_action + cap * B * 2;
+    x.z = z_device;
+    x.alim0 = a_lim[0]; x.alim1 = a_lim[1]; x.dwa_dt = dwa_delta_t; x.lookahead = lookahead;
+    x.nv = num_lin_vel; x.nw = num_ang_vel;
+    x.step0 = h->ad_step;
+    // chained launches on one stream.  A step walks the path twice at most (2 H W hops): the node budget keeps one launch short
+    // on large maps with long paths (64^2: 256 steps, 256^2: 16, 512^2: 4)
+    const int per_launch = (int)std::max<int64_t>(1, std::min<int64_t>(bn::kAstarDwaStepsPerLaunch,
+                                                                          bn::kAstarDwaNodesPerLaunch / ((int64_t)v.H * v.W)));
+    for (int s0 = 0; s0 < n_steps; s0 += per_launch) {
+        x.s0 = s0;
+        x.ns = std::min(per_launch, n_steps - s0);
+        BN_HIP(bn::launch_astar_dwa(h->p, x, h->stream));
+    }
+    if (bn::astar_add_reader(a, h->stream) != BN_OK) return fail(BN_ERR_HIP, "%s", bn_astar_last_error());
+    h->ad_step += n;
+    h->ad_len = n_steps;
+    return BN_OK;
+}
+
+int bn_astar_dwa_episode_log(bn_mppi_t *h, float *states, float *rewards, float *actions, float *sub_goals,
+                             int32_t *done_step, int32_t *status, int32_t *status_step)
+{
+    if (!h) return fail(BN_ERR_INVALID, "null handle");
+    if (!h->d_ad_log || h->ad_len < 1) return fail(BN_ERR_STATE, "no A* + DWA episode has been run");
+    BN_BIND(h);
+    if (int rc = settle_point(h)) return rc;
+    BN_HIP(hipStreamSynchronize(h->stream));
+    const size_t B = h->p.B, n = (size_t)h->ad_len, cap = (size_t)h->ad_cap;
+    const float *lg = h->d_ad_log, *rw = lg + (cap + 1) * B * 3, *ac = rw + cap * B, *sg = ac + cap * B * 2;
+    if (states) BN_HIP(hipMemcpy(states, lg, (n + 1) * B * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    if (rewards) BN_HIP(hipMemcpy(rewards, rw, n * B * sizeof(float), hipMemcpyDeviceToHost));
+    if (actions) BN_HIP(hipMemcpy(actions, ac, n * B * 2 * sizeof(float), hipMemcpyDeviceToHost));
+    if (sub_goals) BN_HIP(hipMemcpy(sub_goals, sg, n * B * 2 * sizeof(float), hipMemcpyDeviceToHost));
+    if (status) BN_HIP(hipMemcpy(status, h->d_ad_i + B, B * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (status_step) BN_HIP(hipMemcpy(status_step, h->d_ad_i + 2 * B, B * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (done_step) BN_HIP(hipMemcpy(done_step, h->d_ad_i + 3 * B, B * sizeof(int32_t), hipMemcpyDeviceToHost));
+    int32_t err = 0;
+    BN_HIP(hipMemcpy(&err, h->d_ad_i + 4 * B, sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (err) return fail(BN_ERR_STATE, "a next-hop walk broke (more than H*W nodes, or onto an unreachable cell): the A* field is not a valid solve");
     return BN_OK;
 }
 

@@ -20,6 +20,7 @@
 // live in rollout_role_*.hip (five-wave role split, one file per noise source), rollout_wave.hip (throughput
 // variant) and rollout_sampled.hip (config 3); the device code they share is mppi_device.h.
 #include "mppi_device.h"
+#include "dwa_device.h"
 #include <cstring>
 
 namespace bn {
@@ -133,11 +134,9 @@ __global__ __launch_bounds__(256) void reroll_kernel(const SolveParams p, int b,
 }
 
 // ------------------------------------------------------------------------------
-// DWA ("next" row N3): reference src/planners/local_planners/dwa.py:116-258.  NA constant-control candidates
-// (the dynamic window grid, built by the host exactly as dwa.py:168-199 does) are rolled out with the same
-// transit / aliasing as MPPI (dwa.py:224-227), costed with the stage cost against the sub-goal and the
-// terminal cost against the goal, accumulated in fp32 in step order like `cost_batch +=` (dwa.py:251-256);
-// argmin (first minimum, dwa.py:139), weights = softmax(-cost) (dwa.py:151).
+// DWA ("next" row N3): reference src/planners/local_planners/dwa.py:116-258, the device code in dwa_device.h (shared with the
+// fused A* + DWA episode, astar_dwa.hip).  dwa_kernel: rollouts, costs, argmin, weights of NA candidates (the dynamic window
+// grid, built by dwa_window_kernel or by the host exactly as dwa.py:168-199 does).
 // grid = B, block = 64 * ceil(NA / 64) <= 1024, lane = candidate.  LDS: [ window | red 2*16 ].
 // ------------------------------------------------------------------------------
 template <int GEO, bool LDSWIN>
@@ -149,101 +148,29 @@ __global__ void dwa_kernel(const SolveParams p, const float *__restrict__ action
     const int T = p.T;
     float *win = smem;
     float *red = win + (LDSWIN ? p.WN * p.WN : 0);
-    int *redi = reinterpret_cast<int *>(red + 16);
     const int tid = threadIdx.x, b = blockIdx.x, nthreads = blockDim.x;
-    const float *__restrict__ map = p.map + (size_t)b * p.map_stride;
-    const float sx = p.state[b * 3 + 0], sy = p.state[b * 3 + 1], sth = p.state[b * 3 + 2];
-    const float gx = p.goal[b * 2 + 0], gy = p.goal[b * 2 + 1];                 // terminal cost: the goal
-    const float hx = stage_goal[b * 2 + 0], hy = stage_goal[b * 2 + 1];         // stage cost: the sub-goal
-    Win w{0, 0, 0.f, 0.f, 0.f, 0.f};
-    if (LDSWIN) {
-        w = window_origin<GEO>(p, sx, sy);
-        stage_window(win, map, w, p.WN, p.G, tid, nthreads);
-    }
-    __syncthreads();
-    const bool active = tid < NA;
-    const int k = active ? tid : NA - 1;
-    const float u0 = clampf(actions[((size_t)b * NA + k) * 2 + 0], p.umin0, p.umax0);   // transit re-clamps (robot_model.py:82-83)
-    const float u1 = clampf(actions[((size_t)b * NA + k) * 2 + 1], p.umin1, p.umax1);
-    Chain c;
-    c.x = sx; c.y = sy; c.th = sth;
-    sincos_spec(c.th, c.sn, c.cs);
-    c.trav = trav_lookup<GEO, LDSWIN, true>(p, win, map, w, c.x, c.y);
-    float *Xk = Xall ? Xall + ((size_t)b * NA + k) * (T + 1) * 3 : nullptr;
-    float cost = 0.0f;
-    const bool ref = p.ref_order != 0;
-    for (int t = 0; t < T; ++t) {
-        float xn, yn, tn;
-        if (ref && t == 0) chain_step<GEO, LDSWIN, true, true, false, 0, true>(p, win, map, w, c, u0, u1, xn, yn, tn);
-        else if (ref) chain_step<GEO, LDSWIN, false, true, false, 0, true>(p, win, map, w, c, u0, u1, xn, yn, tn);
-        else if (t == 0) chain_step<GEO, LDSWIN, true>(p, win, map, w, c, u0, u1, xn, yn, tn);
-        else chain_step<GEO, LDSWIN, false>(p, win, map, w, c, u0, u1, xn, yn, tn);
-        if (Xk && active) { Xk[3 * t] = xn; Xk[3 * t + 1] = yn; Xk[3 * t + 2] = tn; }
-        const float dx = xn - hx, dy = yn - hy;
-        cost = cost + (sqrt_cr(dx * dx + dy * dy) + (c.trav <= p.thr ? 1.0e4f : 0.0f));      // objectives.py:47-53
-    }
-    if (Xk && active) { Xk[3 * T] = c.x; Xk[3 * T + 1] = c.y; Xk[3 * T + 2] = c.th; }
-    const float dxT = c.x - gx, dyT = c.y - gy;
-    cost = cost + (sqrt_cr(dxT * dxT + dyT * dyT) + (c.trav <= p.thr ? 1.0e4f : 0.0f));       // dwa.py:256
-    if (active) cost_out[(size_t)b * NA + tid] = cost;
-
-    // argmin with first-index tie break, then softmax(-cost)
-    float cm = active ? cost : INFINITY;
-    int im = active ? tid : 0x7fffffff;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float oc = __shfl_xor(cm, o);
-        const int oi = __shfl_xor(im, o);
-        if (oc < cm || (oc == cm && oi < im)) { cm = oc; im = oi; }
-    }
-    const int wv = tid >> 6, nw = nthreads >> 6;
-    if ((tid & 63) == 0) { red[wv] = cm; redi[wv] = im; }
-    __syncthreads();
-    float cmin = red[0];
-    int imin = redi[0];
-    for (int i = 1; i < nw; ++i)
-        if (red[i] < cmin || (red[i] == cmin && redi[i] < imin)) { cmin = red[i]; imin = redi[i]; }
-    __syncthreads();
-    const float e = active ? expf((-cost) - (-cmin)) : 0.0f;
-    float es = wave_sum(e);
-    if ((tid & 63) == 0) red[wv] = es;
-    __syncthreads();
-    float tot = 0.0f;
-    for (int i = 0; i < nw; ++i) tot += red[i];
-    if (active) w_out[(size_t)b * NA + tid] = e / tot;
+    const float *act = actions + (size_t)b * NA * 2;
+    const int imin = dwa_rollout_argmin<GEO, LDSWIN>(p, b, p.state[b * 3 + 0], p.state[b * 3 + 1], p.state[b * 3 + 2], act, NA,
+                                                     stage_goal[b * 2 + 0], stage_goal[b * 2 + 1], p.goal[b * 2 + 0], p.goal[b * 2 + 1],
+                                                     win, red, tid, nthreads, Xall ? Xall + (size_t)b * NA * (T + 1) * 3 : nullptr,
+                                                     cost_out + (size_t)b * NA, w_out + (size_t)b * NA);
     if (tid == 0) {
         best_out[b] = imin;
         if (best_action) {                             // optimal_action_seq = actions[argmin] (dwa.py:140); also the next window's centre (dwa.py:147)
-            best_action[b * 2 + 0] = actions[((size_t)b * NA + imin) * 2 + 0];
-            best_action[b * 2 + 1] = actions[((size_t)b * NA + imin) * 2 + 1];
+            best_action[b * 2 + 0] = act[imin * 2 + 0];
+            best_action[b * 2 + 1] = act[imin * 2 + 1];
         }
     }
     // optimal_state_seq = the argmin candidate's trajectory (dwa.py:139-143): its stores are complete and visible to
-    // the workgroup since the barriers above
+    // the workgroup since the barriers in dwa_rollout_argmin
     if (Xall && best_states)
         for (int i = tid; i < (T + 1) * 3; i += nthreads) best_states[(size_t)b * (T + 1) * 3 + i] = Xall[((size_t)b * NA + imin) * (T + 1) * 3 + i];
 }
 
 // ------------------------------------------------------------------------------
-// DWA host geometry on the device (so that DWA.forward needs no host round trip): the dynamic window grid and the
-// sub-goal.  grid = B, block = 256.
-//   window   dwa.py:168-199: lo = max(u_min, prev - a_lim * dt), hi = min(u_max, prev + a_lim * dt) around the previous first
-//            control; vs = linspace(lo_v, hi_v, nv), ws = linspace(lo_w, hi_w, nw); actions = cartesian_prod(vs, ws) (v major).
-//            linspace as ATen's scalar kernel computes it: step = (end - start) / (n - 1); element i < n/2 is
-//            start + step * i, the others end - step * (n - 1 - i).  (On AVX2 hosts torch's vectorised path evaluates the
-//            first 8 elements from `start` alone, so torch itself is machine dependent in the last bit; this is the form
-//            AVX-512 hosts and every scalar tail use.)
-//   sub-goal dwa.py:240-244 + 260-285, evaluated like the reference on candidate 0's ALIASED slot-0 state (the start state
-//            advanced by one un-clamped, un-wrapped step of candidate 0 = (lo_v, lo_w)): nearest path point with
-//            |bearing| < pi/2 and distance > lookahead -- the first point at that distance -- else the path's end.
+// DWA host geometry on the device (so that DWA.forward needs no host round trip): the dynamic window grid and the sub-goal on
+// the reference path `path` (P, 2) (dwa_device.h).  grid = B, block = 256.
 // ------------------------------------------------------------------------------
-__device__ __forceinline__ float linspace_at(float start, float end, int n, int i)
-{
-    if (n == 1) return start;
-    const float step = (end - start) / (float)(n - 1);
-    return i < n / 2 ? start + step * (float)i : end - step * (float)(n - 1 - i);
-}
-
 template <int GEO>
 __global__ __launch_bounds__(256) void dwa_window_kernel(const SolveParams p, const float *__restrict__ prev_action, float alim0, float alim1,
                                                          float dwa_dt, int nv, int nw, const float *__restrict__ path, int P, float lookahead,
@@ -253,55 +180,24 @@ __global__ __launch_bounds__(256) void dwa_window_kernel(const SolveParams p, co
     __shared__ int redi[8];
     __shared__ float sel[3];
     const int b = blockIdx.x, tid = threadIdx.x, NA = nv * nw;
-    const float pv = prev_action[b * 2 + 0], pw = prev_action[b * 2 + 1];
-    const float lo0 = fmaxf(p.umin0, pv - alim0 * dwa_dt), hi0 = fminf(p.umax0, pv + alim0 * dwa_dt);
-    const float lo1 = fmaxf(p.umin1, pw - alim1 * dwa_dt), hi1 = fminf(p.umax1, pw + alim1 * dwa_dt);
-    for (int k = tid; k < NA; k += 256) {
-        const int iv = k / nw, iw = k - iv * nw;
-        actions[((size_t)b * NA + k) * 2 + 0] = linspace_at(lo0, hi0, nv, iv);
-        actions[((size_t)b * NA + k) * 2 + 1] = linspace_at(lo1, hi1, nw, iw);
-    }
+    const DwaWindow d = dwa_window(p, prev_action[b * 2 + 0], prev_action[b * 2 + 1], alim0, alim1, dwa_dt);
+    dwa_window_actions(d, nv, nw, actions + (size_t)b * NA * 2, tid, 256);
     if (!path || P < 1) {                               // no reference path: the stage cost runs against the goal (dwa.py:243-247)
         if (tid < 2) stage_goal[b * 2 + tid] = p.goal[b * 2 + tid];
         return;
     }
-    if (tid == 0) {                                     // candidate 0's slot 0 after the rollouts (aliasing, robot_model.py:86-88)
-        const float *__restrict__ map = p.map + (size_t)b * p.map_stride;
-        const float sx = p.state[b * 3 + 0], sy = p.state[b * 3 + 1], sth = p.state[b * 3 + 2];
-        const Win w{0, 0, 0.f, 0.f, 0.f, 0.f};
-        const float trav = trav_lookup<GEO, false, true>(p, nullptr, map, w, sx, sy);
-        const float v = clampf(linspace_at(lo0, hi0, nv, 0), p.umin0, p.umax0), om = clampf(linspace_at(lo1, hi1, nw, 0), p.umin1, p.umax1);
-        float sn, cs;
-        sincos_spec(sth, sn, cs);
-        sel[0] = sx + ((trav * v) * cs) * p.dt;
-        sel[1] = sy + ((trav * v) * sn) * p.dt;
-        sel[2] = sth + (trav * om) * p.dt;
-    }
+    if (tid == 0) dwa_subgoal_state<GEO>(p, b, p.state[b * 3 + 0], p.state[b * 3 + 1], p.state[b * 3 + 2], d, nv, nw, sel[0], sel[1], sel[2]);
     __syncthreads();
     const float x = sel[0], y = sel[1], th = sel[2];
     float best = INFINITY;
-    for (int i = tid; i < P; i += 256) {
-        const float dx = path[2 * i] - x, dy = path[2 * i + 1] - y;
-        const float dist = sqrt_cr(dx * dx + dy * dy);
-        const float ang = atan2f(dy, dx) - th;
-        if (fabsf(ang) < kPi / 2.0f && dist > lookahead) best = fminf(best, dist);
-    }
-    best = -wave_max(-best);
-    if ((tid & 63) == 0) red[tid >> 6] = best;
-    __syncthreads();
-    best = fminf(fminf(red[0], red[1]), fminf(red[2], red[3]));
+    for (int i = tid; i < P; i += 256) best = fminf(best, dwa_ahead_dist(path[2 * i], path[2 * i + 1], x, y, th, lookahead));
+    best = block_min(best, red, tid, 256);
     int idx = 0x7fffffff;
     if (best < INFINITY)
-        for (int i = tid; i < P; i += 256) {
-            const float dx = path[2 * i] - x, dy = path[2 * i + 1] - y;
-            if (sqrt_cr(dx * dx + dy * dy) == best) { idx = i; break; }      // torch.where(distances == min)[0][0]: over ALL points
-        }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) idx = min(idx, __shfl_xor(idx, o));
-    if ((tid & 63) == 0) redi[tid >> 6] = idx;
-    __syncthreads();
+        for (int i = tid; i < P; i += 256)
+            if (dwa_point_dist(path[2 * i], path[2 * i + 1], x, y) == best) { idx = i; break; }   // torch.where(distances == min)[0][0]: over ALL points
+    idx = block_min_i(idx, redi, tid, 256);
     if (tid == 0) {
-        idx = min(min(redi[0], redi[1]), min(redi[2], redi[3]));
         if (best == INFINITY || idx >= P) idx = P - 1;                       // nothing ahead: the path's last point
         stage_goal[b * 2 + 0] = path[2 * idx];
         stage_goal[b * 2 + 1] = path[2 * idx + 1];

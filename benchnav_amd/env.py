@@ -84,6 +84,7 @@ class BatchedPlanetaryEnv:
         self._elapsed_time = 0.0
         self._steps = 0
         self._draws = 0
+        self._on_reset = []                        # weak references to the reset() of loops driving this environment (AStarDWALoop)
         if bool(self.collision_check(torch.cat([self._start_pos, torch.zeros(self.B, 1, device=dev)], 1).unsqueeze(1)).any()) or \
            bool(self.collision_check(torch.cat([self._goal_pos, torch.zeros(self.B, 1, device=dev)], 1).unsqueeze(1)).any()):
             raise ValueError("Start or goal position is not traversable.")          # planetary_env.py:124-125
@@ -113,6 +114,10 @@ class BatchedPlanetaryEnv:
         self._robot_state = self._initialize_robot_state()
         self._reward.fill_(float("nan"))
         self._terminated.zero_()
+        for ref in self._on_reset:
+            fn = ref()
+            if fn is not None:
+                fn()
         return self._robot_state
 
     def step(self, action: torch.Tensor, z: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, bool]:

@@ -68,6 +68,7 @@ class NativeMPPI:
                      | {"auto": 0, "wave": _capi.BN_FLAG_WAVE_KERNEL, "role": _capi.BN_FLAG_ROLE_KERNEL, "lat": _capi.BN_FLAG_LAT_KERNEL}[kernel])
         cfg.stream = stream        # an int hipStream_t; 0 is the null stream (torch's default); None = private stream
         self.K, self.T, self.G, self.B = num_samples, horizon, grid_size, num_instances
+        self.resolution, self.x_limits, self.y_limits = float(resolution), tuple(x_limits), tuple(y_limits)
         self.device_id, self.stream = device_id, stream       # stream: the hipStream_t the handle enqueues on (None: private)
         self.store_controls = store_controls
         self._shared_map = shared_map or num_instances == 1

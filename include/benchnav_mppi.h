@@ -538,6 +538,43 @@ int bn_astar_path(bn_astar_t *h, int32_t inst, int32_t ix, int32_t iy, int32_t *
 int bn_astar_buffers(bn_astar_t *h, int32_t inst, void **D_dev, void **next_dev);
 const char *bn_astar_last_error(void);
 
+/*
+ * The A* + DWA closed loop of test_astar_dwa.py:179-211 on the device for the B instances of h (csrc/astar_dwa.hip), one
+ * workgroup per instance, no host round trip: per control step the A* path from the current cell (astar.py:73-122 as a walk of
+ * a's solved next-hop map), DWA.forward (dwa.py:116-153) and PlanetaryEnv.step (planetary_env.py:189-219).
+ *   start cell  int((x - x_limits[0]) / res) in f32, truncated (AStar._pos_to_index).  A start out of bounds, a goal out of
+ *               bounds or in collision (astar.py:88-94) freezes the instance with a status and the step (the reference raises).
+ *   path        point = (f32(ix) * f32(res), f32(iy) * f32(res)), start cell included.  An unreachable start is the reference's
+ *               None: DWA keeps the previous path, the walk from the instance's root cell (the last start whose walk reached
+ *               the goal); no root cell yet: the stage cost runs against the goal (dwa.py:243-247).
+ *   env step    observation-mode transit with the slip draw of episode step j: z_device row j of this call, or Philox keyed by
+ *               (env seed, j) as bn_mppi_env_step(..., step_index = j); honours bn_mppi_env_set_freeze.
+ * Steps are counted from bn_astar_dwa_reset; the root cells, the step count and the statuses persist across calls until then,
+ * the window centre in the caller's prev_action_device: episode(n) == episode(k) then episode(n - k), bit for bit.
+ */
+typedef enum bn_astar_dwa_status {
+    BN_AD_OK = 0,               /* running                                                                  */
+    BN_AD_OUT_OF_BOUNDS = 1,    /* ValueError("Start or goal position is out of bounds.") (astar.py:88-92)  */
+    BN_AD_GOAL_COLLISION = 2,   /* ValueError("Goal position is not traversable.") (astar.py:93-94)         */
+    BN_AD_FIELD_ERROR = 3       /* the A* solve failed, or a next-hop walk broke (not a valid field)        */
+} bn_astar_dwa_status;
+/* n_steps control steps on h's stream, ordered behind a's latest bn_astar_solve_async by an event.  Needs bn_mppi_env_attach and
+ * the goals of h; a on h's device with h's B and H = W = grid_size; num_lin_vel * num_ang_vel <= 1024.  states0 (B,3) the
+ * current environment states; prev_action_device (B,2) in/out; z_device (n_steps, B) or NULL. */
+int bn_astar_dwa_episode_async(bn_mppi_t *h, bn_astar_t *a, int32_t n_steps, const float *states0, bn_mem_kind where,
+                               float *prev_action_device, const float a_lim[2], float dwa_delta_t, int32_t num_lin_vel,
+                               int32_t num_ang_vel, float lookahead, const float *z_device);
+/* The latest call's log (any pointer may be NULL): states (n+1,B,3) with [0] the call's start, rewards (n,B), actions (n,B,2),
+ * sub_goals (n,B,2) (the stage-cost target); a frozen instance's rows keep its state and hold NaN elsewhere.  done_step (B): first
+ * episode step whose resulting state is within the goal threshold, or -1; status (B) bn_astar_dwa_status; status_step (B): the
+ * episode step at which it was set.  BN_ERR_STATE if a walk broke (the kernel's error word). */
+int bn_astar_dwa_episode_log(bn_mppi_t *h, float *states, float *rewards, float *actions, float *sub_goals,
+                             int32_t *done_step, int32_t *status, int32_t *status_step);
+/* Forget the root cells, the statuses and the step count: a new episode, or a new A* solve. */
+int bn_astar_dwa_reset(bn_mppi_t *h);
+/* Set instance b's root cell (ix, iy), or forget it with ix < 0: starts a teacher-forced step from a given previous path. */
+int bn_astar_dwa_set_root(bn_mppi_t *h, int32_t instance, int32_t ix, int32_t iy);
+
 /* Test hook: the library's device arithmetic (DESIGN.md "Arithmetic spec") applied elementwise to n device floats:
  * fn 0 = correctly rounded sqrt, 1 / 2 = sin / cos of the spec, 3 = heading wrap (theta + pi) % 2pi - pi with
  * torch.remainder semantics (robot_model.py:90), 4 = its in-loop form, 5 = the sqrt for zero / normal finite arguments.  Lets the tests compare the kernels' building
