@@ -5,6 +5,7 @@
     from benchnav_amd import AStar         # drop-in for src/planners/global_planners/search_based/astar.py:AStar
     from benchnav_amd import BatchedPlanetaryEnv   # reset / step / collision_check of PlanetaryEnv for B environments on the GPU
     from benchnav_amd import AStarDWALoop  # test_astar_dwa.py's A* + DWA loop on the device, B rovers per launch
+    from benchnav_amd import TerrainGenerator   # DatasetGenerator's map instances (geometry + slip model), B per launch
 """
 from .native import NativeMPPI  # noqa: F401
 
@@ -25,4 +26,7 @@ def __getattr__(name):
     if name == "AStarDWALoop":
         from .astar_dwa import AStarDWALoop
         return AStarDWALoop
+    if name == "TerrainGenerator":
+        from .terrain import TerrainGenerator
+        return TerrainGenerator
     raise AttributeError(name)

@@ -130,6 +130,17 @@ SYMBOLS = {
     "bn_astar_dwa_episode_log": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bn_astar_dwa_reset": (C.c_int, [_H]),
     "bn_astar_dwa_set_root": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32]),
+    "bn_terrain_create": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(_H)]),
+    "bn_terrain_destroy": (None, [_H]),
+    "bn_terrain_set_geometry": (C.c_int, [_H, C.c_double, C.c_double, C.c_double, C.c_int32]),
+    "bn_terrain_set_draws": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64]),
+    "bn_terrain_set_slip": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int32]),
+    "bn_terrain_generate_async": (C.c_int, [_H, C.c_void_p]),
+    "bn_terrain_sync": (C.c_int, [_H]),
+    "bn_terrain_buffers": (C.c_int, [_H, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "bn_terrain_copy_out": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bn_terrain_spectrum": (C.c_int, [_H, C.c_int32, C.c_void_p]),
+    "bn_terrain_last_error": (C.c_char_p, []),
     "bn_device_math_eval": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "bn_device_rng_eval": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "bn_last_error": (C.c_char_p, []),

@@ -1,0 +1,550 @@
+// Terrain generation for B map instances of one grid size G (padded G' = G + 2): TerrainGeometry.set_terrain_geometry and
+// TerrainTraversability.set_traversability of the reference (src/environments/terrain_properties.py) on the device.
+//
+// The draws come from the host (benchnav_amd/terrain.py replays the reference's CPU generator); the kernels do the arithmetic:
+//   terrain_crater_kernel     one workgroup per instance, craters in order: carve the footprint (generate_crater :151-206),
+//                             then the min-reduction and shift (adjust_height_values) -- float32 operations in the reference's order
+//   terrain_spectrum_kernel   the final state of generate_fractal_surface's complex64 grid (:254-290), scaled (:293-295)
+//   terrain_dft_rows_kernel   T = S W, W[l, x] = exp(+2 pi i l x / G'): the row pass of the inverse DFT, float64 accumulation
+//   terrain_dft_cols_kernel   Re(W^T T) / G'^2, then the reference's float32 scaling, added to the padded heights (:296-299)
+//   terrain_minshift_kernel   heights -= min(heights), one workgroup per instance
+//   terrain_surface_kernel    crop, Horn slopes on the padded heights (generate_slopes :316-352), the per-class slip mean / std
+//                             (slip_model.py model_mean / model_stddev; set_traversability :544-579)
+// Every index is bounded by the handle's G and B; crater slices are validated on the host and clamped here again.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/benchnav_mppi.h"
+
+namespace bn {
+namespace {
+
+constexpr int kReduceThreads = 1024;
+constexpr int kTile = 16;                  // DFT output tile (kTile x kTile threads) and reduction depth per LDS stage
+constexpr int kMaxN = 1026;                // G' up to 1026 (G <= 1024): the twiddle table lives in LDS
+constexpr int kClassParams = 6;            // present, f32(sens * 1e-3), nonlinearity, offset, base noise, slope noise
+
+struct TerrainArgs {
+    float *hp;                 // (B, N, N) padded heights
+    float2 *S;                 // (B, N, N) scaled spectrum (complex64, as the reference's grid)
+    double2 *T;                // (B, N, N) row pass
+    const double2 *tw;         // (N) exp(+2 pi i m / N), host float64
+    const float *phases;       // (B, nph)
+    const int32_t *cr_count;   // (B)
+    const int32_t *cr_int;     // (B, maxc, 8): sx, sy, ex, ey, psx, psy, n, lin offset
+    const float *cr_val;       // (B, maxc, 2): f32 radius, f32 -tan(deg2rad(angle))
+    const float *lin;          // profile coordinates of every crater
+    const int32_t *classes;    // (B, G, G)
+    const float *cparams;      // (C, kClassParams)
+    float *heights, *slopes, *mean, *stddev;   // (B, G, G)
+    int G, N, B, nph, maxc, lin_len, nclass;
+    double expo;               // -(H + 1) / 2
+    double scale;              // f32(|gain| * (N res 1e3)^(H + 1.5)) as a double
+    float c_div;               // f32((res * 1e3)^2)
+    float c_milli;             // f32(1e-3)
+    double inv_8res;           // 1 / (8 res)
+};
+
+// the block's minimum of hp over one instance, then hp -= min (adjust_height_values): every thread returns after the shift
+__device__ void block_min_shift(float *h, int cells, float *red)
+{
+    float m = INFINITY;
+    for (int i = threadIdx.x; i < cells; i += blockDim.x) m = fminf(m, h[i]);
+    red[threadIdx.x] = m;
+    __syncthreads();
+    for (int s = blockDim.x / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) red[threadIdx.x] = fminf(red[threadIdx.x], red[threadIdx.x + s]);
+        __syncthreads();
+    }
+    const float mn = red[0];
+    __syncthreads();
+    for (int i = threadIdx.x; i < cells; i += blockDim.x) h[i] = h[i] - mn;
+    __syncthreads();
+}
+
+// generate_crater for every crater of instance blockIdx.x, in placement order, each followed by the min-shift.
+// profile[i][j] = (-tan) * (r - sqrt(lin[i]^2 + lin[j]^2)) where the distance is <= r, else 0 ('ij' meshgrid: row i, column j);
+// cells whose profile entry is non-zero get heights + profile (f32).
+__global__ __launch_bounds__(kReduceThreads) void terrain_crater_kernel(TerrainArgs a)
+{
+    __shared__ float red[kReduceThreads];
+    const int b = blockIdx.x;
+    const int N = a.N, cells = N * N;
+    float *h = a.hp + (size_t)b * cells;
+    const int nc = a.cr_count[b];
+    for (int c = 0; c < nc && c < a.maxc; ++c) {
+        const int32_t *ci = a.cr_int + ((size_t)b * a.maxc + c) * 8;
+        const int sx = max(ci[0], 0), sy = max(ci[1], 0), ex = min(ci[2], N), ey = min(ci[3], N);
+        const int psx = ci[4], psy = ci[5], n = ci[6], off = ci[7];
+        const float r = a.cr_val[((size_t)b * a.maxc + c) * 2], nt = a.cr_val[((size_t)b * a.maxc + c) * 2 + 1];
+        const int w = ex - sx, hgt = ey - sy;
+        if (w > 0 && hgt > 0 && off >= 0 && off + n <= a.lin_len) {
+            for (int k = threadIdx.x; k < w * hgt; k += blockDim.x) {
+                const int dy = k / w, dx = k - dy * w;
+                const int pi = psy + dy, pj = psx + dx;        // profile row / column
+                if (pi < 0 || pi >= n || pj < 0 || pj >= n) continue;
+                const float xi = a.lin[off + pi], yj = a.lin[off + pj];
+                const float d = sqrtf(__fadd_rn(__fmul_rn(xi, xi), __fmul_rn(yj, yj)));     // IEEE sqrt (bn_device_math.h sqrt_cr)
+                const float p = d <= r ? __fmul_rn(nt, __fsub_rn(r, d)) : 0.0f;
+                if (p != 0.0f) {
+                    float *cell = h + (size_t)(sy + dy) * N + (sx + dx);
+                    *cell = __fadd_rn(*cell, p);
+                }
+            }
+        }
+        __syncthreads();
+        block_min_shift(h, cells, red);
+    }
+}
+
+__global__ __launch_bounds__(kReduceThreads) void terrain_minshift_kernel(TerrainArgs a)
+{
+    __shared__ float red[kReduceThreads];
+    block_min_shift(a.hp + (size_t)blockIdx.x * a.N * a.N, a.N * a.N, red);
+}
+
+// One entry of the fBm grid in its final state.  Loop 1 (y, x <= h = N/2) writes A(y, x) = rad e^{i phi} at (y, x) and, for
+// x, y > 0, conj(A) at (N-y, N-x); the three edge / corner entries are then made real; loop 2 (1 <= y, x <= h-1) writes B(y, x)
+// at (y, N-x) and conj(B) at (N-y, x).  The write sets of loop 2 and loop 1 are disjoint and loop 1's direct and mirrored sets
+// meet only at (h, h) for even N (same iteration, mirror last, then made real), so checking the writers from the last to the
+// first gives the last writer of every cell.  Cells no loop writes stay 0 (odd N leaves some).
+__device__ double2 spectrum_entry(const TerrainArgs &a, const float *ph, int r, int c)
+{
+    const int N = a.N, hN = N / 2;
+    int y, x, idx;
+    bool conj = false, real_only = false;
+    if (r >= N - hN + 1 && r <= N - 1 && c >= 1 && c <= hN - 1) {            // loop 2, mirror
+        y = N - r; x = c; conj = true; idx = (hN + 1) * (hN + 1) + (y - 1) * (hN - 1) + (x - 1);
+    } else if (r >= 1 && r <= hN - 1 && c >= N - hN + 1 && c <= N - 1) {     // loop 2, direct
+        y = r; x = N - c; idx = (hN + 1) * (hN + 1) + (y - 1) * (hN - 1) + (x - 1);
+    } else if ((r == hN && c == 0) || (r == 0 && c == hN) || (r == hN && c == hN)) {
+        y = r; x = c; real_only = true; idx = y * (hN + 1) + x;
+    } else if (r >= N - hN && c >= N - hN && r <= N - 1 && c <= N - 1) {     // loop 1, mirror
+        y = N - r; x = N - c; conj = true; idx = y * (hN + 1) + x;
+    } else if (r <= hN && c <= hN) {                                          // loop 1, direct
+        y = r; x = c; idx = y * (hN + 1) + x;
+    } else {
+        return make_double2(0.0, 0.0);
+    }
+    if (x == 0 && y == 0) return make_double2(0.0, 0.0);                     // rad = 0 at the origin
+    if (idx < 0 || idx >= a.nph) return make_double2(0.0, 0.0);
+    const float phi = __fmul_rn(6.2831855f, ph[idx]);                          // 2 * torch.pi * rand(1), in float32
+    const double rad = pow((double)(x * x + y * y), a.expo) * a.scale;
+    double s, co;
+    sincos((double)phi, &s, &co);
+    const double im = real_only ? 0.0 : (conj ? -s : s);
+    return make_double2(rad * co, rad * im);
+}
+
+__global__ void terrain_spectrum_kernel(TerrainArgs a)
+{
+    const size_t cells = (size_t)a.N * a.N;
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= cells * a.B) return;
+    const int b = (int)(i / cells);
+    const int rem = (int)(i - (size_t)b * cells);
+    const int r = rem / a.N, c = rem - r * a.N;
+    const double2 v = spectrum_entry(a, a.phases + (size_t)b * a.nph, r, c);
+    a.S[i] = make_float2((float)v.x, (float)v.y);
+}
+
+// T[b, k, x] = sum_l S[b, k, l] tw[(l x) mod N]; block (kTile, kTile) = (x, k), grid (x tiles, k tiles, B)
+__global__ __launch_bounds__(kTile * kTile) void terrain_dft_rows_kernel(TerrainArgs a)
+{
+    __shared__ double2 tw[kMaxN];
+    __shared__ double2 st[kTile][kTile + 1];
+    const int N = a.N, b = blockIdx.z;
+    const int tx = threadIdx.x, ty = threadIdx.y, tid = ty * kTile + tx;
+    for (int m = tid; m < N; m += kTile * kTile) tw[m] = a.tw[m];
+    const int x = blockIdx.x * kTile + tx, k = blockIdx.y * kTile + ty;
+    const float2 *S = a.S + (size_t)b * N * N;
+    double re = 0.0, im = 0.0;
+    int idx = 0;                                                 // (l x) mod N, advanced by x per l
+    const int xs = x < N ? x : 0;
+    for (int l0 = 0; l0 < N; l0 += kTile) {
+        __syncthreads();
+        {
+            const int kk = blockIdx.y * kTile + ty, ll = l0 + tx;
+            float2 v = make_float2(0.0f, 0.0f);
+            if (kk < N && ll < N) v = S[(size_t)kk * N + ll];
+            st[ty][tx] = make_double2(v.x, v.y);
+        }
+        __syncthreads();
+        const int lmax = min(kTile, N - l0);
+        for (int j = 0; j < lmax; ++j) {
+            const double2 s = st[ty][j];
+            const double2 w = tw[idx];
+            re = fma(s.x, w.x, re); re = fma(-s.y, w.y, re);
+            im = fma(s.x, w.y, im); im = fma(s.y, w.x, im);
+            idx += xs;
+            if (idx >= N) idx -= N;
+        }
+    }
+    if (x < N && k < N) a.T[((size_t)b * N + k) * N + x] = make_double2(re, im);
+}
+
+// out[b, y, x] = Re sum_k tw[(k y) mod N] T[b, k, x] / N^2 -> float32, then / f32((res 1e3)^2), * f32(1e-3), added to hp
+__global__ __launch_bounds__(kTile * kTile) void terrain_dft_cols_kernel(TerrainArgs a)
+{
+    __shared__ double2 tw[kMaxN];
+    __shared__ double2 tt[kTile][kTile + 1];
+    const int N = a.N, b = blockIdx.z;
+    const int tx = threadIdx.x, ty = threadIdx.y, tid = ty * kTile + tx;
+    for (int m = tid; m < N; m += kTile * kTile) tw[m] = a.tw[m];
+    const int x = blockIdx.x * kTile + tx, y = blockIdx.y * kTile + ty;
+    const double2 *T = a.T + (size_t)b * N * N;
+    double re = 0.0;
+    int idx = 0;
+    const int ys = y < N ? y : 0;
+    for (int k0 = 0; k0 < N; k0 += kTile) {
+        __syncthreads();
+        {
+            const int kk = k0 + ty, xx = blockIdx.x * kTile + tx;
+            tt[ty][tx] = (kk < N && xx < N) ? T[(size_t)kk * N + xx] : make_double2(0.0, 0.0);
+        }
+        __syncthreads();
+        const int kmax = min(kTile, N - k0);
+        for (int j = 0; j < kmax; ++j) {
+            const double2 t = tt[j][tx];
+            const double2 w = tw[idx];
+            re = fma(t.x, w.x, re); re = fma(-t.y, w.y, re);
+            idx += ys;
+            if (idx >= N) idx -= N;
+        }
+    }
+    if (x < N && y < N) {
+        float s = (float)(re / ((double)N * (double)N));
+        s = __fdiv_rn(s, a.c_div);
+        s = __fmul_rn(s, a.c_milli);
+        float *cell = a.hp + ((size_t)b * N + y) * N + x;
+        *cell = __fadd_rn(*cell, s);
+    }
+}
+
+// crop + Horn slopes + latent slip model for every output cell
+__global__ void terrain_surface_kernel(TerrainArgs a)
+{
+    const int G = a.G, N = a.N;
+    const size_t cells = (size_t)G * G;
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= cells * a.B) return;
+    const int b = (int)(i / cells);
+    const int rem = (int)(i - (size_t)b * cells);
+    const int r = rem / G, c = rem - r * G;
+    const float *h = a.hp + (size_t)b * N * N + (size_t)(r + 1) * N + (c + 1);   // padded (r+1, c+1); neighbours are inside
+    const double h00 = h[-N - 1], h01 = h[-N], h02 = h[-N + 1];
+    const double h10 = h[-1], h12 = h[1];
+    const double h20 = h[N - 1], h21 = h[N], h22 = h[N + 1];
+    // Sobel cross-correlation (conv2d): x = [-1 0 1; -2 0 2; -1 0 1], y = [-1 -2 -1; 0 0 0; 1 2 1]
+    const double gx = ((h02 - h00) + 2.0 * (h12 - h10) + (h22 - h20)) * a.inv_8res;
+    const double gy = ((h20 - h00) + 2.0 * (h21 - h01) + (h22 - h02)) * a.inv_8res;
+    const float phi = (float)(atan(sqrt(gx * gx + gy * gy)) * (180.0 / M_PI));
+    a.heights[i] = h[0];
+    a.slopes[i] = phi;
+    const int cls = a.classes[i];
+    float m = INFINITY, sd = INFINITY;                            // set_traversability starts from inf
+    if (cls >= 0 && cls < a.nclass) {
+        const float *p = a.cparams + (size_t)cls * kClassParams;
+        if (p[0] != 0.0f) {
+            const float aphi = fabsf(phi);
+            const float base = __fmul_rn(p[1], powf(aphi, p[2]));
+            const float s = phi >= 0.0f ? __fadd_rn(base, p[3]) : __fadd_rn(-base, p[3]);
+            m = fminf(fmaxf(s, 0.0f), 1.0f);
+            sd = __fadd_rn(p[4], __fmul_rn(p[5], aphi));
+        }
+    }
+    a.mean[i] = m;
+    a.stddev[i] = sd;
+}
+
+// the test hook's copy of one instance's spectrum
+__global__ void terrain_spectrum_one_kernel(TerrainArgs a, int inst, float2 *out)
+{
+    const int cells = a.N * a.N;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= cells) return;
+    const int r = i / a.N, c = i - r * a.N;
+    const double2 v = spectrum_entry(a, a.phases + (size_t)inst * a.nph, r, c);
+    out[i] = make_float2((float)v.x, (float)v.y);
+}
+
+thread_local std::string g_terrain_error;
+
+}  // namespace
+}  // namespace bn
+
+struct bn_terrain {
+    int device = 0, G = 0, N = 0, B = 0, nph = 0;
+    double resolution = 0.5, roughness = 0.75, gain = 10.0;
+    bool fractal = true, have_geometry = false, have_draws = false, have_slip = false, generated = false;
+    float *hp = nullptr, *heights = nullptr, *slopes = nullptr, *mean = nullptr, *stddev = nullptr, *phases = nullptr;
+    float2 *S = nullptr;
+    double2 *T = nullptr, *tw = nullptr;
+    int32_t *classes = nullptr, *cr_count = nullptr, *cr_int = nullptr;
+    float *cr_val = nullptr, *lin = nullptr, *cparams = nullptr;
+    int maxc = 0, lin_len = 0, nclass = 0;
+    hipEvent_t ev_done = nullptr;
+};
+
+namespace {
+
+int terrain_fail(int code, const std::string &msg)
+{
+    bn::g_terrain_error = msg;
+    return code;
+}
+
+struct TerrainDeviceGuard {
+    int prev = -1; bool changed = false, ok = true;
+    explicit TerrainDeviceGuard(int want) { if (hipGetDevice(&prev) != hipSuccess) { ok = false; return; }
+                                            if (prev != want) { ok = hipSetDevice(want) == hipSuccess; changed = ok; } }
+    ~TerrainDeviceGuard() { if (changed) (void)hipSetDevice(prev); }
+};
+
+#define TERRAIN_HIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return terrain_fail(BN_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); } while (0)
+
+template <typename P>
+int realloc_dev(P **p, size_t bytes)
+{
+    if (*p) { (void)hipFree(*p); *p = nullptr; }
+    TERRAIN_HIP(hipMalloc((void **)p, bytes ? bytes : 4));
+    return BN_OK;
+}
+
+int wait_done(bn_terrain_t *h)
+{
+    if (h->generated) TERRAIN_HIP(hipEventSynchronize(h->ev_done));
+    return BN_OK;
+}
+
+bn::TerrainArgs make_args(bn_terrain_t *h)
+{
+    const double res = h->resolution, H = h->roughness;
+    bn::TerrainArgs a{};
+    a.hp = h->hp; a.S = h->S; a.T = h->T; a.tw = h->tw; a.phases = h->phases;
+    a.cr_count = h->cr_count; a.cr_int = h->cr_int; a.cr_val = h->cr_val; a.lin = h->lin;
+    a.classes = h->classes; a.cparams = h->cparams;
+    a.heights = h->heights; a.slopes = h->slopes; a.mean = h->mean; a.stddev = h->stddev;
+    a.G = h->G; a.N = h->N; a.B = h->B; a.nph = h->nph; a.maxc = h->maxc; a.lin_len = h->lin_len; a.nclass = h->nclass;
+    a.expo = -((H + 1.0) / 2.0);
+    a.scale = (double)(float)(std::fabs(h->gain) * std::pow(h->N * res * 1e3, H + 1.0 + 0.5));
+    a.c_div = (float)std::pow(res * 1e3, 2.0);
+    a.c_milli = (float)1e-3;
+    a.inv_8res = 1.0 / (8.0 * res);
+    return a;
+}
+
+}  // namespace
+
+extern "C" {
+
+const char *bn_terrain_last_error(void) { return bn::g_terrain_error.c_str(); }
+
+int bn_terrain_create(int32_t device_id, int32_t G, int32_t B, bn_terrain_t **out)
+{
+    if (!out) return terrain_fail(BN_ERR_INVALID, "null handle pointer");
+    *out = nullptr;
+    if (G < 2 || G + 2 > bn::kMaxN || B < 1 || (int64_t)(G + 2) * (G + 2) * B > ((int64_t)1 << 31))
+        return terrain_fail(BN_ERR_INVALID, "G must be in [2, 1024], B >= 1, and B (G+2)^2 must fit 2^31 cells");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return terrain_fail(BN_ERR_NO_DEVICE, "no HIP device visible: no CPU fallback");
+    if (device_id < 0 || device_id >= ndev) return terrain_fail(BN_ERR_INVALID, "device_id out of range");
+    TerrainDeviceGuard guard(device_id);
+    if (!guard.ok) return terrain_fail(BN_ERR_HIP, "hipSetDevice failed");
+    auto *h = new bn_terrain_t();
+    h->device = device_id; h->G = G; h->N = G + 2; h->B = B;
+    const int hN = h->N / 2;
+    h->nph = (hN + 1) * (hN + 1) + (hN - 1) * (hN - 1);
+    const size_t pc = (size_t)h->N * h->N * B, oc = (size_t)G * G * B;
+    std::vector<double2> tw(h->N);
+    for (int m = 0; m < h->N; ++m) {
+        const double t = 2.0 * M_PI * (double)m / (double)h->N;
+        tw[m] = make_double2(std::cos(t), std::sin(t));
+    }
+    int rc = BN_OK;
+    if ((rc = realloc_dev(&h->hp, pc * 4)) || (rc = realloc_dev(&h->S, pc * 8)) || (rc = realloc_dev(&h->T, pc * 16)) ||
+        (rc = realloc_dev(&h->tw, (size_t)h->N * 16)) || (rc = realloc_dev(&h->heights, oc * 4)) ||
+        (rc = realloc_dev(&h->slopes, oc * 4)) || (rc = realloc_dev(&h->mean, oc * 4)) || (rc = realloc_dev(&h->stddev, oc * 4)) ||
+        (rc = realloc_dev(&h->classes, oc * 4)) || (rc = realloc_dev(&h->phases, (size_t)h->nph * B * 4)) ||
+        (rc = realloc_dev(&h->cr_count, (size_t)B * 4))) {
+        std::string keep = bn::g_terrain_error;
+        bn_terrain_destroy(h);
+        bn::g_terrain_error = keep;
+        return rc;
+    }
+    if (hipMemcpy(h->tw, tw.data(), (size_t)h->N * 16, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemset(h->cr_count, 0, (size_t)B * 4) != hipSuccess || hipEventCreate(&h->ev_done) != hipSuccess) {
+        bn_terrain_destroy(h);
+        return terrain_fail(BN_ERR_HIP, "terrain handle initialisation failed");
+    }
+    *out = h;
+    return BN_OK;
+}
+
+void bn_terrain_destroy(bn_terrain_t *h)
+{
+    if (!h) return;
+    TerrainDeviceGuard guard(h->device);
+    if (h->generated && h->ev_done) (void)hipEventSynchronize(h->ev_done);
+    for (void *p : {(void *)h->hp, (void *)h->S, (void *)h->T, (void *)h->tw, (void *)h->heights, (void *)h->slopes, (void *)h->mean,
+                    (void *)h->stddev, (void *)h->classes, (void *)h->phases, (void *)h->cr_count, (void *)h->cr_int,
+                    (void *)h->cr_val, (void *)h->lin, (void *)h->cparams})
+        if (p) (void)hipFree(p);
+    if (h->ev_done) (void)hipEventDestroy(h->ev_done);
+    delete h;
+}
+
+/* set_terrain_geometry's parameters: the map resolution, TerrainGeometry's roughness exponent and amplitude gain, is_fractal. */
+int bn_terrain_set_geometry(bn_terrain_t *h, double resolution, double roughness_exponent, double amplitude_gain, int32_t is_fractal)
+{
+    if (!h) return terrain_fail(BN_ERR_INVALID, "null handle");
+    if (!(resolution > 0.0) || !std::isfinite(resolution) || !std::isfinite(roughness_exponent) || !std::isfinite(amplitude_gain))
+        return terrain_fail(BN_ERR_INVALID, "resolution must be finite and > 0; exponent and gain finite");
+    h->resolution = resolution; h->roughness = roughness_exponent; h->gain = amplitude_gain; h->fractal = is_fractal != 0;
+    h->have_geometry = true;
+    return BN_OK;
+}
+
+int bn_terrain_set_draws(bn_terrain_t *h, const float *phases, const int32_t *crater_count, const int32_t *crater_int,
+                         const float *crater_val, int32_t max_craters, const float *lin, int64_t lin_len)
+{
+    if (!h || !phases || !crater_count || !crater_int || !crater_val || !lin) return terrain_fail(BN_ERR_INVALID, "null argument");
+    if (max_craters < 1 || lin_len < 1 || lin_len > ((int64_t)1 << 30)) return terrain_fail(BN_ERR_INVALID, "max_craters and lin_len must be >= 1");
+    const int N = h->N;
+    for (int b = 0; b < h->B; ++b) {
+        if (crater_count[b] < 0 || crater_count[b] > max_craters) return terrain_fail(BN_ERR_INVALID, "crater count out of range");
+        for (int c = 0; c < crater_count[b]; ++c) {
+            const int32_t *ci = crater_int + ((size_t)b * max_craters + c) * 8;
+            const int sx = ci[0], sy = ci[1], ex = ci[2], ey = ci[3], psx = ci[4], psy = ci[5], n = ci[6], off = ci[7];
+            if (sx < 0 || sy < 0 || ex > N || ey > N || ex < sx || ey < sy || psx < 0 || psy < 0 || n < 1 ||
+                psx + (ex - sx) > n || psy + (ey - sy) > n || off < 0 || (int64_t)off + n > lin_len)
+                return terrain_fail(BN_ERR_INVALID, "crater " + std::to_string(c) + " of instance " + std::to_string(b) + " is out of range");
+        }
+    }
+    TerrainDeviceGuard guard(h->device);
+    if (!guard.ok) return terrain_fail(BN_ERR_HIP, "hipSetDevice failed");
+    int rc = wait_done(h);
+    if (rc) return rc;
+    if (max_craters != h->maxc) {
+        if ((rc = realloc_dev(&h->cr_int, (size_t)h->B * max_craters * 32)) || (rc = realloc_dev(&h->cr_val, (size_t)h->B * max_craters * 8)))
+            return rc;
+        h->maxc = max_craters;
+    }
+    if (lin_len > h->lin_len) {
+        if ((rc = realloc_dev(&h->lin, (size_t)lin_len * 4))) return rc;
+    }
+    h->lin_len = (int)lin_len;
+    TERRAIN_HIP(hipMemcpy(h->phases, phases, (size_t)h->nph * h->B * 4, hipMemcpyHostToDevice));
+    TERRAIN_HIP(hipMemcpy(h->cr_count, crater_count, (size_t)h->B * 4, hipMemcpyHostToDevice));
+    TERRAIN_HIP(hipMemcpy(h->cr_int, crater_int, (size_t)h->B * max_craters * 32, hipMemcpyHostToDevice));
+    TERRAIN_HIP(hipMemcpy(h->cr_val, crater_val, (size_t)h->B * max_craters * 8, hipMemcpyHostToDevice));
+    TERRAIN_HIP(hipMemcpy(h->lin, lin, (size_t)lin_len * 4, hipMemcpyHostToDevice));
+    h->have_draws = true;
+    return BN_OK;
+}
+
+int bn_terrain_set_slip(bn_terrain_t *h, const int32_t *t_classes, const float *class_params, int32_t num_classes)
+{
+    if (!h || !t_classes || (num_classes > 0 && !class_params)) return terrain_fail(BN_ERR_INVALID, "null argument");
+    if (num_classes < 0 || num_classes > (1 << 20)) return terrain_fail(BN_ERR_INVALID, "num_classes out of range");
+    TerrainDeviceGuard guard(h->device);
+    if (!guard.ok) return terrain_fail(BN_ERR_HIP, "hipSetDevice failed");
+    int rc = wait_done(h);
+    if (rc) return rc;
+    if (num_classes != h->nclass || !h->cparams) {
+        if ((rc = realloc_dev(&h->cparams, (size_t)(num_classes > 0 ? num_classes : 1) * bn::kClassParams * 4))) return rc;
+        h->nclass = num_classes;
+    }
+    TERRAIN_HIP(hipMemcpy(h->classes, t_classes, (size_t)h->G * h->G * h->B * 4, hipMemcpyHostToDevice));
+    if (num_classes > 0)
+        TERRAIN_HIP(hipMemcpy(h->cparams, class_params, (size_t)num_classes * bn::kClassParams * 4, hipMemcpyHostToDevice));
+    h->have_slip = true;
+    return BN_OK;
+}
+
+int bn_terrain_generate_async(bn_terrain_t *h, void *stream)
+{
+    if (!h) return terrain_fail(BN_ERR_INVALID, "null handle");
+    if (!h->have_geometry || !h->have_draws || !h->have_slip) return terrain_fail(BN_ERR_STATE, "geometry, draws and slip models must be set first");
+    TerrainDeviceGuard guard(h->device);
+    if (!guard.ok) return terrain_fail(BN_ERR_HIP, "hipSetDevice failed");
+    hipStream_t s = (hipStream_t)stream;
+    const bn::TerrainArgs a = make_args(h);
+    const size_t pc = (size_t)h->N * h->N * h->B, oc = (size_t)h->G * h->G * h->B;
+    TERRAIN_HIP(hipMemsetAsync(h->hp, 0, pc * 4, s));
+    bn::terrain_crater_kernel<<<h->B, bn::kReduceThreads, 0, s>>>(a);
+    TERRAIN_HIP(hipGetLastError());
+    if (h->fractal) {
+        bn::terrain_spectrum_kernel<<<(unsigned)((pc + 255) / 256), 256, 0, s>>>(a);
+        TERRAIN_HIP(hipGetLastError());
+        const dim3 blk(bn::kTile, bn::kTile), grd((h->N + bn::kTile - 1) / bn::kTile, (h->N + bn::kTile - 1) / bn::kTile, h->B);
+        bn::terrain_dft_rows_kernel<<<grd, blk, 0, s>>>(a);
+        TERRAIN_HIP(hipGetLastError());
+        bn::terrain_dft_cols_kernel<<<grd, blk, 0, s>>>(a);
+        TERRAIN_HIP(hipGetLastError());
+        bn::terrain_minshift_kernel<<<h->B, bn::kReduceThreads, 0, s>>>(a);
+        TERRAIN_HIP(hipGetLastError());
+    }
+    bn::terrain_surface_kernel<<<(unsigned)((oc + 255) / 256), 256, 0, s>>>(a);
+    TERRAIN_HIP(hipGetLastError());
+    TERRAIN_HIP(hipEventRecord(h->ev_done, s));
+    h->generated = true;
+    return BN_OK;
+}
+
+int bn_terrain_sync(bn_terrain_t *h)
+{
+    if (!h) return terrain_fail(BN_ERR_INVALID, "null handle");
+    TerrainDeviceGuard guard(h->device);
+    return wait_done(h);
+}
+
+int bn_terrain_buffers(bn_terrain_t *h, void **heights, void **slopes, void **mean, void **stddev)
+{
+    if (!h || !heights || !slopes || !mean || !stddev) return terrain_fail(BN_ERR_INVALID, "null argument");
+    *heights = h->heights; *slopes = h->slopes; *mean = h->mean; *stddev = h->stddev;
+    return BN_OK;
+}
+
+int bn_terrain_copy_out(bn_terrain_t *h, float *heights, float *slopes, float *mean, float *stddev)
+{
+    if (!h) return terrain_fail(BN_ERR_INVALID, "null handle");
+    if (!h->generated) return terrain_fail(BN_ERR_STATE, "nothing generated yet");
+    TerrainDeviceGuard guard(h->device);
+    if (!guard.ok) return terrain_fail(BN_ERR_HIP, "hipSetDevice failed");
+    int rc = wait_done(h);
+    if (rc) return rc;
+    const size_t bytes = (size_t)h->G * h->G * h->B * 4;
+    if (heights) TERRAIN_HIP(hipMemcpy(heights, h->heights, bytes, hipMemcpyDeviceToHost));
+    if (slopes) TERRAIN_HIP(hipMemcpy(slopes, h->slopes, bytes, hipMemcpyDeviceToHost));
+    if (mean) TERRAIN_HIP(hipMemcpy(mean, h->mean, bytes, hipMemcpyDeviceToHost));
+    if (stddev) TERRAIN_HIP(hipMemcpy(stddev, h->stddev, bytes, hipMemcpyDeviceToHost));
+    return BN_OK;
+}
+
+int bn_terrain_spectrum(bn_terrain_t *h, int32_t inst, float *out)
+{
+    if (!h || !out) return terrain_fail(BN_ERR_INVALID, "null argument");
+    if (inst < 0 || inst >= h->B) return terrain_fail(BN_ERR_INVALID, "instance out of range");
+    if (!h->have_geometry || !h->have_draws) return terrain_fail(BN_ERR_STATE, "geometry and draws must be set first");
+    TerrainDeviceGuard guard(h->device);
+    if (!guard.ok) return terrain_fail(BN_ERR_HIP, "hipSetDevice failed");
+    int rc = wait_done(h);
+    if (rc) return rc;
+    const int cells = h->N * h->N;
+    float2 *d = nullptr;
+    TERRAIN_HIP(hipMalloc((void **)&d, (size_t)cells * 8));
+    bn::terrain_spectrum_one_kernel<<<(cells + 255) / 256, 256>>>(make_args(h), inst, d);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpy(out, d, (size_t)cells * 8, hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    if (e != hipSuccess) return terrain_fail(BN_ERR_HIP, std::string("spectrum hook: ") + hipGetErrorString(e));
+    return BN_OK;
+}
+
+}  // extern "C"

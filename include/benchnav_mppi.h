@@ -575,6 +575,39 @@ int bn_astar_dwa_reset(bn_mppi_t *h);
 /* Set instance b's root cell (ix, iy), or forget it with ix < 0: starts a teacher-forced step from a given previous path. */
 int bn_astar_dwa_set_root(bn_mppi_t *h, int32_t instance, int32_t ix, int32_t iy);
 
+/*
+ * Terrain generation (csrc/terrain_kernels.hip): TerrainGeometry.set_terrain_geometry (craters, fBm, Horn slopes) and
+ * TerrainTraversability.set_traversability (src/environments/terrain_properties.py) for B instances of one grid size G per
+ * launch.  The random draws are made on the host in the reference's order (benchnav_amd/terrain.py) and set here; the device
+ * does the arithmetic.  Outputs are (B, G, G) float32: heights, slopes (degrees), latent slip mean and stddev.  G <= 1024.
+ * Host arguments are copied synchronously.  Errors: bn_terrain_last_error().
+ */
+typedef struct bn_terrain bn_terrain_t;
+int bn_terrain_create(int32_t device_id, int32_t G, int32_t B, bn_terrain_t **out);
+void bn_terrain_destroy(bn_terrain_t *h);
+/* The grid map's resolution, TerrainGeometry's roughness_exponent and amplitude_gain, and is_fractal. */
+int bn_terrain_set_geometry(bn_terrain_t *h, double resolution, double roughness_exponent, double amplitude_gain, int32_t is_fractal);
+/* The draws of every instance: phases (B, nph) float32 uniforms of the fBm spectrum, nph = (G'/2 + 1)^2 + (G'/2 - 1)^2 with
+ * G' = G + 2; crater_count (B); per crater, in placement order, crater_int (B, max_craters, 8) = sx, sy, ex, ey (the padded-grid
+ * slice [sy:ey, sx:ex]), psx, psy (the profile's offset in the slice), n (profile points per axis), lin offset, and crater_val
+ * (B, max_craters, 2) = float32 radius and -tan(deg2rad(angle)); lin (lin_len) holds each crater's linspace(-r, r, n). */
+int bn_terrain_set_draws(bn_terrain_t *h, const float *phases, const int32_t *crater_count, const int32_t *crater_int,
+                         const float *crater_val, int32_t max_craters, const float *lin, int64_t lin_len);
+/* Class maps t_classes (B, G, G) and per-class rows of 6 float32: present (0: the class has no model, its cells stay inf),
+ * f32(slip_sensitivity * 1e-3), slip_nonlinearity, slip_offset, base_noise_scale, slope_noise_scale. */
+int bn_terrain_set_slip(bn_terrain_t *h, const int32_t *t_classes, const float *class_params, int32_t num_classes);
+/* Enqueues the whole generation on `stream`. */
+int bn_terrain_generate_async(bn_terrain_t *h, void *stream);
+/* Waits for the last generation. */
+int bn_terrain_sync(bn_terrain_t *h);
+/* Device pointers of the outputs, (B, G, G) float32 each; valid after the generation on its stream. */
+int bn_terrain_buffers(bn_terrain_t *h, void **heights, void **slopes, void **mean, void **stddev);
+/* Waits and copies the outputs to host memory (any pointer may be NULL). */
+int bn_terrain_copy_out(bn_terrain_t *h, float *heights, float *slopes, float *mean, float *stddev);
+/* Test hook: instance inst's scaled fBm spectrum (G', G') complex64 as interleaved float32 pairs. */
+int bn_terrain_spectrum(bn_terrain_t *h, int32_t inst, float *out);
+const char *bn_terrain_last_error(void);
+
 /* Test hook: the library's device arithmetic (DESIGN.md "Arithmetic spec") applied elementwise to n device floats:
  * fn 0 = correctly rounded sqrt, 1 / 2 = sin / cos of the spec, 3 = heading wrap (theta + pi) % 2pi - pi with
  * torch.remainder semantics (robot_model.py:90), 4 = its in-loop form, 5 = the sqrt for zero / normal finite arguments.  Lets the tests compare the kernels' building
