@@ -32,7 +32,7 @@ BN_FLAG_UNORDERED_OUTPUTS = 16384
 BN_BUF_STATES_ALT, BN_BUF_CONTROLS_ALT = 10, 11
 BN_RISK_EXPECTED, BN_RISK_VAR, BN_RISK_CVAR = 0, 1, 2
 BN_AD_OK, BN_AD_OUT_OF_BOUNDS, BN_AD_GOAL_COLLISION, BN_AD_FIELD_ERROR = 0, 1, 2, 3   # bn_astar_dwa_status
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 
 class Config(C.Structure):
@@ -140,6 +140,11 @@ SYMBOLS = {
     "bn_terrain_buffers": (C.c_int, [_H, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "bn_terrain_copy_out": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bn_terrain_spectrum": (C.c_int, [_H, C.c_int32, C.c_void_p]),
+    "bn_terrain_set_coloring": (C.c_int, [_H, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_float,
+                                          C.c_void_p, C.c_void_p, C.c_int32]),
+    "bn_terrain_colorize": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_float, C.c_void_p]),
+    "bn_terrain_color_buffers": (C.c_int, [_H, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "bn_terrain_class_counts": (C.c_int, [_H, C.c_void_p, C.c_void_p]),
     "bn_terrain_last_error": (C.c_char_p, []),
     "bn_device_math_eval": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "bn_device_rng_eval": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),

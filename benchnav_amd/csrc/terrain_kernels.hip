@@ -10,6 +10,11 @@
 //   terrain_minshift_kernel   heights -= min(heights), one workgroup per instance
 //   terrain_surface_kernel    crop, Horn slopes on the padded heights (generate_slopes :316-352), the per-class slip mean / std
 //                             (slip_model.py model_mean / model_stddev; set_traversability :544-579)
+// and, when colouring is set (TerrainColoring.set_terrain_class_coloring :364-523):
+//   terrain_noise_kernel      the library's own seeded gradient noise (skipped when the caller uploads a field)
+//   terrain_classes_kernel    ahead of the surface kernel: per-instance min / max, the normalised field against the occupancy
+//                             thresholds -> the class map (generate_multi_terrain :421-443), and the two per-instance counters
+//   terrain_color_kernel      after it: surface normals of the cropped heights, the light's shade on the class's colour
 // Every index is bounded by the handle's G and B; crater slices are validated on the host and clamped here again.
 #include <hip/hip_runtime.h>
 
@@ -20,6 +25,7 @@
 #include <vector>
 
 #include "../../include/benchnav_mppi.h"
+#include "bn_device_math.h"
 
 namespace bn {
 namespace {
@@ -273,6 +279,151 @@ __global__ void terrain_spectrum_one_kernel(TerrainArgs a, int inst, float2 *out
     out[i] = make_float2((float)v.x, (float)v.y);
 }
 
+// ---- terrain classes and shaded colours (TerrainColoring.set_terrain_class_coloring, terrain_properties.py:364-523) ----
+struct ColorArgs {
+    float *noise;              // (B, G, G) raw noise field: uploaded, or written by terrain_noise_kernel
+    int32_t *classes;          // (B, G, G): written by terrain_classes_kernel, read by terrain_color_kernel
+    const float *heights;      // (B, G, G) cropped heights
+    float *colors;             // (B, 3, G, G)
+    const float *thr;          // (B, C) float32 cumsum(occupancy) * 100, from the host's torch
+    const int32_t *start;      // (B) first class with occupancy > 0
+    const float *table;        // (C, 3) colour table
+    const float *light;        // (B, 3) light vectors
+    const uint64_t *seeds;     // (B) keys of the library's own noise
+    int32_t *counts;           // (B, 2): cells with class -1, cells with class >= nmodels
+    int G, B, C, nmodels;
+    float feature, ambient;
+};
+
+// The library's own 2-D gradient noise: float32, every operation rounded on its own (no FMA anywhere), in this
+// order.  u = f32(x) / f, v = f32(y) / f (IEEE division); i = floor(u), j = floor(v); p = u - i, q = v - j.  The gradient of
+// lattice point (a, b) is row (w & 7) of kGrad, w the first word of Philox4x32-10 on the counter (a, b, 'TNOI', 0) under the
+// key (lo(seed), hi(seed)).  d00 = gx p + gy q and likewise d10 (p - 1, q), d01 (p, q - 1), d11 (p - 1, q - 1) from the
+// gradients of (i, j), (i+1, j), (i, j+1), (i+1, j+1); fade(t) = ((t t) t) ((t (t 6 - 15)) + 10);
+// n = l0 + fade(q) (l1 - l0), l0 = d00 + fade(p) (d10 - d00), l1 = d01 + fade(p) (d11 - d01).  Zero at lattice points.
+constexpr uint32_t kNoiseWord = 0x544E4F49u;                                  // 'TNOI'
+constexpr float kDiag = 0.70710677f;
+__constant__ float kGrad[8][2] = {{1.0f, 0.0f}, {-1.0f, 0.0f}, {0.0f, 1.0f}, {0.0f, -1.0f},
+                                  {kDiag, kDiag}, {-kDiag, kDiag}, {kDiag, -kDiag}, {-kDiag, -kDiag}};
+
+__device__ __forceinline__ float noise_fade(float t)
+{
+    const float a = __fsub_rn(__fmul_rn(t, 6.0f), 15.0f);
+    const float b = __fadd_rn(__fmul_rn(t, a), 10.0f);
+    return __fmul_rn(__fmul_rn(__fmul_rn(t, t), t), b);
+}
+
+__device__ __forceinline__ float noise_corner(uint64_t seed, int a, int b, float p, float q)
+{
+    const u32x4 w = philox4x32_10(u32x4{(uint32_t)a, (uint32_t)b, kNoiseWord, 0u}, (uint32_t)seed, (uint32_t)(seed >> 32));
+    const int g = (int)(w.x & 7u);
+    return __fadd_rn(__fmul_rn(kGrad[g][0], p), __fmul_rn(kGrad[g][1], q));
+}
+
+__global__ void terrain_noise_kernel(ColorArgs a)
+{
+    const size_t cells = (size_t)a.G * a.G;
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= cells * a.B) return;
+    const int b = (int)(i / cells);
+    const int rem = (int)(i - (size_t)b * cells);
+    const int y = rem / a.G, x = rem - y * a.G;
+    const uint64_t seed = a.seeds[b];
+    const float u = __fdiv_rn((float)x, a.feature), v = __fdiv_rn((float)y, a.feature);
+    const float fi = floorf(u), fj = floorf(v);
+    const int ci = (int)fi, cj = (int)fj;
+    const float p = __fsub_rn(u, fi), q = __fsub_rn(v, fj);
+    const float p1 = __fsub_rn(p, 1.0f), q1 = __fsub_rn(q, 1.0f);
+    const float d00 = noise_corner(seed, ci, cj, p, q), d10 = noise_corner(seed, ci + 1, cj, p1, q);
+    const float d01 = noise_corner(seed, ci, cj + 1, p, q1), d11 = noise_corner(seed, ci + 1, cj + 1, p1, q1);
+    const float wp = noise_fade(p), wq = noise_fade(q);
+    const float l0 = __fadd_rn(d00, __fmul_rn(wp, __fsub_rn(d10, d00)));
+    const float l1 = __fadd_rn(d01, __fmul_rn(wp, __fsub_rn(d11, d01)));
+    a.noise[i] = __fadd_rn(l0, __fmul_rn(wq, __fsub_rn(l1, l0)));
+}
+
+// generate_multi_terrain :421-443 for instance blockIdx.x: the field's min and max, nd = (n - min) / (max - min) * 100 in that
+// order, class = the smallest i >= start with nd <= thr[i], else -1 (every comparison is false on the NaN field of max == min).
+// With thr non-decreasing (a cumsum of non-negative ratios) that is the reference's chain of masks.
+constexpr int kMaxColorClasses = 64;
+
+__global__ __launch_bounds__(kReduceThreads) void terrain_classes_kernel(ColorArgs a)
+{
+    __shared__ float rmin[kReduceThreads], rmax[kReduceThreads];
+    __shared__ float thr[kMaxColorClasses];
+    __shared__ int cnt[2];
+    const int b = blockIdx.x, cells = a.G * a.G, C = min(a.C, kMaxColorClasses);
+    const float *n = a.noise + (size_t)b * cells;
+    int32_t *cls = a.classes + (size_t)b * cells;
+    if ((int)threadIdx.x < C) thr[threadIdx.x] = a.thr[(size_t)b * a.C + threadIdx.x];
+    if (threadIdx.x < 2) cnt[threadIdx.x] = 0;
+    float mn = INFINITY, mx = -INFINITY;
+    for (int i = threadIdx.x; i < cells; i += blockDim.x) { const float v = n[i]; mn = fminf(mn, v); mx = fmaxf(mx, v); }
+    rmin[threadIdx.x] = mn; rmax[threadIdx.x] = mx;
+    __syncthreads();
+    for (int s = blockDim.x / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) {
+            rmin[threadIdx.x] = fminf(rmin[threadIdx.x], rmin[threadIdx.x + s]);
+            rmax[threadIdx.x] = fmaxf(rmax[threadIdx.x], rmax[threadIdx.x + s]);
+        }
+        __syncthreads();
+    }
+    mn = rmin[0]; mx = rmax[0];
+    const float range = __fsub_rn(mx, mn);
+    const int start = min(max(a.start[b], 0), C);
+    int unassigned = 0, beyond = 0;
+    for (int i = threadIdx.x; i < cells; i += blockDim.x) {
+        const float nd = __fmul_rn(__fdiv_rn(__fsub_rn(n[i], mn), range), 100.0f);
+        int c = -1;
+        for (int k = start; k < C; ++k)
+            if (nd <= thr[k]) { c = k; break; }
+        cls[i] = c;
+        unassigned += c < 0;
+        beyond += c >= a.nmodels;
+    }
+    if (unassigned) atomicAdd(&cnt[0], unassigned);
+    if (beyond) atomicAdd(&cnt[1], beyond);
+    __syncthreads();
+    if (threadIdx.x < 2) a.counts[b * 2 + threadIdx.x] = cnt[threadIdx.x];
+}
+
+// create_color_map :462-470 + create_shading :491-523, one thread per cell.  dx, dy one-sided at the borders and halved in the
+// interior, norm = (nx, ny, 1) / sqrt((nx^2 + ny^2) + 1), shade = (Lx nx + Ly ny) + Lz nz, colour = clamp(shade c + ambient c, 0, 1)
+// with c the class's table row: a class below 0 takes row 0 and one above C - 1 row C - 1, as the colour map's under / over entries.
+__global__ __launch_bounds__(256) void terrain_color_kernel(ColorArgs a)
+{
+    __shared__ float tab[kMaxColorClasses * 3];
+    const int G = a.G, C = min(a.C, kMaxColorClasses);
+    for (int k = threadIdx.x; k < C * 3; k += blockDim.x) tab[k] = a.table[k];
+    __syncthreads();
+    const size_t cells = (size_t)G * G;
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= cells * a.B) return;
+    const int b = (int)(i / cells);
+    const int rem = (int)(i - (size_t)b * cells);
+    const int r = rem / G, c = rem - r * G;
+    const float *h = a.heights + (size_t)b * cells + rem;
+    const float h0 = h[0];
+    float nx = 0.0f, ny = 0.0f;
+    if (c < G - 1) nx = __fadd_rn(nx, __fsub_rn(h0, h[1]));
+    if (c > 0) nx = __fadd_rn(nx, __fsub_rn(h[-1], h0));
+    if (c > 0 && c < G - 1) nx = __fdiv_rn(nx, 2.0f);
+    if (r < G - 1) ny = __fadd_rn(ny, __fsub_rn(h0, h[G]));
+    if (r > 0) ny = __fadd_rn(ny, __fsub_rn(h[-G], h0));
+    if (r > 0 && r < G - 1) ny = __fdiv_rn(ny, 2.0f);
+    const float len = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(nx, nx), __fmul_rn(ny, ny)), 1.0f));
+    const float ux = __fdiv_rn(nx, len), uy = __fdiv_rn(ny, len), uz = __fdiv_rn(1.0f, len);
+    const float *L = a.light + (size_t)b * 3;
+    const float shade = __fadd_rn(__fadd_rn(__fmul_rn(L[0], ux), __fmul_rn(L[1], uy)), __fmul_rn(L[2], uz));
+    const int cls = min(max(a.classes[i], 0), C - 1);
+    float *out = a.colors + (size_t)b * 3 * cells + rem;
+    for (int k = 0; k < 3; ++k) {
+        const float col = tab[cls * 3 + k];
+        const float v = __fadd_rn(__fmul_rn(shade, col), __fmul_rn(a.ambient, col));
+        out[(size_t)k * cells] = fminf(fmaxf(v, 0.0f), 1.0f);
+    }
+}
+
 thread_local std::string g_terrain_error;
 
 }  // namespace
@@ -289,6 +440,13 @@ struct bn_terrain {
     float *cr_val = nullptr, *lin = nullptr, *cparams = nullptr;
     int maxc = 0, lin_len = 0, nclass = 0;
     hipEvent_t ev_done = nullptr;
+    // colouring (allocated by the first bn_terrain_set_coloring / bn_terrain_colorize)
+    bool coloring = false, own_noise = false, colored = false, ev_recorded = false;
+    int ncolor = 0, nmodels = 0;
+    float feature = 20.0f, ambient = 0.1f;
+    float *noise = nullptr, *colors = nullptr, *thr = nullptr, *ctable = nullptr, *light = nullptr, *cz_heights = nullptr;
+    int32_t *cstart = nullptr, *counts = nullptr, *cz_classes = nullptr;
+    uint64_t *cseeds = nullptr;
 };
 
 namespace {
@@ -318,7 +476,7 @@ int realloc_dev(P **p, size_t bytes)
 
 int wait_done(bn_terrain_t *h)
 {
-    if (h->generated) TERRAIN_HIP(hipEventSynchronize(h->ev_done));
+    if (h->generated || h->ev_recorded) TERRAIN_HIP(hipEventSynchronize(h->ev_done));
     return BN_OK;
 }
 
@@ -337,6 +495,34 @@ bn::TerrainArgs make_args(bn_terrain_t *h)
     a.c_milli = (float)1e-3;
     a.inv_8res = 1.0 / (8.0 * res);
     return a;
+}
+
+bn::ColorArgs make_color_args(bn_terrain_t *h)
+{
+    bn::ColorArgs a{};
+    a.noise = h->noise; a.classes = h->classes; a.heights = h->heights; a.colors = h->colors; a.thr = h->thr; a.start = h->cstart;
+    a.table = h->ctable; a.light = h->light; a.seeds = h->cseeds; a.counts = h->counts;
+    a.G = h->G; a.B = h->B; a.C = h->ncolor; a.nmodels = h->nmodels; a.feature = h->feature; a.ambient = h->ambient;
+    return a;
+}
+
+// the colouring buffers whose size depends on G and B alone (the first use allocates them), and the (C, 3) table
+int ensure_color_buffers(bn_terrain_t *h, int C)
+{
+    const size_t oc = (size_t)h->G * h->G * h->B;
+    int rc = BN_OK;
+    if (!h->colors) {
+        if ((rc = realloc_dev(&h->noise, oc * 4)) || (rc = realloc_dev(&h->colors, oc * 12)) || (rc = realloc_dev(&h->light, (size_t)h->B * 12)) ||
+            (rc = realloc_dev(&h->cstart, (size_t)h->B * 4)) || (rc = realloc_dev(&h->counts, (size_t)h->B * 8)) ||
+            (rc = realloc_dev(&h->cseeds, (size_t)h->B * 8)))
+            return rc;
+        TERRAIN_HIP(hipMemset(h->counts, 0, (size_t)h->B * 8));
+    }
+    if (C != h->ncolor || !h->ctable) {
+        if ((rc = realloc_dev(&h->thr, (size_t)h->B * C * 4)) || (rc = realloc_dev(&h->ctable, (size_t)C * 12))) return rc;
+        h->ncolor = C;
+    }
+    return BN_OK;
 }
 
 }  // namespace
@@ -390,10 +576,12 @@ void bn_terrain_destroy(bn_terrain_t *h)
 {
     if (!h) return;
     TerrainDeviceGuard guard(h->device);
-    if (h->generated && h->ev_done) (void)hipEventSynchronize(h->ev_done);
+    if ((h->generated || h->ev_recorded) && h->ev_done) (void)hipEventSynchronize(h->ev_done);
     for (void *p : {(void *)h->hp, (void *)h->S, (void *)h->T, (void *)h->tw, (void *)h->heights, (void *)h->slopes, (void *)h->mean,
                     (void *)h->stddev, (void *)h->classes, (void *)h->phases, (void *)h->cr_count, (void *)h->cr_int,
-                    (void *)h->cr_val, (void *)h->lin, (void *)h->cparams})
+                    (void *)h->cr_val, (void *)h->lin, (void *)h->cparams, (void *)h->noise, (void *)h->colors, (void *)h->thr,
+                    (void *)h->ctable, (void *)h->light, (void *)h->cz_heights, (void *)h->cstart, (void *)h->counts,
+                    (void *)h->cz_classes, (void *)h->cseeds})
         if (p) (void)hipFree(p);
     if (h->ev_done) (void)hipEventDestroy(h->ev_done);
     delete h;
@@ -450,7 +638,7 @@ int bn_terrain_set_draws(bn_terrain_t *h, const float *phases, const int32_t *cr
 
 int bn_terrain_set_slip(bn_terrain_t *h, const int32_t *t_classes, const float *class_params, int32_t num_classes)
 {
-    if (!h || !t_classes || (num_classes > 0 && !class_params)) return terrain_fail(BN_ERR_INVALID, "null argument");
+    if (!h || (num_classes > 0 && !class_params)) return terrain_fail(BN_ERR_INVALID, "null argument");
     if (num_classes < 0 || num_classes > (1 << 20)) return terrain_fail(BN_ERR_INVALID, "num_classes out of range");
     TerrainDeviceGuard guard(h->device);
     if (!guard.ok) return terrain_fail(BN_ERR_HIP, "hipSetDevice failed");
@@ -460,7 +648,7 @@ int bn_terrain_set_slip(bn_terrain_t *h, const int32_t *t_classes, const float *
         if ((rc = realloc_dev(&h->cparams, (size_t)(num_classes > 0 ? num_classes : 1) * bn::kClassParams * 4))) return rc;
         h->nclass = num_classes;
     }
-    TERRAIN_HIP(hipMemcpy(h->classes, t_classes, (size_t)h->G * h->G * h->B * 4, hipMemcpyHostToDevice));
+    if (t_classes) TERRAIN_HIP(hipMemcpy(h->classes, t_classes, (size_t)h->G * h->G * h->B * 4, hipMemcpyHostToDevice));
     if (num_classes > 0)
         TERRAIN_HIP(hipMemcpy(h->cparams, class_params, (size_t)num_classes * bn::kClassParams * 4, hipMemcpyHostToDevice));
     h->have_slip = true;
@@ -477,6 +665,15 @@ int bn_terrain_generate_async(bn_terrain_t *h, void *stream)
     const bn::TerrainArgs a = make_args(h);
     const size_t pc = (size_t)h->N * h->N * h->B, oc = (size_t)h->G * h->G * h->B;
     TERRAIN_HIP(hipMemsetAsync(h->hp, 0, pc * 4, s));
+    if (h->coloring) {
+        const bn::ColorArgs ca = make_color_args(h);
+        if (h->own_noise) {
+            bn::terrain_noise_kernel<<<(unsigned)((oc + 255) / 256), 256, 0, s>>>(ca);
+            TERRAIN_HIP(hipGetLastError());
+        }
+        bn::terrain_classes_kernel<<<h->B, bn::kReduceThreads, 0, s>>>(ca);
+        TERRAIN_HIP(hipGetLastError());
+    }
     bn::terrain_crater_kernel<<<h->B, bn::kReduceThreads, 0, s>>>(a);
     TERRAIN_HIP(hipGetLastError());
     if (h->fractal) {
@@ -492,8 +689,13 @@ int bn_terrain_generate_async(bn_terrain_t *h, void *stream)
     }
     bn::terrain_surface_kernel<<<(unsigned)((oc + 255) / 256), 256, 0, s>>>(a);
     TERRAIN_HIP(hipGetLastError());
+    if (h->coloring) {
+        bn::terrain_color_kernel<<<(unsigned)((oc + 255) / 256), 256, 0, s>>>(make_color_args(h));
+        TERRAIN_HIP(hipGetLastError());
+    }
     TERRAIN_HIP(hipEventRecord(h->ev_done, s));
     h->generated = true;
+    h->colored = h->coloring;
     return BN_OK;
 }
 
@@ -524,6 +726,88 @@ int bn_terrain_copy_out(bn_terrain_t *h, float *heights, float *slopes, float *m
     if (slopes) TERRAIN_HIP(hipMemcpy(slopes, h->slopes, bytes, hipMemcpyDeviceToHost));
     if (mean) TERRAIN_HIP(hipMemcpy(mean, h->mean, bytes, hipMemcpyDeviceToHost));
     if (stddev) TERRAIN_HIP(hipMemcpy(stddev, h->stddev, bytes, hipMemcpyDeviceToHost));
+    return BN_OK;
+}
+
+int bn_terrain_set_coloring(bn_terrain_t *h, int32_t enable, const float *thresholds, const int32_t *start, int32_t num_classes,
+                            const float *color_table, const float *light, float ambient_intensity, float feature_size,
+                            const float *noise, const uint64_t *seeds, int32_t num_slip_models)
+{
+    if (!h) return terrain_fail(BN_ERR_INVALID, "null handle");
+    if (!enable) { h->coloring = false; return BN_OK; }
+    if (!thresholds || !start || !color_table || !light) return terrain_fail(BN_ERR_INVALID, "null argument");
+    if (!noise && !seeds) return terrain_fail(BN_ERR_INVALID, "either a noise field or the seeds of the library's noise are needed");
+    if (num_classes < 1 || num_classes > bn::kMaxColorClasses)
+        return terrain_fail(BN_ERR_INVALID, "colouring supports 1 to " + std::to_string(bn::kMaxColorClasses) + " terrain classes");
+    if (!std::isfinite(ambient_intensity) || !std::isfinite(feature_size) || !(feature_size >= 1e-3f))
+        return terrain_fail(BN_ERR_INVALID, "ambient_intensity must be finite and feature_size finite and >= 1e-3");
+    for (int b = 0; b < h->B; ++b)
+        if (start[b] < 0 || start[b] > num_classes) return terrain_fail(BN_ERR_INVALID, "start class out of range");
+    TerrainDeviceGuard guard(h->device);
+    if (!guard.ok) return terrain_fail(BN_ERR_HIP, "hipSetDevice failed");
+    int rc = wait_done(h);
+    if (rc) return rc;
+    if ((rc = ensure_color_buffers(h, num_classes))) return rc;
+    const size_t oc = (size_t)h->G * h->G * h->B;
+    TERRAIN_HIP(hipMemcpy(h->thr, thresholds, (size_t)h->B * num_classes * 4, hipMemcpyHostToDevice));
+    TERRAIN_HIP(hipMemcpy(h->cstart, start, (size_t)h->B * 4, hipMemcpyHostToDevice));
+    TERRAIN_HIP(hipMemcpy(h->ctable, color_table, (size_t)num_classes * 12, hipMemcpyHostToDevice));
+    TERRAIN_HIP(hipMemcpy(h->light, light, (size_t)h->B * 12, hipMemcpyHostToDevice));
+    if (noise) TERRAIN_HIP(hipMemcpy(h->noise, noise, oc * 4, hipMemcpyHostToDevice));
+    else TERRAIN_HIP(hipMemcpy(h->cseeds, seeds, (size_t)h->B * 8, hipMemcpyHostToDevice));
+    h->own_noise = noise == nullptr;
+    h->ambient = ambient_intensity; h->feature = feature_size; h->nmodels = num_slip_models;
+    h->coloring = true;
+    return BN_OK;
+}
+
+int bn_terrain_colorize(bn_terrain_t *h, const float *heights, const int32_t *t_classes, const float *color_table, int32_t num_classes,
+                        const float *light, float ambient_intensity, void *stream)
+{
+    if (!h || !heights || !t_classes || !color_table || !light) return terrain_fail(BN_ERR_INVALID, "null argument");
+    if (num_classes < 1 || num_classes > bn::kMaxColorClasses)
+        return terrain_fail(BN_ERR_INVALID, "colouring supports 1 to " + std::to_string(bn::kMaxColorClasses) + " terrain classes");
+    if (!std::isfinite(ambient_intensity)) return terrain_fail(BN_ERR_INVALID, "ambient_intensity must be finite");
+    TerrainDeviceGuard guard(h->device);
+    if (!guard.ok) return terrain_fail(BN_ERR_HIP, "hipSetDevice failed");
+    int rc = wait_done(h);
+    if (rc) return rc;
+    if ((rc = ensure_color_buffers(h, num_classes))) return rc;
+    const size_t oc = (size_t)h->G * h->G * h->B;
+    if (!h->cz_heights && ((rc = realloc_dev(&h->cz_heights, oc * 4)) || (rc = realloc_dev(&h->cz_classes, oc * 4)))) return rc;
+    TERRAIN_HIP(hipMemcpy(h->cz_heights, heights, oc * 4, hipMemcpyHostToDevice));
+    TERRAIN_HIP(hipMemcpy(h->cz_classes, t_classes, oc * 4, hipMemcpyHostToDevice));
+    TERRAIN_HIP(hipMemcpy(h->ctable, color_table, (size_t)num_classes * 12, hipMemcpyHostToDevice));
+    TERRAIN_HIP(hipMemcpy(h->light, light, (size_t)h->B * 12, hipMemcpyHostToDevice));
+    bn::ColorArgs a = make_color_args(h);
+    a.heights = h->cz_heights; a.classes = h->cz_classes; a.ambient = ambient_intensity;
+    hipStream_t s = (hipStream_t)stream;
+    bn::terrain_color_kernel<<<(unsigned)((oc + 255) / 256), 256, 0, s>>>(a);
+    TERRAIN_HIP(hipGetLastError());
+    TERRAIN_HIP(hipEventRecord(h->ev_done, s));
+    h->ev_recorded = true;
+    return BN_OK;
+}
+
+int bn_terrain_color_buffers(bn_terrain_t *h, void **classes, void **colors, void **noise)
+{
+    if (!h || !classes || !colors || !noise) return terrain_fail(BN_ERR_INVALID, "null argument");
+    if (!h->colors) return terrain_fail(BN_ERR_STATE, "colouring has not been set");
+    *classes = h->classes; *colors = h->colors; *noise = h->noise;
+    return BN_OK;
+}
+
+int bn_terrain_class_counts(bn_terrain_t *h, int32_t *unassigned, int32_t *beyond)
+{
+    if (!h || !unassigned || !beyond) return terrain_fail(BN_ERR_INVALID, "null argument");
+    if (!h->generated || !h->colored || !h->counts) return terrain_fail(BN_ERR_STATE, "no coloured generation yet");
+    TerrainDeviceGuard guard(h->device);
+    if (!guard.ok) return terrain_fail(BN_ERR_HIP, "hipSetDevice failed");
+    int rc = wait_done(h);
+    if (rc) return rc;
+    std::vector<int32_t> c((size_t)h->B * 2);
+    TERRAIN_HIP(hipMemcpy(c.data(), h->counts, c.size() * 4, hipMemcpyDeviceToHost));
+    for (int b = 0; b < h->B; ++b) { unassigned[b] = c[2 * b]; beyond[b] = c[2 * b + 1]; }
     return BN_OK;
 }
 

@@ -1,9 +1,16 @@
-"""BenchNav map instances generated on the GPU: terrain geometry (craters + fBm heights, Horn slopes) and the latent slip model.
+"""BenchNav map instances generated on the GPU: terrain geometry (craters + fBm heights, Horn slopes), terrain classes with shaded
+colours, and the latent slip model.
 
-Mirror of the reference's `DatasetGenerator.generate_map_instance` (src/data/dataset_generator.py:310-358) without its colouring
-step: `TerrainGeometry.set_terrain_geometry` (src/environments/terrain_properties.py:37-134), `TerrainTraversability
-.set_traversability` (:527-579) with `SlipModel.model_mean / model_stddev` (src/environments/slip_model.py), and the slip models of
-`SlipModelsGenerator.generate_slip_models` (src/data/slip_models_generator.py).
+Mirror of the reference's `DatasetGenerator.generate_map_instance` (src/data/dataset_generator.py:310-358):
+`TerrainGeometry.set_terrain_geometry` (src/environments/terrain_properties.py:37-134), on request `TerrainColoring
+.set_terrain_class_coloring` (:364-523), `TerrainTraversability.set_traversability` (:527-579) with `SlipModel.model_mean /
+model_stddev` (src/environments/slip_model.py), and the slip models of `SlipModelsGenerator.generate_slip_models`
+(src/data/slip_models_generator.py).
+
+Colouring is opt-in (`generate(..., occupancy=...)`).  Its noise field is an input: the caller's (with the real `opensimplex`'s
+field the classes are the reference's on that field), or the library's own seeded gradient noise (not OpenSimplex).
+The two uniforms of the light source are replayed after the fBm phases and the light vector is built with the reference's torch
+calls; the class thresholds are torch's float32 cumsum; the copper colour table is computed here without matplotlib.
 
 The random draws stay on the host, in the reference's order on torch's CPU generator (`GridMap(seed=...)` seeds it,
 grid_map.py:52): the crater rejection loop touches a few scalars per attempt, and the fBm phases are then ONE `torch.rand(n)`,
@@ -23,7 +30,7 @@ import ctypes as C
 import math
 import warnings
 from dataclasses import dataclass, field
-from typing import Dict, List, Optional, Sequence, Union
+from typing import Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -36,6 +43,7 @@ SLIP_NONLINEARITY_MINMAX = (1.4, 2.0)
 SLIP_OFFSET_MINMAX = (0.0, 0.1)
 NOISE_SCALE_MINMAX = (0.1, 0.2)
 MAX_ATTEMPTS = 1000                       # terrain_properties.py:124
+MAX_COLOR_CLASSES = 64                    # the colour table lives in LDS (csrc/terrain_kernels.hip)
 
 
 @dataclass
@@ -89,6 +97,9 @@ class Draws:
     attempts: int
     gave_up: bool
     phases: np.ndarray            # (n,) float32 uniforms of generate_fractal_surface, empty without fBm
+    seed: Optional[int] = None                    # the instance seed (keys the library's own noise)
+    light_uniforms: Optional[np.ndarray] = None   # (2,) float32: create_shading's light angle and z draws, with coloring only
+    light: Optional[np.ndarray] = None            # (3,) float32 light vector as the reference's torch calls build it
 
 
 def num_phases(grid_size: int) -> int:
@@ -114,11 +125,91 @@ def _crater_plan(G: int, res: float, center: torch.Tensor, radius: float, angle:
                   lin.numpy().astype(np.float32), float(neg_tan))
 
 
+def _light_draws(g: torch.Generator, lower_threshold: float, upper_threshold: float) -> Tuple[np.ndarray, np.ndarray]:
+    """create_shading's two draws on `g` and its light vector, with the reference's own torch calls (:511-517)."""
+    u_angle, u_z = torch.rand(1, generator=g), torch.rand(1, generator=g)
+    light_angle = u_angle * (2 * torch.pi)
+    z = u_z * (upper_threshold - lower_threshold) + lower_threshold
+    radius = torch.sqrt(1 - z**2)
+    light = torch.tensor([radius * torch.cos(light_angle), radius * torch.sin(light_angle), z])
+    return torch.cat((u_angle, u_z)).numpy().astype(np.float32), light.numpy().astype(np.float32)
+
+
+def light_source(seed_or_generator: Union[int, torch.Generator], lower_threshold: float = 0.8, upper_threshold: float = 1.0) -> np.ndarray:
+    """The (3,) float32 light vector of create_shading (terrain_properties.py:511-517): two uniforms (angle, then z) from a CPU
+    generator seeded with the given seed, or from the given generator where it stands."""
+    g = seed_or_generator if isinstance(seed_or_generator, torch.Generator) else torch.Generator().manual_seed(int(seed_or_generator))
+    return _light_draws(g, lower_threshold, upper_threshold)[1]
+
+
+def _copper_lut() -> np.ndarray:
+    """matplotlib's 256-entry copper table, (256, 3) float64: three piecewise-linear channels through linspace(0, 1, 256)
+    (red rises to 1 at 0.809524, green to 0.7812 and blue to 0.4975 at 1), built the way LinearSegmentedColormap interpolates."""
+    xind = 255 * np.linspace(0, 1, 256)
+    lut = np.empty((256, 3))
+    for ch, data in enumerate((((0.0, 0.0, 0.0), (0.809524, 1.0, 1.0), (1.0, 1.0, 1.0)),
+                               ((0.0, 0.0, 0.0), (1.0, 0.7812, 0.7812)), ((0.0, 0.0, 0.0), (1.0, 0.4975, 0.4975)))):
+        adata = np.array(data)
+        x, y0, y1 = adata[:, 0] * 255, adata[:, 1], adata[:, 2]
+        ind = np.searchsorted(x, xind)[1:-1]
+        distance = (xind[1:-1] - x[ind - 1]) / (x[ind] - x[ind - 1])
+        lut[:, ch] = np.clip(np.concatenate([[y1[0]], distance * (y0[ind] - y1[ind - 1]) + y1[ind - 1], [y0[-1]]]), 0.0, 1.0)
+    return lut
+
+
+def _copper_table(num_classes: int) -> np.ndarray:
+    """(C, 3) float32: plt.cm.copper(Normalize(0, C - 1)(i))[:3] for i = 0..C-1 (create_color_map :462-470), without matplotlib.
+    C = 1 gives black: Normalize(0, 0) maps everything to 0."""
+    C_ = int(num_classes)
+    if C_ < 1 or C_ > MAX_COLOR_CLASSES:
+        raise ValueError(f"colouring supports 1 to {MAX_COLOR_CLASSES} terrain classes, got {C_}")
+    v = np.zeros(C_) if C_ == 1 else np.arange(C_, dtype=np.float64) / (C_ - 1)
+    idx = (v * 256).astype(np.int64)          # Colormap.__call__: X * N truncated, X == 1 in the last entry
+    idx[idx >= 256] = 255
+    return _copper_lut()[idx].astype(np.float32)
+
+
+def occupancies(environment_count: int, num_total_terrain_classes: int = 10, num_selected_terrain_classes: int = 4,
+                seed: int = 0) -> torch.Tensor:
+    """(environments, classes) float32 occupancy rows: DatasetGenerator.generate_occupancy_distribution and
+    balance_occupancy_distribution (dataset_generator.py:192-264) on a private CPU generator: a randperm per environment picks
+    the selected classes (1 / selected each), then up to 1000 rounds swap a selection from every over-represented class to the
+    first under-represented one that has a candidate environment.
+
+    Where the reference returns a table this is that table.  Where a swap has exactly one candidate the reference raises an
+    IndexError (its nonzero(...).squeeze() is 0-dimensional there and it indexes [0]); here that single candidate is taken, the
+    evident intent."""
+    E, T, S = int(environment_count), int(num_total_terrain_classes), int(num_selected_terrain_classes)
+    g = torch.Generator().manual_seed(int(seed))
+    occ = torch.zeros(E, T)
+    for e in range(E):
+        occ[e, torch.randperm(T, generator=g)[:S]] = 1 / S
+    expected = S * E / T
+    current = torch.sum(occ == 1 / S, dim=0)
+    for _ in range(1000):
+        over_classes = torch.where(current > expected)[0]
+        under_classes = torch.where(current < expected)[0]
+        if len(over_classes) == 0 or len(under_classes) == 0:
+            break
+        for over in over_classes:
+            for under in under_classes:
+                candidates = torch.nonzero((occ[:, over] == 1 / S) & (occ[:, under] == 0), as_tuple=False).reshape(-1)
+                if candidates.numel() > 0:
+                    e = candidates[0].item()
+                    occ[e, over] = 0
+                    occ[e, under] = 1 / S
+                    current[over] -= 1
+                    current[under] += 1
+                    break
+    return occ
+
+
 def replay_draws(seed: int, grid_size: int, resolution: float, is_fractal: bool = True, is_crater: bool = True, num_craters: int = 3,
                  crater_margin: float = 5, min_angle: float = 10, max_angle: float = 20, min_radius: float = 5,
-                 max_radius: float = 10) -> Draws:
+                 max_radius: float = 10, coloring: Union[None, bool, Tuple[float, float]] = None) -> Draws:
     """The reference's random draws for one instance seeded with `seed`, on a private CPU generator: the crater rejection loop
-    (terrain_properties.py:70-129) and then the fBm phases (:254-286) as one torch.rand(n)."""
+    (terrain_properties.py:70-129), then the fBm phases (:254-286) as one torch.rand(n), and with `coloring` (True, or the pair
+    (lower_threshold, upper_threshold); True means (0.8, 1.0)) the two draws of create_shading's light source (:511-512)."""
     g = torch.Generator().manual_seed(int(seed))
     G, res, N = grid_size, resolution, grid_size + 2
     x0 = G * res / 2 - G / 2 * res                                                                 # GridMap.x_limits[0]
@@ -140,7 +231,11 @@ def replay_draws(seed: int, grid_size: int, resolution: float, is_fractal: bool 
                 gave_up = True
                 break
     phases = torch.rand(num_phases(G), generator=g).numpy() if is_fractal else np.zeros(0, np.float32)
-    return Draws(craters, count, gave_up, phases)
+    d = Draws(craters, count, gave_up, phases, seed=int(seed))
+    if coloring is not None and coloring is not False:
+        lo, hi = (0.8, 1.0) if coloring is True else coloring
+        d.light_uniforms, d.light = _light_draws(g, float(lo), float(hi))
+    return d
 
 
 def _as_param_table(models):
@@ -155,7 +250,9 @@ def _as_param_table(models):
 
 @dataclass
 class Terrain:
-    """Device tensors of B generated instances, (B, G, G) float32 each, and the per-instance draws."""
+    """Device tensors of B generated instances, (B, G, G) float32 each, and the per-instance draws.  With colouring, `colors`
+    are the shaded colours, `noise` the raw noise field the classes were cut from and `light` the light vectors; without,
+    `colors` are zero and the other two None."""
     heights: torch.Tensor
     slopes: torch.Tensor
     latent_mean: torch.Tensor
@@ -163,6 +260,9 @@ class Terrain:
     t_classes: torch.Tensor                    # (B, G, G) int64 on the host, as the reference stores it
     craters: List[np.ndarray]                  # per instance (k, 4) float64 rows (x, y, radius, angle)
     draws: List[Draws] = field(default_factory=list)
+    colors: Optional[torch.Tensor] = None      # (B, 3, G, G) float32, device
+    noise: Optional[torch.Tensor] = None       # (B, G, G) float32, device
+    light: Optional[np.ndarray] = None         # (B, 3) float32
 
 
 class TerrainGenerator:
@@ -170,6 +270,8 @@ class TerrainGenerator:
 
         gen = TerrainGenerator(64, 0.5, batch=8)
         t = gen.generate(seeds=range(8))            # DatasetGenerator.generate_map_instance(seed) minus the colouring
+        occ = occupancies(10)                       # ... and with it: 4 of 10 classes per environment
+        t = gen.generate(seeds=range(8), occupancy=occ[0], slip_models=slip_models(10))
         insts = gen.to_instances()                  # io.MapInstance: io.save_instance / io.planner_inputs take them
     """
 
@@ -188,22 +290,41 @@ class TerrainGenerator:
 
     def generate(self, seeds: Sequence[int], is_fractal: bool = True, is_crater: bool = True, num_craters: int = 3,
                  crater_margin: float = 5, min_angle: float = 10, max_angle: float = 20, min_radius: float = 5,
-                 max_radius: float = 10, t_classes=None, slip_models=None, start_pos=None, goal_pos=None) -> Terrain:
+                 max_radius: float = 10, t_classes=None, slip_models=None, start_pos=None, goal_pos=None, occupancy=None, noise=None,
+                 feature_size: float = 20, lower_threshold: float = 0.8, upper_threshold: float = 1.0,
+                 ambient_intensity: float = 0.1) -> Terrain:
+        """B instances from B seeds.  `occupancy` ((C,) or (B, C) class ratios, e.g. rows of occupancies()) asks for the colouring
+        step: the terrain classes are cut from a noise field -- `noise` ((G, G) or (B, G, G)), or the library's own keyed by each
+        seed -- and the colours are the classes' copper colours shaded by the heights.  Without it, nothing changes: the classes
+        are `t_classes` (default all zero) and the colours zero."""
         if start_pos is not None or goal_pos is not None:
             raise NotImplementedError("start_pos / goal_pos crater avoidance is not mirrored (DatasetGenerator passes neither)")
         seeds = [int(s) for s in seeds]
         B, G = self.batch, self.grid_size
         if len(seeds) != B:
             raise ValueError(f"expected {B} seeds, got {len(seeds)}")
+        if occupancy is None and noise is not None:
+            raise ValueError("noise= is the colouring step's input: pass occupancy= as well")
+        if occupancy is not None and t_classes is not None:
+            raise ValueError("t_classes= and occupancy= are two sources for one class map: pass one")
+        coloring = None if occupancy is None else (lower_threshold, upper_threshold)
         draws = [replay_draws(s, G, self.resolution, is_fractal, is_crater, num_craters, crater_margin, min_angle, max_angle,
-                              min_radius, max_radius) for s in seeds]
-        return self.generate_from_draws(draws, is_fractal, t_classes, slip_models)
+                              min_radius, max_radius, coloring=coloring) for s in seeds]
+        return self.generate_from_draws(draws, is_fractal, t_classes, slip_models, occupancy=occupancy, noise=noise,
+                                        feature_size=feature_size, ambient_intensity=ambient_intensity)
 
-    def generate_from_draws(self, draws: List[Draws], is_fractal: bool = True, t_classes=None, slip_models=None) -> Terrain:
-        """generate() on given draws (one Draws per instance, e.g. from replay_draws): the device half alone."""
+    def generate_from_draws(self, draws: List[Draws], is_fractal: bool = True, t_classes=None, slip_models=None, occupancy=None,
+                            noise=None, feature_size: float = 20, ambient_intensity: float = 0.1) -> Terrain:
+        """generate() on given draws (one Draws per instance, e.g. from replay_draws): the device half alone.  With `occupancy`
+        the draws carry the light vectors (replay_draws(coloring=...)) and, for the library's own noise, the seeds."""
         if len(draws) != self.batch:
             raise ValueError(f"expected {self.batch} draws, got {len(draws)}")
+        if occupancy is not None:
+            if t_classes is not None:
+                raise ValueError("t_classes= and occupancy= are two sources for one class map: pass one")
+            return self._generate_colored(draws, is_fractal, slip_models, occupancy, noise, feature_size, ambient_intensity)
         self.upload_draws(draws, is_fractal)
+        self._check(self._lib.bn_terrain_set_coloring(self._handle, 0, None, None, 0, None, None, 0.0, 0.0, None, None, 0))
         cls = self._class_maps(t_classes)
         models = _default_slip_models(1) if slip_models is None else slip_models
         tab, nmodels = _as_param_table(models)
@@ -214,10 +335,119 @@ class TerrainGenerator:
         self._check(self._lib.bn_terrain_set_slip(self._handle, cls32.ctypes.data, tab.ctypes.data, tab.shape[0]))
         self._check(self._lib.bn_terrain_generate_async(self._handle, C.c_void_p(torch.cuda.current_stream(self._dev).cuda_stream)))
         out = self.outputs()
-        self._last = Terrain(*out, t_classes=torch.from_numpy(cls.astype(np.int64)),
-                             craters=[np.array([[c.center[0], c.center[1], c.radius, c.angle] for c in d.craters], np.float64).reshape(-1, 4)
-                                      for d in draws], draws=draws)
+        with torch.cuda.device(self._dev):
+            colors = torch.zeros((self.batch, 3, self.grid_size, self.grid_size), device=self._dev)
+        self._last = Terrain(*out, t_classes=torch.from_numpy(cls.astype(np.int64)), craters=self._crater_tables(draws), draws=draws,
+                             colors=colors)
         return self._last
+
+    @staticmethod
+    def _crater_tables(draws):
+        return [np.array([[c.center[0], c.center[1], c.radius, c.angle] for c in d.craters], np.float64).reshape(-1, 4) for d in draws]
+
+    def _occupancy_rows(self, occupancy) -> torch.Tensor:
+        """(B, C) float32 rows, each normalised as set_terrain_class_coloring does (:384-388, torch float32) with its warning."""
+        occ = torch.as_tensor(occupancy).detach().cpu().to(torch.float32).clone()
+        if occ.dim() == 1:
+            occ = occ.unsqueeze(0).repeat(self.batch, 1)
+        if occ.dim() != 2 or occ.shape[0] != self.batch or occ.shape[1] < 1:
+            raise ValueError(f"occupancy must be (C,) or ({self.batch}, C), got {tuple(torch.as_tensor(occupancy).shape)}")
+        if occ.shape[1] > MAX_COLOR_CLASSES:
+            raise ValueError(f"colouring supports 1 to {MAX_COLOR_CLASSES} terrain classes, got {occ.shape[1]}")
+        if not bool(torch.isfinite(occ).all()) or bool((occ < 0).any()):
+            raise ValueError("occupancy ratios must be finite and >= 0")
+        if not bool((occ > 0).any(dim=1).all()):
+            raise ValueError("every occupancy row needs a class with a ratio > 0")
+        warned = False
+        for row in occ:
+            if row.sum() > 1:
+                row /= row.sum()
+                if not warned:
+                    warnings.warn("Sum of occupancy vector exceeds one! The vector has been normalized.")
+                    warned = True
+        return occ
+
+    def _noise_fields(self, noise) -> np.ndarray:
+        B, G = self.batch, self.grid_size
+        n = noise.detach().cpu().numpy() if isinstance(noise, torch.Tensor) else np.asarray(noise)
+        if n.shape == (G, G):
+            n = np.broadcast_to(n, (B, G, G))
+        if n.shape != (B, G, G):
+            raise ValueError(f"noise must be ({G}, {G}) or ({B}, {G}, {G}), got {n.shape}")
+        return np.ascontiguousarray(n, dtype=np.float32)
+
+    def _generate_colored(self, draws, is_fractal, slip_models, occupancy, noise, feature_size, ambient_intensity) -> Terrain:
+        B, G = self.batch, self.grid_size
+        occ = self._occupancy_rows(occupancy)
+        C_ = occ.shape[1]
+        if any(d.light is None for d in draws):
+            raise ValueError("colouring needs the light vectors: make the draws with replay_draws(..., coloring=True)")
+        light = np.ascontiguousarray(np.stack([d.light for d in draws]), dtype=np.float32)
+        thr = np.ascontiguousarray((torch.cumsum(occ, dim=1) * 100).numpy(), dtype=np.float32)          # :428, per row
+        start = np.array([int((row > 0).nonzero().min().item()) for row in occ], np.int32)             # :431
+        table = np.ascontiguousarray(_copper_table(C_))
+        field_, seeds = None, None
+        if noise is not None:
+            field_ = self._noise_fields(noise)
+        else:
+            if any(d.seed is None for d in draws):
+                raise ValueError("the library's own noise is keyed by the instance seeds: draws without a seed need noise=")
+            seeds = np.array([d.seed % (1 << 64) for d in draws], np.uint64)
+        models = _default_slip_models(1) if slip_models is None else slip_models
+        tab, nmodels = _as_param_table(models)
+        self.upload_draws(draws, is_fractal)
+        self._check(self._lib.bn_terrain_set_coloring(
+            self._handle, 1, thr.ctypes.data, start.ctypes.data, C_, table.ctypes.data, light.ctypes.data, float(ambient_intensity),
+            float(feature_size), None if field_ is None else field_.ctypes.data, None if seeds is None else seeds.ctypes.data, nmodels))
+        self._check(self._lib.bn_terrain_set_slip(self._handle, None, tab.ctypes.data, tab.shape[0]))
+        self._check(self._lib.bn_terrain_generate_async(self._handle, C.c_void_p(torch.cuda.current_stream(self._dev).cuda_stream)))
+        unassigned, beyond = np.zeros(B, np.int32), np.zeros(B, np.int32)
+        self._check(self._lib.bn_terrain_class_counts(self._handle, unassigned.ctypes.data, beyond.ctypes.data))
+        if unassigned.any():
+            warnings.warn("Some grid cells have not been assigned a terrain class.")                    # :440-441
+        if unassigned.any() or beyond.any():                                                            # set_traversability :554-557
+            raise ValueError("The number of terrain classes exceeds the number of slip models.")
+        out = self.outputs()
+        cls, colors, nz = self._color_outputs()
+        self._last = Terrain(*out, t_classes=cls.cpu().to(torch.int64), craters=self._crater_tables(draws), draws=draws,
+                             colors=colors, noise=nz, light=light)
+        return self._last
+
+    def _color_outputs(self):
+        """(classes int32 (B, G, G), colours (B, 3, G, G), noise (B, G, G)) device tensors (copies)."""
+        from .astar import _DevArray
+        ptrs = [C.c_void_p() for _ in range(3)]
+        self._check(self._lib.bn_terrain_color_buffers(self._handle, *[C.byref(p) for p in ptrs]))
+        B, G = self.batch, self.grid_size
+        with torch.cuda.device(self._dev):
+            cls = torch.as_tensor(_DevArray(ptrs[0].value, (B, G, G), "<i4"), device=self._dev).clone()
+            colors = torch.as_tensor(_DevArray(ptrs[1].value, (B, 3, G, G)), device=self._dev).clone()
+            nz = torch.as_tensor(_DevArray(ptrs[2].value, (B, G, G)), device=self._dev).clone()
+        return cls, colors, nz
+
+    def colorize(self, heights, t_classes, num_classes: int, light, ambient_intensity: float = 0.1) -> torch.Tensor:
+        """(B, 3, G, G) device colours of create_color_map + create_shading (terrain_properties.py:462-523) for given (B, G, G)
+        heights and classes and (B, 3) light vectors (light_source() makes one the reference's way); `num_classes` sizes the
+        copper table.  Also how an instance stored without colours gets them."""
+        B, G = self.batch, self.grid_size
+        h = heights.detach().cpu().numpy() if isinstance(heights, torch.Tensor) else np.asarray(heights)
+        if h.shape == (G, G):
+            h = h[None]
+        if h.shape != (B, G, G):
+            raise ValueError(f"heights must be ({B}, {G}, {G}), got {h.shape}")
+        h = np.ascontiguousarray(h, dtype=np.float32)
+        cls = np.ascontiguousarray(self._class_maps(t_classes), dtype=np.int32)
+        L = np.asarray(light.detach().cpu().numpy() if isinstance(light, torch.Tensor) else light, dtype=np.float32)
+        if L.shape == (3,):
+            L = np.broadcast_to(L, (B, 3))
+        if L.shape != (B, 3):
+            raise ValueError(f"light must be (3,) or ({B}, 3), got {L.shape}")
+        L = np.ascontiguousarray(L)
+        table = np.ascontiguousarray(_copper_table(num_classes))
+        self._check(self._lib.bn_terrain_colorize(self._handle, h.ctypes.data, cls.ctypes.data, table.ctypes.data, int(num_classes),
+                                                  L.ctypes.data, float(ambient_intensity),
+                                                  C.c_void_p(torch.cuda.current_stream(self._dev).cuda_stream)))
+        return self._color_outputs()[1]
 
     def upload_draws(self, draws: List[Draws], is_fractal: bool) -> None:
         """Ship the draws of B instances: the crater tables (int bounds + float32 radius, -tan, linspace) and the phases."""
@@ -274,7 +504,8 @@ class TerrainGenerator:
         return buf[..., 0] + 1j * buf[..., 1]
 
     def to_instances(self):
-        """The last generate() as io.MapInstance objects (CPU tensors, the reference's on-disk layout; colours are zero)."""
+        """The last generate() as io.MapInstance objects (CPU tensors, the reference's on-disk layout; colours are zero unless
+        the generation coloured them)."""
         from .io import MapInstance
         t = self._last
         if t is None:
@@ -283,7 +514,7 @@ class TerrainGenerator:
         out = []
         for b in range(self.batch):
             tensors = {"heights": t.heights[b].cpu(), "slopes": t.slopes[b].cpu(), "t_classes": t.t_classes[b].clone(),
-                       "colors": torch.zeros(3, G, G)}
+                       "colors": torch.zeros(3, G, G) if t.colors is None else t.colors[b].cpu()}
             out.append(MapInstance(grid_size=G, tensors=tensors, latent_mean=t.latent_mean[b].cpu(),
                                    latent_std=t.latent_std[b].cpu(), extra={"craters": t.craters[b]}))
         return out

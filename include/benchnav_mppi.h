@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define BN_MPPI_ABI_VERSION 4
+#define BN_MPPI_ABI_VERSION 5
 
 typedef enum bn_status {
     BN_OK = 0,
@@ -594,7 +594,8 @@ int bn_terrain_set_geometry(bn_terrain_t *h, double resolution, double roughness
 int bn_terrain_set_draws(bn_terrain_t *h, const float *phases, const int32_t *crater_count, const int32_t *crater_int,
                          const float *crater_val, int32_t max_craters, const float *lin, int64_t lin_len);
 /* Class maps t_classes (B, G, G) and per-class rows of 6 float32: present (0: the class has no model, its cells stay inf),
- * f32(slip_sensitivity * 1e-3), slip_nonlinearity, slip_offset, base_noise_scale, slope_noise_scale. */
+ * f32(slip_sensitivity * 1e-3), slip_nonlinearity, slip_offset, base_noise_scale, slope_noise_scale.  t_classes may be NULL: the
+ * device's class map is left as it is (the colouring step writes it, bn_terrain_set_coloring). */
 int bn_terrain_set_slip(bn_terrain_t *h, const int32_t *t_classes, const float *class_params, int32_t num_classes);
 /* Enqueues the whole generation on `stream`. */
 int bn_terrain_generate_async(bn_terrain_t *h, void *stream);
@@ -604,6 +605,26 @@ int bn_terrain_sync(bn_terrain_t *h);
 int bn_terrain_buffers(bn_terrain_t *h, void **heights, void **slopes, void **mean, void **stddev);
 /* Waits and copies the outputs to host memory (any pointer may be NULL). */
 int bn_terrain_copy_out(bn_terrain_t *h, float *heights, float *slopes, float *mean, float *stddev);
+/* TerrainColoring.set_terrain_class_coloring (terrain_properties.py:364-523) as part of the generation.  enable = 0 switches it off
+ * again (every other argument is ignored).  thresholds (B, C) float32 = cumsum(occupancy) * 100 and start (B) = the first class
+ * with occupancy > 0 (generate_multi_terrain :428-431); color_table (C, 3) float32, row i the colour of class i (create_color_map
+ * :462-470); light (B, 3) float32 light vectors and ambient_intensity (create_shading :511-521); C <= 64.  The noise field of :418-420
+ * is either `noise` (B, G, G) float32, or, with noise = NULL, the library's own gradient noise at (x, y) / feature_size keyed by
+ * seeds (B).  The generation then writes the class map ahead of the slip maps and the colours after them, and counts
+ * per instance the cells left without a class and the cells whose class is >= num_slip_models. */
+int bn_terrain_set_coloring(bn_terrain_t *h, int32_t enable, const float *thresholds, const int32_t *start, int32_t num_classes,
+                            const float *color_table, const float *light, float ambient_intensity, float feature_size,
+                            const float *noise, const uint64_t *seeds, int32_t num_slip_models);
+/* create_color_map + create_shading (:462-523) on the caller's heights (B, G, G) float32 and classes (B, G, G) int32, host
+ * pointers: enqueues the colour kernel on `stream`; the result is the colours buffer of bn_terrain_color_buffers.  A class below 0
+ * takes row 0 of the table, one above C - 1 row C - 1 (the colour map's under and over entries). */
+int bn_terrain_colorize(bn_terrain_t *h, const float *heights, const int32_t *t_classes, const float *color_table, int32_t num_classes,
+                        const float *light, float ambient_intensity, void *stream);
+/* Device pointers: classes (B, G, G) int32, colours (B, 3, G, G) float32, the raw noise field (B, G, G) float32. */
+int bn_terrain_color_buffers(bn_terrain_t *h, void **classes, void **colors, void **noise);
+/* Waits for the last coloured generation; per instance, the cells with class -1 (the warning of :440-441) and the cells whose
+ * class has no slip model (set_traversability's ValueError, :554-557). */
+int bn_terrain_class_counts(bn_terrain_t *h, int32_t *unassigned, int32_t *beyond);
 /* Test hook: instance inst's scaled fBm spectrum (G', G') complex64 as interleaved float32 pairs. */
 int bn_terrain_spectrum(bn_terrain_t *h, int32_t inst, float *out);
 const char *bn_terrain_last_error(void);
