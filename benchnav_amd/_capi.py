@@ -32,7 +32,7 @@ BN_FLAG_UNORDERED_OUTPUTS = 16384
 BN_BUF_STATES_ALT, BN_BUF_CONTROLS_ALT = 10, 11
 BN_RISK_EXPECTED, BN_RISK_VAR, BN_RISK_CVAR = 0, 1, 2
 BN_AD_OK, BN_AD_OUT_OF_BOUNDS, BN_AD_GOAL_COLLISION, BN_AD_FIELD_ERROR = 0, 1, 2, 3   # bn_astar_dwa_status
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 
 class Config(C.Structure):
@@ -134,6 +134,11 @@ SYMBOLS = {
     "bn_terrain_destroy": (None, [_H]),
     "bn_terrain_set_geometry": (C.c_int, [_H, C.c_double, C.c_double, C.c_double, C.c_int32]),
     "bn_terrain_set_draws": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64]),
+    "bn_terrain_set_draw_params": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32,
+                                             C.c_double, C.c_double]),
+    "bn_terrain_draw_async": (C.c_int, [_H, C.c_void_p, C.c_void_p]),
+    "bn_terrain_draw_layout": (C.c_int, [_H, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "bn_terrain_read_draws": (C.c_int, [_H] + [C.c_void_p] * 9),
     "bn_terrain_set_slip": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int32]),
     "bn_terrain_generate_async": (C.c_int, [_H, C.c_void_p]),
     "bn_terrain_sync": (C.c_int, [_H]),

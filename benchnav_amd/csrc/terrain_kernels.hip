@@ -1,7 +1,10 @@
 // Terrain generation for B map instances of one grid size G (padded G' = G + 2): TerrainGeometry.set_terrain_geometry and
 // TerrainTraversability.set_traversability of the reference (src/environments/terrain_properties.py) on the device.
 //
-// The draws come from the host (benchnav_amd/terrain.py replays the reference's CPU generator); the kernels do the arithmetic:
+// The draws come from the host (benchnav_amd/terrain.py replays the reference's CPU generator) or from
+//   terrain_draws_kernel      one workgroup per instance: torch's MT19937 stream of the instance's seed in LDS, the crater rejection
+//                             loop, the crater tables, the fBm phases and the light source, written where the kernels below read
+// and the kernels do the arithmetic:
 //   terrain_crater_kernel     one workgroup per instance, craters in order: carve the footprint (generate_crater :151-206),
 //                             then the min-reduction and shift (adjust_height_values) -- float32 operations in the reference's order
 //   terrain_spectrum_kernel   the final state of generate_fractal_surface's complex64 grid (:254-290), scaled (:293-295)
@@ -18,6 +21,7 @@
 // Every index is bounded by the handle's G and B; crater slices are validated on the host and clamped here again.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -424,6 +428,211 @@ __global__ __launch_bounds__(256) void terrain_color_kernel(ColorArgs a)
     }
 }
 
+// ---- the random draws on the device (DESIGN.md 4.5 "The draws on the device") ----
+// What terrain.replay_draws makes on torch's CPU generator, for instance blockIdx.x from seeds[blockIdx.x]: MT19937 seeded with
+// the seed's low 32 bits, one float32 uniform f32(r & 0xFFFFFF) 2^-24 per 32-bit output r; the crater rejection loop (three
+// uniforms per attempt, a fourth for an accepted one), each accepted crater's table entry, then the nph fBm phases and, for
+// the colouring, the two uniforms of the light source.  The 624-word state lives in LDS twice (the block being read and the
+// block being built); every thread follows the same control flow on the same LDS words, so the barriers stay uniform.
+constexpr int kMtN = 624, kMtM = 397;
+constexpr int kDrawThreads = 256;          // >= 227: each of the twist's parallel segments is one word per thread
+constexpr int kMaxDrawCraters = 64;        // placed craters' centres and radii live in LDS
+constexpr int kMaxAttempts = 1000;         // terrain_properties.py:124
+constexpr int kDrawRecord = 4;             // attempts, gave_up, status (0, or 1 + the first crater that does not fit), craters placed
+
+struct DrawArgs {
+    const uint64_t *seeds;     // (B)
+    float *phases;             // (B, nph)
+    int32_t *cr_count, *cr_int;
+    float *cr_val, *lin;       // lin: (B, maxc, stride), slot (b, c) at offset (b maxc + c) stride
+    float *light;              // (B, 3), with_light only
+    int32_t *rec;              // (B, kDrawRecord)
+    float *centers;            // (B, maxc, 2)
+    double *angles;            // (B, maxc) degrees
+    float *light_u;            // (B, 2)
+    int G, N, nph, maxc, stride, want, fractal, with_light;
+    float span, org, res;      // f32((N - 1) res - x0), f32(x0), f32(res)
+    float rspan, rmin, margin; // f32(max_radius - min_radius), f32(min_radius), f32(crater_margin)
+    float lspan, llo;          // f32(upper_threshold - lower_threshold), f32(lower_threshold)
+    double aspan, amin;        // max_angle - min_angle, min_angle
+};
+
+__device__ __forceinline__ uint32_t mt_mix(uint32_t hi, uint32_t lo)
+{
+    const uint32_t y = (hi & 0x80000000u) | (lo & 0x7fffffffu);
+    return (y >> 1) ^ ((y & 1u) ? 0x9908B0DFu : 0u);
+}
+
+__device__ __forceinline__ float mt_uniform(uint32_t y)
+{
+    y ^= y >> 11;
+    y ^= (y << 7) & 0x9D2C5680u;
+    y ^= (y << 15) & 0xEFC60000u;
+    y ^= y >> 18;
+    return __fmul_rn((float)(y & 0xFFFFFFu), 5.9604644775390625e-08f);       // exact: 24 bits times 2^-24
+}
+
+struct MtStream {
+    uint32_t (*mt)[kMtN];      // LDS, two blocks
+    int cur, pos;              // the block being read and the next word in it: the same in every thread
+};
+
+// The next 624 words from mt[cur] into mt[cur ^ 1], in the twist's four dependent segments.  Every thread of the block calls it.
+// mt[cur ^ 1] was last read before the previous refill's barriers, so nobody still reads what this one writes.
+__device__ void mt_refill(MtStream &s)
+{
+    const uint32_t *o = s.mt[s.cur];
+    uint32_t *n = s.mt[s.cur ^ 1];
+    const int t = threadIdx.x;
+    if (t < kMtN - kMtM) n[t] = o[t + kMtM] ^ mt_mix(o[t], o[t + 1]);                                    // i < 227
+    __syncthreads();
+    if (t < kMtN - kMtM) n[t + 227] = n[t] ^ mt_mix(o[t + 227], o[t + 228]);                             // 227 <= i < 454
+    __syncthreads();
+    if (t < 169) n[t + 454] = n[t + 227] ^ mt_mix(o[t + 454], o[t + 455]);                               // 454 <= i < 623
+    __syncthreads();
+    if (t == 0) n[623] = n[396] ^ mt_mix(o[623], n[0]);
+    __syncthreads();
+    s.cur ^= 1;
+    s.pos = 0;
+}
+
+__device__ __forceinline__ uint32_t mt_word(MtStream &s)
+{
+    if (s.pos == kMtN) mt_refill(s);
+    return s.mt[s.cur][s.pos++];
+}
+
+__device__ __forceinline__ float mt_next(MtStream &s) { return mt_uniform(mt_word(s)); }
+
+// One attempt of the crater loop from its three state words: the centre and the radius, and whether it overlaps a placed crater
+// (check_circle_overlap: norm(p - c) < (r_p + r) + margin for any p).
+__device__ __forceinline__ bool crater_attempt(const DrawArgs &a, const uint32_t *w, const float *px, const float *py, const float *pr,
+                                               int placed, float &cx, float &cy, float &r)
+{
+    cx = __fadd_rn(__fmul_rn(mt_uniform(w[0]), a.span), a.org);
+    cy = __fadd_rn(__fmul_rn(mt_uniform(w[1]), a.span), a.org);
+    r = __fadd_rn(__fmul_rn(mt_uniform(w[2]), a.rspan), a.rmin);
+    bool overlap = false;
+    for (int p = 0; p < placed; ++p) {
+        const float dx = __fsub_rn(px[p], cx), dy = __fsub_rn(py[p], cy);
+        const float dist = sqrtf(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)));
+        overlap = overlap || dist < __fadd_rn(__fadd_rn(pr[p], r), a.margin);
+    }
+    return overlap;
+}
+
+__global__ __launch_bounds__(kDrawThreads) void terrain_draws_kernel(DrawArgs a)
+{
+    __shared__ uint32_t mt[2][kMtN];
+    __shared__ float px[kMaxDrawCraters], py[kMaxDrawCraters], pr[kMaxDrawCraters];
+    __shared__ int first;
+    const int b = blockIdx.x, t = threadIdx.x, G = a.G, N = a.N;
+    if (t == 0) {                                                            // init_genrand: a dependent chain
+        uint32_t x = (uint32_t)a.seeds[b];
+        mt[0][0] = x;
+        for (int i = 1; i < kMtN; ++i) {
+            x = 1812433253u * (x ^ (x >> 30)) + (uint32_t)i;
+            mt[0][i] = x;
+        }
+    }
+    __syncthreads();
+    MtStream s{mt, 0, kMtN};                                                 // the first draw twists first
+    const int want = min(a.want, min(a.maxc, kMaxDrawCraters));
+    int placed = 0, attempts = 0, gave_up = 0, status = 0;
+    // A rejected attempt takes exactly three uniforms, so until one is accepted attempt j of a run reads words pos + 3 j ...
+    // pos + 3 j + 2: the threads try the attempts that fit the rest of this block of the stream at once, against the same placed
+    // craters, and the first one that does not overlap is the accepted one.  An attempt that straddles two blocks is tried alone.
+    while (placed < want) {
+        const int room = (kMtN - s.pos) / 3;
+        float cx = 0.0f, cy = 0.0f, r = 0.0f;
+        bool accepted;
+        if (room > 0) {
+            const int w = min(min(room, kMaxAttempts + 1 - attempts), kDrawThreads);
+            const uint32_t *m = s.mt[s.cur] + s.pos;
+            if (t == 0) first = w;
+            __syncthreads();
+            if (t < w && !crater_attempt(a, m + 3 * t, px, py, pr, placed, cx, cy, r)) atomicMin(&first, t);
+            __syncthreads();
+            const int k = __builtin_amdgcn_readfirstlane(first);
+            __syncthreads();                                                 // everyone has read `first` before it is set again
+            accepted = k < w;
+            const int used = accepted ? k + 1 : w;
+            if (accepted) crater_attempt(a, m + 3 * k, px, py, pr, placed, cx, cy, r);
+            s.pos += 3 * used;
+            attempts += used;
+        } else {
+            uint32_t u[3];
+            for (int i = 0; i < 3; ++i) u[i] = mt_word(s);
+            accepted = __builtin_amdgcn_readfirstlane((int)!crater_attempt(a, u, px, py, pr, placed, cx, cy, r)) != 0;
+            ++attempts;
+        }
+        if (accepted) {
+            const double angle = (double)mt_next(s) * a.aspan + a.amin;      // no FMA (-ffp-contract=off)
+            // _crater_plan: profile size, centre cell, slice bounds
+            const float two_r = __fadd_rn(r, r);
+            const int n = (int)ceilf(__fdiv_rn(two_r, a.res));
+            const int ccx = min(max((int)floorf(__fdiv_rn(__fsub_rn(cx, a.org), a.res)), 0), G - 1);
+            const int ccy = min(max((int)floorf(__fdiv_rn(__fsub_rn(cy, a.org), a.res)), 0), G - 1);
+            const int half = n / 2;
+            const int sx = max(ccx - half, 0), sy = max(ccy - half, 0), ex = min(ccx + half, N), ey = min(ccy + half, N);
+            const int psx = max(half - ccx, 0), psy = max(half - ccy, 0);
+            const bool fits = n >= 1 && n <= a.stride && psx + (ex - sx) <= n && psy + (ey - sy) <= n;
+            if (!fits && status == 0) status = placed + 1;
+            const size_t slot = (size_t)b * a.maxc + placed;
+            const int off = (int)(slot * a.stride);
+            // torch's scalar linspace(-r, r, n)
+            const float step = n > 1 ? __fdiv_rn(two_r, (float)(n - 1)) : 0.0f;
+            for (int i = t; i < n && i < a.stride; i += kDrawThreads)
+                a.lin[off + i] = i < half ? __fadd_rn(-r, __fmul_rn(step, (float)i)) : __fsub_rn(r, __fmul_rn(step, (float)(n - 1 - i)));
+            if (t == 0) {
+                px[placed] = cx; py[placed] = cy; pr[placed] = r;
+                int32_t *ci = a.cr_int + slot * 8;
+                ci[0] = sx; ci[1] = sy; ci[2] = ex; ci[3] = ey; ci[4] = psx; ci[5] = psy; ci[6] = n;
+                ci[7] = fits ? off : -1;                                     // the crater kernel carves offsets >= 0 only
+                const float rad = __fmul_rn((float)angle, (float)(M_PI / 180.0));          // deg2rad in float32
+                a.cr_val[slot * 2] = r;
+                a.cr_val[slot * 2 + 1] = (float)(-tan((double)rad));
+                a.centers[slot * 2] = cx; a.centers[slot * 2 + 1] = cy;
+                a.angles[slot] = angle;
+            }
+            __syncthreads();
+            ++placed;
+        }
+        if (attempts > kMaxAttempts) { gave_up = 1; break; }                 // count > 1000 after the attempt, accepted or not
+    }
+    if (a.fractal) {                                                         // generate_fractal_surface's uniforms, a block at a time
+        float *ph = a.phases + (size_t)b * a.nph;
+        for (int k = 0; k < a.nph;) {
+            if (s.pos == kMtN) mt_refill(s);
+            const int m = min(a.nph - k, kMtN - s.pos);
+            for (int i = t; i < m; i += kDrawThreads) ph[k + i] = mt_uniform(s.mt[s.cur][s.pos + i]);
+            k += m;
+            s.pos += m;
+        }
+    }
+    float ua = 0.0f, uz = 0.0f;
+    if (a.with_light) {                                                      // create_shading :511-517
+        ua = mt_next(s);
+        uz = mt_next(s);
+    }
+    if (t == 0) {
+        a.cr_count[b] = placed;
+        int32_t *rec = a.rec + (size_t)b * kDrawRecord;
+        rec[0] = attempts; rec[1] = gave_up; rec[2] = status; rec[3] = placed;
+        a.light_u[b * 2] = ua; a.light_u[b * 2 + 1] = uz;
+        if (a.with_light) {
+            const float ang = __fmul_rn(ua, (float)(2.0 * M_PI));
+            const float z = __fadd_rn(__fmul_rn(uz, a.lspan), a.llo);
+            const float rad = sqrtf(__fsub_rn(1.0f, __fmul_rn(z, z)));
+            double sn, cs;
+            sincos((double)ang, &sn, &cs);
+            a.light[b * 3] = __fmul_rn(rad, (float)cs);
+            a.light[b * 3 + 1] = __fmul_rn(rad, (float)sn);
+            a.light[b * 3 + 2] = z;
+        }
+    }
+}
+
 thread_local std::string g_terrain_error;
 
 }  // namespace
@@ -447,6 +656,14 @@ struct bn_terrain {
     float *noise = nullptr, *colors = nullptr, *thr = nullptr, *ctable = nullptr, *light = nullptr, *cz_heights = nullptr;
     int32_t *cstart = nullptr, *counts = nullptr, *cz_classes = nullptr;
     uint64_t *cseeds = nullptr;
+    // the draws on the device (bn_terrain_set_draw_params / bn_terrain_draw_async)
+    bool have_draw_params = false, drawn = false, dr_crater = true, dr_light = false;
+    int dr_num = 0, dr_slots = 0;            // craters asked for; slots the record buffers were sized for
+    double dr_margin = 5.0, dr_amin = 10.0, dr_amax = 20.0, dr_rmin = 5.0, dr_rmax = 10.0, dr_llo = 0.8, dr_lhi = 1.0;
+    uint64_t *dseeds = nullptr, *dseeds_pinned = nullptr;      // pinned staging: the seeds reach the device on the caller's stream
+    int32_t *drec = nullptr;
+    float *dcenters = nullptr, *dlight_u = nullptr;
+    double *dangles = nullptr;
 };
 
 namespace {
@@ -525,6 +742,49 @@ int ensure_color_buffers(bn_terrain_t *h, int C)
     return BN_OK;
 }
 
+// profile points a crater slot of the device draws holds: ceil(f32(2 r) / f32(res)) for the largest radius, and two to spare
+int64_t draw_stride(const bn_terrain_t *h)
+{
+    const double rmax = std::max(h->dr_rmin, h->dr_rmax);
+    return (int64_t)std::ceil(2.0 * rmax / h->resolution) + 2;
+}
+
+// Size the crater tables, the profile slots and the per-instance records for the draw parameters as they stand (a host
+// bn_terrain_set_draws in between may have resized the tables).  Waits for the handle's work before it frees anything.
+int ensure_draw_buffers(bn_terrain_t *h)
+{
+    const int slots = std::max(h->dr_crater ? h->dr_num : 0, 1);
+    const int64_t need = (int64_t)h->B * slots * draw_stride(h);
+    if (need > ((int64_t)1 << 30)) return terrain_fail(BN_ERR_INVALID, "the crater profiles (B x num_craters x 2 max_radius / resolution) must fit 2^30 values");
+    int rc = BN_OK;
+    if (slots != h->maxc || slots != h->dr_slots || need > h->lin_len || !h->drec) {
+        if ((rc = wait_done(h))) return rc;
+    }
+    if (slots != h->maxc) {
+        if ((rc = realloc_dev(&h->cr_int, (size_t)h->B * slots * 32)) || (rc = realloc_dev(&h->cr_val, (size_t)h->B * slots * 8))) return rc;
+        TERRAIN_HIP(hipMemset(h->cr_int, 0, (size_t)h->B * slots * 32));
+        TERRAIN_HIP(hipMemset(h->cr_val, 0, (size_t)h->B * slots * 8));
+        h->maxc = slots;
+    }
+    if (slots != h->dr_slots) {
+        if ((rc = realloc_dev(&h->dcenters, (size_t)h->B * slots * 8)) || (rc = realloc_dev(&h->dangles, (size_t)h->B * slots * 8))) return rc;
+        TERRAIN_HIP(hipMemset(h->dcenters, 0, (size_t)h->B * slots * 8));
+        TERRAIN_HIP(hipMemset(h->dangles, 0, (size_t)h->B * slots * 8));
+        h->dr_slots = slots;
+    }
+    if (need > h->lin_len) {
+        if ((rc = realloc_dev(&h->lin, (size_t)need * 4))) return rc;
+    }
+    h->lin_len = (int)need;
+    if (!h->drec) {
+        if ((rc = realloc_dev(&h->dseeds, (size_t)h->B * 8)) || (rc = realloc_dev(&h->drec, (size_t)h->B * bn::kDrawRecord * 4)) ||
+            (rc = realloc_dev(&h->dlight_u, (size_t)h->B * 8)))
+            return rc;
+        if (!h->dseeds_pinned) TERRAIN_HIP(hipHostMalloc((void **)&h->dseeds_pinned, (size_t)h->B * 8, hipHostMallocDefault));
+    }
+    return BN_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -581,8 +841,10 @@ void bn_terrain_destroy(bn_terrain_t *h)
                     (void *)h->stddev, (void *)h->classes, (void *)h->phases, (void *)h->cr_count, (void *)h->cr_int,
                     (void *)h->cr_val, (void *)h->lin, (void *)h->cparams, (void *)h->noise, (void *)h->colors, (void *)h->thr,
                     (void *)h->ctable, (void *)h->light, (void *)h->cz_heights, (void *)h->cstart, (void *)h->counts,
-                    (void *)h->cz_classes, (void *)h->cseeds})
+                    (void *)h->cz_classes, (void *)h->cseeds, (void *)h->dseeds, (void *)h->drec, (void *)h->dcenters,
+                    (void *)h->dlight_u, (void *)h->dangles})
         if (p) (void)hipFree(p);
+    if (h->dseeds_pinned) (void)hipHostFree(h->dseeds_pinned);
     if (h->ev_done) (void)hipEventDestroy(h->ev_done);
     delete h;
 }
@@ -633,6 +895,95 @@ int bn_terrain_set_draws(bn_terrain_t *h, const float *phases, const int32_t *cr
     TERRAIN_HIP(hipMemcpy(h->cr_val, crater_val, (size_t)h->B * max_craters * 8, hipMemcpyHostToDevice));
     TERRAIN_HIP(hipMemcpy(h->lin, lin, (size_t)lin_len * 4, hipMemcpyHostToDevice));
     h->have_draws = true;
+    h->drawn = false;
+    return BN_OK;
+}
+
+int bn_terrain_set_draw_params(bn_terrain_t *h, int32_t is_crater, int32_t num_craters, double crater_margin, double min_angle,
+                               double max_angle, double min_radius, double max_radius, int32_t with_light, double lower_threshold,
+                               double upper_threshold)
+{
+    if (!h) return terrain_fail(BN_ERR_INVALID, "null handle");
+    if (!h->have_geometry) return terrain_fail(BN_ERR_STATE, "the geometry (resolution) must be set first");
+    if (num_craters < 0 || num_craters > bn::kMaxDrawCraters)
+        return terrain_fail(BN_ERR_INVALID, "num_craters must be in [0, " + std::to_string(bn::kMaxDrawCraters) + "], the crater slots of the device draws");
+    for (double v : {crater_margin, min_angle, max_angle, min_radius, max_radius, lower_threshold, upper_threshold})
+        if (!std::isfinite(v)) return terrain_fail(BN_ERR_INVALID, "the draw parameters must be finite");
+    if (!(min_radius > 0.0) || !(max_radius > 0.0)) return terrain_fail(BN_ERR_INVALID, "min_radius and max_radius must be > 0");
+    const int slots = std::max(is_crater ? num_craters : 0, 1);
+    const double stride = std::ceil(2.0 * std::max(min_radius, max_radius) / h->resolution) + 2.0;
+    if (!(stride * slots * h->B <= (double)((int64_t)1 << 30)))
+        return terrain_fail(BN_ERR_INVALID, "the crater profiles (B x num_craters x 2 max_radius / resolution) must fit 2^30 values");
+    TerrainDeviceGuard guard(h->device);
+    if (!guard.ok) return terrain_fail(BN_ERR_HIP, "hipSetDevice failed");
+    h->dr_crater = is_crater != 0; h->dr_num = num_craters; h->dr_light = with_light != 0;
+    h->dr_margin = crater_margin; h->dr_amin = min_angle; h->dr_amax = max_angle; h->dr_rmin = min_radius; h->dr_rmax = max_radius;
+    h->dr_llo = lower_threshold; h->dr_lhi = upper_threshold;
+    h->have_draw_params = true;
+    return ensure_draw_buffers(h);
+}
+
+int bn_terrain_draw_async(bn_terrain_t *h, const uint64_t *seeds, void *stream)
+{
+    if (!h || !seeds) return terrain_fail(BN_ERR_INVALID, "null argument");
+    if (!h->have_geometry || !h->have_draw_params) return terrain_fail(BN_ERR_STATE, "geometry and draw parameters must be set first");
+    if (h->dr_light && !h->light) return terrain_fail(BN_ERR_STATE, "the light source is drawn for the colouring: set it first");
+    TerrainDeviceGuard guard(h->device);
+    if (!guard.ok) return terrain_fail(BN_ERR_HIP, "hipSetDevice failed");
+    int rc = wait_done(h);                   // the last draws or generation: the staging buffer and the tables are free again
+    if (rc || (rc = ensure_draw_buffers(h))) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    std::memcpy(h->dseeds_pinned, seeds, (size_t)h->B * 8);                  // the caller's seeds are consumed before this returns
+    TERRAIN_HIP(hipMemcpyAsync(h->dseeds, h->dseeds_pinned, (size_t)h->B * 8, hipMemcpyHostToDevice, s));
+    const double res = h->resolution, x0 = h->G * res / 2 - h->G / 2.0 * res;
+    bn::DrawArgs a{};
+    a.seeds = h->dseeds; a.phases = h->phases; a.cr_count = h->cr_count; a.cr_int = h->cr_int; a.cr_val = h->cr_val; a.lin = h->lin;
+    a.light = h->light; a.rec = h->drec; a.centers = h->dcenters; a.angles = h->dangles; a.light_u = h->dlight_u;
+    a.G = h->G; a.N = h->N; a.nph = h->nph; a.maxc = h->maxc; a.stride = (int)draw_stride(h);
+    a.want = h->dr_crater ? h->dr_num : 0; a.fractal = h->fractal; a.with_light = h->dr_light;
+    a.span = (float)((h->N - 1) * res - x0); a.org = (float)x0; a.res = (float)res;
+    a.rspan = (float)(h->dr_rmax - h->dr_rmin); a.rmin = (float)h->dr_rmin; a.margin = (float)h->dr_margin;
+    a.lspan = (float)(h->dr_lhi - h->dr_llo); a.llo = (float)h->dr_llo;
+    a.aspan = h->dr_amax - h->dr_amin; a.amin = h->dr_amin;
+    bn::terrain_draws_kernel<<<h->B, bn::kDrawThreads, 0, s>>>(a);
+    TERRAIN_HIP(hipGetLastError());
+    TERRAIN_HIP(hipEventRecord(h->ev_done, s));
+    h->ev_recorded = true;
+    h->have_draws = true;
+    h->drawn = true;
+    return BN_OK;
+}
+
+int bn_terrain_draw_layout(bn_terrain_t *h, int32_t *slots, int32_t *stride)
+{
+    if (!h || !slots || !stride) return terrain_fail(BN_ERR_INVALID, "null argument");
+    if (!h->have_draw_params) return terrain_fail(BN_ERR_STATE, "the draw parameters must be set first");
+    *slots = std::max(h->dr_crater ? h->dr_num : 0, 1);
+    *stride = (int32_t)draw_stride(h);
+    return BN_OK;
+}
+
+int bn_terrain_read_draws(bn_terrain_t *h, int32_t *records, float *centers, double *angles, float *light_uniforms, float *light,
+                          int32_t *crater_int, float *crater_val, float *lin, float *phases)
+{
+    if (!h) return terrain_fail(BN_ERR_INVALID, "null handle");
+    if (!h->drawn) return terrain_fail(BN_ERR_STATE, "no draws made on the device yet");
+    if (h->maxc != h->dr_slots) return terrain_fail(BN_ERR_STATE, "the crater tables were replaced by host draws since the device drew");
+    if (light && !h->light) return terrain_fail(BN_ERR_STATE, "colouring has not been set");
+    TerrainDeviceGuard guard(h->device);
+    if (!guard.ok) return terrain_fail(BN_ERR_HIP, "hipSetDevice failed");
+    int rc = wait_done(h);
+    if (rc) return rc;
+    const size_t B = (size_t)h->B, slots = (size_t)h->dr_slots;
+    if (records) TERRAIN_HIP(hipMemcpy(records, h->drec, B * bn::kDrawRecord * 4, hipMemcpyDeviceToHost));
+    if (centers) TERRAIN_HIP(hipMemcpy(centers, h->dcenters, B * slots * 8, hipMemcpyDeviceToHost));
+    if (angles) TERRAIN_HIP(hipMemcpy(angles, h->dangles, B * slots * 8, hipMemcpyDeviceToHost));
+    if (light_uniforms) TERRAIN_HIP(hipMemcpy(light_uniforms, h->dlight_u, B * 8, hipMemcpyDeviceToHost));
+    if (light) TERRAIN_HIP(hipMemcpy(light, h->light, B * 12, hipMemcpyDeviceToHost));
+    if (crater_int) TERRAIN_HIP(hipMemcpy(crater_int, h->cr_int, B * slots * 32, hipMemcpyDeviceToHost));
+    if (crater_val) TERRAIN_HIP(hipMemcpy(crater_val, h->cr_val, B * slots * 8, hipMemcpyDeviceToHost));
+    if (lin) TERRAIN_HIP(hipMemcpy(lin, h->lin, B * slots * (size_t)draw_stride(h) * 4, hipMemcpyDeviceToHost));
+    if (phases) TERRAIN_HIP(hipMemcpy(phases, h->phases, B * (size_t)h->nph * 4, hipMemcpyDeviceToHost));
     return BN_OK;
 }
 

@@ -12,7 +12,7 @@ field the classes are the reference's on that field), or the library's own seede
 The two uniforms of the light source are replayed after the fBm phases and the light vector is built with the reference's torch
 calls; the class thresholds are torch's float32 cumsum; the copper colour table is computed here without matplotlib.
 
-The random draws stay on the host, in the reference's order on torch's CPU generator (`GridMap(seed=...)` seeds it,
+By default the random draws are made on the host, in the reference's order on torch's CPU generator (`GridMap(seed=...)` seeds it,
 grid_map.py:52): the crater rejection loop touches a few scalars per attempt, and the fBm phases are then ONE `torch.rand(n)`,
 which on torch's CPU generator equals n successive `torch.rand(1)` calls (tests/test_terrain_host.py asserts this).  A reference
 run on a CUDA generator draws another stream: parity with it is out of scope.  Each crater's profile coordinates and slope come
@@ -20,6 +20,10 @@ from the reference's own torch calls (linspace, tan) on the host; torch's CPU li
 like the reference's own output, they can differ by an ulp between CPUs.  The device (csrc/terrain_kernels.hip) does the
 arithmetic for B instances per launch: crater carving with a min-shift after every crater, the fBm spectrum, a dense 2-D inverse
 DFT in float64, the Horn slopes and the per-class slip maps.
+
+`generate(..., draws="device")` makes the same draws on the device instead (terrain_draws_kernel: torch's MT19937 stream per
+seed, the crater loop, the crater tables, the phases, the light source), so a batch of seeds becomes a batch of
+instances with no per-instance host work; one small read-back then fills the crater tables of the result.
 
 Only `start_pos = goal_pos = None` is supported (how DatasetGenerator calls set_terrain_geometry); with a start and a goal the
 reference's overlap test compares a (2, 1, 2) centre table per coordinate, a path not mirrored here.
@@ -238,6 +242,17 @@ def replay_draws(seed: int, grid_size: int, resolution: float, is_fractal: bool 
     return d
 
 
+def check_draw_records(records: np.ndarray, radii: np.ndarray, grid_size: int) -> None:
+    """What replay_draws raises, from the device draws' records ((B, 4) int32: attempts, gave_up, status, craters placed) and the
+    (B, slots) float32 radii: the ValueError of the first crater whose slices disagree in shape (status = 1 + its index), else one
+    "Failed to place all craters" warning if an instance gave up."""
+    for b in np.flatnonzero(records[:, 2] != 0):
+        radius = float(radii[b, int(records[b, 2]) - 1])
+        raise ValueError(f"crater of radius {radius} does not fit a {grid_size}x{grid_size} map: the reference's slices disagree in shape")
+    if records[:, 1].any():
+        warnings.warn("Failed to place all craters after 1000 attempts. Consider adjusting the parameters.")
+
+
 def _as_param_table(models):
     """((C, 6) float32 rows, number of models): the rows are (present, f32(sens * 1e-3), nonlinearity, offset, base noise, slope noise) for class indices 0..C-1."""
     items = dict(enumerate(models)) if isinstance(models, (list, tuple)) else dict(models)
@@ -292,11 +307,17 @@ class TerrainGenerator:
                  crater_margin: float = 5, min_angle: float = 10, max_angle: float = 20, min_radius: float = 5,
                  max_radius: float = 10, t_classes=None, slip_models=None, start_pos=None, goal_pos=None, occupancy=None, noise=None,
                  feature_size: float = 20, lower_threshold: float = 0.8, upper_threshold: float = 1.0,
-                 ambient_intensity: float = 0.1) -> Terrain:
+                 ambient_intensity: float = 0.1, draws: str = "host") -> Terrain:
         """B instances from B seeds.  `occupancy` ((C,) or (B, C) class ratios, e.g. rows of occupancies()) asks for the colouring
         step: the terrain classes are cut from a noise field -- `noise` ((G, G) or (B, G, G)), or the library's own keyed by each
         seed -- and the colours are the classes' copper colours shaded by the heights.  Without it, nothing changes: the classes
-        are `t_classes` (default all zero) and the colours zero."""
+        are `t_classes` (default all zero) and the colours zero.
+
+        `draws="host"` replays every instance's draws on torch's CPU generator (replay_draws); `draws="device"` makes the same draws
+        in one kernel launch ahead of the generation, with no per-instance host work: the result's `draws` then carry the crater
+        tables without the profile coordinates and without the phases (device_draws() fetches everything)."""
+        if draws not in ("host", "device"):
+            raise ValueError(f'draws must be "host" or "device", got {draws!r}')
         if start_pos is not None or goal_pos is not None:
             raise NotImplementedError("start_pos / goal_pos crater avoidance is not mirrored (DatasetGenerator passes neither)")
         seeds = [int(s) for s in seeds]
@@ -308,6 +329,10 @@ class TerrainGenerator:
         if occupancy is not None and t_classes is not None:
             raise ValueError("t_classes= and occupancy= are two sources for one class map: pass one")
         coloring = None if occupancy is None else (lower_threshold, upper_threshold)
+        if draws == "device":
+            return self._generate_device(seeds, is_fractal, (is_crater, num_craters, crater_margin, min_angle, max_angle, min_radius,
+                                                             max_radius), coloring, t_classes, slip_models, occupancy, noise,
+                                         feature_size, ambient_intensity)
         draws = [replay_draws(s, G, self.resolution, is_fractal, is_crater, num_craters, crater_margin, min_angle, max_angle,
                               min_radius, max_radius, coloring=coloring) for s in seeds]
         return self.generate_from_draws(draws, is_fractal, t_classes, slip_models, occupancy=occupancy, noise=noise,
@@ -376,42 +401,140 @@ class TerrainGenerator:
             raise ValueError(f"noise must be ({G}, {G}) or ({B}, {G}, {G}), got {n.shape}")
         return np.ascontiguousarray(n, dtype=np.float32)
 
-    def _generate_colored(self, draws, is_fractal, slip_models, occupancy, noise, feature_size, ambient_intensity) -> Terrain:
+    def _set_colored(self, draws, seeds, is_fractal, slip_models, occupancy, noise, feature_size, ambient_intensity) -> np.ndarray:
+        """Validate and set the colouring step's inputs and the slip table; with `draws` (host draws) they are uploaded too and
+        carry the light vectors, without, the light is left to the device draws of `seeds`.  Returns the (B, 3) light set."""
         B, G = self.batch, self.grid_size
         occ = self._occupancy_rows(occupancy)
         C_ = occ.shape[1]
-        if any(d.light is None for d in draws):
-            raise ValueError("colouring needs the light vectors: make the draws with replay_draws(..., coloring=True)")
-        light = np.ascontiguousarray(np.stack([d.light for d in draws]), dtype=np.float32)
+        if draws is None:
+            light = np.zeros((B, 3), np.float32)
+        else:
+            if any(d.light is None for d in draws):
+                raise ValueError("colouring needs the light vectors: make the draws with replay_draws(..., coloring=True)")
+            light = np.ascontiguousarray(np.stack([d.light for d in draws]), dtype=np.float32)
         thr = np.ascontiguousarray((torch.cumsum(occ, dim=1) * 100).numpy(), dtype=np.float32)          # :428, per row
         start = np.array([int((row > 0).nonzero().min().item()) for row in occ], np.int32)             # :431
         table = np.ascontiguousarray(_copper_table(C_))
-        field_, seeds = None, None
+        field_ = None
         if noise is not None:
-            field_ = self._noise_fields(noise)
-        else:
+            field_, seeds = self._noise_fields(noise), None
+        elif draws is not None:
             if any(d.seed is None for d in draws):
                 raise ValueError("the library's own noise is keyed by the instance seeds: draws without a seed need noise=")
             seeds = np.array([d.seed % (1 << 64) for d in draws], np.uint64)
         models = _default_slip_models(1) if slip_models is None else slip_models
         tab, nmodels = _as_param_table(models)
-        self.upload_draws(draws, is_fractal)
+        if draws is not None:
+            self.upload_draws(draws, is_fractal)
         self._check(self._lib.bn_terrain_set_coloring(
             self._handle, 1, thr.ctypes.data, start.ctypes.data, C_, table.ctypes.data, light.ctypes.data, float(ambient_intensity),
             float(feature_size), None if field_ is None else field_.ctypes.data, None if seeds is None else seeds.ctypes.data, nmodels))
         self._check(self._lib.bn_terrain_set_slip(self._handle, None, tab.ctypes.data, tab.shape[0]))
-        self._check(self._lib.bn_terrain_generate_async(self._handle, C.c_void_p(torch.cuda.current_stream(self._dev).cuda_stream)))
+        return light
+
+    def _check_class_counts(self) -> None:
+        B = self.batch
         unassigned, beyond = np.zeros(B, np.int32), np.zeros(B, np.int32)
         self._check(self._lib.bn_terrain_class_counts(self._handle, unassigned.ctypes.data, beyond.ctypes.data))
         if unassigned.any():
             warnings.warn("Some grid cells have not been assigned a terrain class.")                    # :440-441
         if unassigned.any() or beyond.any():                                                            # set_traversability :554-557
             raise ValueError("The number of terrain classes exceeds the number of slip models.")
+
+    def _generate_colored(self, draws, is_fractal, slip_models, occupancy, noise, feature_size, ambient_intensity) -> Terrain:
+        light = self._set_colored(draws, None, is_fractal, slip_models, occupancy, noise, feature_size, ambient_intensity)
+        self._check(self._lib.bn_terrain_generate_async(self._handle, C.c_void_p(torch.cuda.current_stream(self._dev).cuda_stream)))
+        self._check_class_counts()
         out = self.outputs()
         cls, colors, nz = self._color_outputs()
         self._last = Terrain(*out, t_classes=cls.cpu().to(torch.int64), craters=self._crater_tables(draws), draws=draws,
                              colors=colors, noise=nz, light=light)
         return self._last
+
+    def _generate_device(self, seeds, is_fractal, geometry, coloring, t_classes, slip_models, occupancy, noise, feature_size,
+                         ambient_intensity) -> Terrain:
+        """generate() with the draws made on the device: parameters, one draws launch, the generation, one small read-back."""
+        B, G = self.batch, self.grid_size
+        is_crater, num_craters, crater_margin, min_angle, max_angle, min_radius, max_radius = geometry
+        lo, hi = (0.8, 1.0) if coloring is None else coloring
+        keys = np.array([s % (1 << 64) for s in seeds], np.uint64)
+        stream = C.c_void_p(torch.cuda.current_stream(self._dev).cuda_stream)
+        self._check(self._lib.bn_terrain_set_geometry(self._handle, self.resolution, self.roughness_exponent, self.amplitude_gain,
+                                                      int(bool(is_fractal))))
+        self._check(self._lib.bn_terrain_set_draw_params(self._handle, int(bool(is_crater)), int(num_craters), float(crater_margin),
+                                                         float(min_angle), float(max_angle), float(min_radius), float(max_radius),
+                                                         int(coloring is not None), float(lo), float(hi)))
+        if coloring is not None:
+            self._set_colored(None, keys, is_fractal, slip_models, occupancy, noise, feature_size, ambient_intensity)
+        else:
+            self._check(self._lib.bn_terrain_set_coloring(self._handle, 0, None, None, 0, None, None, 0.0, 0.0, None, None, 0))
+            cls = self._class_maps(t_classes)
+            models = _default_slip_models(1) if slip_models is None else slip_models
+            tab, nmodels = _as_param_table(models)
+            present = np.unique(cls)
+            if present.min() < 0 or present.max() >= nmodels:                                    # set_traversability :556-559
+                raise ValueError("The number of terrain classes exceeds the number of slip models.")
+            cls32 = np.ascontiguousarray(cls, dtype=np.int32)
+            self._check(self._lib.bn_terrain_set_slip(self._handle, cls32.ctypes.data, tab.ctypes.data, tab.shape[0]))
+        self._check(self._lib.bn_terrain_draw_async(self._handle, keys.ctypes.data, stream))
+        slots, stride = C.c_int32(), C.c_int32()                  # the sizes of the tables the read-back copies
+        self._check(self._lib.bn_terrain_draw_layout(self._handle, C.byref(slots), C.byref(stride)))
+        self._device = {"seeds": [int(s) for s in seeds], "light": coloring is not None, "fractal": bool(is_fractal),
+                        "slots": slots.value, "stride": stride.value}
+        self._check(self._lib.bn_terrain_generate_async(self._handle, stream))
+        drawn = self._read_draws(full=False)
+        if coloring is not None:
+            self._check_class_counts()
+        out = self.outputs()
+        if coloring is not None:
+            cls_t, colors, nz = self._color_outputs()
+            self._last = Terrain(*out, t_classes=cls_t.cpu().to(torch.int64), craters=self._crater_tables(drawn), draws=drawn,
+                                 colors=colors, noise=nz, light=np.stack([d.light for d in drawn]))
+        else:
+            with torch.cuda.device(self._dev):
+                colors = torch.zeros((B, 3, G, G), device=self._dev)
+            self._last = Terrain(*out, t_classes=torch.from_numpy(cls.astype(np.int64)), craters=self._crater_tables(drawn),
+                                 draws=drawn, colors=colors)
+        return self._last
+
+    def _read_draws(self, full: bool) -> List[Draws]:
+        """The draws the device made last, one Draws per instance: the records and crater tables and, with `full`, each crater's
+        profile coordinates and the phases.  Raises what replay_draws raises (check_draw_records)."""
+        B, G = self.batch, self.grid_size
+        dev = getattr(self, "_device", None)
+        if dev is None:
+            raise RuntimeError('generate(..., draws="device") has not run')
+        slots, stride = dev["slots"], dev["stride"]
+        rec = np.zeros((B, 4), np.int32)
+        centers, angles = np.zeros((B, slots, 2), np.float32), np.zeros((B, slots), np.float64)
+        ints, vals = np.zeros((B, slots, 8), np.int32), np.zeros((B, slots, 2), np.float32)
+        light_u, light = np.zeros((B, 2), np.float32), np.zeros((B, 3), np.float32)
+        lin = np.zeros((B, slots, stride), np.float32) if full else None
+        ph = np.zeros((B, num_phases(G)), np.float32) if full and dev["fractal"] else None
+        self._check(self._lib.bn_terrain_read_draws(
+            self._handle, rec.ctypes.data, centers.ctypes.data, angles.ctypes.data, light_u.ctypes.data,
+            light.ctypes.data if dev["light"] else None, ints.ctypes.data, vals.ctypes.data,
+            None if lin is None else lin.ctypes.data, None if ph is None else ph.ctypes.data))
+        check_draw_records(rec, vals[:, :, 0], G)
+        out = []
+        for b in range(B):
+            craters = []
+            for j in range(int(rec[b, 3])):
+                n = int(ints[b, j, 6])
+                craters.append(Crater(centers[b, j].copy(), float(vals[b, j, 0]), float(angles[b, j]), n, tuple(int(v) for v in ints[b, j, :6]),
+                                      lin[b, j, :n].copy() if full else np.zeros(0, np.float32), float(vals[b, j, 1])))
+            d = Draws(craters, int(rec[b, 0]), bool(rec[b, 1]), ph[b].copy() if ph is not None else np.zeros(0, np.float32),
+                      seed=dev["seeds"][b])
+            if dev["light"]:
+                d.light_uniforms, d.light = light_u[b].copy(), light[b].copy()
+            out.append(d)
+        return out
+
+    def device_draws(self) -> List[Draws]:
+        """The draws of the last generate(..., draws="device") as full Draws objects (profile coordinates and phases included), as
+        replay_draws would return them: generate_from_draws() takes them."""
+        return self._read_draws(full=True)
 
     def _color_outputs(self):
         """(classes int32 (B, G, G), colours (B, 3, G, G), noise (B, G, G)) device tensors (copies)."""

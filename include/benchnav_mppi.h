@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define BN_MPPI_ABI_VERSION 5
+#define BN_MPPI_ABI_VERSION 6
 
 typedef enum bn_status {
     BN_OK = 0,
@@ -578,8 +578,9 @@ int bn_astar_dwa_set_root(bn_mppi_t *h, int32_t instance, int32_t ix, int32_t iy
 /*
  * Terrain generation (csrc/terrain_kernels.hip): TerrainGeometry.set_terrain_geometry (craters, fBm, Horn slopes) and
  * TerrainTraversability.set_traversability (src/environments/terrain_properties.py) for B instances of one grid size G per
- * launch.  The random draws are made on the host in the reference's order (benchnav_amd/terrain.py) and set here; the device
- * does the arithmetic.  Outputs are (B, G, G) float32: heights, slopes (degrees), latent slip mean and stddev.  G <= 1024.
+ * launch.  The random draws are either made on the host in the reference's order (benchnav_amd/terrain.py) and set here
+ * (bn_terrain_set_draws), or made on the device from the seeds (bn_terrain_set_draw_params + bn_terrain_draw_async: the same
+ * MT19937 stream); the device does the arithmetic.  Outputs are (B, G, G) float32: heights, slopes (degrees), latent slip mean and stddev.  G <= 1024.
  * Host arguments are copied synchronously.  Errors: bn_terrain_last_error().
  */
 typedef struct bn_terrain bn_terrain_t;
@@ -593,6 +594,28 @@ int bn_terrain_set_geometry(bn_terrain_t *h, double resolution, double roughness
  * (B, max_craters, 2) = float32 radius and -tan(deg2rad(angle)); lin (lin_len) holds each crater's linspace(-r, r, n). */
 int bn_terrain_set_draws(bn_terrain_t *h, const float *phases, const int32_t *crater_count, const int32_t *crater_int,
                          const float *crater_val, int32_t max_craters, const float *lin, int64_t lin_len);
+/* The parameters of the draws made on the device (set_terrain_geometry's, and create_shading's thresholds): is_crater, num_craters
+ * (at most 64, the crater slots of the device draws), crater_margin, the angle range in degrees and the radius range (> 0) in
+ * metres; with_light != 0 also draws the light source of the colouring between lower_threshold and upper_threshold.  Needs the
+ * geometry (the resolution sizes the profile slots: B x num_craters x (2 max_radius / resolution + 2) values, at most 2^30). */
+int bn_terrain_set_draw_params(bn_terrain_t *h, int32_t is_crater, int32_t num_craters, double crater_margin, double min_angle,
+                               double max_angle, double min_radius, double max_radius, int32_t with_light, double lower_threshold,
+                               double upper_threshold);
+/* Enqueues the draws of B instances on `stream` from seeds (B, host; the low 32 bits seed MT19937 as torch's CPU generator does):
+ * the crater loop, the crater tables, the phases and, with with_light, the light vectors (bn_terrain_set_coloring comes first and
+ * its `light` is then replaced).  Writes what bn_terrain_set_draws would upload, so it counts as "draws set" for
+ * bn_terrain_generate_async on the same stream. */
+int bn_terrain_draw_async(bn_terrain_t *h, const uint64_t *seeds, void *stream);
+/* The sizes bn_terrain_read_draws' tables have under the draw parameters as they stand: S crater slots per instance and the
+ * profile stride of a slot. */
+int bn_terrain_draw_layout(bn_terrain_t *h, int32_t *slots, int32_t *stride);
+/* Waits and copies what the device drew (any pointer may be NULL): records (B, 4) int32 = attempts, gave_up, status (0, or 1 + the
+ * first crater whose slices disagree in shape: it was not carved), craters placed; centers (B, S, 2) float32, angles (B, S) float64
+ * degrees, S slots (bn_terrain_draw_layout); light_uniforms (B, 2) and light (B, 3) float32; crater_int (B, S, 8) and crater_val
+ * (B, S, 2) as in bn_terrain_set_draws, the lin offset being slot * stride (-1 for a crater that
+ * does not fit); lin (B, S, stride) float32; phases (B, nph) float32. */
+int bn_terrain_read_draws(bn_terrain_t *h, int32_t *records, float *centers, double *angles, float *light_uniforms, float *light,
+                          int32_t *crater_int, float *crater_val, float *lin, float *phases);
 /* Class maps t_classes (B, G, G) and per-class rows of 6 float32: present (0: the class has no model, its cells stay inf),
  * f32(slip_sensitivity * 1e-3), slip_nonlinearity, slip_offset, base_noise_scale, slope_noise_scale.  t_classes may be NULL: the
  * device's class map is left as it is (the colouring step writes it, bn_terrain_set_coloring). */
