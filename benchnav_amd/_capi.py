@@ -32,7 +32,7 @@ BN_FLAG_UNORDERED_OUTPUTS = 16384
 BN_BUF_STATES_ALT, BN_BUF_CONTROLS_ALT = 10, 11
 BN_RISK_EXPECTED, BN_RISK_VAR, BN_RISK_CVAR = 0, 1, 2
 BN_AD_OK, BN_AD_OUT_OF_BOUNDS, BN_AD_GOAL_COLLISION, BN_AD_FIELD_ERROR = 0, 1, 2, 3   # bn_astar_dwa_status
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 
 class Config(C.Structure):
@@ -124,12 +124,18 @@ SYMBOLS = {
     "bn_astar_kernel_ms": (C.c_int, [_H, _FP]),
     "bn_astar_path": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32]),
     "bn_astar_buffers": (C.c_int, [_H, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "bn_astar_jump_build_async": (C.c_int, [_H, C.c_void_p]),
+    "bn_astar_jump_ms": (C.c_int, [_H, _FP]),
+    "bn_astar_paths_async": (C.c_int, [_H, C.c_int32, C.c_void_p, C.c_int, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bn_astar_jump_buffers": (C.c_int, [_H, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int32),
+                                        C.POINTER(C.c_int32)]),
     "bn_astar_last_error": (C.c_char_p, []),
     "bn_astar_dwa_episode_async": (C.c_int, [_H, _H, C.c_int32, C.c_void_p, C.c_int, C.c_void_p, _FP, C.c_float, C.c_int32,
                                              C.c_int32, C.c_float, C.c_void_p]),
     "bn_astar_dwa_episode_log": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bn_astar_dwa_reset": (C.c_int, [_H]),
     "bn_astar_dwa_set_root": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32]),
+    "bn_astar_dwa_set_walk": (C.c_int, [_H, C.c_int32]),
     "bn_terrain_create": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(_H)]),
     "bn_terrain_destroy": (None, [_H]),
     "bn_terrain_set_geometry": (C.c_int, [_H, C.c_double, C.c_double, C.c_double, C.c_int32]),

@@ -4,7 +4,9 @@ Mirror of `AStar(nn.Module)` in the reference's src/planners/global_planners/sea
 forward :73-122).  The reference searches from the new start on every forward() call; the goal and the maps are fixed at
 construction and the edge weight is symmetric, so here the constructor enqueues ONE goal-rooted shortest-path solve on the
 GPU (csrc/astar_kernels.hip: the cost-to-go field and a one-byte next-hop map, copied to pinned host memory), and forward()
-walks the next-hop map on the host from the start cell: O(path length), no GPU round trip.
+walks the next-hop map on the host from the start cell: O(path length), no GPU round trip.  build_jump_tables() adds
+pointer-doubling tables over that map on the device: hop_counts() (reachability and path length of every cell) and paths()
+(forward() for many starts at once, the result staying on the device).
 
 It returns A shortest path (first minimiser in the reference's direction order among equal-cost hops); the reference returns
 one too where its search is exact, and otherwise a costlier one ("AStar").
@@ -66,6 +68,7 @@ class AStar(nn.Module):
         self._check(self._lib.bn_astar_set_goal(self._handle, 0, gx, gy))
         self._check(self._lib.bn_astar_solve_async(self._handle, C.c_void_p(torch.cuda.current_stream(self._dev).cuda_stream)))
         self._buf = np.empty((self._h * self._w, 2), np.int32)
+        self._jump_built = False                                                   # the tables come with the first use
 
     def forward(self, state: torch.Tensor) -> Optional[torch.Tensor]:
         state = state[:2] if state.shape[0] == 3 else state                        # astar.py:84
@@ -94,6 +97,69 @@ class AStar(nn.Module):
         D = torch.as_tensor(_DevArray(d.value, (self._h, self._w)), device=self._dev).clone()
         n = torch.as_tensor(_DevArray(nx.value, (self._h, self._w), typestr="|u1"), device=self._dev).clone()
         return D, n
+
+    # ---- jump tables (csrc/astar_kernels.hip): hop counts and batched paths that stay on the device --------------------------
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self._dev).cuda_stream)
+
+    def build_jump_tables(self) -> None:
+        """Build the pointer-doubling tables behind the solve (bn_astar_jump_build_async) on the current stream: hops to the
+        goal for every cell and the cell 2^k hops on, max(1, ceil(log2(H W))) levels.  hop_counts() and paths()
+        call it on first use."""
+        self._check(self._lib.bn_astar_jump_build_async(self._handle, self._stream()))
+        self._jump_built = True
+
+    def _tables(self):
+        if not self._jump_built:
+            self.build_jump_tables()
+
+    def hop_counts(self) -> torch.Tensor:
+        """(H, W) int32 device tensor: hops from every cell to the goal along the next-hop map, 0 at the goal, -1 where the goal
+        is unreachable (everywhere for a goal out of bounds or in collision).  The path from a cell has hops + 1 nodes."""
+        self._tables()
+        self._check(self._lib.bn_astar_sync(self._handle))
+        hp, jp, lv, eb = C.c_void_p(), C.c_void_p(), C.c_int32(), C.c_int32()
+        self._check(self._lib.bn_astar_jump_buffers(self._handle, 0, C.byref(hp), C.byref(jp), C.byref(lv), C.byref(eb)))
+        return torch.as_tensor(_DevArray(hp.value, (self._h, self._w), typestr="<i4"), device=self._dev).clone()
+
+    def paths(self, states: torch.Tensor, max_len: Optional[int] = None):
+        """forward() for N starts at once, on the device.  states: (N, 2) or (N, 3) positions, host or device.  Returns
+        (points, lengths): points (N, max_len, 2), points[i, :lengths[i]] == forward(states[i]) (the same node * resolution
+        arithmetic and dtype), NaN beyond; lengths (N,) int32, 0 where forward() returns None.  A path longer than max_len is
+        truncated and lengths keeps the full count; max_len=None sizes the output from the largest length (one small read-back).
+        Raises as forward() does for the goal, and for a start out of bounds (naming the first such row)."""
+        states = torch.as_tensor(states)
+        if states.dim() != 2 or states.shape[1] not in (2, 3):
+            raise ValueError(f"states must be (N, 2) or (N, 3), got {tuple(states.shape)}")
+        n = int(states.shape[0])
+        pos = states.detach()[:, :2]
+        # _pos_to_index (astar.py:215-228) per row, in the caller's dtype as forward() does it: the quotient, truncated toward zero
+        qx = ((pos[:, 0] - self.x_limits[0]) / self.resolution).trunc()
+        qy = ((pos[:, 1] - self.y_limits[0]) / self.resolution).trunc()
+        inb = (qx >= 0) & (qx < self._w) & (qy >= 0) & (qy < self._h)
+        if not self._goal_in_bounds or not bool(inb.all()):                        # astar.py:88-92
+            row = "" if bool(inb.all()) else f" (states[{int(torch.nonzero(~inb)[0, 0])}])"
+            raise ValueError("Start or goal position is out of bounds." + row)
+        if self._goal_collision:                                                   # astar.py:93-94
+            raise ValueError("Goal position is not traversable.")
+        self._tables()
+        starts = torch.stack([qx, qy], dim=1).to(torch.int32).to(self._dev).contiguous()
+        lengths = torch.empty(n, dtype=torch.int32, device=self._dev)
+
+        def run(cap, out):
+            self._check(self._lib.bn_astar_paths_async(self._handle, 0, C.c_void_p(starts.data_ptr()), _capi.BN_MEM_DEVICE, n, cap,
+                                                       C.c_void_p(None if out is None else out.data_ptr()),
+                                                       C.c_void_p(lengths.data_ptr()), self._stream()))
+        if max_len is None:
+            run(0, None)
+            max_len = int(lengths.max()) if n else 0
+        cap = int(max_len)
+        if cap < 0:
+            raise ValueError("max_len must be >= 0")
+        nodes = torch.empty((n, cap, 2), dtype=torch.int32, device=self._dev)
+        run(cap, nodes)
+        points = nodes.to(torch.int64).to(self.device) * self.resolution           # _reconstruct_path, astar.py:213
+        return torch.where(nodes.to(self.device) < 0, float("nan"), points), lengths
 
     def _pos_to_index(self, pos: torch.Tensor) -> tuple[int, int]:               # astar.py:215-228
         return (

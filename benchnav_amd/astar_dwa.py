@@ -45,10 +45,15 @@ def _per_instance(a, B: int, G: int, what: str) -> np.ndarray:
 
 class AStarDWALoop:
     def __init__(self, env, heights, risks, stuck_threshold: float, a_lim, delta_t: float, num_lin_vel: int = 10,
-                 num_ang_vel: int = 10, lookahead_distance: float = 1.0):
+                 num_ang_vel: int = 10, lookahead_distance: float = 1.0, walk: str = "serial"):
         """env: a BatchedPlanetaryEnv; its planner (NativeMPPI, horizon = DWA's horizon) rolls out the candidates on `risks` and
         its goals are the A* goals.  heights, risks: (G, G) or (B, G, G).  a_lim: DWA's acceleration limits (2,); delta_t: DWA's
-        time step for the window (dwa.py:168-199)."""
+        time step for the window (dwa.py:168-199).  walk: how the kernel reads the A* path -- "serial": one lane walks the next-hop
+        map node by node; "jump": every lane fetches its own node through the A* handle's jump tables (built here, after the
+        solve).  The outputs are bit-identical."""
+        if walk not in ("serial", "jump"):
+            raise ValueError(f"walk must be 'serial' or 'jump', got {walk!r}")
+        self.walk = walk
         planner = env.planner
         self.env, self.B, self.G = env, planner.B, planner.G
         self._lib, self._h = planner._lib, planner._h
@@ -85,6 +90,8 @@ class AStarDWALoop:
             gx, gy = self.pos_to_index(goals[b])
             self._check_astar(self._lib.bn_astar_set_goal(self._astar, b, gx, gy))
         self._check_astar(self._lib.bn_astar_solve_async(self._astar, C.c_void_p(torch.cuda.current_stream(self._dev).cuda_stream)))
+        if walk == "jump":
+            self._check_astar(self._lib.bn_astar_jump_build_async(self._astar, C.c_void_p(torch.cuda.current_stream(self._dev).cuda_stream)))
         self._prev = torch.zeros(B, 2, device=self._dev)          # the window centre: DWA's _previous_action_seq[0] (zeros, dwa.py:59)
         self._steps = 0
         self.status = np.zeros(B, np.int32)
@@ -131,6 +138,7 @@ class AStarDWALoop:
             if zp.shape != (n, self.B):
                 raise ValueError(f"z must be (n_steps, B) = {(n, self.B)}, got {tuple(zp.shape)}")
         state = env._robot_state.contiguous()
+        _capi.check(self._lib.bn_astar_dwa_set_walk(self._h, 1 if self.walk == "jump" else 0))   # (the planner handle may serve other loops)
         _capi.check(self._lib.bn_astar_dwa_episode_async(
             self._h, self._astar, n, C.c_void_p(state.data_ptr()), _capi.BN_MEM_DEVICE, C.c_void_p(self._prev.data_ptr()),
             self._a_lim, self.delta_t, self.num_lin_vel, self.num_ang_vel, self.lookahead_distance,

@@ -13,6 +13,10 @@ struct AstarDwaArgs {
     const float *arisk;           // (B, H, W) its risk maps (the goal's collision test, astar.py:93-94)
     const AStarInst *ainst;       // (B) its goal cells and stuck thresholds
     const int32_t *aerr;          // its field kernel's error word
+    const int32_t *hops;          // (B, H, W) its jump tables (walk mode 1; nullptr: the serial walk): hops to the goal, -1 unreachable
+    const int32_t *jump;          // (B, levels, H, W) the cell 2^k hops on
+    const int32_t *jerr;          // the table build's error word
+    int levels;
     int H, W;
     float *state;                 // (B, 3) in/out: the environment states
     float *prev;                  // (B, 2) in/out: the window centre (the previous argmin action, dwa.py:147)
@@ -32,7 +36,8 @@ struct AstarDwaArgs {
 
 size_t astar_dwa_lds_bytes(const SolveParams &p, int nv, int nw, int H, int W, bool next_in_lds);
 int astar_dwa_threads(int nv, int nw);
-// grid = B, one workgroup per instance; the next-hop map is staged in LDS when it fits
+// grid = B, one workgroup per instance; the next-hop map is staged in LDS when it fits.  a.hops set: the lanes fetch the path's
+// nodes through the jump tables instead of lane 0 walking next (which is then not read)
 hipError_t launch_astar_dwa(const SolveParams &p, const AstarDwaArgs &a, hipStream_t s);
 
 }  // namespace bn

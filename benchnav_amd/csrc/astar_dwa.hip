@@ -13,8 +13,10 @@
 //   3. window + sub-goal, 4. rollouts + argmin: DWA.forward (dwa.py:116-153) with dwa_device.h, the code of the stand-alone kernels.
 //   5. env step     PlanetaryEnv.step (planetary_env.py:189-219): env_advance of mppi_device.h with the argmin action.
 // The path is never materialised: one lane chases `next` (staged in LDS when it fits) a segment of nthreads nodes at a time and
-// the workgroup evaluates the segment's distances.  Pass 1 finds the nearest ahead distance over the whole path, pass 2 the first
-// index at that distance (usually in the first segment: the sub-goal lies a look-ahead distance from the rover).
+// the workgroup evaluates the segment's distances.  With the A* handle's jump tables (walk mode 1, JUMP) every lane fetches its
+// own node of the segment instead, by pointer doubling: the same nodes in the same order, so the outputs are bit-identical.
+// Pass 1 finds the nearest ahead distance over the whole path, pass 2 the first index at that distance (usually in the first
+// segment: the sub-goal lies a look-ahead distance from the rover).
 #include "../../include/benchnav_mppi.h"
 #include "astar_dwa.h"
 #include "dwa_device.h"
@@ -57,6 +59,31 @@ __device__ __forceinline__ WalkSeg walk_segment(const uint8_t *nx, int W, int ce
     return r;
 }
 
+// The same segment through the jump tables: node total + t of the path is the segment's first cell advanced over the set bits
+// of t, fetched by lane t itself.  *cur is the segment's first cell and *left the nodes of the path from it on (hops + 1; <= 0:
+// the walk does not end at the goal, a broken walk as walk_segment reports one).  t < *left <= H W <= 2^levels, so every set bit
+// of t is a kept level.  The next segment starts one hop past this one's last node.
+__device__ __forceinline__ WalkSeg jump_segment(const int32_t *jump, int cells, int *cur, int *left, int *seg, int tid, int nthreads)
+{
+    const int first = *cur, rem = *left;
+    if (rem <= 0) return WalkSeg{0, 2, first};
+    const int n = rem < nthreads ? rem : nthreads;
+    if (tid < n) {
+        int c = first;
+        for (int r = tid, lvl = 0; r; r >>= 1, ++lvl)
+            if (r & 1) c = jump[(size_t)lvl * cells + c];
+        seg[tid] = c;
+    }
+    __syncthreads();
+    const int last = seg[n - 1];
+    if (rem > nthreads) {
+        *cur = jump[last];
+        *left = rem - nthreads;
+        return WalkSeg{n, 0, last};
+    }
+    return WalkSeg{n, 1, last};
+}
+
 // row gs of the call's logs for instance b (one lane)
 __device__ __forceinline__ void log_step(const AstarDwaArgs &a, int gs, int b, float x, float y, float th, float reward, float u0, float u1,
                                          float hx, float hy)
@@ -75,7 +102,7 @@ __device__ __forceinline__ void log_frozen(const AstarDwaArgs &a, int gs, int b,
     log_step(a, gs, b, x, y, th, NAN, NAN, NAN, NAN, NAN);
 }
 
-template <int GEO, bool LDSWIN, bool NEXT_LDS>
+template <int GEO, bool LDSWIN, bool NEXT_LDS, bool JUMP>
 __global__ void astar_dwa_kernel(const SolveParams p, const AstarDwaArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -108,7 +135,9 @@ __global__ void astar_dwa_kernel(const SolveParams p, const AstarDwaArgs a)
     // the checks of AStar.forward that do not depend on the start (astar.py:88-94), in its order after a failed solve
     const AStarInst gi = a.ainst[b];
     int goal_code = BN_AD_OK;
-    if (*a.aerr != 0) goal_code = BN_AD_FIELD_ERROR;
+    const int32_t *hops = JUMP ? a.hops + (size_t)b * cells : nullptr;
+    const int32_t *jump = JUMP ? a.jump + (size_t)b * a.levels * cells : nullptr;
+    if (*a.aerr != 0 || (JUMP && *a.jerr != 0)) goal_code = BN_AD_FIELD_ERROR;
     else if (gi.gx < 0) goal_code = BN_AD_OUT_OF_BOUNDS;
     else if (a.arisk[(size_t)b * cells + (size_t)gi.gy * W + gi.gx] <= gi.thr) goal_code = BN_AD_GOAL_COLLISION;
     const size_t B = p.B;
@@ -137,7 +166,7 @@ __global__ void astar_dwa_kernel(const SolveParams p, const AstarDwaArgs a)
         dwa_window_actions(d, a.nv, a.nw, act, tid, nthreads);
         __syncthreads();                                   // (the LDS copy of next, on the first step)
         // the path: from the start cell, or -- unreachable, the reference's None -- the previous one, from the root cell
-        const int origin = nx[start] == 255 ? root : start;
+        const int origin = (JUMP ? hops[start] < 0 : nx[start] == 255) ? root : start;
         float hx = gx, hy = gy;                            // no path yet: the goal (dwa.py:243-247)
         if (origin >= 0) {
             float x, y, th;
@@ -145,9 +174,12 @@ __global__ void astar_dwa_kernel(const SolveParams p, const AstarDwaArgs a)
             // pass 1: the nearest ahead distance over the path, and the path's last point
             float best = INFINITY;
             int cur = origin, total = 0;
+            const int nodes = JUMP ? hops[origin] + 1 : 0;     // of the whole path (JUMP)
+            int left = nodes;
             WalkSeg ws;
             do {
-                ws = walk_segment(nx, W, cells, &cur, total, seg, ctl, tid, nthreads);
+                ws = JUMP ? jump_segment(jump, cells, &cur, &left, seg, tid, nthreads)
+                          : walk_segment(nx, W, cells, &cur, total, seg, ctl, tid, nthreads);
                 if (tid < ws.n) {
                     const int c = seg[tid], iy = c / W, ix = c - iy * W;
                     best = fminf(best, dwa_ahead_dist((float)ix * p.res, (float)iy * p.res, x, y, th, a.lookahead));
@@ -169,11 +201,12 @@ __global__ void astar_dwa_kernel(const SolveParams p, const AstarDwaArgs a)
             int pick = ws.last;                            // nothing ahead: the path's last point
             if (best < INFINITY) {
                 // pass 2: the first index over ALL points at that distance (torch.where(distances == min)[0][0])
-                cur = origin; total = 0;
+                cur = origin; total = 0; left = nodes;
                 int found = 0x7fffffff;
                 do {
                     __syncthreads();                       // redi of the previous segment's minimum has been read
-                    ws = walk_segment(nx, W, cells, &cur, total, seg, ctl, tid, nthreads);
+                    ws = JUMP ? jump_segment(jump, cells, &cur, &left, seg, tid, nthreads)
+                              : walk_segment(nx, W, cells, &cur, total, seg, ctl, tid, nthreads);
                     int idx = 0x7fffffff;
                     if (tid < ws.n) {
                         const int c = seg[tid], iy = c / W, ix = c - iy * W;
@@ -205,14 +238,14 @@ __global__ void astar_dwa_kernel(const SolveParams p, const AstarDwaArgs a)
     }
 }
 
-template <int GEO, bool LDSWIN, bool NEXT_LDS>
+template <int GEO, bool LDSWIN, bool NEXT_LDS, bool JUMP>
 hipError_t launch_t(const SolveParams &p, const AstarDwaArgs &a, hipStream_t s)
 {
     const int threads = astar_dwa_threads(a.nv, a.nw);
     const size_t lds = astar_dwa_lds_bytes(p, a.nv, a.nw, a.H, a.W, NEXT_LDS);
-    hipError_t e = ensure_lds(astar_dwa_kernel<GEO, LDSWIN, NEXT_LDS>, lds);
+    hipError_t e = ensure_lds(astar_dwa_kernel<GEO, LDSWIN, NEXT_LDS, JUMP>, lds);
     if (e != hipSuccess) return e;
-    astar_dwa_kernel<GEO, LDSWIN, NEXT_LDS><<<dim3(p.B), dim3(threads), lds, s>>>(p, a);
+    astar_dwa_kernel<GEO, LDSWIN, NEXT_LDS, JUMP><<<dim3(p.B), dim3(threads), lds, s>>>(p, a);
     return hipGetLastError();
 }
 
@@ -220,9 +253,11 @@ template <int GEO>
 hipError_t launch_g(const SolveParams &p, const AstarDwaArgs &a, hipStream_t s)
 {
     const bool win = p.WN > 0;
+    if (a.hops)                                            // the jump walk reads the tables from global memory, next not at all
+        return win ? launch_t<GEO, true, false, true>(p, a, s) : launch_t<GEO, false, false, true>(p, a, s);
     const bool nl = astar_dwa_lds_bytes(p, a.nv, a.nw, a.H, a.W, true) <= 160 * 1024;
-    if (win) return nl ? launch_t<GEO, true, true>(p, a, s) : launch_t<GEO, true, false>(p, a, s);
-    return nl ? launch_t<GEO, false, true>(p, a, s) : launch_t<GEO, false, false>(p, a, s);
+    if (win) return nl ? launch_t<GEO, true, true, false>(p, a, s) : launch_t<GEO, true, false, false>(p, a, s);
+    return nl ? launch_t<GEO, false, true, false>(p, a, s) : launch_t<GEO, false, false, false>(p, a, s);
 }
 
 }  // namespace

@@ -288,6 +288,123 @@ __global__ __launch_bounds__(256) void astar_next_kernel(FieldArgs a)
     a.next[i] = arg;
 }
 
+// ---- jump tables: pointer doubling over next ------------------------------------------------------------------------------
+// jump[k][c] = the cell 2^k hops from c along next (the goal and cells without a hop map to themselves); hops[c] = hops from c
+// to the goal, -1 where the walk ends on kNextNone.  Cell indices (iy * W + ix) are int32 at every map size.  levels =
+// max(1, ceil(log2(H W))) levels are kept whatever the largest hop count is: a path has at most H W nodes, so every node index
+// is a sum of kept powers of two.  Footprint: B * (levels + 2) * H W * 4 bytes (the levels and two hop buffers, read and
+// written in turn), e.g. 64^2: 224 KiB * B, 256^2: 4.5 MiB * B, 512^2: 20 MiB * B.
+//
+// The build is levels + 1 launches in stream order (level 0, levels - 1 doublings, one closing round), a fixed number whatever
+// the map holds, one thread per cell, every index read from a table written by an earlier launch and in bounds by construction:
+// a corrupt map can neither hang nor misdirect it.  Validation: level 0 rejects a code in 9-254 and a hop off the map (the cell
+// then maps to itself); the closing round composes level levels - 1 with itself, 2^levels >= H W hops, and a cell that is then
+// still on a stepping cell lies on, or leads into, a cycle.  Each sets a bit of the tables' error word and the smallest
+// offending cell index next to it.
+struct JumpArgs {
+    const uint8_t *next;     // (B, H, W)
+    int32_t *jump;           // (B, levels, H W)
+    const int32_t *hops_in;  // (B, H W) hops within the 2^k already composed
+    int32_t *hops_out;
+    int32_t *err;            // [0] error bits, [1] smallest offending cell (b * H W + c)
+    int H, W, B, levels, k;
+};
+constexpr int kJumpBadCode = 1, kJumpOffMap = 2, kJumpCycle = 4;
+
+__device__ __forceinline__ void jump_report(int32_t *err, int bit, size_t i)
+{
+    atomicOr(&err[0], bit);
+    atomicMin(&err[1], (int32_t)i);
+}
+
+__global__ __launch_bounds__(256) void astar_jump_init_kernel(JumpArgs a)
+{
+    const size_t cells = (size_t)a.H * a.W;
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= cells * a.B) return;
+    const int b = (int)(i / cells);
+    const int c = (int)(i - (size_t)b * cells);
+    const uint32_t code = a.next[i];
+    int tgt = c, hp = 0;
+    if (code < kNextGoal) {
+        const int nx = c % a.W + c_dx[code], ny = c / a.W + c_dy[code];
+        if (nx < 0 || nx >= a.W || ny < 0 || ny >= a.H) jump_report(a.err, kJumpOffMap, i);
+        else { tgt = ny * a.W + nx; hp = 1; }
+    } else if (code != kNextGoal && code != kNextNone) {
+        jump_report(a.err, kJumpBadCode, i);
+    }
+    a.jump[(size_t)b * a.levels * cells + c] = tgt;
+    a.hops_out[i] = hp;
+}
+
+// level k -> k + 1
+__global__ __launch_bounds__(256) void astar_jump_level_kernel(JumpArgs a)
+{
+    const size_t cells = (size_t)a.H * a.W;
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= cells * a.B) return;
+    const int b = (int)(i / cells);
+    const int c = (int)(i - (size_t)b * cells);
+    int32_t *lv = a.jump + ((size_t)b * a.levels + a.k) * cells;
+    const int j = lv[c];
+    lv[cells + c] = lv[j];
+    a.hops_out[i] = a.hops_in[i] + a.hops_in[(size_t)b * cells + j];
+}
+
+// the closing round: 2^levels hops from every cell, the final hop counts and the cycle test
+__global__ __launch_bounds__(256) void astar_jump_close_kernel(JumpArgs a)
+{
+    const size_t cells = (size_t)a.H * a.W;
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= cells * a.B) return;
+    const int b = (int)(i / cells);
+    const int c = (int)(i - (size_t)b * cells);
+    const int32_t *lv = a.jump + ((size_t)b * a.levels + a.levels - 1) * cells;
+    const int j = lv[c];
+    const int e = lv[j];
+    int hp = a.hops_in[i] + a.hops_in[(size_t)b * cells + j];
+    const uint32_t code = a.next[(size_t)b * cells + e];
+    if (code < kNextGoal) { jump_report(a.err, kJumpCycle, i); hp = -1; }
+    else if (code != kNextGoal) hp = -1;
+    a.hops_out[i] = hp;
+}
+
+// One thread per (start, node index): node k of the path from a start is the start advanced over the set bits of k.
+struct PathsArgs {
+    const int32_t *hops;     // (H W) of the instance
+    const int32_t *jump;     // (levels, H W) of the instance
+    const int32_t *starts;   // (n, 2) (ix, iy)
+    int32_t *out_xy;         // (n, max_len, 2)
+    int32_t *out_len;        // (n)
+    int H, W, n, max_len;
+};
+
+__global__ __launch_bounds__(256) void astar_paths_kernel(PathsArgs a)
+{
+    const int row = a.max_len > 0 ? a.max_len : 1;
+    const size_t id = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (id >= (size_t)a.n * row) return;
+    const int i = (int)(id / row);
+    const int k = (int)(id - (size_t)i * row);
+    const int sx = a.starts[2 * i], sy = a.starts[2 * i + 1];
+    const size_t cells = (size_t)a.H * a.W;
+    int len = -1, x = -1, y = -1;
+    if (sx >= 0 && sx < a.W && sy >= 0 && sy < a.H) {
+        int c = sy * a.W + sx;
+        len = a.hops[c] + 1;                     // -1 hops: unreachable, 0 nodes
+        if (k < len) {                           // k <= hops < H W <= 2^levels: every set bit is a kept level
+            for (int r = k, lvl = 0; r; r >>= 1, ++lvl)
+                if (r & 1) c = a.jump[lvl * cells + c];
+            x = c % a.W; y = c / a.W;
+        }
+    }
+    if (k == 0) a.out_len[i] = len;
+    if (k < a.max_len) {
+        a.out_xy[2 * id] = x;
+        a.out_xy[2 * id + 1] = y;
+    }
+}
+
 thread_local std::string g_astar_error;
 
 }  // namespace
@@ -309,7 +426,17 @@ struct bn_astar {
     hipEvent_t ev_start = nullptr, ev_kernels = nullptr, ev_done = nullptr;
     hipEvent_t ev_reader = nullptr;             // behind the latest fused episode that reads the buffers (bn::astar_add_reader)
     bool solved = false, pending_check = false, reader_pending = false;
+    hipStream_t reader_stream = nullptr;        // the stream ev_reader was last recorded on
     uint64_t deadline_ticks = 0;
+    // jump tables (bn_astar_jump_build_async), allocated by the first build
+    int levels = 1;
+    int32_t *jump = nullptr;                    // (B, levels, H W)
+    int32_t *hopbuf[2] = {nullptr, nullptr};    // (B, H W) each; the closing round writes hopbuf[0]
+    int32_t *jerr = nullptr, *jerr_host = nullptr;   // error bits, smallest offending cell; the pinned copy of the latest build
+    int32_t *starts_dev = nullptr;              // staging of host-side starts (bn_astar_paths_async)
+    size_t starts_cap = 0;
+    hipEvent_t ev_jump_start = nullptr, ev_jump_kernels = nullptr, ev_jump_done = nullptr;
+    bool jump_valid = false, jump_pending = false;   // built behind the latest solve and not stale; error word not yet read
 };
 
 namespace {
@@ -332,9 +459,58 @@ struct DeviceGuard {
 // an enqueued episode still reads the buffers: wait for it before they are rewritten or freed
 void wait_readers(bn_astar_t *h)
 {
+    if (h->jump_pending) {                       // a table build still reads next
+        (void)hipEventSynchronize(h->ev_jump_done);
+        h->jump_pending = false;
+    }
     if (!h->reader_pending) return;
     (void)hipEventSynchronize(h->ev_reader);
     h->reader_pending = false;
+}
+
+// the tables' buffers and events, allocated together by the first build; h->jump is set last, so it stands for all of them
+void jump_free(bn_astar_t *h)
+{
+    for (int32_t **p : {&h->jump, &h->hopbuf[0], &h->hopbuf[1], &h->jerr})
+        if (*p) { (void)hipFree(*p); *p = nullptr; }
+    if (h->jerr_host) { (void)hipHostFree(h->jerr_host); h->jerr_host = nullptr; }
+    for (hipEvent_t *e : {&h->ev_jump_start, &h->ev_jump_kernels, &h->ev_jump_done})
+        if (*e) { (void)hipEventDestroy(*e); *e = nullptr; }
+}
+
+hipError_t jump_alloc(bn_astar_t *h, size_t total)
+{
+    hipError_t e;
+    if ((e = hipMalloc((void **)&h->hopbuf[0], total * 4)) != hipSuccess) return e;
+    if ((e = hipMalloc((void **)&h->hopbuf[1], total * 4)) != hipSuccess) return e;
+    if ((e = hipMalloc((void **)&h->jerr, 2 * 4)) != hipSuccess) return e;
+    if ((e = hipHostMalloc((void **)&h->jerr_host, 2 * 4, hipHostMallocDefault)) != hipSuccess) return e;
+    if ((e = hipEventCreate(&h->ev_jump_start)) != hipSuccess) return e;
+    if ((e = hipEventCreate(&h->ev_jump_kernels)) != hipSuccess) return e;
+    if ((e = hipEventCreate(&h->ev_jump_done)) != hipSuccess) return e;
+    return hipMalloc((void **)&h->jump, total * h->levels * 4);
+}
+
+// BN_OK when the tables are current and their build found next valid (waits for a pending build)
+int jump_ready(bn_astar_t *h)
+{
+    if (!h->jump_valid)
+        return astar_fail(BN_ERR_STATE, "the jump tables are stale or were never built: bn_astar_jump_build_async must follow the latest "
+                                        "bn_astar_set_map / bn_astar_set_goal / bn_astar_solve_async");
+    if (h->jump_pending) {
+        ASTAR_HIP(hipEventSynchronize(h->ev_jump_done));
+        h->jump_pending = false;
+    }
+    const int bits = h->jerr_host[0];
+    if (bits != 0) {
+        const int64_t cells = (int64_t)h->H * h->W, i = (uint32_t)h->jerr_host[1];
+        const int64_t c = i % cells;
+        return astar_fail(BN_ERR_STATE, std::string("jump tables: next is not a valid next-hop map (") +
+                                        ((bits & bn::kJumpBadCode) ? "unknown code; " : "") + ((bits & bn::kJumpOffMap) ? "hop off the map; " : "") +
+                                        ((bits & bn::kJumpCycle) ? "cycle; " : "") + "first at instance " + std::to_string(i / cells) +
+                                        ", cell (" + std::to_string(c % h->W) + ", " + std::to_string(c / h->W) + "))");
+    }
+    return BN_OK;
 }
 
 // waits for the last solve, copies nothing: the pinned `next` and error word are already on the host
@@ -374,6 +550,7 @@ int bn_astar_create(int32_t device_id, int32_t H, int32_t W, int32_t B, bn_astar
     h->device = device_id; h->H = H; h->W = W; h->B = B;
     h->TX = (W + bn::kTile - 1) / bn::kTile;
     h->TY = (H + bn::kTile - 1) / bn::kTile;
+    while (((int64_t)1 << h->levels) < (int64_t)H * W) ++h->levels;
     const size_t cells = (size_t)H * W * B;
     h->inst.assign(B, bn::InstParams{-1, -1, 0.0f, 0});
     h->have_map.assign(B, 0);
@@ -414,11 +591,12 @@ void bn_astar_destroy(bn_astar_t *h)
     DeviceGuard guard(h->device);
     if (h->pending_check) (void)hipEventSynchronize(h->ev_done);
     wait_readers(h);
-    for (void *p : {(void *)h->heights, (void *)h->risk, (void *)h->D, (void *)h->next, (void *)h->flags, (void *)h->ctl, (void *)h->inst_dev})
+    for (void *p : {(void *)h->heights, (void *)h->risk, (void *)h->D, (void *)h->next, (void *)h->flags, (void *)h->ctl, (void *)h->inst_dev,
+                    (void *)h->jump, (void *)h->hopbuf[0], (void *)h->hopbuf[1], (void *)h->jerr, (void *)h->starts_dev})
         if (p) (void)hipFree(p);
-    for (void *p : {(void *)h->inst_pinned, (void *)h->next_host, (void *)h->ctl_host})
+    for (void *p : {(void *)h->inst_pinned, (void *)h->next_host, (void *)h->ctl_host, (void *)h->jerr_host})
         if (p) (void)hipHostFree(p);
-    for (hipEvent_t e : {h->ev_start, h->ev_kernels, h->ev_done, h->ev_reader})
+    for (hipEvent_t e : {h->ev_start, h->ev_kernels, h->ev_done, h->ev_reader, h->ev_jump_start, h->ev_jump_kernels, h->ev_jump_done})
         if (e) (void)hipEventDestroy(e);
     delete h;
 }
@@ -450,6 +628,7 @@ int bn_astar_set_map(bn_astar_t *h, int32_t inst, const float *heights, const fl
     h->p_diag = (float)(resolution * resolution + resolution * resolution);
     h->inst[inst].thr = stuck_threshold;
     h->have_map[inst] = 1;
+    h->jump_valid = false;
     return BN_OK;
 }
 
@@ -462,6 +641,7 @@ int bn_astar_set_goal(bn_astar_t *h, int32_t inst, int32_t ix, int32_t iy)
     const bool in = ix >= 0 && ix < h->W && iy >= 0 && iy < h->H;
     h->inst[inst].gx = in ? ix : -1;
     h->inst[inst].gy = in ? iy : -1;
+    h->jump_valid = false;
     return BN_OK;
 }
 
@@ -502,6 +682,7 @@ int bn_astar_solve_async(bn_astar_t *h, void *stream)
     ASTAR_HIP(hipEventRecord(h->ev_done, s));
     h->solved = true;
     h->pending_check = true;
+    h->jump_valid = false;
     return BN_OK;
 }
 
@@ -510,7 +691,9 @@ int bn_astar_sync(bn_astar_t *h)
 {
     if (!h) return astar_fail(BN_ERR_INVALID, "null handle");
     DeviceGuard guard(h->device);
-    return astar_wait(h);
+    int rc = astar_wait(h);
+    if (rc != BN_OK || !h->jump_valid) return rc;
+    return jump_ready(h);
 }
 
 /* Device time of the last solve's kernels (init, field, next), in ms: for the rate tool. */
@@ -564,6 +747,114 @@ int bn_astar_buffers(bn_astar_t *h, int32_t inst, void **D_dev, void **next_dev)
     return BN_OK;
 }
 
+/* The jump tables behind the latest solve, for all B instances: levels + 1 launches on `stream`, ordered behind the solve's
+ * kernels by an event, then an async copy of the error word to pinned memory (read by bn_astar_sync and the consumers). */
+int bn_astar_jump_build_async(bn_astar_t *h, void *stream)
+{
+    if (!h) return astar_fail(BN_ERR_INVALID, "null handle");
+    if (!h->solved) return astar_fail(BN_ERR_STATE, "no solve has been enqueued: bn_astar_solve_async must precede the table build");
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return astar_fail(BN_ERR_HIP, "hipSetDevice failed");
+    wait_readers(h);                              // an earlier build (its pinned word), episodes and paths reading the old tables
+    const size_t cells = (size_t)h->H * h->W, total = cells * h->B;
+    h->jump_valid = false;                        // until this build is enqueued whole: a failure below leaves no current tables
+    if (!h->jump) {
+        const hipError_t e = jump_alloc(h, total);
+        if (e != hipSuccess) {
+            jump_free(h);                         // all or nothing: the next build allocates again
+            return astar_fail(BN_ERR_HIP, std::string("jump table allocation: ") + hipGetErrorString(e));
+        }
+    }
+    hipStream_t s = (hipStream_t)stream;
+    ASTAR_HIP(hipStreamWaitEvent(s, h->ev_kernels, 0));
+    ASTAR_HIP(hipEventRecord(h->ev_jump_start, s));
+    ASTAR_HIP(hipMemsetAsync(h->jerr, 0, 4, s));
+    ASTAR_HIP(hipMemsetAsync(h->jerr + 1, 0x7f, 4, s));            // above every cell index: atomicMin keeps the smallest
+    const int blocks = (int)((total + 255) / 256);
+    int w = h->levels & 1;                        // levels + 1 rounds write the hop buffers in turn; the last one writes hopbuf[0]
+    bn::JumpArgs a{h->next, h->jump, nullptr, h->hopbuf[w], h->jerr, h->H, h->W, h->B, h->levels, 0};
+    bn::astar_jump_init_kernel<<<blocks, 256, 0, s>>>(a);
+    ASTAR_HIP(hipGetLastError());
+    for (int k = 0; k + 1 < h->levels; ++k) {
+        a.k = k; a.hops_in = h->hopbuf[w]; a.hops_out = h->hopbuf[w ^ 1]; w ^= 1;
+        bn::astar_jump_level_kernel<<<blocks, 256, 0, s>>>(a);
+        ASTAR_HIP(hipGetLastError());
+    }
+    a.hops_in = h->hopbuf[w]; a.hops_out = h->hopbuf[w ^ 1];
+    bn::astar_jump_close_kernel<<<blocks, 256, 0, s>>>(a);
+    ASTAR_HIP(hipGetLastError());
+    ASTAR_HIP(hipEventRecord(h->ev_jump_kernels, s));
+    ASTAR_HIP(hipMemcpyAsync(h->jerr_host, h->jerr, 2 * 4, hipMemcpyDeviceToHost, s));
+    ASTAR_HIP(hipEventRecord(h->ev_jump_done, s));
+    h->jump_valid = true;
+    h->jump_pending = true;
+    return BN_OK;
+}
+
+/* Device time of the last table build's kernels, in ms: for the rate tool. */
+int bn_astar_jump_ms(bn_astar_t *h, float *ms)
+{
+    if (!h || !ms) return astar_fail(BN_ERR_INVALID, "null argument");
+    DeviceGuard guard(h->device);
+    int rc = jump_ready(h);
+    if (rc != BN_OK) return rc;
+    ASTAR_HIP(hipEventElapsedTime(ms, h->ev_jump_start, h->ev_jump_kernels));
+    return BN_OK;
+}
+
+int bn_astar_paths_async(bn_astar_t *h, int32_t inst, const int32_t *starts_xy, bn_mem_kind where, int32_t n, int32_t max_len,
+                         int32_t *out_xy_device, int32_t *out_len_device, void *stream)
+{
+    if (!h) return astar_fail(BN_ERR_INVALID, "null handle");
+    if (inst < 0 || inst >= h->B) return astar_fail(BN_ERR_INVALID, "instance out of range");
+    if (n < 0 || max_len < 0) return astar_fail(BN_ERR_INVALID, "n and max_len must be >= 0");
+    if (where != BN_MEM_HOST && where != BN_MEM_DEVICE) return astar_fail(BN_ERR_INVALID, "unknown memory kind");
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return astar_fail(BN_ERR_HIP, "hipSetDevice failed");
+    int rc = jump_ready(h);
+    if (rc != BN_OK) return rc;
+    if (n == 0) return BN_OK;
+    if (!starts_xy || !out_len_device || (max_len > 0 && !out_xy_device)) return astar_fail(BN_ERR_INVALID, "null argument");
+    const size_t threads = (size_t)n * (max_len > 0 ? max_len : 1);
+    if (threads > ((size_t)1 << 31) * 256) return astar_fail(BN_ERR_INVALID, "n * max_len is too large for one launch");
+    hipStream_t s = (hipStream_t)stream;
+    const int32_t *starts = starts_xy;
+    if (where == BN_MEM_HOST) {
+        wait_readers(h);                          // an earlier call's kernel may still read the staging buffer
+        if ((size_t)n > h->starts_cap) {
+            if (h->starts_dev) ASTAR_HIP(hipFree(h->starts_dev));
+            h->starts_dev = nullptr; h->starts_cap = 0;
+            ASTAR_HIP(hipMalloc((void **)&h->starts_dev, (size_t)n * 2 * 4));
+            h->starts_cap = (size_t)n;
+        }
+        ASTAR_HIP(hipMemcpyAsync(h->starts_dev, starts_xy, (size_t)n * 2 * 4, hipMemcpyHostToDevice, s));
+        ASTAR_HIP(hipStreamSynchronize(s));       // (pageable source: the caller's buffer is free on return)
+        starts = h->starts_dev;
+    }
+    ASTAR_HIP(hipStreamWaitEvent(s, h->ev_jump_kernels, 0));
+    const size_t cells = (size_t)h->H * h->W;
+    bn::PathsArgs a{h->hopbuf[0] + cells * inst, h->jump + cells * h->levels * inst, starts, out_xy_device, out_len_device,
+                    h->H, h->W, n, max_len};
+    bn::astar_paths_kernel<<<(unsigned)((threads + 255) / 256), 256, 0, s>>>(a);
+    ASTAR_HIP(hipGetLastError());
+    return bn::astar_add_reader(h, s);
+}
+
+/* Test hook: the device tables of instance `inst` -- hops (H*W int32) and jump (levels, H*W int32).  Valid after a build and
+ * bn_astar_sync. */
+int bn_astar_jump_buffers(bn_astar_t *h, int32_t inst, void **hops_dev, void **jump_dev, int32_t *levels, int32_t *elem_bytes)
+{
+    if (!h || !hops_dev || !jump_dev || !levels || !elem_bytes) return astar_fail(BN_ERR_INVALID, "null argument");
+    if (inst < 0 || inst >= h->B) return astar_fail(BN_ERR_INVALID, "instance out of range");
+    if (!h->jump) return astar_fail(BN_ERR_STATE, "the jump tables were never built");
+    const size_t cells = (size_t)h->H * h->W;
+    *hops_dev = h->hopbuf[0] + cells * inst;
+    *jump_dev = h->jump + cells * h->levels * inst;
+    *levels = h->levels;
+    *elem_bytes = 4;
+    return BN_OK;
+}
+
 }  // extern "C"
 
 namespace bn {
@@ -572,7 +863,8 @@ int astar_view(bn_astar_t *h, AStarView *v)
 {
     if (!h || !v) return astar_fail(BN_ERR_INVALID, "null argument");
     if (!h->solved) return astar_fail(BN_ERR_STATE, "no A* solve has been enqueued");
-    *v = AStarView{h->device, h->H, h->W, h->B, h->next, h->risk, h->inst_dev, h->ctl + 1, h->ev_kernels};
+    *v = AStarView{h->device, h->H, h->W, h->B, h->next, h->risk, h->inst_dev, h->ctl + 1, h->ev_kernels,
+                   h->jump_valid, h->levels, h->hopbuf[0], h->jump, h->jerr, h->ev_jump_kernels};
     return BN_OK;
 }
 
@@ -580,8 +872,11 @@ int astar_add_reader(bn_astar_t *h, hipStream_t s)
 {
     DeviceGuard guard(h->device);
     if (!h->ev_reader) ASTAR_HIP(hipEventCreateWithFlags(&h->ev_reader, hipEventDisableTiming));
+    // one event stands for every reader: `s` waits, on the device, for the readers another stream enqueued before it is re-recorded
+    if (h->reader_pending && h->reader_stream != s) ASTAR_HIP(hipStreamWaitEvent(s, h->ev_reader, 0));
     ASTAR_HIP(hipEventRecord(h->ev_reader, s));
     h->reader_pending = true;
+    h->reader_stream = s;
     return BN_OK;
 }
 

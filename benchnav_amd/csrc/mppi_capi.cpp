@@ -284,6 +284,7 @@ struct bn_mppi {
     float *d_ad_log = nullptr;   // (n+1, B, 3) states | (n, B) rewards | (n, B, 2) actions | (n, B, 2) sub-goals
     int ad_cap = 0, ad_len = 0;  // steps the log holds / the latest call ran
     uint64_t ad_step = 0;        // episode steps since bn_astar_dwa_reset
+    int ad_walk = 0;             // bn_astar_dwa_set_walk: 0 the serial next-hop walk, 1 the A* handle's jump tables
     size_t scratch_bytes = 0, eps_bytes = 0, idx_count = 0;
     float *h_pinned = nullptr;   // pinned staging for (B,3) states
     // profiling
@@ -2500,6 +2501,14 @@ int bn_astar_dwa_set_root(bn_mppi_t *h, int32_t instance, int32_t ix, int32_t iy
     return BN_OK;
 }
 
+int bn_astar_dwa_set_walk(bn_mppi_t *h, int32_t mode)
+{
+    if (!h) return fail(BN_ERR_INVALID, "null handle");
+    if (mode != 0 && mode != 1) return fail(BN_ERR_INVALID, "walk mode must be 0 (serial) or 1 (jump tables)");
+    h->ad_walk = mode;
+    return BN_OK;
+}
+
 int bn_astar_dwa_episode_async(bn_mppi_t *h, bn_astar_t *a, int32_t n_steps, const float *states0, bn_mem_kind where,
                                float *prev_action_device, const float a_lim[2], float dwa_delta_t, int32_t num_lin_vel,
                                int32_t num_ang_vel, float lookahead, const float *z_device)
@@ -2516,6 +2525,8 @@ int bn_astar_dwa_episode_async(bn_mppi_t *h, bn_astar_t *a, int32_t n_steps, con
     if (v.device != h->cfg.device_id) return fail(BN_ERR_INVALID, "the A* handle is on device %d, the planner on device %d", v.device, h->cfg.device_id);
     if (v.B != h->p.B) return fail(BN_ERR_INVALID, "the A* handle has %d instances, the planner %d", v.B, h->p.B);
     if (v.H != h->p.G || v.W != h->p.G) return fail(BN_ERR_INVALID, "the A* maps are %d x %d, the planner's grid is %d x %d", v.H, v.W, h->p.G, h->p.G);
+    if (h->ad_walk == 1 && !v.jump_current)
+        return fail(BN_ERR_STATE, "walk mode 1 needs current jump tables: bn_astar_jump_build_async must follow the A* handle's latest solve");
     BN_BIND(h);
     if (int rc = settle_point(h)) return rc;
     if (int rc = flush_tail(h)) return rc;
@@ -2534,10 +2545,12 @@ int bn_astar_dwa_episode_async(bn_mppi_t *h, bn_astar_t *a, int32_t n_steps, con
     BN_HIP(hipMemcpyAsync(h->d_ad_state, states0, B * 3 * sizeof(float), kind, h->stream));
     if (where == BN_MEM_HOST) BN_HIP(hipStreamSynchronize(h->stream));   // (pageable source: one upload, before the loop)
     BN_HIP(hipStreamWaitEvent(h->stream, v.solved, 0));                 // behind a's latest solve, without the host
+    if (h->ad_walk == 1) BN_HIP(hipStreamWaitEvent(h->stream, v.jump_built, 0));   // ... and its table build
     float *lg = h->d_ad_log;
     const size_t cap = (size_t)h->ad_cap;                                 // the log's layout is by capacity (bn_astar_dwa_episode_log)
     bn::AstarDwaArgs x{};
     x.next = v.next; x.arisk = v.risk; x.ainst = v.inst; x.aerr = v.err; x.H = v.H; x.W = v.W;
+    if (h->ad_walk == 1) { x.hops = v.hops; x.jump = v.jump; x.jerr = v.jerr; x.levels = v.levels; }
     x.state = h->d_ad_state; x.prev = prev_action_device;
     x.root = h->d_ad_i; x.status = h->d_ad_i + B; x.status_step = h->d_ad_i + 2 * B; x.done = h->d_ad_i + 3 * B; x.err = h->d_ad_i + 4 * B;
     x.log_states = lg; x.log_reward = lg + (cap + 1) * B * 3; x.log_action = x.log_reward + cap * B; x.log_subgoal = x.log_action + cap * B * 2;

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define BN_MPPI_ABI_VERSION 6
+#define BN_MPPI_ABI_VERSION 7
 
 typedef enum bn_status {
     BN_OK = 0,
@@ -536,6 +536,31 @@ int bn_astar_path(bn_astar_t *h, int32_t inst, int32_t ix, int32_t iy, int32_t *
 /* Test hook: device pointers of instance inst's D (H*W float32) and next (H*W uint8: 0-7 direction in astar.py:154-163
  * order, 8 goal, 255 unreachable). */
 int bn_astar_buffers(bn_astar_t *h, int32_t inst, void **D_dev, void **next_dev);
+/*
+ * Jump tables behind the latest solve (csrc/astar_kernels.hip), per instance: hops (H*W int32), the number of hops along next to
+ * the goal (0 at the goal, -1 where the walk ends on an unreachable cell: everywhere for a goal out of bounds or in collision),
+ * and jump (levels, H*W) int32, jump[k][c] = the cell (iy * W + ix) reached from c after 2^k hops (the goal and unreachable cells
+ * map to themselves), levels = max(1, ceil(log2(H*W))): every node index of a path is a sum of kept powers of two.  Footprint
+ * B * (levels + 2) * H*W * 4 bytes (the levels and two hop buffers), allocated by the first build.  The build is levels + 1
+ * launches on `stream` behind the solve, whatever the map holds.  It validates next: a code in 9-254, a hop off the map, or a
+ * cycle (a walk still stepping after 2^levels hops) sets the tables' error word, reported as BN_ERR_STATE by bn_astar_sync and by
+ * every consumer, with the first offending cell in the message.  bn_astar_set_map, bn_astar_set_goal and bn_astar_solve_async
+ * make the tables stale: consumers then return BN_ERR_STATE.
+ */
+int bn_astar_jump_build_async(bn_astar_t *h, void *stream);
+/* Device time of the last table build in ms. */
+int bn_astar_jump_ms(bn_astar_t *h, float *ms);
+/* Paths for n start cells of instance inst from the tables, on the device: starts_xy (n, 2) int32 (ix, iy), host or device;
+ * out_len_device (n) int32: the node count of the path, goal included (bn_astar_path's return value), 0 where the goal is
+ * unreachable, -1 for a start out of bounds; out_xy_device (n, max_len, 2) int32: the first min(len, max_len) nodes of each row,
+ * the rest -1 (may be NULL with max_len = 0).  Waits on the host for a pending table build (its validation); the paths
+ * themselves are enqueued on `stream`.  Starts on the host (BN_MEM_HOST) go through one staging buffer per handle: the call
+ * then also waits on the host for earlier readers of the handle and for the copy on `stream`, so it is synchronous up to the
+ * paths kernel; pass the starts on the device to keep the call asynchronous.  n = 0 is a no-op. */
+int bn_astar_paths_async(bn_astar_t *h, int32_t inst, const int32_t *starts_xy, bn_mem_kind where, int32_t n, int32_t max_len,
+                         int32_t *out_xy_device, int32_t *out_len_device, void *stream);
+/* Test hook: device pointers of instance inst's hops (H*W) and jump (levels, H*W), the level count and the element size. */
+int bn_astar_jump_buffers(bn_astar_t *h, int32_t inst, void **hops_dev, void **jump_dev, int32_t *levels, int32_t *elem_bytes);
 const char *bn_astar_last_error(void);
 
 /*
@@ -574,6 +599,11 @@ int bn_astar_dwa_episode_log(bn_mppi_t *h, float *states, float *rewards, float 
 int bn_astar_dwa_reset(bn_mppi_t *h);
 /* Set instance b's root cell (ix, iy), or forget it with ix < 0: starts a teacher-forced step from a given previous path. */
 int bn_astar_dwa_set_root(bn_mppi_t *h, int32_t instance, int32_t ix, int32_t iy);
+/* How the episode reads the path: 0 (default) one lane walks next node by node; 1 every lane fetches its own node through a's
+ * jump tables (bn_astar_jump_build_async), the same nodes in the same order, so every output is bit-identical.  With 1,
+ * bn_astar_dwa_episode_async returns BN_ERR_STATE unless a's tables are current, and the tables' error word freezes the
+ * instances with BN_AD_FIELD_ERROR as the field's does. */
+int bn_astar_dwa_set_walk(bn_mppi_t *h, int32_t mode);
 
 /*
  * Terrain generation (csrc/terrain_kernels.hip): TerrainGeometry.set_terrain_geometry (craters, fBm, Horn slopes) and

@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
-"""A* global planner rates: the field solve (HIP events around its kernels, bn_astar_kernel_ms) for 256^2 and 512^2 maps,
+"""A* global planner rates: the field solve (HIP events around its kernels, bn_astar_kernel_ms) and the jump-table build behind
+it (bn_astar_jump_ms) for 256^2 and 512^2 maps (--sizes),
 smooth / i.i.d. / serpentine-maze terrain, B = 1, 8, 64 instances per launch (each with its own goal); and AStar.forward()
 wall time per call (the host walk of the next-hop map + the path tensor).
 
-    python tools/astar_rate.py [--reps 10] [--out result.json]
+    python tools/astar_rate.py [--reps 10] [--sizes 64 256 512] [--no-forward] [--no-jump] [--out result.json]
 """
 from __future__ import annotations
 
@@ -41,7 +42,7 @@ def goals(risk, B, seed):
     return [(int(fx[j]), int(fy[j])) for j in idx]
 
 
-def solve_ms(lib, kind, G, B, reps):
+def solve_ms(lib, kind, G, B, reps, jump=True):
     h_map, r_map = maps(kind, G)
     h = C.c_void_p()
     rc = lib.bn_astar_create(0, G, G, B, C.byref(h))
@@ -51,14 +52,22 @@ def solve_ms(lib, kind, G, B, reps):
         for b, g in enumerate(goals(r_map, B, G + B)):
             assert lib.bn_astar_set_map(h, b, h_map.ctypes.data, r_map.ctypes.data, _capi.BN_MEM_HOST, THR, RES) == 0
             assert lib.bn_astar_set_goal(h, b, *g) == 0
-        ms, t = C.c_float(), []
+        ms, t, tj = C.c_float(), [], []
         for i in range(reps + 2):
             assert lib.bn_astar_solve_async(h, None) == 0
             if lib.bn_astar_kernel_ms(h, C.byref(ms)) != 0:
                 raise RuntimeError(lib.bn_astar_last_error())
             if i >= 2:
                 t.append(ms.value)
-        return float(np.median(t)), float(np.min(t)), float(np.max(t))
+            if not jump:                                           # the solve alone: no tables are allocated
+                continue
+            assert lib.bn_astar_jump_build_async(h, None) == 0     # the jump tables behind this solve
+            if lib.bn_astar_jump_ms(h, C.byref(ms)) != 0:
+                raise RuntimeError(lib.bn_astar_last_error())
+            if i >= 2:
+                tj.append(ms.value)
+        tj = tj or [float("nan")]
+        return float(np.median(t)), float(np.min(t)), float(np.max(t)), float(np.median(tj)), float(np.min(tj)), float(np.max(tj))
     finally:
         lib.bn_astar_destroy(h)
 
@@ -89,15 +98,22 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--calls", type=int, default=200)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--sizes", type=int, nargs="+", default=[256, 512], help="map edge lengths")
+    ap.add_argument("--no-forward", action="store_true", help="solve and table-build times only")
+    ap.add_argument("--no-jump", action="store_true", help="time the solve alone: the jump tables are neither allocated nor built")
     a = ap.parse_args()
     lib = _capi.load()
     rows = []
-    for G in (256, 512):
+    for G in a.sizes:
         for kind in ("smooth", "iid", "maze"):
             for B in (1, 8, 64):
-                med, lo, hi = solve_ms(lib, kind, G, B, a.reps)
+                med, lo, hi, jmed, jlo, jhi = solve_ms(lib, kind, G, B, a.reps, not a.no_jump)
                 rows.append(dict(what="solve", G=G, kind=kind, B=B, ms_median=round(med, 4), ms_min=round(lo, 4), ms_max=round(hi, 4)))
+                if not a.no_jump:
+                    rows[-1].update(jump_ms_median=round(jmed, 4), jump_ms_min=round(jlo, 4), jump_ms_max=round(jhi, 4))
                 print(json.dumps(rows[-1]), flush=True)
+            if a.no_forward:
+                continue
             med, p90, plen = forward_us(kind, G, a.calls)
             rows.append(dict(what="forward", G=G, kind=kind, us_median=round(med, 1), us_p90=round(p90, 1), median_path_nodes=plen))
             print(json.dumps(rows[-1]), flush=True)
