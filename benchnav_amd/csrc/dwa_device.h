@@ -68,12 +68,18 @@ __device__ __forceinline__ float dwa_point_dist(float px, float py, float x, flo
     return sqrt_cr(dx * dx + dy * dy);
 }
 
+// the bearing's atan2 (dwa.py:272): one definition, so that the test hook (bn_device_math_eval fn 6) evaluates the very function
+__device__ __forceinline__ float dwa_bearing_atan2(float dy, float dx)
+{
+    return atan2f(dy, dx);
+}
+
 // ... and whether it is a candidate: ahead (|bearing| < 90 deg) and beyond the look-ahead distance (dwa.py:272-277); INFINITY if not
 __device__ __forceinline__ float dwa_ahead_dist(float px, float py, float x, float y, float th, float lookahead)
 {
     const float dx = px - x, dy = py - y;
     const float dist = sqrt_cr(dx * dx + dy * dy);
-    const float ang = atan2f(dy, dx) - th;
+    const float ang = dwa_bearing_atan2(dy, dx) - th;
     return (fabsf(ang) < kPi / 2.0f && dist > lookahead) ? dist : INFINITY;
 }
 

@@ -3014,7 +3014,7 @@ void bn_mppi_debug_trace_by_parity(bn_mppi_t *h, int on) { h->p.trace_by_parity 
 
 int bn_device_math_eval(int32_t fn, const float *in_device, float *out_device, int64_t n, void *stream)
 {
-    if (fn < 0 || fn > 5 || !in_device || !out_device || n < 0) return fail(BN_ERR_INVALID, "bad argument");
+    if (fn < 0 || fn > 6 || !in_device || !out_device || n < 0) return fail(BN_ERR_INVALID, "bad argument");
     if (n == 0) return BN_OK;
     BN_HIP(bn::launch_math_eval(fn, in_device, out_device, (size_t)n, (hipStream_t)stream));
     return BN_OK;

@@ -204,7 +204,7 @@ hipError_t launch_queue_probe(int *flag_and_seen, hipStream_t waiter, hipStream_
 hipError_t launch_echo64(const unsigned long long *src, unsigned long long *dst, hipStream_t s);   // one thread: *dst = *src (system scope both ways)
 hipError_t launch_stamp(int *word, int value, hipStream_t s);      // one thread: *word = value (system scope) -- a marker in a queue, for the host
 hipError_t launch_quotient_check(float res, float inv_res, float d_max, unsigned long long *bad, hipStream_t s);
-hipError_t launch_math_eval(int fn, const float *in, float *out, size_t n, hipStream_t s);   // 0 sqrt, 1 sin, 2 cos, 3 wrap, 4 wrap_near
+hipError_t launch_math_eval(int fn, const float *in, float *out, size_t n, hipStream_t s);   // 0 sqrt, 1 sin, 2 cos, 3 wrap, 4 wrap_near, 5 sqrt_cr_normal, 6 atan2f of (dy, dx) pairs
 hipError_t launch_rng_eval(int fn, const uint32_t *in, uint32_t *out, size_t n, hipStream_t s);   // 0 philox4x32<10>, 1 <kStreamRounds>, 2 box_muller
 
 // layout conversion helpers (planner-native k-fastest <-> reference k-major)

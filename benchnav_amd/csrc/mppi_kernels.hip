@@ -252,6 +252,10 @@ __global__ void env_collision_kernel(const SolveParams p, const float *__restric
 __global__ void math_eval_kernel(int fn, const float *__restrict__ in, float *__restrict__ out, size_t n)
 {
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        if (fn == 6) {                                   // pairs: in[2 i] = dy, in[2 i + 1] = dx -> the sub-goal bearing's atan2f(dy, dx)
+            out[i] = dwa_bearing_atan2(in[2 * i], in[2 * i + 1]);
+            continue;
+        }
         const float x = in[i];
         float sn, cs, r;
         switch (fn) {

@@ -685,7 +685,9 @@ const char *bn_terrain_last_error(void);
 /* Test hook: the library's device arithmetic (DESIGN.md "Arithmetic spec") applied elementwise to n device floats:
  * fn 0 = correctly rounded sqrt, 1 / 2 = sin / cos of the spec, 3 = heading wrap (theta + pi) % 2pi - pi with
  * torch.remainder semantics (robot_model.py:90), 4 = its in-loop form, 5 = the sqrt for zero / normal finite arguments.  Lets the tests compare the kernels' building
- * blocks with the oracle's one value at a time. */
+ * blocks with the oracle's one value at a time.
+ * fn 6 = the atan2f of DWA's sub-goal bearing (dwa.py:272), on PAIRS: in_device holds 2 n floats, record i = (dy, dx) =
+ * (in[2 i], in[2 i + 1]), and out_device n floats, out[i] = atan2f(dy, dx) as the sub-goal kernels evaluate it. */
 int bn_device_math_eval(int32_t fn, const float *in_device, float *out_device, int64_t n, void *stream);
 /* Test hook: the generator every noise stream is built from, on n caller-supplied device records (uint32 words):
  * fn 0 = Philox4x32-10, 1 = Philox4x32 with the per-rollout streams' eight rounds: record 6 words (c0, c1, c2, c3, k0, k1)

@@ -171,6 +171,15 @@ def dwa_sub_goal(p: OracleParams, R, state, action0, path, lookahead):
     return sg, sel, int(idx)
 
 
+def atan2f(dy, dx):
+    """The host libm's atan2f -- the one oracle_dwa_sub_goal's bearing calls -- elementwise on float32 arrays."""
+    dy = _f32(dy).ravel(); dx = _f32(dx).ravel()
+    assert dy.size == dx.size
+    out = np.empty_like(dy)
+    lib().oracle_atan2f(C.c_int64(dy.size), _fp(dy), _fp(dx), _fp(out))
+    return out
+
+
 def solve_sampled(p: OracleParams, MU, SG, state, mean, eps, zt, zc, zo):
     """MPPI solve with sampled slip (BASELINE config 3); zt (K,T), zc (K,T+1), zo (T) standard normals."""
     K, T, G = p.K, p.T, p.G

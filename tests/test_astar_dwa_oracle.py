@@ -1,11 +1,14 @@
 """CPU: the rules of the A* + DWA closed loop (tests/astar_dwa_oracle.py, stated from the reference) that the device loop
 (csrc/astar_dwa.hip, tests/test_gpu_astar_dwa.py) follows: truncation of the start cell, the edge start, None with and without a
-previous path, and a short free-running episode."""
+previous path, and a short free-running episode; the grid limits, the bearing margin and the measured error of the host's atan2f
+that set the ambiguity band DELTA; and the oracle free-running on every scenario of tests/test_gpu_astar_dwa_oracle.py."""
 import numpy as np
 import pytest
 
 import astar_dwa_oracle as L
+import astar_dwa_scenarios as S
 import astar_maps as M
+from oracle import oracle as O
 
 G, RES, THR, T = 64, 0.5, 0.2, 50
 
@@ -97,6 +100,142 @@ def test_free_running_episode_is_deterministic_and_on_the_path():
         runs.append(np.stack(rows))
     assert np.array_equal(runs[0], runs[1])
     assert np.linalg.norm(runs[0][-1, :2] - np.float32([4.0, 5.0])) > 1.0       # it moved toward the goal
+
+
+# ---- limits, the bearing margin, the host's atan2f ---------------------------------------------------------------------------
+def test_a_non_zero_origin_moves_the_cells_but_not_the_path_points():
+    lim = (-8.0, 24.0)
+    assert L.start_cell((-8.0, -7.6), lim[0], lim[0], RES) == (0, 0)
+    assert L.start_cell((-8.4, 3.0), lim[0], lim[0], RES) == (0, 22)            # truncation, not floor, about the origin too
+    assert L.start_cell((-8.5, 3.0), lim[0], lim[0], RES) == (-1, 22)
+    assert L.start_cell((24.0, 0.0), lim[0], lim[0], RES) == (G, 16)            # the upper limit, where the environment clamps
+    mu = np.full((G, G), 0.25, np.float32)
+    mk = lambda goal: L.Loop(M.smooth_heights(G, G, 5), _risk(), THR, RES, goal, T, mu, np.full((G, G), 0.05, np.float32), x_limits=lim)
+    lp = mk((10.0, 9.0))
+    assert lp.goal == (36, 34) and (lp.p.x0, lp.p.y0, lp.pe.x0, lp.pe.x_hi, lp.pe.y_lo) == (-8.0, -8.0, -8.0, 24.0, -8.0)
+    state = np.float32([-3.0, -2.0, 0.6])
+    status, path = lp.astar(state)
+    assert status == L.OK and np.array_equal(path[0], np.float32([10, 12]) * np.float32(RES))    # cell (10, 12); x_limits[0] ignored
+    assert np.array_equal(path[-1], np.float32([36, 34]) * np.float32(RES))
+    ns, rw, term, sg, a = lp.step(0, state, 0.0)
+    assert np.any(np.all(path == sg, axis=1))
+    # the edge start: x = x_limits[1] indexes to G
+    lp = mk((10.0, 9.0))
+    assert lp.step(0, np.float32([24.0, 3.0, 0.0]), 0.0) is None and (lp.status, lp.status_step) == (L.OUT_OF_BOUNDS, 0)
+    lp = mk((10.0, 9.0))
+    assert lp.step(0, np.float32([-8.4, 3.0, 0.0]), 0.0) is not None and lp.status == L.OK
+    # a goal that is in bounds only about the origin, and one that is out of bounds only about it
+    assert mk((-7.0, -7.0)).goal_in and not mk((25.0, 9.0)).goal_in
+
+
+def test_bearing_margin_on_hand_made_paths():
+    sel = np.float32([2.0, 3.0, 0.0])
+    far = np.float32([[6.0, 3.0], [2.0, 7.0], [5.0, 7.0]])                      # dead ahead; exactly abeam; 53 degrees off
+    assert L.bearing_margin(far[:1], sel, 1.0) == pytest.approx(np.pi / 2)
+    assert L.bearing_margin(far, sel, 1.0) == 0.0                              # atan2(4, 0) - 0 is pi/2 in float64
+    assert L.bearing_margin(far[[0, 2]], sel, 1.0) == pytest.approx(np.pi / 2 - np.arctan2(4.0, 3.0))
+    assert L.bearing_margin(far, sel, 4.5) == pytest.approx(np.pi / 2 - np.arctan2(4.0, 3.0))    # the abeam point is within the look-ahead
+    assert L.bearing_margin(far, sel, 5.0) == np.inf                           # dist == lookahead is not beyond it: no point left
+    assert L.bearing_margin(np.float32([[2.0, -1.0]]), sel, 1.0) == 0.0        # abeam on the other side
+    # the heading enters unwrapped, in float64 from the float32 value
+    th = np.float32(0.3)
+    got = L.bearing_margin(far[1:2], np.float32([2.0, 3.0, th]), 1.0)
+    assert got == abs(abs(np.pi / 2 - np.float64(th)) - np.pi / 2) and got > 0.29
+    assert L.bearing_margin(far[:1], np.float32([2.0, 3.0, -3.0]), 1.0) == pytest.approx(3.0 - np.pi / 2)   # |0 - (-3)| = 3: unwrapped
+    # a one-ulp nudge off abeam is inside the band, a coarse one is outside
+    near = np.float32([[np.nextafter(np.float32(2.0), np.float32(3.0)), 7.0]])
+    assert 0.0 < L.bearing_margin(near, sel, 1.0) <= L.DELTA
+    assert L.bearing_margin(np.float32([[2.001, 7.0]]), sel, 1.0) > L.DELTA
+
+
+def test_loop_bearing_margin_uses_the_step_s_path_and_slot_0_state():
+    risk = _risk()
+    risk[8:15, 8:15] = 0.05
+    lp = _loop(risk)
+    state = np.float32([5.75, 5.75, 0.3])                                       # no path from here and none kept
+    assert lp.bearing_margin(state) == np.inf and lp.path is None
+    outside = np.float32([3.0, 3.0, 0.6])
+    m = lp.bearing_margin(outside)                                              # the fresh path, although none is kept yet
+    fresh = lp.astar(outside)[1]
+    a0 = L.window(lp.prev, lp.a_lim, lp.dwa_dt, lp.nv, lp.nw)[0]
+    sel = O.dwa_sub_goal(lp.p, lp.risk, outside, a0, fresh, lp.look)[1]
+    assert lp.path is None and m == L.bearing_margin(fresh, sel, lp.look) and 0.0 < m < np.pi / 2
+    lp.step(0, outside, 0.0)
+    kept = lp.path.copy()
+    sel = O.dwa_sub_goal(lp.p, lp.risk, state, L.window(lp.prev, lp.a_lim, lp.dwa_dt, lp.nv, lp.nw)[0], kept, lp.look)[1]
+    assert lp.bearing_margin(state) == L.bearing_margin(kept, sel, lp.look)     # the kept path where the cell has none
+    assert not np.array_equal(sel, state)                                       # ... seen from the slot-0 state, not the start
+    assert lp.bearing_margin(np.float32([G * RES, 3.0, 0.0])) == np.inf         # AStar.forward raises: nothing is picked
+    assert np.array_equal(lp.path, kept) and lp.status == L.OK                  # and asking changes nothing
+
+
+def test_host_atan2f_error_is_the_recorded_one():
+    """E_host of the ambiguity band: glibc's atan2f (what oracle_dwa_sub_goal calls) against float64 arctan2 of the same inputs."""
+    dy, dx = L.atan2_pairs()
+    e = L.atan2_ulp_error(O.atan2f(dy, dx), dy, dx)
+    print(f"E_host = {e:.4f} ulp over {len(dy)} pairs")
+    assert e <= L.ATAN2_E_HOST
+    ax_y = np.float32([0, 0, -0.0, -0.0, 0, 0, -0.0, -0.0, 1, -1, 1, -1])
+    ax_x = np.float32([0, -0.0, 0, -0.0, 1, -1, 1, -1, 0, 0, -0.0, -0.0])
+    assert np.array_equal(O.atan2f(ax_y, ax_x).view(np.uint32), np.arctan2(ax_y, ax_x).view(np.uint32))
+    assert L.DELTA == (max(L.ATAN2_E_DEV, L.ATAN2_E_HOST) + 1) * 2.0 ** -22
+
+
+# ---- the scenarios of tests/test_gpu_astar_dwa_oracle.py, oracle alone: few steps hang on the last bits of atan2f ----------------
+CAP = 0.02         # of a scenario's steps may have bearing_margin <= DELTA (and are then not compared on the device)
+
+
+@pytest.mark.parametrize("name", S.SCENARIOS)
+def test_free_running_scenarios_stay_under_the_cap_on_ambiguous_steps(name):
+    sc = S.scenario(name)
+    statuses, kept_idx = [], []
+    for b in range(len(sc["starts"])):
+        ran, flagged, lp, idx, kept = S.free_run(sc, b)
+        print(f"{name}[{b}]: {flagged} of {ran} steps within DELTA = {L.DELTA:.3e}; status {lp.status} at {lp.status_step}")
+        assert flagged <= CAP * sc["n"], (name, b, flagged)
+        statuses.append(lp.status)
+        kept_idx += [i for i, k in zip(idx, kept) if k and i is not None]
+    # what each scenario is there for, from the oracle's side
+    if name == "late_fallback":
+        assert max(kept_idx) >= 64
+    if name == "general33":
+        assert L.OK in statuses and sc["G"] ** 2 % 4 != 0
+    if name.startswith("last_byte_"):            # two rovers stand in the last cell of their slices: one has a hop there, one has none
+        hop, none = (1, 2) if name == "last_byte_a" else (2, 1)
+        loops = [S.oracle_loop(sc, b) for b in range(3)]
+        assert sc["G"] ** 2 % 4 != 0 and loops[hop].nxt[32, 32] < 8 and loops[none].nxt[32, 32] == 255
+        for b in (hop, none):
+            st = S.initial_state(sc, b)
+            assert L.start_cell(st, 0.0, 0.0, sc["res"]) == (32, 32) and (loops[b].astar(st)[1] is None) == (b == none)
+        assert statuses == [L.OK] * 3
+    if name == "big416":
+        assert S.lds_bytes(sc, 0) > 160 * 1024
+    if name.startswith("spiral_"):
+        assert len(lp.path) > 1024
+    if name in ("case_edge", "case_goal_collision"):
+        assert statuses[0] != L.OK
+
+
+# ---- the inputs of tests/test_gpu_dwa_subgoal.py, oracle alone -------------------------------------------------------------------
+def test_sub_goal_cases_are_clear_of_the_band_and_pick_what_they_are_built_to_pick():
+    import dwa_subgoal_cases as D
+    for name, cfg in D.all_fixed():
+        assert D.margin(cfg) > L.DELTA, name
+        if "expect" in cfg:
+            a0 = L.window(cfg["prev"][0], D.A_LIM, D.DWA_DT, cfg["nv"], cfg["nw"], *cfg["bounds"])[0]
+            sg, sel, idx = O.dwa_sub_goal(D.params(cfg), D.risk_map(cfg["geo"][0]), cfg["states"][0], a0, cfg["path"], cfg["look"])
+            assert idx == cfg["expect"], (name, idx)
+            if name.startswith(("tie", "look", "none")):
+                assert np.array_equal(sel[:2], cfg["states"][0, :2]), name     # v = 0: the slot-0 position is the start, exactly
+
+
+def test_at_most_two_fuzz_seeds_are_redrawn():
+    import dwa_subgoal_cases as D
+    drawn = [D.fuzz_case(s) for s in D.FUZZ_SEEDS]
+    print("redrawn seeds:", [s for s, (c, r) in zip(D.FUZZ_SEEDS, drawn) if r])
+    assert len(D.FUZZ_SEEDS) == 24 and sum(r for c, r in drawn) <= 2
+    assert all(D.margin(c) > L.DELTA for c, r in drawn)
+    assert sum(c["path"] is not None for c, r in drawn) >= 18 and len({c["geo"] for c, r in drawn}) == 3
 
 
 # ---- the reference fixture (tests/golden/make_golden_astar_dwa.py): the reference's own loop, teacher-forced step by step ----

@@ -9,50 +9,12 @@ import pytest
 import torch
 
 import astar_maps as M
+from astar_dwa_scenarios import G, RES, THR, T, A_LIM, DWA_DT, NV, NW, LOOK, CASES     # the problem, shared with the oracle tests
+from astar_dwa_scenarios import case as _case, smooth_risk as _smooth_risk
 
 pytestmark = pytest.mark.gpu
 
-G, RES, THR, T = 64, 0.5, 0.2, 50
-A_LIM, DWA_DT, NV, NW, LOOK = (0.5, 0.5), 0.1, 10, 10, 1.0
 STEPS = 300
-
-
-def _smooth_risk(seed, lo=0.3, hi=0.95):
-    from benchnav_amd import synth
-    r = synth.smooth_risk_map(G, seed).numpy()
-    return (lo + (hi - lo) * (r - r.min()) / (r.max() - r.min())).astype(np.float32)
-
-
-def _case(name):
-    """(heights, risk, start (x, y), goal (x, y), planner kwargs) of one scenario on the test_astar_dwa.py problem."""
-    h = M.smooth_heights(G, G, 5)
-    kw = {}
-    if name == "smooth":
-        return h, _smooth_risk(1), (5.0, 6.0), (26.0, 25.0), kw
-    if name == "maze":                         # the serpentine corridor of astar_maps.spiral: paths of ~2000 nodes
-        h, risk, thr, res, goal = M.spiral(G)
-        return h, risk.astype(np.float32), (0.3, 0.3), ((goal[0] + 0.5) * RES, (goal[1] + 0.5) * RES), kw
-    if name == "low_risk_patch":               # risk <= THR is a collision for A*: the patch interior has no path (None).  Driven
-        risk = _smooth_risk(2)                 # straight at the goal, the rover crosses the patch the path leads round
-        yy, xx = np.mgrid[0:G, 0:G]
-        risk[(xx - 30) ** 2 + (yy - 30) ** 2 <= 36] = 0.05
-        return h, risk, (8.0, 8.0), (26.0, 26.0), dict(u_min=(0.5, 0.0), u_max=(1.0, 0.0))
-    if name == "disconnected":                 # the start's region is walled off from the goal: no path, the goal is the stage goal
-        risk = _smooth_risk(3)
-        risk[:, 20] = 0.05
-        risk[:, 21] = 0.05
-        return h, risk, (4.0, 16.0), (26.0, 16.0), kw
-    if name == "edge":                         # forced straight ahead through the goal into the x = G * res edge: out of bounds
-        kw = dict(u_min=(0.5, 0.0), u_max=(1.0, 0.0))
-        return h, _smooth_risk(4, 0.3, 0.5), (27.0, 16.0), (30.25, 16.25), kw
-    if name == "goal_collision":
-        risk = _smooth_risk(5)
-        risk[50, 50] = 0.1
-        return h, risk, (5.0, 5.0), (25.25, 25.25), kw
-    raise KeyError(name)
-
-
-CASES = ("smooth", "maze", "low_risk_patch", "disconnected", "edge", "goal_collision")
 
 
 def _env(B, risks, starts, goals, freeze=False, **kw):

@@ -62,3 +62,43 @@ def test_sincos_and_wrap_equal_the_oracle_bit_for_bit():
     near = th[np.abs(th) <= np.pi + 0.15]
     a = (near + pi32).astype(np.float32)
     assert np.array_equal(_eval(4, near), (np.mod(a, two_pi32).astype(np.float32) - pi32).astype(np.float32))
+
+
+def _eval_pairs(dy, dx):
+    """fn 6 on (dy, dx) records."""
+    import torch
+    from benchnav_amd import _capi
+    lib = _capi.load()
+    pairs = torch.from_numpy(np.ascontiguousarray(np.stack([dy, dx], 1), np.float32)).cuda()
+    out = torch.empty(len(dy), device="cuda")
+    torch.cuda.synchronize()
+    _capi.check(lib.bn_device_math_eval(6, C.c_void_p(pairs.data_ptr()), C.c_void_p(out.data_ptr()), len(dy), C.c_void_p(0)))
+    torch.cuda.synchronize()
+    return out.cpu().numpy()
+
+
+def _rejects_fn(fn):
+    import torch
+    from benchnav_amd import _capi
+    lib = _capi.load()
+    x, out = torch.zeros(4, device="cuda"), torch.zeros(2, device="cuda")
+    return lib.bn_device_math_eval(fn, C.c_void_p(x.data_ptr()), C.c_void_p(out.data_ptr()), 2, C.c_void_p(0)) == _capi.BN_ERR_INVALID
+
+
+def test_the_bearing_atan2f_against_float64_arctan2():
+    """The atan2f of DWA's sub-goal bearing (dwa_device.h) value by value: exact at the axes and at (0, 0), signs included, and
+    elsewhere within E_dev + 1 ulp of float64 arctan2 of the same float32 inputs.  E_dev is the maximum measured on the MI355X
+    over these inputs and, with the host's E_host, sets the ambiguity band astar_dwa_oracle.DELTA ("Arithmetic spec"):
+    a math library whose atan2f errs more shows up here, before it shows up as a flipped sub-goal."""
+    import astar_dwa_oracle as L
+    x = np.float32([1.0, 0.3, 64.5, 1e-45, 1e-38, 3e38])
+    zero = np.zeros_like(x)
+    ax_y = np.concatenate([np.float32([0, 0, -0.0, -0.0]), zero, zero, -zero, -zero, x, -x, x, -x])
+    ax_x = np.concatenate([np.float32([0, -0.0, 0, -0.0]), x, -x, x, -x, zero, zero, -zero, -zero])
+    got, want = _eval_pairs(ax_y, ax_x), np.arctan2(ax_y, ax_x)
+    assert want.dtype == np.float32 and np.array_equal(got.view(np.uint32), want.view(np.uint32)), (got, want)
+    dy, dx = L.atan2_pairs()
+    e = L.atan2_ulp_error(_eval_pairs(dy, dx), dy, dx)
+    print(f"E_dev = {e:.4f} ulp over {len(dy)} pairs")
+    assert e <= L.ATAN2_E_DEV + 1
+    assert _rejects_fn(7)
