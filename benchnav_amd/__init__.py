@@ -6,6 +6,7 @@
     from benchnav_amd import BatchedPlanetaryEnv   # reset / step / collision_check of PlanetaryEnv for B environments on the GPU
     from benchnav_amd import AStarDWALoop  # test_astar_dwa.py's A* + DWA loop on the device, B rovers per launch
     from benchnav_amd import TerrainGenerator   # DatasetGenerator's map instances (geometry + slip model), B per launch
+    from benchnav_amd import RRT           # drop-in for src/planners/global_planners/sampling_based/rrt.py:RRT, B plans per launch
 """
 from .native import NativeMPPI  # noqa: F401
 
@@ -29,4 +30,7 @@ def __getattr__(name):
     if name == "TerrainGenerator":
         from .terrain import TerrainGenerator
         return TerrainGenerator
+    if name == "RRT":
+        from .rrt import RRT
+        return RRT
     raise AttributeError(name)

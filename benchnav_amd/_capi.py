@@ -32,6 +32,9 @@ BN_FLAG_UNORDERED_OUTPUTS = 16384
 BN_BUF_STATES_ALT, BN_BUF_CONTROLS_ALT = 10, 11
 BN_RISK_EXPECTED, BN_RISK_VAR, BN_RISK_CVAR = 0, 1, 2
 BN_AD_OK, BN_AD_OUT_OF_BOUNDS, BN_AD_GOAL_COLLISION, BN_AD_FIELD_ERROR = 0, 1, 2, 3   # bn_astar_dwa_status
+BN_RRT_FLAG_GLOBAL_NODES, BN_RRT_FLAG_ONE_WAVE, BN_RRT_FLAG_FOUR_WAVES = 1, 2, 4
+(BN_RRT_BUF_NODES, BN_RRT_BUF_EDGES, BN_RRT_BUF_COSTS, BN_RRT_BUF_COUNTS, BN_RRT_BUF_SAMPLES, BN_RRT_BUF_SAMPLE_FLAGS,
+ BN_RRT_BUF_PATHS, BN_RRT_BUF_RESULTS) = range(8)
 ABI_VERSION = 7
 
 
@@ -44,6 +47,14 @@ class Config(C.Structure):
         ("u_min", C.c_float * 2), ("u_max", C.c_float * 2), ("dt", C.c_float),
         ("stuck_threshold", C.c_float), ("seed", C.c_uint64), ("flags", C.c_uint32),
         ("stream", C.c_void_p),
+    ]
+
+
+class RRTConfig(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("device_id", C.c_int32), ("num_instances", C.c_int32), ("max_iterations", C.c_int32),
+        ("path_cap", C.c_int32), ("flags", C.c_uint32), ("x_limits", C.c_double * 2), ("y_limits", C.c_double * 2),
+        ("delta_distance", C.c_double), ("goal_sample_rate", C.c_double), ("goal_threshold", C.c_double), ("seed", C.c_uint64),
     ]
 
 
@@ -157,6 +168,15 @@ SYMBOLS = {
     "bn_terrain_color_buffers": (C.c_int, [_H, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "bn_terrain_class_counts": (C.c_int, [_H, C.c_void_p, C.c_void_p]),
     "bn_terrain_last_error": (C.c_char_p, []),
+    "bn_rrt_config_init": (None, [C.POINTER(RRTConfig)]),
+    "bn_rrt_create": (C.c_int, [C.POINTER(RRTConfig), C.POINTER(_H)]),
+    "bn_rrt_destroy": (None, [_H]),
+    "bn_rrt_plan_async": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bn_rrt_grow_from_samples_async": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "bn_rrt_sync": (C.c_int, [_H]),
+    "bn_rrt_device_buffer": (C.c_int, [_H, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
+    "bn_rrt_node_storage": (C.c_int32, [_H]),
+    "bn_rrt_last_error": (C.c_char_p, []),
     "bn_device_math_eval": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "bn_device_rng_eval": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "bn_last_error": (C.c_char_p, []),

@@ -30,6 +30,7 @@
 
 #include "../../include/benchnav_mppi.h"
 #include "bn_device_math.h"
+#include "mt19937.h"
 
 namespace bn {
 namespace {
@@ -432,9 +433,7 @@ __global__ __launch_bounds__(256) void terrain_color_kernel(ColorArgs a)
 // What terrain.replay_draws makes on torch's CPU generator, for instance blockIdx.x from seeds[blockIdx.x]: MT19937 seeded with
 // the seed's low 32 bits, one float32 uniform f32(r & 0xFFFFFF) 2^-24 per 32-bit output r; the crater rejection loop (three
 // uniforms per attempt, a fourth for an accepted one), each accepted crater's table entry, then the nph fBm phases and, for
-// the colouring, the two uniforms of the light source.  The 624-word state lives in LDS twice (the block being read and the
-// block being built); every thread follows the same control flow on the same LDS words, so the barriers stay uniform.
-constexpr int kMtN = 624, kMtM = 397;
+// the colouring, the two uniforms of the light source.  The generator is mt19937.h's (two 624-word blocks in LDS).
 constexpr int kDrawThreads = 256;          // >= 227: each of the twist's parallel segments is one word per thread
 constexpr int kMaxDrawCraters = 64;        // placed craters' centres and radii live in LDS
 constexpr int kMaxAttempts = 1000;         // terrain_properties.py:124
@@ -456,53 +455,6 @@ struct DrawArgs {
     float lspan, llo;          // f32(upper_threshold - lower_threshold), f32(lower_threshold)
     double aspan, amin;        // max_angle - min_angle, min_angle
 };
-
-__device__ __forceinline__ uint32_t mt_mix(uint32_t hi, uint32_t lo)
-{
-    const uint32_t y = (hi & 0x80000000u) | (lo & 0x7fffffffu);
-    return (y >> 1) ^ ((y & 1u) ? 0x9908B0DFu : 0u);
-}
-
-__device__ __forceinline__ float mt_uniform(uint32_t y)
-{
-    y ^= y >> 11;
-    y ^= (y << 7) & 0x9D2C5680u;
-    y ^= (y << 15) & 0xEFC60000u;
-    y ^= y >> 18;
-    return __fmul_rn((float)(y & 0xFFFFFFu), 5.9604644775390625e-08f);       // exact: 24 bits times 2^-24
-}
-
-struct MtStream {
-    uint32_t (*mt)[kMtN];      // LDS, two blocks
-    int cur, pos;              // the block being read and the next word in it: the same in every thread
-};
-
-// The next 624 words from mt[cur] into mt[cur ^ 1], in the twist's four dependent segments.  Every thread of the block calls it.
-// mt[cur ^ 1] was last read before the previous refill's barriers, so nobody still reads what this one writes.
-__device__ void mt_refill(MtStream &s)
-{
-    const uint32_t *o = s.mt[s.cur];
-    uint32_t *n = s.mt[s.cur ^ 1];
-    const int t = threadIdx.x;
-    if (t < kMtN - kMtM) n[t] = o[t + kMtM] ^ mt_mix(o[t], o[t + 1]);                                    // i < 227
-    __syncthreads();
-    if (t < kMtN - kMtM) n[t + 227] = n[t] ^ mt_mix(o[t + 227], o[t + 228]);                             // 227 <= i < 454
-    __syncthreads();
-    if (t < 169) n[t + 454] = n[t + 227] ^ mt_mix(o[t + 454], o[t + 455]);                               // 454 <= i < 623
-    __syncthreads();
-    if (t == 0) n[623] = n[396] ^ mt_mix(o[623], n[0]);
-    __syncthreads();
-    s.cur ^= 1;
-    s.pos = 0;
-}
-
-__device__ __forceinline__ uint32_t mt_word(MtStream &s)
-{
-    if (s.pos == kMtN) mt_refill(s);
-    return s.mt[s.cur][s.pos++];
-}
-
-__device__ __forceinline__ float mt_next(MtStream &s) { return mt_uniform(mt_word(s)); }
 
 // One attempt of the crater loop from its three state words: the centre and the radius, and whether it overlaps a placed crater
 // (check_circle_overlap: norm(p - c) < (r_p + r) + margin for any p).
@@ -527,14 +479,7 @@ __global__ __launch_bounds__(kDrawThreads) void terrain_draws_kernel(DrawArgs a)
     __shared__ float px[kMaxDrawCraters], py[kMaxDrawCraters], pr[kMaxDrawCraters];
     __shared__ int first;
     const int b = blockIdx.x, t = threadIdx.x, G = a.G, N = a.N;
-    if (t == 0) {                                                            // init_genrand: a dependent chain
-        uint32_t x = (uint32_t)a.seeds[b];
-        mt[0][0] = x;
-        for (int i = 1; i < kMtN; ++i) {
-            x = 1812433253u * (x ^ (x >> 30)) + (uint32_t)i;
-            mt[0][i] = x;
-        }
-    }
+    if (t == 0) mt_seed(mt[0], (uint32_t)a.seeds[b]);                        // init_genrand: a dependent chain
     __syncthreads();
     MtStream s{mt, 0, kMtN};                                                 // the first draw twists first
     const int want = min(a.want, min(a.maxc, kMaxDrawCraters));

@@ -682,6 +682,63 @@ int bn_terrain_class_counts(bn_terrain_t *h, int32_t *unassigned, int32_t *beyon
 int bn_terrain_spectrum(bn_terrain_t *h, int32_t inst, float *out);
 const char *bn_terrain_last_error(void);
 
+/* ------------------------------------------------------------------------------------------------------------------------------
+ * The RRT global planner (csrc/rrt_kernels.hip): `RRT` and `Tree` of src/planners/global_planners/sampling_based/{rrt,tree}.py for
+ * B planners that share limits and parameters, one workgroup each, bit for bit with the reference's CPU run:
+ * torch's MT19937 stream of each instance's seed parsed into samples, the tree grown by nearest neighbour + steer, then the goal
+ * test, the pick (lowest cost, then lowest index among the near-goal nodes) and the path.  Errors: the rrt error string below.
+ * ---------------------------------------------------------------------------------------------------------------------------- */
+typedef enum bn_rrt_flags {
+    BN_RRT_FLAG_GLOBAL_NODES = 1,  /* keep the nodes in global memory at any size (the path taken above 8191 iterations) */
+    BN_RRT_FLAG_ONE_WAVE = 2,      /* grow with one wave per instance (the slower of the two, DESIGN.md 4.6: kept for measurements) */
+    BN_RRT_FLAG_FOUR_WAVES = 4     /* grow with 256 threads per instance (the default) */
+} bn_rrt_flags;
+
+typedef enum bn_rrt_buffer_id {
+    BN_RRT_BUF_NODES = 0,          /* (B, max_iterations + 1, 2) float32 */
+    BN_RRT_BUF_EDGES = 1,          /* (B, max_iterations + 1) int32, the parent; -1 at the root */
+    BN_RRT_BUF_COSTS = 2,          /* (B, max_iterations + 1) float32 */
+    BN_RRT_BUF_COUNTS = 3,         /* (B) int32 nodes in the tree */
+    BN_RRT_BUF_SAMPLES = 4,        /* (B, max_iterations, 2) float32: the sample of every iteration */
+    BN_RRT_BUF_SAMPLE_FLAGS = 5,   /* (B, max_iterations) int32: 1 where the sample is the goal */
+    BN_RRT_BUF_PATHS = 6,          /* (B, path_cap, 2) float32, root first, NaN beyond the path */
+    BN_RRT_BUF_RESULTS = 7         /* (B, 4) int32: found, picked node (-1), path length, near-goal nodes */
+} bn_rrt_buffer_id;
+
+typedef struct bn_rrt_config {
+    uint32_t struct_size;          /* sizeof(bn_rrt_config), set by the init function */
+    int32_t device_id;
+    int32_t num_instances;         /* B */
+    int32_t max_iterations;        /* rrt.py:34; every iteration adds a node (_steer always returns feasible) */
+    int32_t path_cap;              /* rows of the path buffer per instance; 0 = max_iterations + 1 (no path is longer) */
+    uint32_t flags;                /* bn_rrt_flags */
+    double x_limits[2], y_limits[2];
+    double delta_distance;         /* rrt.py:35 */
+    double goal_sample_rate;       /* rrt.py:36 */
+    double goal_threshold;         /* _is_goal_reached's 0.1 */
+    uint64_t seed;                 /* 0 ... 2^32 - 1: the stream every instance starts from when the first plan passes no seeds */
+} bn_rrt_config;
+
+typedef struct bn_rrt bn_rrt_t;
+void bn_rrt_config_init(bn_rrt_config *cfg);
+/* Arguments are checked before the device is touched; without a device BN_ERR_NO_DEVICE ("no CPU fallback"). */
+int bn_rrt_create(const bn_rrt_config *cfg, bn_rrt_t **out);
+void bn_rrt_destroy(bn_rrt_t *h);
+/* One forward() of every instance on `stream`: starts and goals are HOST (B, 2) float32 (consumed before the call returns; a
+ * position out of the limits is BN_ERR_INVALID and nothing is launched).  seeds: HOST (B) uint64, each 0 ... 2^32 - 1, reseeds the
+ * streams as constructing the planner does; NULL continues every stream where its last plan left it (the reference does not
+ * reseed between forward() calls). */
+int bn_rrt_plan_async(bn_rrt_t *h, void *stream, const float *starts, const float *goals, const uint64_t *seeds);
+/* The growth, the goal test and the path on the caller's samples (B, max_iterations, 2) float32, `where` a bn_mem_kind, in place
+ * of the stream's (which is left where it is). */
+int bn_rrt_grow_from_samples_async(bn_rrt_t *h, void *stream, const float *starts, const float *goals, const void *samples, int where);
+int bn_rrt_sync(bn_rrt_t *h);
+/* Device pointer and size in bytes of one of the handle's buffers (bn_rrt_buffer_id); valid until the handle is destroyed. */
+int bn_rrt_device_buffer(bn_rrt_t *h, int which, void **ptr, size_t *bytes);
+/* Where the growth kernel keeps the tree: 0 = global memory, 1 = nodes in LDS, 2 = nodes and costs in LDS. */
+int32_t bn_rrt_node_storage(bn_rrt_t *h);
+const char *bn_rrt_last_error(void);
+
 /* Test hook: the library's device arithmetic (DESIGN.md "Arithmetic spec") applied elementwise to n device floats:
  * fn 0 = correctly rounded sqrt, 1 / 2 = sin / cos of the spec, 3 = heading wrap (theta + pi) % 2pi - pi with
  * torch.remainder semantics (robot_model.py:90), 4 = its in-loop form, 5 = the sqrt for zero / normal finite arguments.  Lets the tests compare the kernels' building
