@@ -7,6 +7,7 @@
     from benchnav_amd import AStarDWALoop  # test_astar_dwa.py's A* + DWA loop on the device, B rovers per launch
     from benchnav_amd import TerrainGenerator   # DatasetGenerator's map instances (geometry + slip model), B per launch
     from benchnav_amd import RRT           # drop-in for src/planners/global_planners/sampling_based/rrt.py:RRT, B plans per launch
+    from benchnav_amd import CLRRT         # drop-in for src/planners/global_planners/sampling_based/cl_rrt.py:CLRRT, B plans per launch
 """
 from .native import NativeMPPI  # noqa: F401
 
@@ -33,4 +34,7 @@ def __getattr__(name):
     if name == "RRT":
         from .rrt import RRT
         return RRT
+    if name == "CLRRT":
+        from .clrrt import CLRRT
+        return CLRRT
     raise AttributeError(name)

@@ -35,6 +35,11 @@ BN_AD_OK, BN_AD_OUT_OF_BOUNDS, BN_AD_GOAL_COLLISION, BN_AD_FIELD_ERROR = 0, 1, 2
 BN_RRT_FLAG_GLOBAL_NODES, BN_RRT_FLAG_ONE_WAVE, BN_RRT_FLAG_FOUR_WAVES = 1, 2, 4
 (BN_RRT_BUF_NODES, BN_RRT_BUF_EDGES, BN_RRT_BUF_COSTS, BN_RRT_BUF_COUNTS, BN_RRT_BUF_SAMPLES, BN_RRT_BUF_SAMPLE_FLAGS,
  BN_RRT_BUF_PATHS, BN_RRT_BUF_RESULTS) = range(8)
+(BN_CLRRT_BUF_NODES, BN_CLRRT_BUF_EDGES, BN_CLRRT_BUF_COSTS, BN_CLRRT_BUF_COUNTS, BN_CLRRT_BUF_SEQ_LENGTHS, BN_CLRRT_BUF_CONTROLLERS,
+ BN_CLRRT_BUF_ACTION_SEQS, BN_CLRRT_BUF_STATE_SEQS, BN_CLRRT_BUF_SAMPLES, BN_CLRRT_BUF_SAMPLE_FLAGS, BN_CLRRT_BUF_NEAREST,
+ BN_CLRRT_BUF_FEASIBLE, BN_CLRRT_BUF_PATH_ACTIONS, BN_CLRRT_BUF_PATH_STATES, BN_CLRRT_BUF_RESULTS, BN_CLRRT_BUF_STEER_ACTIONS,
+ BN_CLRRT_BUF_STEER_STATES, BN_CLRRT_BUF_STEER_PATHS, BN_CLRRT_BUF_STEER_TARGETS, BN_CLRRT_BUF_STEER_RESULTS, BN_CLRRT_BUF_STEER_COSTS,
+ BN_CLRRT_BUF_STEER_CONTROLLERS) = range(22)
 ABI_VERSION = 7
 
 
@@ -55,6 +60,16 @@ class RRTConfig(C.Structure):
         ("struct_size", C.c_uint32), ("device_id", C.c_int32), ("num_instances", C.c_int32), ("max_iterations", C.c_int32),
         ("path_cap", C.c_int32), ("flags", C.c_uint32), ("x_limits", C.c_double * 2), ("y_limits", C.c_double * 2),
         ("delta_distance", C.c_double), ("goal_sample_rate", C.c_double), ("goal_threshold", C.c_double), ("seed", C.c_uint64),
+    ]
+
+
+class CLRRTConfig(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("device_id", C.c_int32), ("num_instances", C.c_int32), ("max_iterations", C.c_int32),
+        ("max_seqs", C.c_int32), ("path_cap", C.c_int32), ("grid_size", C.c_int32), ("reserved", C.c_int32), ("resolution", C.c_double),
+        ("x_limits", C.c_double * 2), ("y_limits", C.c_double * 2), ("delta_distance", C.c_double), ("goal_sample_rate", C.c_double),
+        ("goal_threshold", C.c_double), ("delta_t", C.c_double), ("transit_dt", C.c_double), ("u_min", C.c_double * 2),
+        ("u_max", C.c_double * 2), ("seed", C.c_uint64),
     ]
 
 
@@ -177,6 +192,17 @@ SYMBOLS = {
     "bn_rrt_device_buffer": (C.c_int, [_H, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
     "bn_rrt_node_storage": (C.c_int32, [_H]),
     "bn_rrt_last_error": (C.c_char_p, []),
+    "bn_clrrt_config_init": (None, [C.POINTER(CLRRTConfig)]),
+    "bn_clrrt_create": (C.c_int, [C.POINTER(CLRRTConfig), C.POINTER(_H)]),
+    "bn_clrrt_destroy": (None, [_H]),
+    "bn_clrrt_set_map": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_double]),
+    "bn_clrrt_plan_async": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bn_clrrt_grow_from_samples_async": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "bn_clrrt_steer_async": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bn_clrrt_sync": (C.c_int, [_H]),
+    "bn_clrrt_device_buffer": (C.c_int, [_H, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
+    "bn_clrrt_path_cap": (C.c_int32, [_H]),
+    "bn_clrrt_last_error": (C.c_char_p, []),
     "bn_device_math_eval": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "bn_device_rng_eval": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "bn_last_error": (C.c_char_p, []),

@@ -1,0 +1,334 @@
+"""MI355X-native closed-loop RRT global planner with the reference's Python interface.
+
+Mirror of `CLRRT(RRT)` in the reference's src/planners/global_planners/sampling_based/cl_rrt.py: every iteration samples a pose,
+finds the nearest node, lays a Dubins path to the sample (src/planners/local_planners/dubins.py), follows it in closed loop with
+pure pursuit and two PID controllers (pure_pursuit.py) on the unicycle dynamics, and appends the last state as a node where the
+follower came within 1 m of the path's end.  The tree is grown on the device (csrc/clrrt_kernels.hip, one wave per planner);
+DESIGN.md 4.7 states the arithmetic and the rules taken over from the reference, among them: the goal node's heading is the FIRST
+forward()'s for the life of the planner, and a steer from a node other than the root updates that node's stored integrals in
+place, feasible or not.
+
+Like `RRT`, this class does not touch torch's, NumPy's or Python's global generators: every planner owns its MT19937 stream on
+the device, seeded like the reference's and continued across forward() calls.
+
+    planner = CLRRT(3, 2, dynamics, objectives, grid_map, delta_t=0.1, max_iterations=500, seed=42)
+    action_seq, state_seq = planner(state)               # (L, 2), (1, L + 1, 3) or (None, None), as the reference
+    actions, states, lengths, found = planner.plan_batch(states, goals, seeds)       # B planners per launch
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+from . import _capi
+from .rrt import _DevArray, _check_seed, _INITIAL_CAPACITY
+
+WORDS = ("LSL", "RSR", "RSL", "LSR", "RLR", "LRL")
+_POINTS = 64
+
+
+class Tree:
+    """The reference Tree's public state after forward() (planner_name="cl_rrt"): `nodes` (capacity, 3), `nodes_count`, `edges`
+    (capacity,) int64, `costs`, `action_seqs` (capacity, max_seqs, 2), `state_seqs` (capacity, max_seqs + 1, 3), `seq_lengths`
+    (capacity,) int64 and `controllers_states` (capacity, 4); zeros (-1, inf) where unset.  The capacity is the reference's: 1000,
+    doubled while the tree does not fit."""
+
+    def __init__(self, n: int, nodes, edges, costs, action_seqs, state_seqs, seq_lengths, controllers_states):
+        cap = _INITIAL_CAPACITY
+        while cap < n:
+            cap *= 2
+        dev, S = nodes.device, int(action_seqs.shape[1])
+        self.nodes = torch.zeros((cap, 3), dtype=torch.float32, device=dev)
+        self.edges = -torch.ones(cap, dtype=torch.int64, device=dev)
+        self.costs = torch.full((cap,), torch.inf, dtype=torch.float32, device=dev)
+        self.action_seqs = torch.zeros((cap, S, 2), dtype=torch.float32, device=dev)
+        self.state_seqs = torch.zeros((cap, S + 1, 3), dtype=torch.float32, device=dev)
+        self.seq_lengths = torch.zeros(cap, dtype=torch.int64, device=dev)
+        self.controllers_states = torch.zeros((cap, 4), dtype=torch.float32, device=dev)
+        self.nodes[:n] = nodes[:n]
+        self.edges[:n] = edges[:n].to(torch.int64)
+        self.costs[:n] = costs[:n]
+        self.action_seqs[:n] = action_seqs[:n]
+        self.state_seqs[:n] = state_seqs[:n]
+        self.seq_lengths[:n] = seq_lengths[:n].to(torch.int64)
+        self.controllers_states[:n] = controllers_states[:n]
+        self.nodes_count = n
+
+
+def _check(lib, code: int):
+    if code != _capi.BN_OK:
+        raise _capi.BenchnavError(code, lib.bn_clrrt_last_error().decode("utf-8", "replace"))
+
+
+class _Handle:
+    """One bn_clrrt handle: B instances of one parameter set on one map."""
+
+    def __init__(self, lib, dev: torch.device, B: int, owner: "CLRRT"):
+        cfg = _capi.CLRRTConfig()
+        lib.bn_clrrt_config_init(C.byref(cfg))
+        cfg.device_id, cfg.num_instances, cfg.max_iterations, cfg.max_seqs = dev.index, B, owner._max_iterations, owner._max_seqs
+        cfg.path_cap = owner._path_cap
+        cfg.grid_size, cfg.resolution = owner._grid_size, owner.resolution
+        cfg.x_limits[0], cfg.x_limits[1] = float(owner.x_limits[0]), float(owner.x_limits[1])
+        cfg.y_limits[0], cfg.y_limits[1] = float(owner.y_limits[0]), float(owner.y_limits[1])
+        cfg.delta_distance, cfg.goal_sample_rate = float(owner._delta_distance), float(owner._goal_sample_rate)
+        cfg.goal_threshold, cfg.delta_t = float(owner._goal_threshold), float(owner._delta_t)
+        for i in range(2):
+            cfg.u_min[i], cfg.u_max[i] = float(owner._u_min[i]), float(owner._u_max[i])
+        cfg.seed = owner._seed
+        self.lib, self.dev, self.B, self.iters, self.S = lib, dev, B, owner._max_iterations, owner._max_seqs
+        self.h = C.c_void_p()
+        _check(lib, lib.bn_clrrt_create(C.byref(cfg), C.byref(self.h)))
+        self.path_cap = int(lib.bn_clrrt_path_cap(self.h))
+        goal = np.ascontiguousarray(owner._goal_host.numpy()[:2], np.float32)
+        _check(lib, lib.bn_clrrt_set_map(self.h, owner._risk.ctypes.data, goal.ctypes.data, float(owner._stuck_threshold)))
+        self.used = False
+
+    def buffer(self, which: int, shape, typestr="<f4") -> torch.Tensor:
+        ptr, nbytes = C.c_void_p(), C.c_size_t()
+        _check(self.lib, self.lib.bn_clrrt_device_buffer(self.h, which, C.byref(ptr), C.byref(nbytes)))
+        return torch.as_tensor(_DevArray(ptr.value, shape, typestr), device=self.dev)
+
+    def close(self):
+        if self.h:
+            self.lib.bn_clrrt_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class CLRRT(nn.Module):
+    def __init__(self, dim_state: int, dim_control: int, dynamics, objectives, grid_map, delta_t: float, max_iterations: int = 500,
+                 delta_distance: float = 5, goal_sample_rate: float = 0.25, max_seqs: int = 250, goal_threshold: float = 1.0,
+                 device: Optional[str] = None, dtype: torch.dtype = torch.float32, seed: int = 42, path_cap: Optional[int] = None) -> None:
+        """The reference's constructor (cl_rrt.py:26-136).  `dynamics` and `objectives` are read like MPPI's and DWA's here: the
+        risk map, the grid's geometry, the action bounds, the goal and the stuck threshold.  path_cap: the longest action sequence
+        forward() can return (default min(max_iterations * max_seqs, 65536)); a longer path raises."""
+        super().__init__()
+        from .mppi import _planner_inputs
+        if dim_state != 3 or dim_control != 2:
+            raise ValueError("CLRRT plans for the unicycle model: dim_state=3, dim_control=2")
+        if dtype != torch.float32:
+            raise ValueError(f"CLRRT runs the float32 dynamics of the device (dtype={dtype}); the reference's default is float32 too")
+        assert dynamics.min_action.shape == (dim_control,), "minimum actions must be a tensor of shape (dim_control,)"
+        assert dynamics.max_action.shape == (dim_control,), "maximum actions must be a tensor of shape (dim_control,)"
+        try:
+            inp = _planner_inputs(dynamics, objectives)
+        except TypeError as e:
+            raise TypeError("CLRRT needs dynamics in 'inference' mode: the device transit reads the predicted risk map, and the "
+                            "reference's own CLRRT fails on observation mode's (state, traversability) tuple") from e
+        self._seed = _check_seed(seed)
+        self.resolution = float(grid_map.resolution)
+        self.x_limits, self.y_limits = grid_map.x_limits, grid_map.y_limits
+        self.device = device if device is not None else "cuda" if torch.cuda.is_available() else "cpu"
+        self._max_iterations, self._max_seqs = int(max_iterations), int(max_seqs)
+        if self._max_iterations < 1 or self._max_seqs < 1:
+            raise ValueError("max_iterations and max_seqs must be >= 1")
+        self._delta_distance, self._goal_sample_rate, self._goal_threshold = delta_distance, goal_sample_rate, goal_threshold
+        self._delta_t = float(delta_t)
+        self._dim_state, self._dim_control, self._dtype = dim_state, dim_control, dtype
+        self._path_cap = 0 if path_cap is None else int(path_cap)
+        self._grid_size = inp["grid_size"]
+        self._stuck_threshold = inp["stuck_threshold"]
+        self._risk = np.ascontiguousarray(inp["risks"].detach().to("cpu", torch.float32).numpy())
+        if self._risk.shape != (self._grid_size, self._grid_size):
+            raise ValueError(f"the risk map must be ({self._grid_size}, {self._grid_size}), got {self._risk.shape}")
+        self._u_min = dynamics.min_action.detach().to("cpu", torch.float32).tolist()
+        self._u_max = dynamics.max_action.detach().to("cpu", torch.float32).tolist()
+        self._goal_host = torch.as_tensor(inp["goal"]).detach().to("cpu", torch.float32)[:2].contiguous()
+        self.tree = None
+        self._planner_name = "cl_rrt"
+        self._start_node = None
+        if not torch.cuda.is_available():
+            raise RuntimeError("benchnav_amd.CLRRT needs an MI355X (gfx950) device; there is no CPU fallback")
+        dev = torch.device(self.device)
+        self._dev = dev if dev.type == "cuda" and dev.index is not None else torch.device("cuda", torch.cuda.current_device())
+        self._goal_node = self._goal_host.clone()                 # grows by one heading per forward(), as the reference's does
+        self._lib = _capi.load()
+        self._handles = {}
+        self._goal_node_indices = []
+        self.last_batch = None
+        self._last_handle = None
+
+    # ---- the reference's interface ---------------------------------------------------------------------------------------
+    def forward(self, state: torch.Tensor):
+        start = torch.as_tensor(state).detach().to("cpu", torch.float32)
+        if tuple(start.shape) != (3,):
+            raise ValueError(f"state must be (3,), got {tuple(start.shape)}")
+        self._start_node = start
+        theta = torch.atan2(self._goal_node[1] - start[1], self._goal_node[0] - start[0])             # cl_rrt.py:150-154
+        self._goal_node = torch.cat((self._goal_node, theta.unsqueeze(0)), dim=0)                   # index 2 stays the first call's
+        if not self._is_within_bounds(start) or not self._is_within_bounds(self._goal_node):        # before any launch
+            raise ValueError("Start or goal position is out of bounds.")
+        h = self._handle(1)
+        seeds = None if h.used else np.array([self._seed], np.uint64)
+        self._launch(h, start.numpy()[None], self._goal_node[:3].numpy()[None], seeds)
+        res = h.buffer(_capi.BN_CLRRT_BUF_RESULTS, (1, 6), "<i4").cpu().numpy()[0]
+        self.tree = self._tree(h, 0, int(res[5]))
+        self._near_goal_count = int(res[3])
+        self._goal_node_indices = [int(res[1])] if res[0] else []     # the pick only: the reference sorts every near-goal node here
+        if not res[0]:
+            return None, None
+        self._raise_unless_path(res)
+        L = int(res[2])
+        actions = h.buffer(_capi.BN_CLRRT_BUF_PATH_ACTIONS, (1, h.path_cap, 2))[0, :L].clone()
+        states = h.buffer(_capi.BN_CLRRT_BUF_PATH_STATES, (1, h.path_cap + 1, 3))[:, :L + 1].clone()
+        return actions.to(self.device), states.to(self.device)
+
+    def _is_within_bounds(self, node: torch.Tensor) -> bool:
+        x, y = node[:2]
+        return self.x_limits[0] <= x.item() <= self.x_limits[1] and self.y_limits[0] <= y.item() <= self.y_limits[1]
+
+    @staticmethod
+    def _raise_unless_path(res):
+        if res[4] != 0:
+            raise RuntimeError(f"the path has {int(res[2])} actions and does not fit the path buffer: construct CLRRT with a larger path_cap")
+        if res[1] == 0:
+            # the reference fails here too (torch.cat of an empty list): the start lies within the goal threshold
+            raise RuntimeError("the start node is the cheapest node within the goal threshold: there is no sequence to return")
+
+    # ---- B planners per launch -------------------------------------------------------------------------------------------
+    def _batch_inputs(self, states, goals):
+        states = torch.as_tensor(states).detach().to("cpu", torch.float32)
+        if states.dim() != 2 or states.shape[1] != 3:
+            raise ValueError(f"states must be (B, 3), got {tuple(states.shape)}")
+        B = int(states.shape[0])
+        g = self._goal_host[None].expand(B, 2) if goals is None else torch.as_tensor(goals).detach().to("cpu", torch.float32)
+        if g.dim() != 2 or g.shape[0] != B or g.shape[1] not in (2, 3):
+            raise ValueError(f"goals must be (B, 2) or (B, 3), got {tuple(g.shape)}")
+        if g.shape[1] == 2:                    # a fresh planner's first forward(): the heading from the start to the goal
+            g = torch.cat((g, torch.atan2(g[:, 1] - states[:, 1], g[:, 0] - states[:, 0])[:, None]), dim=1)
+        for b in range(B):
+            if not self._is_within_bounds(states[b]) or not self._is_within_bounds(g[b]):
+                raise ValueError("Start or goal position is out of bounds.")
+        return B, np.ascontiguousarray(states.numpy()), np.ascontiguousarray(g.numpy())
+
+    def plan_batch(self, states, goals=None, seeds=None):
+        """forward() of B planners that share this one's map and parameters, in one launch.  states: (B, 3); goals: (B, 2) -- the
+        goal heading is then each instance's own atan2(goal - start), a fresh planner's -- or (B, 3) goal nodes, default this
+        planner's goal; seeds: B integers in 0 ... 2^32 - 1, each reseeding its planner's stream as constructing it does; None
+        continues the B streams of the last plan_batch of this batch size.  The costs of instance b run against ITS goal.
+        Returns (actions (B, Lmax, 2), states (B, Lmax + 1, 3), lengths (B,) int32, found (B,) bool) on the device, NaN beyond a
+        path; `batch_tree(b)` and `last_batch` hold the rest."""
+        B, sn, gn = self._batch_inputs(states, goals)
+        sd = None
+        if seeds is not None:
+            if len(seeds) != B:
+                raise ValueError("one seed per instance")
+            sd = np.array([_check_seed(s) for s in seeds], np.uint64)
+        h = self._handle(B)
+        if sd is None and not h.used:
+            sd = np.full(B, self._seed, np.uint64)
+        self._launch(h, sn, gn, sd)
+        return self._batch_result(h)
+
+    def grow_from_samples(self, states, samples, goals=None):
+        """plan_batch on the caller's samples in place of the stream's: samples (B, max_iterations, 3) float32, host or device."""
+        B, sn, gn = self._batch_inputs(states, goals)
+        samples = torch.as_tensor(samples).detach().to(torch.float32).contiguous()
+        if tuple(samples.shape) != (B, self._max_iterations, 3):
+            raise ValueError(f"samples must be ({B}, {self._max_iterations}, 3), got {tuple(samples.shape)}")
+        h = self._handle(B)
+        if samples.is_cuda:
+            samples = samples.to(self._dev)
+            where, ptr = _capi.BN_MEM_DEVICE, samples.data_ptr()
+        else:
+            keep = samples.numpy()
+            where, ptr = _capi.BN_MEM_HOST, keep.ctypes.data
+        _check(self._lib, self._lib.bn_clrrt_grow_from_samples_async(h.h, self._stream(), sn.ctypes.data, gn.ctypes.data, ptr, where))
+        torch.cuda.current_stream(self._dev).synchronize()
+        return self._batch_result(h)
+
+    def steer_batch(self, from_states, controller_states, targets):
+        """One _steer per instance with no tree: from_states (B, 3), controller_states (B, 4) (previous error and integral of the
+        linear, then the angular controller), targets (B, 3).  The costs run against this planner's goal.  Returns a dict of
+        device tensors: `path` (B, 64, 2) float64 truncated reference paths (NaN beyond), `points` (B,), `word` (B,) index into
+        WORDS, `targets` (B, max_seqs) target index per step, `actions` (B, max_seqs, 2), `states` (B, max_seqs + 1, 3),
+        `feasible`, `length`, `cost`, `controllers` (B, 4) float64."""
+        f = np.ascontiguousarray(torch.as_tensor(from_states).detach().to("cpu", torch.float32).numpy())
+        c = np.ascontiguousarray(torch.as_tensor(controller_states).detach().to("cpu", torch.float32).numpy())
+        t = np.ascontiguousarray(torch.as_tensor(targets).detach().to("cpu", torch.float32).numpy())
+        B = f.shape[0]
+        if f.shape != (B, 3) or c.shape != (B, 4) or t.shape != (B, 3):
+            raise ValueError("from_states (B, 3), controller_states (B, 4), targets (B, 3)")
+        h = self._handle(B)
+        _check(self._lib, self._lib.bn_clrrt_steer_async(h.h, self._stream(), f.ctypes.data, c.ctypes.data, t.ctypes.data))
+        torch.cuda.current_stream(self._dev).synchronize()
+        res = h.buffer(_capi.BN_CLRRT_BUF_STEER_RESULTS, (B, 4), "<i4").clone()
+        return {"path": h.buffer(_capi.BN_CLRRT_BUF_STEER_PATHS, (B, _POINTS, 2), "<f8").clone(), "points": res[:, 3], "word": res[:, 2],
+                "targets": h.buffer(_capi.BN_CLRRT_BUF_STEER_TARGETS, (B, h.S), "<i4").clone(),
+                "actions": h.buffer(_capi.BN_CLRRT_BUF_STEER_ACTIONS, (B, h.S, 2)).clone(),
+                "states": h.buffer(_capi.BN_CLRRT_BUF_STEER_STATES, (B, h.S + 1, 3)).clone(), "feasible": res[:, 0] != 0, "length": res[:, 1],
+                "cost": h.buffer(_capi.BN_CLRRT_BUF_STEER_COSTS, (B,)).clone(),
+                "controllers": h.buffer(_capi.BN_CLRRT_BUF_STEER_CONTROLLERS, (B, 4), "<f8").clone()}
+
+    def batch_tree(self, b: int) -> Tree:
+        """Instance b's tree of the last plan_batch / grow_from_samples."""
+        if self._last_handle is None:
+            raise RuntimeError("no batch has been planned")
+        h = self._last_handle
+        n = int(h.buffer(_capi.BN_CLRRT_BUF_COUNTS, (h.B,), "<i4")[int(b)].item())
+        return self._tree(h, int(b), n)
+
+    def sample_table(self):
+        """The samples of the last plan: (samples (B, max_iterations, 3) float32, is_goal (B, max_iterations) bool)."""
+        h = self._last_handle
+        xy = h.buffer(_capi.BN_CLRRT_BUF_SAMPLES, (h.B, h.iters, 3)).clone()
+        fl = h.buffer(_capi.BN_CLRRT_BUF_SAMPLE_FLAGS, (h.B, h.iters), "<i4").clone()
+        return xy, fl != 0
+
+    def iteration_log(self):
+        """What every iteration of the last plan did: (nearest (B, max_iterations) int32 node indices, feasible (B, max_iterations)
+        bool), device tensors."""
+        h = self._last_handle
+        return (h.buffer(_capi.BN_CLRRT_BUF_NEAREST, (h.B, h.iters), "<i4").clone(),
+                h.buffer(_capi.BN_CLRRT_BUF_FEASIBLE, (h.B, h.iters), "<i4").clone() != 0)
+
+    # ---- plumbing --------------------------------------------------------------------------------------------------------
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self._dev).cuda_stream)
+
+    def _handle(self, B: int) -> _Handle:
+        if B not in self._handles:
+            self._handles[B] = _Handle(self._lib, self._dev, B, self)
+        return self._handles[B]
+
+    def _launch(self, h: _Handle, starts: np.ndarray, goals: np.ndarray, seeds: Optional[np.ndarray]) -> None:
+        starts, goals = np.ascontiguousarray(starts, np.float32), np.ascontiguousarray(goals, np.float32)
+        sp = seeds.ctypes.data if seeds is not None else None
+        _check(self._lib, self._lib.bn_clrrt_plan_async(h.h, self._stream(), starts.ctypes.data, goals.ctypes.data, sp))
+        h.used = True
+        self._last_handle = h
+        torch.cuda.current_stream(self._dev).synchronize()
+
+    def _tree(self, h: _Handle, b: int, n: int) -> Tree:
+        c = h.iters + 1
+        return Tree(n, h.buffer(_capi.BN_CLRRT_BUF_NODES, (h.B, c, 3))[b], h.buffer(_capi.BN_CLRRT_BUF_EDGES, (h.B, c), "<i4")[b],
+                    h.buffer(_capi.BN_CLRRT_BUF_COSTS, (h.B, c))[b], h.buffer(_capi.BN_CLRRT_BUF_ACTION_SEQS, (h.B, c, h.S, 2))[b],
+                    h.buffer(_capi.BN_CLRRT_BUF_STATE_SEQS, (h.B, c, h.S + 1, 3))[b],
+                    h.buffer(_capi.BN_CLRRT_BUF_SEQ_LENGTHS, (h.B, c), "<i4")[b], h.buffer(_capi.BN_CLRRT_BUF_CONTROLLERS, (h.B, c, 4))[b])
+
+    def _batch_result(self, h: _Handle):
+        self._last_handle = h
+        res = h.buffer(_capi.BN_CLRRT_BUF_RESULTS, (h.B, 6), "<i4").clone()
+        host = res.cpu().numpy()
+        for b in range(h.B):
+            if host[b, 0] and host[b, 4] != 0:
+                self._raise_unless_path(host[b])
+        found = (res[:, 0] != 0) & (res[:, 1] > 0)
+        lengths = torch.where(found, res[:, 2], torch.zeros_like(res[:, 2])).contiguous()
+        lmax = max(int(lengths.max().item()), 1)
+        actions = h.buffer(_capi.BN_CLRRT_BUF_PATH_ACTIONS, (h.B, h.path_cap, 2))[:, :lmax].clone()
+        states = h.buffer(_capi.BN_CLRRT_BUF_PATH_STATES, (h.B, h.path_cap + 1, 3))[:, :lmax + 1].clone()
+        self.last_batch = {"near_goal_counts": res[:, 3].clone(), "picks": res[:, 1].clone(), "node_counts": res[:, 5].clone(),
+                           "nearest": h.buffer(_capi.BN_CLRRT_BUF_NEAREST, (h.B, h.iters), "<i4").clone(),
+                           "feasible": h.buffer(_capi.BN_CLRRT_BUF_FEASIBLE, (h.B, h.iters), "<i4").clone() != 0}
+        return actions, states, lengths, found

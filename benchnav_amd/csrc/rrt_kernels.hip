@@ -20,6 +20,7 @@
 
 #include "../../include/benchnav_mppi.h"
 #include "mt19937.h"
+#include "rrt_device.h"
 
 namespace bn {
 namespace {
@@ -29,28 +30,6 @@ constexpr int kRrtPathThreads = 256;
 constexpr int kRrtMaxWaves = 4;            // the growth kernel runs 64 or 256 threads
 constexpr int kRrtLdsNodes = 8192;         // float2 nodes in 64 KB: up to 8191 iterations
 constexpr int kRrtResult = 4;              // found, picked node, path length, near-goal count
-
-__device__ __forceinline__ float rrt_norm(float dx, float dy)
-{
-    return sqrtf(__builtin_fmaf(dy, dy, __fmul_rn(dx, dx)));
-}
-
-template <int THREADS>
-__device__ __forceinline__ unsigned long long block_min_u64(unsigned long long key, unsigned long long *part)
-{
-    for (int m = 32; m > 0; m >>= 1) {
-        const unsigned long long o = __shfl_xor(key, m, 64);
-        key = o < key ? o : key;
-    }
-    if (THREADS > 64) {
-        // part[] is written here and read before the barrier that ends the caller's iteration: the next write comes after that barrier
-        if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = key;
-        __syncthreads();
-        key = part[0];
-        for (int w = 1; w < THREADS / 64; ++w) key = part[w] < key ? part[w] : key;
-    }
-    return key;
-}
 
 struct RrtSampleArgs {
     const uint64_t *seeds;     // (B), read when reseed

@@ -739,6 +739,82 @@ int bn_rrt_device_buffer(bn_rrt_t *h, int which, void **ptr, size_t *bytes);
 int32_t bn_rrt_node_storage(bn_rrt_t *h);
 const char *bn_rrt_last_error(void);
 
+/* ------------------------------------------------------------------------------------------------------------------------------
+ * The closed-loop RRT planner (csrc/clrrt_kernels.hip): `CLRRT` of src/planners/global_planners/sampling_based/cl_rrt.py for B
+ * planners that share the map, limits and parameters, one wave each: the MT19937 stream of each instance parsed
+ * into (x, y, theta) samples, the tree grown by nearest neighbour + Dubins path + pure-pursuit closed-loop simulation on the
+ * library's float32 transit and costs, then the goal test, the pick and the concatenated action / state sequences.
+ * Errors: the clrrt error string below.
+ * ---------------------------------------------------------------------------------------------------------------------------- */
+typedef enum bn_clrrt_buffer_id {
+    BN_CLRRT_BUF_NODES = 0,            /* (B, max_iterations + 1, 3) float32 */
+    BN_CLRRT_BUF_EDGES = 1,            /* (B, max_iterations + 1) int32, the parent; -1 at the root */
+    BN_CLRRT_BUF_COSTS = 2,            /* (B, max_iterations + 1) float32 */
+    BN_CLRRT_BUF_COUNTS = 3,           /* (B) int32 nodes in the tree */
+    BN_CLRRT_BUF_SEQ_LENGTHS = 4,      /* (B, max_iterations + 1) int32 */
+    BN_CLRRT_BUF_CONTROLLERS = 5,      /* (B, max_iterations + 1, 4) float32: previous error, integral (linear), the same (angular) */
+    BN_CLRRT_BUF_ACTION_SEQS = 6,      /* (B, max_iterations + 1, max_seqs, 2) float32 */
+    BN_CLRRT_BUF_STATE_SEQS = 7,       /* (B, max_iterations + 1, max_seqs + 1, 3) float32 */
+    BN_CLRRT_BUF_SAMPLES = 8,          /* (B, max_iterations, 3) float32 */
+    BN_CLRRT_BUF_SAMPLE_FLAGS = 9,     /* (B, max_iterations) int32: 1 where the sample is the goal node */
+    BN_CLRRT_BUF_NEAREST = 10,         /* (B, max_iterations) int32: the nearest node of every iteration */
+    BN_CLRRT_BUF_FEASIBLE = 11,        /* (B, max_iterations) int32: 1 where the iteration added a node */
+    BN_CLRRT_BUF_PATH_ACTIONS = 12,    /* (B, path_cap, 2) float32, NaN beyond the path */
+    BN_CLRRT_BUF_PATH_STATES = 13,     /* (B, path_cap + 1, 3) float32, NaN beyond the path */
+    BN_CLRRT_BUF_RESULTS = 14,         /* (B, 6) int32: found, picked node (-1), path length, near-goal nodes, error (BN_ERR_STATE: the path
+                                          does not fit path_cap and was not written), node count */
+    BN_CLRRT_BUF_STEER_ACTIONS = 15,   /* bn_clrrt_steer_async: (B, max_seqs, 2) float32 */
+    BN_CLRRT_BUF_STEER_STATES = 16,    /* (B, max_seqs + 1, 3) float32 */
+    BN_CLRRT_BUF_STEER_PATHS = 17,     /* (B, 64, 2) float64: the truncated reference path, NaN beyond it */
+    BN_CLRRT_BUF_STEER_TARGETS = 18,   /* (B, max_seqs) int32: the target point's index at every step */
+    BN_CLRRT_BUF_STEER_RESULTS = 19,   /* (B, 4) int32: feasible, length, Dubins word (LSL RSR RSL LSR RLR LRL), path points */
+    BN_CLRRT_BUF_STEER_COSTS = 20,     /* (B) float32 */
+    BN_CLRRT_BUF_STEER_CONTROLLERS = 21 /* (B, 4) float64: the controllers' state after the steer */
+} bn_clrrt_buffer_id;
+
+typedef struct bn_clrrt_config {
+    uint32_t struct_size;          /* sizeof(bn_clrrt_config), set by the init function */
+    int32_t device_id;
+    int32_t num_instances;         /* B */
+    int32_t max_iterations;        /* cl_rrt.py:34; at most 2047 (the nodes live in LDS) */
+    int32_t max_seqs;              /* cl_rrt.py:37: closed-loop steps per steer */
+    int32_t path_cap;              /* actions the path buffers hold per instance; 0 = min(max_iterations * max_seqs, 65536) */
+    int32_t grid_size;             /* G: the risk map is (G, G) */
+    int32_t reserved;
+    double resolution;             /* a power of two */
+    double x_limits[2], y_limits[2];
+    double delta_distance;         /* cl_rrt.py:35, at most 12 */
+    double goal_sample_rate;       /* cl_rrt.py:36 */
+    double goal_threshold;         /* cl_rrt.py:38 */
+    double delta_t;                /* the PID controllers' time step */
+    double transit_dt;             /* UnicycleModel.transit's delta_t (its default 0.1: CLRRT does not pass its own) */
+    double u_min[2], u_max[2];     /* action bounds of the transit */
+    uint64_t seed;                 /* 0 ... 2^32 - 1 */
+} bn_clrrt_config;
+
+typedef struct bn_clrrt bn_clrrt_t;
+void bn_clrrt_config_init(bn_clrrt_config *cfg);
+/* Arguments are checked before the device is touched; without a device BN_ERR_NO_DEVICE ("no CPU fallback"). */
+int bn_clrrt_create(const bn_clrrt_config *cfg, bn_clrrt_t **out);
+void bn_clrrt_destroy(bn_clrrt_t *h);
+/* The risk map the dynamics reads, HOST (G, G) float32 (traversability = 1 - clamp(risk, 0, 1)), shared by the instances; the
+ * goal (2) the costs of bn_clrrt_steer_async run against; the stuck threshold.  Synchronous. */
+int bn_clrrt_set_map(bn_clrrt_t *h, const float *risk, const float *goal, double stuck_threshold);
+/* One forward() of every instance on `stream`: starts HOST (B, 3) float32 states, goals HOST (B, 3) float32 goal nodes (x, y,
+ * heading; the costs run against (x, y)), consumed before the call returns; a position out of the limits is BN_ERR_INVALID and
+ * nothing is launched.  seeds as bn_rrt_plan_async. */
+int bn_clrrt_plan_async(bn_clrrt_t *h, void *stream, const float *starts, const float *goals, const uint64_t *seeds);
+/* The growth, the goal test and the path on the caller's samples (B, max_iterations, 3) float32, `where` a bn_mem_kind. */
+int bn_clrrt_grow_from_samples_async(bn_clrrt_t *h, void *stream, const float *starts, const float *goals, const void *samples, int where);
+/* One steer per instance with no tree: from_states HOST (B, 3), controller_states HOST (B, 4), targets HOST (B, 3) float32; the
+ * results are the BN_CLRRT_BUF_STEER_* buffers. */
+int bn_clrrt_steer_async(bn_clrrt_t *h, void *stream, const float *from_states, const float *controller_states, const float *targets);
+int bn_clrrt_sync(bn_clrrt_t *h);
+/* Device pointer and size in bytes of one of the handle's buffers (bn_clrrt_buffer_id); valid until the handle is destroyed. */
+int bn_clrrt_device_buffer(bn_clrrt_t *h, int which, void **ptr, size_t *bytes);
+int32_t bn_clrrt_path_cap(bn_clrrt_t *h);
+const char *bn_clrrt_last_error(void);
+
 /* Test hook: the library's device arithmetic (DESIGN.md "Arithmetic spec") applied elementwise to n device floats:
  * fn 0 = correctly rounded sqrt, 1 / 2 = sin / cos of the spec, 3 = heading wrap (theta + pi) % 2pi - pi with
  * torch.remainder semantics (robot_model.py:90), 4 = its in-loop form, 5 = the sqrt for zero / normal finite arguments.  Lets the tests compare the kernels' building
