@@ -8,6 +8,7 @@
     from benchnav_amd import TerrainGenerator   # DatasetGenerator's map instances (geometry + slip model), B per launch
     from benchnav_amd import RRT           # drop-in for src/planners/global_planners/sampling_based/rrt.py:RRT, B plans per launch
     from benchnav_amd import CLRRT         # drop-in for src/planners/global_planners/sampling_based/cl_rrt.py:CLRRT, B plans per launch
+    from benchnav_amd import CLRRTLoop     # test_cl_rrt.py's plan-follow-replan loop on the device, B rovers per launch
 """
 from .native import NativeMPPI  # noqa: F401
 
@@ -37,4 +38,7 @@ def __getattr__(name):
     if name == "CLRRT":
         from .clrrt import CLRRT
         return CLRRT
+    if name == "CLRRTLoop":
+        from .clrrt_loop import CLRRTLoop
+        return CLRRTLoop
     raise AttributeError(name)

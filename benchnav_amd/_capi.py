@@ -39,7 +39,10 @@ BN_RRT_FLAG_GLOBAL_NODES, BN_RRT_FLAG_ONE_WAVE, BN_RRT_FLAG_FOUR_WAVES = 1, 2, 4
  BN_CLRRT_BUF_ACTION_SEQS, BN_CLRRT_BUF_STATE_SEQS, BN_CLRRT_BUF_SAMPLES, BN_CLRRT_BUF_SAMPLE_FLAGS, BN_CLRRT_BUF_NEAREST,
  BN_CLRRT_BUF_FEASIBLE, BN_CLRRT_BUF_PATH_ACTIONS, BN_CLRRT_BUF_PATH_STATES, BN_CLRRT_BUF_RESULTS, BN_CLRRT_BUF_STEER_ACTIONS,
  BN_CLRRT_BUF_STEER_STATES, BN_CLRRT_BUF_STEER_PATHS, BN_CLRRT_BUF_STEER_TARGETS, BN_CLRRT_BUF_STEER_RESULTS, BN_CLRRT_BUF_STEER_COSTS,
- BN_CLRRT_BUF_STEER_CONTROLLERS) = range(22)
+ BN_CLRRT_BUF_STEER_CONTROLLERS, BN_CLRRT_BUF_MT_STATE, BN_CLRRT_BUF_MT_POS) = range(24)
+(BN_CL_RUNNING, BN_CL_GOAL, BN_CL_TIME_LIMIT, BN_CL_NO_PLAN, BN_CL_NO_SEQUENCE, BN_CL_PLAN_EXHAUSTED, BN_CL_PATH_OVERFLOW,
+ BN_CL_OUT_OF_BOUNDS) = range(8)                                                       # bn_clrrt_loop_status
+BN_CL_EVENT_STEP, BN_CL_EVENT_REPLAN, BN_CL_EVENT_FROZEN = 0, 1, 2                     # bn_clrrt_loop_event
 ABI_VERSION = 7
 
 
@@ -203,6 +206,10 @@ SYMBOLS = {
     "bn_clrrt_device_buffer": (C.c_int, [_H, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
     "bn_clrrt_path_cap": (C.c_int32, [_H]),
     "bn_clrrt_last_error": (C.c_char_p, []),
+    "bn_clrrt_loop_reset": (C.c_int, [_H, _H, C.c_void_p, C.c_void_p, C.c_double, C.c_double]),
+    "bn_clrrt_loop_run": (C.c_int, [_H, _H, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, _FP]),
+    "bn_clrrt_loop_log": (C.c_int, [_H] + [C.c_void_p] * 10),
+    "bn_clrrt_loop_set_plans": (C.c_int, [_H, _H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),
     "bn_device_math_eval": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "bn_device_rng_eval": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "bn_last_error": (C.c_char_p, []),

@@ -22,6 +22,7 @@
 #include <string>
 
 #include "../../include/benchnav_mppi.h"
+#include "clrrt_view.h"
 #include "dwa_device.h"
 #include "mt19937.h"
 #include "rrt_device.h"
@@ -34,6 +35,7 @@ constexpr int kClrrtSampleThreads = 256;   // >= 227 (mt19937.h)
 constexpr int kClrrtPathThreads = 256;
 constexpr int kClrrtPoints = 64;           // path points a steer can hold: bn_clrrt_create bounds delta_distance accordingly
 constexpr int kClrrtResult = 6;            // found, picked node, path length, near-goal count, error, node count
+static_assert(kClrrtResult == kClrrtResultWords, "clrrt_view.h: the follow kernel reads the result rows");
 constexpr int kClrrtSteerResult = 4;       // feasible, length, word, points
 constexpr int kClrrtMaxNodes = 2048;       // 24 bytes of LDS per node
 constexpr float kHalfPi32 = 1.57079637050628662f;      // f32(pi / 2)
@@ -68,12 +70,14 @@ struct ClrrtSampleArgs {
     int32_t *flags;            // (B, iters) 1 where the sample is the goal
     int iters, reseed;
     float rate, xspan, x0, yspan, y0;
+    const int32_t *active;     // (B) or nullptr = every instance: an instance whose word is 0 returns before touching anything
 };
 
 __global__ __launch_bounds__(kClrrtSampleThreads) void clrrt_samples_kernel(ClrrtSampleArgs a)
 {
     __shared__ uint32_t mt[2][kMtN];
     const int b = blockIdx.x, t = threadIdx.x;
+    if (a.active && a.active[b] == 0) return;              // (uniform over the workgroup: no barrier is left waiting)
     int pos = kMtN;
     if (a.reseed) {
         if (t == 0) mt_seed(mt[0], (uint32_t)a.seeds[b]);
@@ -359,6 +363,7 @@ struct ClrrtGrowArgs {
     int32_t *near;             // (B, iters) nearest index of every iteration
     int32_t *feasible;         // (B, iters)
     int iters, cap;
+    const int32_t *active;     // (B) or nullptr = every instance
 };
 
 template <int GEO>
@@ -368,6 +373,7 @@ __global__ __launch_bounds__(kClrrtThreads) void clrrt_grow_kernel(ClrrtGrowArgs
     __shared__ double2 lpts[kClrrtPoints];
     __shared__ double lseg[kClrrtPoints];
     const int b = blockIdx.x, t = threadIdx.x, S = a.c.max_seqs;
+    if (a.active && a.active[b] == 0) return;
     float4 *laux = (float4 *)(lxy + ((a.cap + 1) & ~1));          // 16-byte aligned behind the (x, y) pairs
     float *nodes = a.nodes + (size_t)b * a.cap * 3;
     int32_t *edges = a.edges + (size_t)b * a.cap, *lens = a.seq_lengths + (size_t)b * a.cap;
@@ -481,6 +487,7 @@ struct ClrrtPathArgs {
     int32_t *results;          // (B, kClrrtResult)
     int cap, path_cap, max_seqs;
     float threshold;
+    const int32_t *active;     // (B) or nullptr = every instance
 };
 
 __global__ __launch_bounds__(kClrrtPathThreads) void clrrt_path_kernel(ClrrtPathArgs a)
@@ -489,6 +496,7 @@ __global__ __launch_bounds__(kClrrtPathThreads) void clrrt_path_kernel(ClrrtPath
     __shared__ int cnt[4];
     __shared__ int sh[3];                                   // pick, total length, fits
     const int b = blockIdx.x, t = threadIdx.x, S = a.max_seqs;
+    if (a.active && a.active[b] == 0) return;
     const float *nodes = a.nodes + (size_t)b * a.cap * 3, *costs = a.costs + (size_t)b * a.cap;
     const int32_t *edges = a.edges + (size_t)b * a.cap, *lens = a.seq_lengths + (size_t)b * a.cap;
     const float *aseq = a.action_seqs + (size_t)b * a.cap * S * 2, *sseq = a.state_seqs + (size_t)b * a.cap * (S + 1) * 3;
@@ -544,6 +552,15 @@ __global__ __launch_bounds__(kClrrtPathThreads) void clrrt_path_kernel(ClrrtPath
     const int rows = pick > 0 && fits ? L + 1 : 0;
     for (int i = 2 * L + t; i < 2 * a.path_cap; i += kClrrtPathThreads) pa[i] = NAN;
     for (int i = 3 * rows + t; i < 3 * (a.path_cap + 1); i += kClrrtPathThreads) ps[i] = NAN;
+}
+
+// A new episode of the plan-follow-replan loop: every instance's stream seeded as constructing its planner does, nothing drawn.
+__global__ void clrrt_seed_kernel(const uint64_t *seeds, uint32_t *state, int32_t *pos, int B)
+{
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    mt_seed(state + (size_t)b * kMtN, (uint32_t)seeds[b]);
+    pos[b] = kMtN;
 }
 
 thread_local std::string g_clrrt_error;
@@ -628,19 +645,21 @@ int clrrt_stage(bn_clrrt_t *h, const float *starts, const float *goals, hipStrea
     return BN_OK;
 }
 
-int clrrt_grow_and_pick(bn_clrrt_t *h, hipStream_t s)
+int clrrt_draw_samples(bn_clrrt_t *h, hipStream_t s, bool reseed, const int32_t *active);
+
+int clrrt_grow_and_pick(bn_clrrt_t *h, hipStream_t s, const int32_t *active = nullptr)
 {
     bn::ClrrtGrowArgs g{};
     g.c = h->c; g.starts = h->starts; g.goals = h->goals; g.samples = h->samples; g.nodes = h->nodes; g.edges = h->edges; g.costs = h->costs;
     g.seq_lengths = h->lens; g.ctrl = h->ctrl; g.action_seqs = h->aseq; g.state_seqs = h->sseq; g.counts = h->counts; g.near = h->near;
-    g.feasible = h->feasible; g.iters = h->iters; g.cap = h->cap;
+    g.feasible = h->feasible; g.iters = h->iters; g.cap = h->cap; g.active = active;
     if (h->geo == bn::kGeoPow2) bn::clrrt_grow_kernel<bn::kGeoPow2><<<h->B, bn::kClrrtThreads, h->lds_bytes, s>>>(g);
     else bn::clrrt_grow_kernel<bn::kGeoPow2Origin0><<<h->B, bn::kClrrtThreads, h->lds_bytes, s>>>(g);
     CLRRT_HIP(hipGetLastError());
     bn::ClrrtPathArgs p{};
     p.nodes = h->nodes; p.edges = h->edges; p.costs = h->costs; p.seq_lengths = h->lens; p.action_seqs = h->aseq; p.state_seqs = h->sseq;
     p.counts = h->counts; p.goals = h->goals; p.path_actions = h->path_actions; p.path_states = h->path_states; p.results = h->results;
-    p.cap = h->cap; p.path_cap = h->path_cap; p.max_seqs = h->S; p.threshold = (float)h->cfg.goal_threshold;
+    p.cap = h->cap; p.path_cap = h->path_cap; p.max_seqs = h->S; p.threshold = (float)h->cfg.goal_threshold; p.active = active;
     bn::clrrt_path_kernel<<<h->B, bn::kClrrtPathThreads, 0, s>>>(p);
     CLRRT_HIP(hipGetLastError());
     CLRRT_HIP(hipEventRecord(h->ev_done, s));
@@ -648,7 +667,70 @@ int clrrt_grow_and_pick(bn_clrrt_t *h, hipStream_t s)
     return BN_OK;
 }
 
+int clrrt_draw_samples(bn_clrrt_t *h, hipStream_t s, bool reseed, const int32_t *active)
+{
+    bn::ClrrtSampleArgs a{};
+    a.seeds = h->seeds; a.state = h->state; a.pos = h->pos; a.goals = h->goals; a.samples = h->samples; a.flags = h->flags;
+    a.iters = h->iters; a.reseed = reseed; a.active = active;
+    a.rate = (float)h->cfg.goal_sample_rate;
+    a.xspan = (float)(h->cfg.x_limits[1] - h->cfg.x_limits[0]); a.x0 = (float)h->cfg.x_limits[0];
+    a.yspan = (float)(h->cfg.y_limits[1] - h->cfg.y_limits[0]); a.y0 = (float)h->cfg.y_limits[0];
+    bn::clrrt_samples_kernel<<<h->B, bn::kClrrtSampleThreads, 0, s>>>(a);
+    CLRRT_HIP(hipGetLastError());
+    return BN_OK;
+}
+
 }  // namespace
+
+// ---- what the plan-follow-replan loop drives (clrrt_view.h) ----
+namespace bn {
+
+int clrrt_view(bn_clrrt *h, ClrrtView *v)
+{
+    if (!h || !v) return clrrt_fail(BN_ERR_INVALID, "null argument");
+    v->cfg = h->cfg; v->device = h->cfg.device_id; v->B = h->B; v->iters = h->iters; v->path_cap = h->path_cap; v->have_map = h->have_map;
+    v->starts = h->starts; v->goals = h->goals; v->samples = h->samples; v->path_actions = h->path_actions; v->path_states = h->path_states;
+    v->results = h->results;
+    return BN_OK;
+}
+
+int clrrt_loop_reset(bn_clrrt *h, hipStream_t s, const float *goal_nodes, const uint64_t *seeds)
+{
+    if (!h || !goal_nodes || !seeds) return clrrt_fail(BN_ERR_INVALID, "null argument");
+    for (int b = 0; b < h->B; ++b) {
+        if (seeds[b] > 0xFFFFFFFFull) return clrrt_fail(BN_ERR_INVALID, "Seed must be between 0 and 2**32 - 1");
+        if (!std::isfinite(goal_nodes[3 * b]) || !std::isfinite(goal_nodes[3 * b + 1]) || !std::isfinite(goal_nodes[3 * b + 2]))
+            return clrrt_fail(BN_ERR_INVALID, "goal nodes must be finite");
+    }
+    ClrrtDeviceGuard guard(h->cfg.device_id);
+    if (!guard.ok) return clrrt_fail(BN_ERR_HIP, "hipSetDevice failed");
+    if (h->ev_recorded) CLRRT_HIP(hipEventSynchronize(h->ev_done));                    // the staging block is free again
+    const size_t B = h->B;
+    std::memcpy(h->pinned + B * 12, goal_nodes, B * 12);
+    uint64_t *ps = (uint64_t *)(h->pinned + B * 40);
+    for (size_t b = 0; b < B; ++b) ps[b] = seeds[b];
+    CLRRT_HIP(hipMemcpyAsync(h->goals, h->pinned + B * 12, B * 12, hipMemcpyHostToDevice, s));
+    CLRRT_HIP(hipMemcpyAsync(h->seeds, ps, B * 8, hipMemcpyHostToDevice, s));
+    clrrt_seed_kernel<<<(h->B + 63) / 64, 64, 0, s>>>(h->seeds, h->state, h->pos, h->B);
+    CLRRT_HIP(hipGetLastError());
+    CLRRT_HIP(hipEventRecord(h->ev_done, s));
+    h->ev_recorded = true;
+    h->seeded = true;
+    return BN_OK;
+}
+
+int clrrt_plan_masked(bn_clrrt *h, hipStream_t s, const int32_t *active, int draw)
+{
+    if (!h || !active) return clrrt_fail(BN_ERR_INVALID, "null argument");
+    if (!h->have_map) return clrrt_fail(BN_ERR_STATE, "bn_clrrt_set_map has not been called");
+    ClrrtDeviceGuard guard(h->cfg.device_id);
+    if (!guard.ok) return clrrt_fail(BN_ERR_HIP, "hipSetDevice failed");
+    if (draw)
+        if (int rc = clrrt_draw_samples(h, s, false, active)) return rc;
+    return clrrt_grow_and_pick(h, s, active);
+}
+
+}  // namespace bn
 
 extern "C" {
 
@@ -799,14 +881,7 @@ int bn_clrrt_plan_async(bn_clrrt_t *h, void *stream, const float *starts, const 
         for (int b = 0; b < h->B; ++b) ps[b] = seeds ? seeds[b] : h->cfg.seed;
         CLRRT_HIP(hipMemcpyAsync(h->seeds, ps, (size_t)h->B * 8, hipMemcpyHostToDevice, s));
     }
-    bn::ClrrtSampleArgs a{};
-    a.seeds = h->seeds; a.state = h->state; a.pos = h->pos; a.goals = h->goals; a.samples = h->samples; a.flags = h->flags;
-    a.iters = h->iters; a.reseed = reseed;
-    a.rate = (float)h->cfg.goal_sample_rate;
-    a.xspan = (float)(h->cfg.x_limits[1] - h->cfg.x_limits[0]); a.x0 = (float)h->cfg.x_limits[0];
-    a.yspan = (float)(h->cfg.y_limits[1] - h->cfg.y_limits[0]); a.y0 = (float)h->cfg.y_limits[0];
-    bn::clrrt_samples_kernel<<<h->B, bn::kClrrtSampleThreads, 0, s>>>(a);
-    CLRRT_HIP(hipGetLastError());
+    if ((rc = clrrt_draw_samples(h, s, reseed, nullptr))) return rc;
     h->seeded = true;
     return clrrt_grow_and_pick(h, s);
 }
@@ -899,6 +974,8 @@ int bn_clrrt_device_buffer(bn_clrrt_t *h, int which, void **ptr, size_t *bytes)
     case BN_CLRRT_BUF_STEER_RESULTS: *ptr = h->st_results; *bytes = B * bn::kClrrtSteerResult * 4; break;
     case BN_CLRRT_BUF_STEER_COSTS: *ptr = h->st_cost; *bytes = B * 4; break;
     case BN_CLRRT_BUF_STEER_CONTROLLERS: *ptr = h->st_ctrl_out; *bytes = B * 32; break;
+    case BN_CLRRT_BUF_MT_STATE: *ptr = h->state; *bytes = B * bn::kMtN * 4; break;
+    case BN_CLRRT_BUF_MT_POS: *ptr = h->pos; *bytes = B * 4; break;
     default: return clrrt_fail(BN_ERR_INVALID, "unknown CL-RRT buffer id");
     }
     return BN_OK;

@@ -6,6 +6,7 @@
 #include "../../include/benchnav_mppi.h"
 #include "mppi_kernels.h"
 #include "astar_dwa.h"
+#include "clrrt_view.h"
 
 #include <algorithm>
 #include <atomic>
@@ -285,6 +286,17 @@ struct bn_mppi {
     int ad_cap = 0, ad_len = 0;  // steps the log holds / the latest call ran
     uint64_t ad_step = 0;        // episode steps since bn_astar_dwa_reset
     int ad_walk = 0;             // bn_astar_dwa_set_walk: 0 the serial next-hop walk, 1 the A* handle's jump tables
+    // CL-RRT plan-follow-replan loop (bn_clrrt_loop_run)
+    bn::ClrrtRover *d_cl_rover = nullptr;   // (B)
+    int32_t *d_cl_flags = nullptr;          // (B) the replan mask | the pending counter
+    float *d_cl_goal = nullptr;             // (B, 3) goal nodes
+    float *d_cl_log = nullptr;              // (cap+1, B, 3) states | (cap, B) rewards | (cap, B, 2) actions | (cap, B) deviations | plan index | events
+    int32_t *h_cl_pending = nullptr;        // pinned: the pending counter of the latest round
+    hipEvent_t cl_ev[2] = {};               // around a follow launch (follow_ms)
+    int cl_cap = 0, cl_len = 0;             // iterations the log holds / the latest call ran
+    int32_t cl_iter = 0, cl_limit_steps = 0;   // iterations since the reset; the step count at which elapsed > time_limit
+    bool cl_ready = false;                  // bn_clrrt_loop_reset has run
+    bn_clrrt_t *cl_planner = nullptr;       // ... with this CL-RRT handle: the episode's goals, streams and paths live in it
     size_t scratch_bytes = 0, eps_bytes = 0, idx_count = 0;
     float *h_pinned = nullptr;   // pinned staging for (B,3) states
     // profiling
@@ -1156,11 +1168,15 @@ void bn_mppi_destroy(bn_mppi_t *h)
                     h->d_w, h->d_ustar /* d_xstar lives in the same block */, h->d_stats, h->d_scratch, h->d_idx, h->d_lat_mean, h->d_lat_std,
                     h->d_ep_states, h->d_ep_reward, h->d_env_state, h->d_ep_done, h->d_ep_action, h->d_slip_std,
                     h->d_ustar2[0], h->d_ustar2[1], h->d_ustar2[2], h->d_ustar2[3], h->d_stats2[0], h->d_stats2[1], h->d_stats2[2], h->d_stats2[3],
-                    h->d_ticket, h->d_gpart, h->d_mean_used, h->d_ad_i, h->d_ad_state, h->d_ad_log};
+                    h->d_ticket, h->d_gpart, h->d_mean_used, h->d_ad_i, h->d_ad_state, h->d_ad_log,
+                    h->d_cl_rover, h->d_cl_flags, h->d_cl_goal, h->d_cl_log};
     static_assert(kSlots == 4, "the list above names the four slots");
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (h->d_flags) (void)hipFree(h->d_flags);
+    if (h->h_cl_pending) (void)hipHostFree(h->h_cl_pending);
+    for (hipEvent_t e : h->cl_ev)
+        if (e) (void)hipEventDestroy(e);
     for (int q = 0; q < kSlots; ++q) {
         if (h->d_gran[q]) (void)hipFree(h->d_gran[q]);
         if (h->d_cost[q]) (void)hipFree(h->d_cost[q]);
@@ -2593,6 +2609,183 @@ int bn_astar_dwa_episode_log(bn_mppi_t *h, float *states, float *rewards, float 
     int32_t err = 0;
     BN_HIP(hipMemcpy(&err, h->d_ad_i + 4 * B, sizeof(int32_t), hipMemcpyDeviceToHost));
     if (err) return fail(BN_ERR_STATE, "a next-hop walk broke (more than H*W nodes, or onto an unreachable cell): the A* field is not a valid solve");
+    return BN_OK;
+}
+
+// ---- the CL-RRT plan-follow-replan loop (clrrt_loop.hip) ----
+
+// what bn_clrrt_loop_reset verified once: the CL-RRT handle plans on the environment's grid
+static int clrrt_loop_view(bn_mppi *h, bn_clrrt_t *c, bn::ClrrtView *v)
+{
+    if (bn::clrrt_view(c, v) != BN_OK) return fail(BN_ERR_INVALID, "%s", bn_clrrt_last_error());
+    const bn_clrrt_config &k = v->cfg;
+    const bn::SolveParams &p = h->p;
+    if (v->device != h->cfg.device_id) return fail(BN_ERR_INVALID, "the CL-RRT handle is on device %d, the environment on device %d", v->device, h->cfg.device_id);
+    if (v->B != p.B) return fail(BN_ERR_INVALID, "the CL-RRT handle has %d instances, the environment %d", v->B, p.B);
+    if (k.grid_size != p.G || (float)k.resolution != p.res) return fail(BN_ERR_INVALID, "the CL-RRT handle's grid (%d cells of %g) is not the environment's (%d of %g)", k.grid_size, k.resolution, p.G, (double)p.res);
+    if ((float)k.x_limits[0] != p.x0 || (float)k.x_limits[1] != p.x_hi || (float)k.y_limits[0] != p.y0 || (float)k.y_limits[1] != p.y_hi)
+        return fail(BN_ERR_INVALID, "the CL-RRT handle's limits are not the environment's");
+    if ((float)k.u_min[0] != p.umin0 || (float)k.u_min[1] != p.umin1 || (float)k.u_max[0] != p.umax0 || (float)k.u_max[1] != p.umax1)
+        return fail(BN_ERR_INVALID, "the CL-RRT handle's action bounds are not the environment's");
+    if (!v->have_map) return fail(BN_ERR_STATE, "bn_clrrt_set_map must precede the loop");
+    return BN_OK;
+}
+
+int bn_clrrt_loop_reset(bn_mppi_t *h, bn_clrrt_t *c, const float *goal_nodes, const uint64_t *seeds, double delta_t, double time_limit)
+{
+    if (!h || !c || !goal_nodes || !seeds) return fail(BN_ERR_INVALID, "null argument");
+    if (!std::isfinite(time_limit)) return fail(BN_ERR_INVALID, "time_limit must be finite");
+    if (!h->env_attached) return fail(BN_ERR_STATE, "bn_mppi_env_attach must precede bn_clrrt_loop_reset");
+    if ((float)delta_t != h->p.env_dt) return fail(BN_ERR_INVALID, "delta_t (%g) is not the environment's (%g)", delta_t, (double)h->p.env_dt);
+    bn::ClrrtView v;
+    if (int rc = clrrt_loop_view(h, c, &v)) return rc;
+    BN_BIND(h);
+    if (int rc = settle_point(h)) return rc;
+    if (int rc = flush_tail(h)) return rc;
+    const size_t B = h->p.B;
+    if (!h->d_cl_rover) {
+        BN_HIP(hipMalloc((void **)&h->d_cl_rover, B * sizeof(bn::ClrrtRover)));
+        BN_HIP(hipMalloc((void **)&h->d_cl_flags, (B + 1) * sizeof(int32_t)));
+        BN_HIP(hipMalloc((void **)&h->d_cl_goal, B * 3 * sizeof(float)));
+        BN_HIP(hipHostMalloc((void **)&h->h_cl_pending, sizeof(int32_t), hipHostMallocDefault));
+        BN_HIP(hipEventCreate(&h->cl_ev[0]));
+        BN_HIP(hipEventCreate(&h->cl_ev[1]));
+    }
+    BN_HIP(hipStreamSynchronize(h->stream));                               // a previous episode's launches are done with the words below
+    std::vector<bn::ClrrtRover> r0(B, bn::ClrrtRover{0, BN_CL_RUNNING, 1, 0, 0, 0, 0, -1});
+    BN_HIP(hipMemcpy(h->d_cl_rover, r0.data(), B * sizeof(bn::ClrrtRover), hipMemcpyHostToDevice));
+    BN_HIP(hipMemset(h->d_cl_flags, 0, (B + 1) * sizeof(int32_t)));
+    BN_HIP(hipMemcpy(h->d_cl_goal, goal_nodes, B * 3 * sizeof(float), hipMemcpyHostToDevice));
+    if (bn::clrrt_loop_reset(c, h->stream, goal_nodes, seeds) != BN_OK) return fail(BN_ERR_INVALID, "%s", bn_clrrt_last_error());
+    // PlanetaryEnv: elapsed += delta_t in float64, elapsed > time_limit after the step: the first step count at which that holds
+    double elapsed = 0.0;
+    int32_t k = 0;
+    const double dt = delta_t;                     // the Python float, not its float32 rounding: 5 x 0.1 is exactly 0.5, 5 x 0.1f is above it
+    if (dt > 0.0) {
+        while (!(elapsed > time_limit) && k < INT32_MAX) { elapsed += dt; ++k; }
+    } else {
+        k = INT32_MAX;
+    }
+    h->cl_limit_steps = k;
+    h->cl_iter = 0;
+    h->cl_len = 0;
+    h->cl_ready = true;
+    h->cl_planner = c;
+    return BN_OK;
+}
+
+int bn_clrrt_loop_run(bn_mppi_t *h, bn_clrrt_t *c, int32_t n, float *states_device, const float *z_device,
+                      const float *samples_device, int32_t num_tables, uint32_t flags, float *follow_ms)
+{
+    if (!h || !c || !states_device) return fail(BN_ERR_INVALID, "null argument");
+    if (n < 1 || n > (1 << 24)) return fail(BN_ERR_INVALID, "n must be in [1, 2^24]");
+    if (num_tables < 0) return fail(BN_ERR_INVALID, "num_tables must be >= 0");
+    if (!h->cl_ready) return fail(BN_ERR_STATE, "bn_clrrt_loop_reset must precede bn_clrrt_loop_run");
+    if (c != h->cl_planner) return fail(BN_ERR_INVALID, "this is not the CL-RRT handle bn_clrrt_loop_reset was given: the episode's goals, streams and plans live in that one");
+    if (!h->env_attached || !h->goal_set) return fail(BN_ERR_STATE, "bn_mppi_env_attach and the goals must precede bn_clrrt_loop_run");
+    if ((int64_t)h->cl_iter + n > INT32_MAX) return fail(BN_ERR_INVALID, "the episode's iteration count exceeds 2^31 - 1");
+    bn::ClrrtView v;
+    if (int rc = clrrt_loop_view(h, c, &v)) return rc;
+    BN_BIND(h);
+    if (int rc = settle_point(h)) return rc;
+    if (int rc = flush_tail(h)) return rc;
+    if (int rc = guard_foreign_overlap(h)) return rc;
+    const size_t B = h->p.B, N = (size_t)n;
+    if (n > h->cl_cap) {
+        BN_HIP(hipStreamSynchronize(h->stream));
+        if (h->d_cl_log) BN_HIP(hipFree(h->d_cl_log));
+        h->d_cl_log = nullptr;
+        BN_HIP(hipMalloc((void **)&h->d_cl_log, ((N + 1) * 3 + N * 6) * B * sizeof(float)));
+        h->cl_cap = n;
+    }
+    const size_t cap = (size_t)h->cl_cap;
+    bn::ClrrtFollowArgs x{};
+    x.rover = h->d_cl_rover; x.state = states_device; x.starts = v.starts; x.goal_nodes = h->d_cl_goal;
+    x.path_actions = v.path_actions; x.path_states = v.path_states; x.results = v.results;
+    x.active = h->d_cl_flags; x.pending = h->d_cl_flags + B; x.psamples = v.samples;
+    x.inj = samples_device; x.P = samples_device ? num_tables : 0; x.iters = v.iters; x.path_cap = v.path_cap;
+    float *lg = h->d_cl_log;
+    x.log_states = lg; x.log_reward = lg + (cap + 1) * B * 3; x.log_action = x.log_reward + cap * B; x.log_dev = x.log_action + cap * B * 2;
+    x.log_plan = reinterpret_cast<int32_t *>(x.log_dev + cap * B); x.log_event = x.log_plan + cap * B;
+    x.z = z_device; x.iter0 = h->cl_iter; x.n = n; x.limit_steps = h->cl_limit_steps; x.use_lds = (flags & 1u) ? 0 : 1;
+    x.xlo = v.cfg.x_limits[0]; x.xhi = v.cfg.x_limits[1]; x.ylo = v.cfg.y_limits[0]; x.yhi = v.cfg.y_limits[1];
+    float ms_total = 0.0f;
+    // One host round trip per ROUND of replans: every pending rover takes its plan and at least one iteration (or a status) in the
+    // next follow launch, so n + 2 rounds bound the loop.
+    for (int64_t round = 0; round < (int64_t)n + 2; ++round) {
+        if (follow_ms) BN_HIP(hipEventRecord(h->cl_ev[0], h->stream));
+        BN_HIP(bn::launch_clrrt_follow(h->p, x, h->stream));
+        if (follow_ms) BN_HIP(hipEventRecord(h->cl_ev[1], h->stream));
+        BN_HIP(hipMemcpyAsync(h->h_cl_pending, h->d_cl_flags + B, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+        BN_HIP(hipStreamSynchronize(h->stream));
+        if (follow_ms) {
+            float ms = 0.0f;
+            BN_HIP(hipEventElapsedTime(&ms, h->cl_ev[0], h->cl_ev[1]));
+            ms_total += ms;
+        }
+        if (*h->h_cl_pending == 0) break;
+        if (bn::clrrt_plan_masked(c, h->stream, h->d_cl_flags, samples_device ? 0 : 1) != BN_OK) return fail(BN_ERR_HIP, "%s", bn_clrrt_last_error());
+        BN_HIP(hipMemsetAsync(h->d_cl_flags + B, 0, sizeof(int32_t), h->stream));     // (the follow kernel clears the mask words it takes)
+    }
+    if (follow_ms) *follow_ms = ms_total;
+    h->cl_iter += n;
+    h->cl_len = n;
+    return BN_OK;
+}
+
+int bn_clrrt_loop_log(bn_mppi_t *h, float *states, float *rewards, float *actions, float *deviations, int32_t *plan_index,
+                      int32_t *events, int32_t *done_iter, int32_t *status, int32_t *plans, int32_t *steps)
+{
+    if (!h) return fail(BN_ERR_INVALID, "null handle");
+    if (!h->d_cl_log || h->cl_len < 1) return fail(BN_ERR_STATE, "no CL-RRT loop has been run");
+    BN_BIND(h);
+    if (int rc = settle_point(h)) return rc;
+    BN_HIP(hipStreamSynchronize(h->stream));
+    const size_t B = h->p.B, n = (size_t)h->cl_len, cap = (size_t)h->cl_cap;
+    const float *lg = h->d_cl_log, *rw = lg + (cap + 1) * B * 3, *ac = rw + cap * B, *dv = ac + cap * B * 2, *pl = dv + cap * B, *ev = pl + cap * B;
+    if (states) BN_HIP(hipMemcpy(states, lg, (n + 1) * B * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    if (rewards) BN_HIP(hipMemcpy(rewards, rw, n * B * sizeof(float), hipMemcpyDeviceToHost));
+    if (actions) BN_HIP(hipMemcpy(actions, ac, n * B * 2 * sizeof(float), hipMemcpyDeviceToHost));
+    if (deviations) BN_HIP(hipMemcpy(deviations, dv, n * B * sizeof(float), hipMemcpyDeviceToHost));
+    if (plan_index) BN_HIP(hipMemcpy(plan_index, pl, n * B * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (events) BN_HIP(hipMemcpy(events, ev, n * B * sizeof(int32_t), hipMemcpyDeviceToHost));
+    std::vector<bn::ClrrtRover> r(B);
+    BN_HIP(hipMemcpy(r.data(), h->d_cl_rover, B * sizeof(bn::ClrrtRover), hipMemcpyDeviceToHost));
+    for (size_t b = 0; b < B; ++b) {
+        if (done_iter) done_iter[b] = r[b].done_iter;
+        if (status) status[b] = r[b].status;
+        if (plans) plans[b] = r[b].plans;
+        if (steps) steps[b] = r[b].steps;
+    }
+    return BN_OK;
+}
+
+int bn_clrrt_loop_set_plans(bn_mppi_t *h, bn_clrrt_t *c, const float *actions, const float *states, const int32_t *lengths,
+                            int32_t max_length, int32_t iteration)
+{
+    if (!h || !c || !actions || !states || !lengths) return fail(BN_ERR_INVALID, "null argument");
+    if (!h->cl_ready) return fail(BN_ERR_STATE, "bn_clrrt_loop_reset must precede bn_clrrt_loop_set_plans");
+    if (c != h->cl_planner) return fail(BN_ERR_INVALID, "this is not the CL-RRT handle bn_clrrt_loop_reset was given: the episode's goals, streams and plans live in that one");
+    bn::ClrrtView v;
+    if (int rc = clrrt_loop_view(h, c, &v)) return rc;
+    if (max_length < 1 || max_length > v.path_cap) return fail(BN_ERR_INVALID, "max_length must be in [1, path_cap = %d]", v.path_cap);
+    const size_t B = h->p.B, Lm = (size_t)max_length;
+    for (size_t b = 0; b < B; ++b)
+        if (lengths[b] < 1 || lengths[b] > max_length) return fail(BN_ERR_INVALID, "lengths must be in [1, max_length]");
+    BN_BIND(h);
+    if (int rc = settle_point(h)) return rc;
+    BN_HIP(hipStreamSynchronize(h->stream));
+    std::vector<bn::ClrrtRover> r(B);
+    BN_HIP(hipMemcpy(r.data(), h->d_cl_rover, B * sizeof(bn::ClrrtRover), hipMemcpyDeviceToHost));
+    for (size_t b = 0; b < B; ++b) {
+        BN_HIP(hipMemcpy(v.path_actions + b * (size_t)v.path_cap * 2, actions + b * Lm * 2, (size_t)lengths[b] * 2 * sizeof(float), hipMemcpyHostToDevice));
+        BN_HIP(hipMemcpy(v.path_states + b * ((size_t)v.path_cap + 1) * 3, states + b * (Lm + 1) * 3, ((size_t)lengths[b] + 1) * 3 * sizeof(float), hipMemcpyHostToDevice));
+        r[b].need = 0; r[b].aidx = 0; r[b].length = lengths[b];
+        if (iteration >= 0) r[b].iter = iteration;
+    }
+    BN_HIP(hipMemcpy(h->d_cl_rover, r.data(), B * sizeof(bn::ClrrtRover), hipMemcpyHostToDevice));
+    BN_HIP(hipMemset(h->d_cl_flags, 0, (B + 1) * sizeof(int32_t)));
+    if (iteration >= 0) h->cl_iter = iteration;
     return BN_OK;
 }
 

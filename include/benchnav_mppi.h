@@ -769,7 +769,9 @@ typedef enum bn_clrrt_buffer_id {
     BN_CLRRT_BUF_STEER_TARGETS = 18,   /* (B, max_seqs) int32: the target point's index at every step */
     BN_CLRRT_BUF_STEER_RESULTS = 19,   /* (B, 4) int32: feasible, length, Dubins word (LSL RSR RSL LSR RLR LRL), path points */
     BN_CLRRT_BUF_STEER_COSTS = 20,     /* (B) float32 */
-    BN_CLRRT_BUF_STEER_CONTROLLERS = 21 /* (B, 4) float64: the controllers' state after the steer */
+    BN_CLRRT_BUF_STEER_CONTROLLERS = 21, /* (B, 4) float64: the controllers' state after the steer */
+    BN_CLRRT_BUF_MT_STATE = 22,        /* (B, 624) uint32: the MT19937 state block of every instance's stream */
+    BN_CLRRT_BUF_MT_POS = 23           /* (B) int32: the next word of the block */
 } bn_clrrt_buffer_id;
 
 typedef struct bn_clrrt_config {
@@ -814,6 +816,58 @@ int bn_clrrt_sync(bn_clrrt_t *h);
 int bn_clrrt_device_buffer(bn_clrrt_t *h, int which, void **ptr, size_t *bytes);
 int32_t bn_clrrt_path_cap(bn_clrrt_t *h);
 const char *bn_clrrt_last_error(void);
+
+/*
+ * The CL-RRT plan-follow-replan loop (csrc/clrrt_loop.hip): the reference's driver loop test/test_cl_rrt.py:167-200
+ * for the B environments of h (bn_mppi_env_attach) and the B instances of a CL-RRT handle c on the same grid.  Per rover, with t
+ * counting LOOP ITERATIONS: a plan where one is needed (t = 0, or flagged by the previous iteration); for t > 0 the deviation
+ * min over all L + 1 planned states of |plan_xy - state_xy| in float32, and deviation > 1 flags a replan -- that iteration takes
+ * no step; else action_seq[action_index++] through PlanetaryEnv.step with the slip draw of iteration t (z row t of the call, or
+ * Philox keyed by (env seed, t)); terminated stops the rover (GOAL), then elapsed > time_limit (TIME_LIMIT).  Where the reference
+ * raises or fails the rover alone stops with a status.  The follow kernel runs every rover to the call's end or to its next
+ * replan; the host reads one counter per ROUND of replans and runs c's kernels for the flagged rovers only.  c's streams are
+ * seeded by the reset and continue across a rover's replans; c serves the loop alone between a reset and the episode's end, and run / set_plans
+ * take the handle the reset was given (another one is BN_ERR_INVALID).
+ */
+typedef enum bn_clrrt_loop_status {
+    BN_CL_RUNNING = 0,
+    BN_CL_GOAL = 1,             /* is_terminated: the loop breaks (test_cl_rrt.py:194-196)                                  */
+    BN_CL_TIME_LIMIT = 2,       /* is_truncated (:198-200)                                                                  */
+    BN_CL_NO_PLAN = 3,          /* forward returned (None, None): the reference's loop fails on it with a TypeError         */
+    BN_CL_NO_SEQUENCE = 4,      /* the root is the cheapest node within the goal threshold: forward raises                  */
+    BN_CL_PLAN_EXHAUSTED = 5,   /* action_index == L: the reference's IndexError                                            */
+    BN_CL_PATH_OVERFLOW = 6,    /* the plan does not fit c's path_cap                                                        */
+    BN_CL_OUT_OF_BOUNDS = 7     /* forward's ValueError("Start or goal position is out of bounds.")                         */
+} bn_clrrt_loop_status;
+typedef enum bn_clrrt_loop_event {
+    BN_CL_EVENT_STEP = 0,       /* the iteration took an environment step */
+    BN_CL_EVENT_REPLAN = 1,     /* deviation > 1: a replan is flagged, no step */
+    BN_CL_EVENT_FROZEN = 2      /* the rover has stopped (from the iteration on at which a status without a step was set) */
+} bn_clrrt_loop_event;
+/* A new episode (test_cl_rrt.py:167): iteration 0, no plan, statuses cleared; goal_nodes HOST (B, 3) (x, y, heading: the
+ * heading of the rover's FIRST forward, kept for every replan) and seeds HOST (B) uint64 of c's MT19937 streams.  Verifies that
+ * c's B, grid size, resolution, limits and action bounds are h's.  delta_t and time_limit: PlanetaryEnv's, in double as the
+ * reference holds them: it accumulates elapsed += delta_t in float64 and stops a rover once elapsed > time_limit; delta_t must
+ * round to the float32 step of bn_mppi_env_attach. */
+int bn_clrrt_loop_reset(bn_mppi_t *h, bn_clrrt_t *c, const float *goal_nodes, const uint64_t *seeds, double delta_t, double time_limit);
+/* n loop iterations on h's stream from states_device (B, 3), which receives the final states.  z_device (n, B) slip draws or
+ * NULL; samples_device (P, B, max_iterations, 3) or NULL: rover b's p-th plan since the reset grows from table p instead of
+ * its stream, and a rover that needs a plan beyond P stops with BN_CL_NO_PLAN (teacher forcing).  flags bit 0: read the plan
+ * from global memory even where it fits the LDS budget (test knob; the outputs are bit-identical).  Synchronises once per
+ * round of replans.  follow_ms (may be NULL): the time between HIP events around the follow launches, summed. */
+int bn_clrrt_loop_run(bn_mppi_t *h, bn_clrrt_t *c, int32_t n, float *states_device, const float *z_device,
+                      const float *samples_device, int32_t num_tables, uint32_t flags, float *follow_ms);
+/* The latest run's log (any pointer may be NULL), rows by iteration of the call: states (n+1,B,3) with [0] the call's start,
+ * rewards (n,B), actions (n,B,2), deviations (n,B), plan_index (n,B) int32, events (n,B) int32 bn_clrrt_loop_event; a row
+ * without a step holds the state and NaN elsewhere (a flagged replan keeps its deviation).  Per rover (B) int32: done_iter
+ * (the iteration its status was set at, or -1), status, plans (forward calls), steps (environment steps) since the reset. */
+int bn_clrrt_loop_log(bn_mppi_t *h, float *states, float *rewards, float *actions, float *deviations, int32_t *plan_index,
+                      int32_t *events, int32_t *done_iter, int32_t *status, int32_t *plans, int32_t *steps);
+/* Teacher forcing: actions HOST (B, Lmax, 2), states HOST (B, Lmax + 1, 3) and lengths HOST (B) int32 (1 <= L <= min(Lmax,
+ * path_cap)) become the rovers' current plans, action_index 0, no replan pending; iteration >= 0 also sets every rover's
+ * iteration counter.  The follow kernel can be driven with this alone. */
+int bn_clrrt_loop_set_plans(bn_mppi_t *h, bn_clrrt_t *c, const float *actions, const float *states, const int32_t *lengths,
+                            int32_t max_length, int32_t iteration);
 
 /* Test hook: the library's device arithmetic (DESIGN.md "Arithmetic spec") applied elementwise to n device floats:
  * fn 0 = correctly rounded sqrt, 1 / 2 = sin / cos of the spec, 3 = heading wrap (theta + pi) % 2pi - pi with
