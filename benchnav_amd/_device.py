@@ -1,0 +1,119 @@
+"""What the planner wrappers share on the Python side: the view of library-owned device memory, torch's current stream as the
+library takes it, the seed checks, the reference Tree's capacity rule, and the handle and plumbing of the two tree planners
+(rrt.py, clrrt.py)."""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import _capi
+
+
+class _DevArray:
+    """Library-owned device memory exposed to torch through __cuda_array_interface__."""
+
+    def __init__(self, ptr: int, shape, typestr="<f4"):
+        self.__cuda_array_interface__ = {"shape": tuple(int(v) for v in shape), "typestr": typestr, "data": (int(ptr), False),
+                                         "version": 2, "strides": None}
+
+
+def stream_ptr(dev) -> C.c_void_p:
+    """torch's current stream on `dev`, as the `void *stream` of the library's *_async entry points."""
+    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def _check_seed(seed) -> int:
+    s = int(seed)
+    if s < 0 or s > 0xFFFFFFFF:              # np.random.seed's range (set_randomness)
+        raise ValueError("Seed must be between 0 and 2**32 - 1")
+    return s
+
+
+def seed_array(seeds, B: int) -> np.ndarray:
+    if len(seeds) != B:
+        raise ValueError("one seed per instance")
+    return np.array([_check_seed(s) for s in seeds], np.uint64)
+
+
+def tree_capacity(n: int) -> int:
+    """The reference Tree's capacity for n nodes: 1000 (tree.py:17), doubled while the tree does not fit."""
+    cap = 1000
+    while cap < n:
+        cap *= 2
+    return cap
+
+
+def check(lib, family: str, code: int):
+    if code != _capi.BN_OK:
+        raise _capi.BenchnavError(code, getattr(lib, f"bn_{family}_last_error")().decode("utf-8", "replace"))
+
+
+class _PlannerHandle:
+    """One handle of the library's `family` ("rrt", "clrrt": bn_<family>_create / _destroy / _device_buffer / _last_error): B
+    instances of one parameter set.  A subclass fills the family's config struct."""
+    family = ""
+
+    def __init__(self, lib, dev: torch.device, B: int, cfg):
+        self.lib, self.dev, self.B = lib, dev, B
+        self.used = False                    # a plan has run: its streams are seeded
+        self.h = C.c_void_p()
+        check(lib, self.family, getattr(lib, f"bn_{self.family}_create")(C.byref(cfg), C.byref(self.h)))
+
+    def buffer(self, which: int, shape, typestr="<f4") -> torch.Tensor:
+        ptr, nbytes = C.c_void_p(), C.c_size_t()
+        check(self.lib, self.family, getattr(self.lib, f"bn_{self.family}_device_buffer")(self.h, which, C.byref(ptr), C.byref(nbytes)))
+        return torch.as_tensor(_DevArray(ptr.value, shape, typestr), device=self.dev)
+
+    def close(self):
+        if self.h:
+            getattr(self.lib, f"bn_{self.family}_destroy")(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _TreePlanner:
+    """The plumbing RRT and CLRRT share.  The planner class names its handle type (`_handle_type`, constructed as
+    (lib, dev, B, owner)) and carries `_lib`, `_dev`, `_handles`, `x_limits` and `y_limits`."""
+    _handle_type = None
+    _last_handle = None
+
+    def _is_within_bounds(self, node: torch.Tensor) -> bool:
+        x, y = node[:2]
+        return self.x_limits[0] <= x.item() <= self.x_limits[1] and self.y_limits[0] <= y.item() <= self.y_limits[1]
+
+    def _stream(self):
+        return stream_ptr(self._dev)
+
+    def _handle(self, B: int):
+        if B not in self._handles:
+            self._handles[B] = self._handle_type(self._lib, self._dev, B, self)
+        return self._handles[B]
+
+    def _launch(self, h, starts: np.ndarray, goals: np.ndarray, seeds: Optional[np.ndarray]) -> None:
+        starts, goals = np.ascontiguousarray(starts, np.float32), np.ascontiguousarray(goals, np.float32)
+        sp = seeds.ctypes.data if seeds is not None else None
+        plan = getattr(self._lib, f"bn_{h.family}_plan_async")
+        check(self._lib, h.family, plan(h.h, self._stream(), starts.ctypes.data, goals.ctypes.data, sp))
+        h.used = True
+        self._last_handle = h
+        torch.cuda.current_stream(self._dev).synchronize()
+
+    def _grow(self, h, starts: np.ndarray, goals: np.ndarray, samples: torch.Tensor) -> None:
+        """bn_<family>_grow_from_samples_async on a contiguous float32 sample table, host or device, and the wait for it."""
+        if samples.is_cuda:
+            samples = samples.to(self._dev)
+            where, ptr = _capi.BN_MEM_DEVICE, samples.data_ptr()
+        else:
+            keep = samples.numpy()
+            where, ptr = _capi.BN_MEM_HOST, keep.ctypes.data
+        grow = getattr(self._lib, f"bn_{h.family}_grow_from_samples_async")
+        check(self._lib, h.family, grow(h.h, self._stream(), starts.ctypes.data, goals.ctypes.data, ptr, where))
+        torch.cuda.current_stream(self._dev).synchronize()

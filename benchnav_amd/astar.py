@@ -21,14 +21,7 @@ import torch
 import torch.nn as nn
 
 from . import _capi
-
-
-class _DevArray:
-    """Library-owned device memory exposed to torch through __cuda_array_interface__."""
-
-    def __init__(self, ptr: int, shape, typestr="<f4"):
-        self.__cuda_array_interface__ = {"shape": tuple(int(v) for v in shape), "typestr": typestr, "data": (int(ptr), False),
-                                         "version": 2, "strides": None}
+from ._device import _DevArray, stream_ptr
 
 
 class AStar(nn.Module):
@@ -66,7 +59,7 @@ class AStar(nn.Module):
             where, hp, rp = _capi.BN_MEM_HOST, hn.ctypes.data, rn.ctypes.data
         self._check(self._lib.bn_astar_set_map(self._handle, 0, hp, rp, where, float(stuck_threshold), float(self.resolution)))
         self._check(self._lib.bn_astar_set_goal(self._handle, 0, gx, gy))
-        self._check(self._lib.bn_astar_solve_async(self._handle, C.c_void_p(torch.cuda.current_stream(self._dev).cuda_stream)))
+        self._check(self._lib.bn_astar_solve_async(self._handle, stream_ptr(self._dev)))
         self._buf = np.empty((self._h * self._w, 2), np.int32)
         self._jump_built = False                                                   # the tables come with the first use
 
@@ -100,7 +93,7 @@ class AStar(nn.Module):
 
     # ---- jump tables (csrc/astar_kernels.hip): hop counts and batched paths that stay on the device --------------------------
     def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self._dev).cuda_stream)
+        return stream_ptr(self._dev)
 
     def build_jump_tables(self) -> None:
         """Build the pointer-doubling tables behind the solve (bn_astar_jump_build_async) on the current stream: hops to the

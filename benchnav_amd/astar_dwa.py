@@ -27,6 +27,7 @@ import numpy as np
 import torch
 
 from . import _capi
+from ._device import stream_ptr
 
 _MESSAGES = {
     _capi.BN_AD_OUT_OF_BOUNDS: "Start or goal position is out of bounds.",       # astar.py:88-92
@@ -89,9 +90,9 @@ class AStarDWALoop:
                                                          self.stuck_threshold, self.resolution))
             gx, gy = self.pos_to_index(goals[b])
             self._check_astar(self._lib.bn_astar_set_goal(self._astar, b, gx, gy))
-        self._check_astar(self._lib.bn_astar_solve_async(self._astar, C.c_void_p(torch.cuda.current_stream(self._dev).cuda_stream)))
+        self._check_astar(self._lib.bn_astar_solve_async(self._astar, stream_ptr(self._dev)))
         if walk == "jump":
-            self._check_astar(self._lib.bn_astar_jump_build_async(self._astar, C.c_void_p(torch.cuda.current_stream(self._dev).cuda_stream)))
+            self._check_astar(self._lib.bn_astar_jump_build_async(self._astar, stream_ptr(self._dev)))
         self._prev = torch.zeros(B, 2, device=self._dev)          # the window centre: DWA's _previous_action_seq[0] (zeros, dwa.py:59)
         self._steps = 0
         self.status = np.zeros(B, np.int32)

@@ -25,7 +25,7 @@ import torch
 import torch.nn as nn
 
 from . import _capi
-from .rrt import _DevArray, _check_seed, _INITIAL_CAPACITY
+from ._device import _PlannerHandle, _TreePlanner, _check_seed, check, seed_array, tree_capacity
 
 WORDS = ("LSL", "RSR", "RSL", "LSR", "RLR", "LRL")
 _POINTS = 64
@@ -38,9 +38,7 @@ class Tree:
     doubled while the tree does not fit."""
 
     def __init__(self, n: int, nodes, edges, costs, action_seqs, state_seqs, seq_lengths, controllers_states):
-        cap = _INITIAL_CAPACITY
-        while cap < n:
-            cap *= 2
+        cap = tree_capacity(n)
         dev, S = nodes.device, int(action_seqs.shape[1])
         self.nodes = torch.zeros((cap, 3), dtype=torch.float32, device=dev)
         self.edges = -torch.ones(cap, dtype=torch.int64, device=dev)
@@ -60,12 +58,12 @@ class Tree:
 
 
 def _check(lib, code: int):
-    if code != _capi.BN_OK:
-        raise _capi.BenchnavError(code, lib.bn_clrrt_last_error().decode("utf-8", "replace"))
+    check(lib, "clrrt", code)
 
 
-class _Handle:
+class _Handle(_PlannerHandle):
     """One bn_clrrt handle: B instances of one parameter set on one map."""
+    family = "clrrt"
 
     def __init__(self, lib, dev: torch.device, B: int, owner: "CLRRT"):
         cfg = _capi.CLRRTConfig()
@@ -80,32 +78,16 @@ class _Handle:
         for i in range(2):
             cfg.u_min[i], cfg.u_max[i] = float(owner._u_min[i]), float(owner._u_max[i])
         cfg.seed = owner._seed
-        self.lib, self.dev, self.B, self.iters, self.S = lib, dev, B, owner._max_iterations, owner._max_seqs
-        self.h = C.c_void_p()
-        _check(lib, lib.bn_clrrt_create(C.byref(cfg), C.byref(self.h)))
+        self.iters, self.S = owner._max_iterations, owner._max_seqs
+        super().__init__(lib, dev, B, cfg)
         self.path_cap = int(lib.bn_clrrt_path_cap(self.h))
         goal = np.ascontiguousarray(owner._goal_host.numpy()[:2], np.float32)
         _check(lib, lib.bn_clrrt_set_map(self.h, owner._risk.ctypes.data, goal.ctypes.data, float(owner._stuck_threshold)))
-        self.used = False
-
-    def buffer(self, which: int, shape, typestr="<f4") -> torch.Tensor:
-        ptr, nbytes = C.c_void_p(), C.c_size_t()
-        _check(self.lib, self.lib.bn_clrrt_device_buffer(self.h, which, C.byref(ptr), C.byref(nbytes)))
-        return torch.as_tensor(_DevArray(ptr.value, shape, typestr), device=self.dev)
-
-    def close(self):
-        if self.h:
-            self.lib.bn_clrrt_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
-class CLRRT(nn.Module):
+class CLRRT(_TreePlanner, nn.Module):
+    _handle_type = _Handle
+
     def __init__(self, dim_state: int, dim_control: int, dynamics, objectives, grid_map, delta_t: float, max_iterations: int = 500,
                  delta_distance: float = 5, goal_sample_rate: float = 0.25, max_seqs: int = 250, goal_threshold: float = 1.0,
                  device: Optional[str] = None, dtype: torch.dtype = torch.float32, seed: int = 42, path_cap: Optional[int] = None) -> None:
@@ -183,10 +165,6 @@ class CLRRT(nn.Module):
         states = h.buffer(_capi.BN_CLRRT_BUF_PATH_STATES, (1, h.path_cap + 1, 3))[:, :L + 1].clone()
         return actions.to(self.device), states.to(self.device)
 
-    def _is_within_bounds(self, node: torch.Tensor) -> bool:
-        x, y = node[:2]
-        return self.x_limits[0] <= x.item() <= self.x_limits[1] and self.y_limits[0] <= y.item() <= self.y_limits[1]
-
     @staticmethod
     def _raise_unless_path(res):
         if res[4] != 0:
@@ -219,11 +197,7 @@ class CLRRT(nn.Module):
         Returns (actions (B, Lmax, 2), states (B, Lmax + 1, 3), lengths (B,) int32, found (B,) bool) on the device, NaN beyond a
         path; `batch_tree(b)` and `last_batch` hold the rest."""
         B, sn, gn = self._batch_inputs(states, goals)
-        sd = None
-        if seeds is not None:
-            if len(seeds) != B:
-                raise ValueError("one seed per instance")
-            sd = np.array([_check_seed(s) for s in seeds], np.uint64)
+        sd = None if seeds is None else seed_array(seeds, B)
         h = self._handle(B)
         if sd is None and not h.used:
             sd = np.full(B, self._seed, np.uint64)
@@ -237,14 +211,7 @@ class CLRRT(nn.Module):
         if tuple(samples.shape) != (B, self._max_iterations, 3):
             raise ValueError(f"samples must be ({B}, {self._max_iterations}, 3), got {tuple(samples.shape)}")
         h = self._handle(B)
-        if samples.is_cuda:
-            samples = samples.to(self._dev)
-            where, ptr = _capi.BN_MEM_DEVICE, samples.data_ptr()
-        else:
-            keep = samples.numpy()
-            where, ptr = _capi.BN_MEM_HOST, keep.ctypes.data
-        _check(self._lib, self._lib.bn_clrrt_grow_from_samples_async(h.h, self._stream(), sn.ctypes.data, gn.ctypes.data, ptr, where))
-        torch.cuda.current_stream(self._dev).synchronize()
+        self._grow(h, sn, gn, samples)
         return self._batch_result(h)
 
     def steer_batch(self, from_states, controller_states, targets):
@@ -293,22 +260,6 @@ class CLRRT(nn.Module):
                 h.buffer(_capi.BN_CLRRT_BUF_FEASIBLE, (h.B, h.iters), "<i4").clone() != 0)
 
     # ---- plumbing --------------------------------------------------------------------------------------------------------
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self._dev).cuda_stream)
-
-    def _handle(self, B: int) -> _Handle:
-        if B not in self._handles:
-            self._handles[B] = _Handle(self._lib, self._dev, B, self)
-        return self._handles[B]
-
-    def _launch(self, h: _Handle, starts: np.ndarray, goals: np.ndarray, seeds: Optional[np.ndarray]) -> None:
-        starts, goals = np.ascontiguousarray(starts, np.float32), np.ascontiguousarray(goals, np.float32)
-        sp = seeds.ctypes.data if seeds is not None else None
-        _check(self._lib, self._lib.bn_clrrt_plan_async(h.h, self._stream(), starts.ctypes.data, goals.ctypes.data, sp))
-        h.used = True
-        self._last_handle = h
-        torch.cuda.current_stream(self._dev).synchronize()
-
     def _tree(self, h: _Handle, b: int, n: int) -> Tree:
         c = h.iters + 1
         return Tree(n, h.buffer(_capi.BN_CLRRT_BUF_NODES, (h.B, c, 3))[b], h.buffer(_capi.BN_CLRRT_BUF_EDGES, (h.B, c), "<i4")[b],

@@ -30,7 +30,7 @@ import torch
 
 from . import _capi
 from .clrrt import _Handle
-from .rrt import _check_seed
+from ._device import _check_seed
 
 STATUS_NAMES = ("RUNNING", "GOAL", "TIME_LIMIT", "NO_PLAN", "NO_SEQUENCE", "PLAN_EXHAUSTED", "PATH_OVERFLOW", "OUT_OF_BOUNDS")
 EVENT_NAMES = ("STEP", "REPLAN", "FROZEN")

@@ -21,8 +21,10 @@
 // whose halo holds an improved border cell.  `pending` counts dirty flags plus tiles in flight: the workers exit when it is 0.
 // No co-residency is assumed (a workgroup that starts after the work is done exits at once), and every wait is bounded by
 // a wall-clock deadline that reports through the error word.
+// The host side takes its device guard and HIP check from bn_host.h.
 #include "../../include/benchnav_mppi.h"
 #include "bn_device_math.h"
+#include "bn_host.h"
 #include "astar_view.h"
 
 #include <hip/hip_runtime.h>
@@ -447,14 +449,9 @@ int astar_fail(int code, const std::string &msg)
     return code;
 }
 
-struct DeviceGuard {
-    int prev = -1; bool changed = false, ok = true;
-    explicit DeviceGuard(int want) { if (hipGetDevice(&prev) != hipSuccess) { ok = false; return; }
-                                     if (prev != want) { ok = hipSetDevice(want) == hipSuccess; changed = ok; } }
-    ~DeviceGuard() { if (changed) (void)hipSetDevice(prev); }
-};
+using bn::DeviceGuard;
 
-#define ASTAR_HIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return astar_fail(BN_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); } while (0)
+#define ASTAR_HIP(expr) BN_HIP_AS(astar_fail, expr, #expr)
 
 // an enqueued episode still reads the buffers: wait for it before they are rewritten or freed
 void wait_readers(bn_astar_t *h)

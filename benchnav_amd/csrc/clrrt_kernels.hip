@@ -1,19 +1,21 @@
 // The closed-loop RRT planner for B instances per launch: `CLRRT` of the reference (src/planners/global_planners/sampling_based/
 // cl_rrt.py, with Dubins and PurePursuit of src/planners/local_planners) on the device.  One workgroup of ONE wave
 // per instance: everything a closed-loop step does is at most 64 wide (a truncated reference path has at most 64 points).
-//   clrrt_samples_kernel   the instance's MT19937 stream parsed into the sample of every iteration: one uniform u; u < f32(rate) ->
-//                          the goal node (x, y, heading), else three more uniforms -> (x, y, theta).  An infeasible steer only
-//                          `continue`s, so the sequence does not depend on the tree.
+//   tree_samples_kernel<3> (rrt_device.h) the sample of every iteration: one uniform u; u < f32(rate) -> the goal node (x, y,
+//                          heading), else three more uniforms -> (x, y, theta).  An infeasible steer only `continue`s, so the
+//                          sequence does not depend on the tree.
 //   clrrt_grow_kernel      per iteration: nearest node on (x, y) (rrt_device.h), the steer, and where it is feasible the append.
 //                          x, y, heading, cost and the two integrals of every node live in LDS; sequences go straight to global.
 //   clrrt_steer_kernel     one steer per instance from a given state, controller state and target, with no tree: the teacher-forced
 //                          comparison with the reference, with the truncated path and the target index of every step written out.
-//   clrrt_path_kernel      goal test, pick (lowest cost, then lowest index), parent walk, concatenation of the segments.
+//   clrrt_path_kernel      goal test and pick (near_goal_pick, rrt_device.h: lowest cost, then lowest index), parent walk,
+//                          concatenation of the segments.
 // One steer (clrrt_steer): the six Dubins words in float32 as NumPy evaluates them on float32 scalars (each transcendental is the
 // float64 function rounded to float32), lane p = path point p in float64 from its arc length 0.25 p, a sequential float64 sum of the
 // segment lengths for the truncation, then the serial follow loop: validity mask on the lanes, first set lane, PID in float64, the
 // float32 cast of the action, the library's reference-order transit (chain_step<..., REF>) and costs in float32.
 // Every loop is bounded (iterations, max_seqs, 64 points, the parent walk by the node count); no workgroup waits for another.
+// The host side is written with bn_host.h (guard, HIP check, buffer table) and shares its plan steps with RRT (rrt_host.h).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -24,14 +26,12 @@
 #include "../../include/benchnav_mppi.h"
 #include "clrrt_view.h"
 #include "dwa_device.h"
-#include "mt19937.h"
-#include "rrt_device.h"
+#include "rrt_host.h"
 
 namespace bn {
 namespace {
 
 constexpr int kClrrtThreads = 64;          // the growth and steer kernels: one wave
-constexpr int kClrrtSampleThreads = 256;   // >= 227 (mt19937.h)
 constexpr int kClrrtPathThreads = 256;
 constexpr int kClrrtPoints = 64;           // path points a steer can hold: bn_clrrt_create bounds delta_distance accordingly
 constexpr int kClrrtResult = 6;            // found, picked node, path length, near-goal count, error, node count
@@ -60,55 +60,6 @@ __device__ __forceinline__ float mod2pi32(float a)
 // np.linalg.norm of a float32 2-vector: sqrt of the dot product, no FMA
 __device__ __forceinline__ float norm32(float dx, float dy) { return sqrtf(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy))); }
 __device__ __forceinline__ float sign32(float v) { return v > 0.0f ? 1.0f : (v < 0.0f ? -1.0f : 0.0f); }
-
-struct ClrrtSampleArgs {
-    const uint64_t *seeds;     // (B), read when reseed
-    uint32_t *state;           // (B, 624)
-    int32_t *pos;              // (B)
-    const float *goals;        // (B, 3) the goal node: x, y, heading
-    float *samples;            // (B, iters, 3)
-    int32_t *flags;            // (B, iters) 1 where the sample is the goal
-    int iters, reseed;
-    float rate, xspan, x0, yspan, y0;
-    const int32_t *active;     // (B) or nullptr = every instance: an instance whose word is 0 returns before touching anything
-};
-
-__global__ __launch_bounds__(kClrrtSampleThreads) void clrrt_samples_kernel(ClrrtSampleArgs a)
-{
-    __shared__ uint32_t mt[2][kMtN];
-    const int b = blockIdx.x, t = threadIdx.x;
-    if (a.active && a.active[b] == 0) return;              // (uniform over the workgroup: no barrier is left waiting)
-    int pos = kMtN;
-    if (a.reseed) {
-        if (t == 0) mt_seed(mt[0], (uint32_t)a.seeds[b]);
-    } else {
-        for (int i = t; i < kMtN; i += kClrrtSampleThreads) mt[0][i] = a.state[(size_t)b * kMtN + i];
-        pos = min(max(a.pos[b], 0), kMtN);
-    }
-    __syncthreads();
-    MtStream s{mt, 0, pos};
-    const float gx = a.goals[3 * b], gy = a.goals[3 * b + 1], gth = a.goals[3 * b + 2];
-    float *out = a.samples + (size_t)b * a.iters * 3;
-    int32_t *fl = a.flags + (size_t)b * a.iters;
-    // every thread walks the same words (1 or 4 draws per iteration); they take turns to write
-    for (int it = 0; it < a.iters; ++it) {
-        const bool goal = mt_next(s) < a.rate;
-        float x = gx, y = gy, th = gth;
-        if (!goal) {
-            x = __fadd_rn(__fmul_rn(mt_next(s), a.xspan), a.x0);
-            y = __fadd_rn(__fmul_rn(mt_next(s), a.yspan), a.y0);
-            th = __fmul_rn(__fmul_rn(mt_next(s), 2.0f), kPi);
-        }
-        if (t == (it & (kClrrtSampleThreads - 1))) {
-            out[3 * it] = x;
-            out[3 * it + 1] = y;
-            out[3 * it + 2] = th;
-            fl[it] = goal ? 1 : 0;
-        }
-    }
-    for (int i = t; i < kMtN; i += kClrrtSampleThreads) a.state[(size_t)b * kMtN + i] = s.mt[s.cur][i];
-    if (t == 0) a.pos[b] = s.pos;
-}
 
 // What the steer needs beside the states: geometry, map and bounds travel in the library's SolveParams, so that the transit and
 // the lookups are the library's own (mppi_device.h).
@@ -492,8 +443,6 @@ struct ClrrtPathArgs {
 
 __global__ __launch_bounds__(kClrrtPathThreads) void clrrt_path_kernel(ClrrtPathArgs a)
 {
-    __shared__ unsigned long long part[4];
-    __shared__ int cnt[4];
     __shared__ int sh[3];                                   // pick, total length, fits
     const int b = blockIdx.x, t = threadIdx.x, S = a.max_seqs;
     if (a.active && a.active[b] == 0) return;
@@ -502,25 +451,13 @@ __global__ __launch_bounds__(kClrrtPathThreads) void clrrt_path_kernel(ClrrtPath
     const float *aseq = a.action_seqs + (size_t)b * a.cap * S * 2, *sseq = a.state_seqs + (size_t)b * a.cap * (S + 1) * 3;
     float *pa = a.path_actions + (size_t)b * a.path_cap * 2, *ps = a.path_states + (size_t)b * (a.path_cap + 1) * 3;
     const int n = min(max(a.counts[b], 1), a.cap);
-    const float gx = a.goals[3 * b], gy = a.goals[3 * b + 1];
-    unsigned long long key = ~0ull;
-    int near = 0;
-    for (int i = t; i < n; i += kClrrtPathThreads) {
-        if (rrt_norm(__fsub_rn(nodes[3 * i], gx), __fsub_rn(nodes[3 * i + 1], gy)) < a.threshold) {
-            ++near;
-            const unsigned long long k = ((unsigned long long)__float_as_uint(costs[i]) << 32) | (unsigned)i;
-            key = k < key ? k : key;
-        }
-    }
-    for (int m = 32; m > 0; m >>= 1) near += __shfl_xor(near, m, 64);
-    if ((t & 63) == 0) cnt[t >> 6] = near;
-    key = block_min_u64<kClrrtPathThreads>(key, part);
+    const NearGoal g = near_goal_pick<3, kClrrtPathThreads>(nodes, costs, n, a.goals[3 * b], a.goals[3 * b + 1], a.threshold);
     if (t == 0) {
-        const int total = cnt[0] + cnt[1] + cnt[2] + cnt[3];
+        const int total = g.total;
         int32_t *res = a.results + (size_t)b * kClrrtResult;
         int L = 0, pick = -1, fits = 1;
         if (total > 0) {
-            pick = min((int)(unsigned)(key & 0xffffffffu), n - 1);
+            pick = min((int)(unsigned)(g.key & 0xffffffffu), n - 1);
             int hops = 0;
             for (int cur = pick; cur != 0 && hops < n; ++hops) {                      // a parent has a lower index than its child
                 L += min(max(lens[cur], 0), S);
@@ -574,6 +511,7 @@ struct bn_clrrt {
     int B = 0, iters = 0, cap = 0, path_cap = 0, S = 0, geo = 0;
     bool seeded = false, ev_recorded = false, have_map = false;
     size_t lds_bytes = 0;
+    bn::DeviceBuffers bufs;                  // every device pointer below, filled by bn_clrrt_create
     float *map = nullptr, *goal = nullptr;
     float *nodes = nullptr, *costs = nullptr, *ctrl = nullptr, *aseq = nullptr, *sseq = nullptr, *samples = nullptr, *starts = nullptr, *goals = nullptr;
     float *path_actions = nullptr, *path_states = nullptr;
@@ -585,6 +523,7 @@ struct bn_clrrt {
     double *st_paths = nullptr, *st_ctrl_out = nullptr;
     int32_t *st_tgt = nullptr, *st_results = nullptr;
     unsigned char *pinned = nullptr;         // staging: 10 floats per instance, then a uint64 per instance
+    uint64_t *pinned_seeds = nullptr;        // ... the seeds in it
     hipEvent_t ev_done = nullptr;
 };
 
@@ -596,56 +535,13 @@ int clrrt_fail(int code, const std::string &msg)
     return code;
 }
 
-struct ClrrtDeviceGuard {
-    int prev = -1; bool changed = false, ok = true;
-    explicit ClrrtDeviceGuard(int want) { if (hipGetDevice(&prev) != hipSuccess) { ok = false; return; }
-                                          if (prev != want) { ok = hipSetDevice(want) == hipSuccess; changed = ok; } }
-    ~ClrrtDeviceGuard() { if (changed) (void)hipSetDevice(prev); }
-};
-
-#define CLRRT_HIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return clrrt_fail(BN_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); } while (0)
-
-template <typename P>
-int clrrt_alloc(P **p, size_t bytes)
-{
-    CLRRT_HIP(hipMalloc((void **)p, bytes ? bytes : 4));
-    CLRRT_HIP(hipMemset(*p, 0, bytes ? bytes : 4));
-    return BN_OK;
-}
-
-bool clrrt_in_bounds(const bn_clrrt_config &c, const float *p)
-{
-    return c.x_limits[0] <= (double)p[0] && (double)p[0] <= c.x_limits[1] && c.y_limits[0] <= (double)p[1] && (double)p[1] <= c.y_limits[1];
-}
+#define CLRRT_HIP(expr) BN_HIP_AS(clrrt_fail, expr, #expr)
 
 bool clrrt_pow2(double v)
 {
     int e = 0;
     return v > 0.0 && std::frexp(v, &e) == 0.5;
 }
-
-int clrrt_check_positions(const bn_clrrt_t *h, const float *starts, const float *goals)
-{
-    for (int b = 0; b < h->B; ++b) {
-        if (!clrrt_in_bounds(h->cfg, starts + 3 * b) || !clrrt_in_bounds(h->cfg, goals + 3 * b))
-            return clrrt_fail(BN_ERR_INVALID, "Start or goal position is out of bounds (instance " + std::to_string(b) + ")");
-        if (!std::isfinite(starts[3 * b + 2]) || !std::isfinite(goals[3 * b + 2])) return clrrt_fail(BN_ERR_INVALID, "headings must be finite");
-    }
-    return BN_OK;
-}
-
-int clrrt_stage(bn_clrrt_t *h, const float *starts, const float *goals, hipStream_t s)
-{
-    if (h->ev_recorded) CLRRT_HIP(hipEventSynchronize(h->ev_done));                    // the staging block is free again
-    const size_t pb = (size_t)h->B * 12;
-    std::memcpy(h->pinned, starts, pb);
-    std::memcpy(h->pinned + pb, goals, pb);
-    CLRRT_HIP(hipMemcpyAsync(h->starts, h->pinned, pb, hipMemcpyHostToDevice, s));
-    CLRRT_HIP(hipMemcpyAsync(h->goals, h->pinned + pb, pb, hipMemcpyHostToDevice, s));
-    return BN_OK;
-}
-
-int clrrt_draw_samples(bn_clrrt_t *h, hipStream_t s, bool reseed, const int32_t *active);
 
 int clrrt_grow_and_pick(bn_clrrt_t *h, hipStream_t s, const int32_t *active = nullptr)
 {
@@ -662,22 +558,7 @@ int clrrt_grow_and_pick(bn_clrrt_t *h, hipStream_t s, const int32_t *active = nu
     p.cap = h->cap; p.path_cap = h->path_cap; p.max_seqs = h->S; p.threshold = (float)h->cfg.goal_threshold; p.active = active;
     bn::clrrt_path_kernel<<<h->B, bn::kClrrtPathThreads, 0, s>>>(p);
     CLRRT_HIP(hipGetLastError());
-    CLRRT_HIP(hipEventRecord(h->ev_done, s));
-    h->ev_recorded = true;
-    return BN_OK;
-}
-
-int clrrt_draw_samples(bn_clrrt_t *h, hipStream_t s, bool reseed, const int32_t *active)
-{
-    bn::ClrrtSampleArgs a{};
-    a.seeds = h->seeds; a.state = h->state; a.pos = h->pos; a.goals = h->goals; a.samples = h->samples; a.flags = h->flags;
-    a.iters = h->iters; a.reseed = reseed; a.active = active;
-    a.rate = (float)h->cfg.goal_sample_rate;
-    a.xspan = (float)(h->cfg.x_limits[1] - h->cfg.x_limits[0]); a.x0 = (float)h->cfg.x_limits[0];
-    a.yspan = (float)(h->cfg.y_limits[1] - h->cfg.y_limits[0]); a.y0 = (float)h->cfg.y_limits[0];
-    bn::clrrt_samples_kernel<<<h->B, bn::kClrrtSampleThreads, 0, s>>>(a);
-    CLRRT_HIP(hipGetLastError());
-    return BN_OK;
+    return bn::tree_mark_done(h, s, clrrt_fail);
 }
 
 }  // namespace
@@ -702,7 +583,7 @@ int clrrt_loop_reset(bn_clrrt *h, hipStream_t s, const float *goal_nodes, const 
         if (!std::isfinite(goal_nodes[3 * b]) || !std::isfinite(goal_nodes[3 * b + 1]) || !std::isfinite(goal_nodes[3 * b + 2]))
             return clrrt_fail(BN_ERR_INVALID, "goal nodes must be finite");
     }
-    ClrrtDeviceGuard guard(h->cfg.device_id);
+    bn::DeviceGuard guard(h->cfg.device_id);
     if (!guard.ok) return clrrt_fail(BN_ERR_HIP, "hipSetDevice failed");
     if (h->ev_recorded) CLRRT_HIP(hipEventSynchronize(h->ev_done));                    // the staging block is free again
     const size_t B = h->B;
@@ -713,8 +594,7 @@ int clrrt_loop_reset(bn_clrrt *h, hipStream_t s, const float *goal_nodes, const 
     CLRRT_HIP(hipMemcpyAsync(h->seeds, ps, B * 8, hipMemcpyHostToDevice, s));
     clrrt_seed_kernel<<<(h->B + 63) / 64, 64, 0, s>>>(h->seeds, h->state, h->pos, h->B);
     CLRRT_HIP(hipGetLastError());
-    CLRRT_HIP(hipEventRecord(h->ev_done, s));
-    h->ev_recorded = true;
+    if (int rc = tree_mark_done(h, s, clrrt_fail)) return rc;
     h->seeded = true;
     return BN_OK;
 }
@@ -723,10 +603,10 @@ int clrrt_plan_masked(bn_clrrt *h, hipStream_t s, const int32_t *active, int dra
 {
     if (!h || !active) return clrrt_fail(BN_ERR_INVALID, "null argument");
     if (!h->have_map) return clrrt_fail(BN_ERR_STATE, "bn_clrrt_set_map has not been called");
-    ClrrtDeviceGuard guard(h->cfg.device_id);
+    bn::DeviceGuard guard(h->cfg.device_id);
     if (!guard.ok) return clrrt_fail(BN_ERR_HIP, "hipSetDevice failed");
     if (draw)
-        if (int rc = clrrt_draw_samples(h, s, false, active)) return rc;
+        if (int rc = tree_draw_samples<3>(h, s, false, active, clrrt_fail)) return rc;
     return clrrt_grow_and_pick(h, s, active);
 }
 
@@ -788,7 +668,7 @@ int bn_clrrt_create(const bn_clrrt_config *cfg, bn_clrrt_t **out)
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return clrrt_fail(BN_ERR_NO_DEVICE, "no HIP device visible: no CPU fallback");
     if (cfg->device_id < 0 || cfg->device_id >= ndev) return clrrt_fail(BN_ERR_INVALID, "device_id out of range");
-    ClrrtDeviceGuard guard(cfg->device_id);
+    bn::DeviceGuard guard(cfg->device_id);
     if (!guard.ok) return clrrt_fail(BN_ERR_HIP, "hipSetDevice failed");
     auto *h = new bn_clrrt_t();
     h->cfg = *cfg;
@@ -805,19 +685,40 @@ int bn_clrrt_create(const bn_clrrt_config *cfg, bn_clrrt_t **out)
     p.ref_order = 1; p.wrap_near = 0; p.map_stride = 0;
     h->c.max_seqs = h->S; h->c.delta = cfg->delta_distance; h->c.pid_dt = cfg->delta_t;
     const size_t B = h->B, nc = B * h->cap, ni = B * h->iters, S = h->S;
-    int rc = BN_OK;
-    if ((rc = clrrt_alloc(&h->map, (size_t)p.G * p.G * 4)) || (rc = clrrt_alloc(&h->goal, 8)) || (rc = clrrt_alloc(&h->nodes, nc * 12)) ||
-        (rc = clrrt_alloc(&h->edges, nc * 4)) || (rc = clrrt_alloc(&h->costs, nc * 4)) || (rc = clrrt_alloc(&h->lens, nc * 4)) ||
-        (rc = clrrt_alloc(&h->ctrl, nc * 16)) || (rc = clrrt_alloc(&h->aseq, nc * S * 8)) || (rc = clrrt_alloc(&h->sseq, nc * (S + 1) * 12)) ||
-        (rc = clrrt_alloc(&h->counts, B * 4)) || (rc = clrrt_alloc(&h->samples, ni * 12)) || (rc = clrrt_alloc(&h->flags, ni * 4)) ||
-        (rc = clrrt_alloc(&h->near, ni * 4)) || (rc = clrrt_alloc(&h->feasible, ni * 4)) ||
-        (rc = clrrt_alloc(&h->path_actions, B * h->path_cap * 8)) || (rc = clrrt_alloc(&h->path_states, B * ((size_t)h->path_cap + 1) * 12)) ||
-        (rc = clrrt_alloc(&h->results, B * bn::kClrrtResult * 4)) || (rc = clrrt_alloc(&h->state, B * bn::kMtN * 4)) ||
-        (rc = clrrt_alloc(&h->pos, B * 4)) || (rc = clrrt_alloc(&h->starts, B * 12)) || (rc = clrrt_alloc(&h->goals, B * 12)) ||
-        (rc = clrrt_alloc(&h->seeds, B * 8)) || (rc = clrrt_alloc(&h->st_from, B * 12)) || (rc = clrrt_alloc(&h->st_ctrl, B * 16)) ||
-        (rc = clrrt_alloc(&h->st_targets, B * 12)) || (rc = clrrt_alloc(&h->st_actions, B * S * 8)) || (rc = clrrt_alloc(&h->st_states, B * (S + 1) * 12)) ||
-        (rc = clrrt_alloc(&h->st_cost, B * 4)) || (rc = clrrt_alloc(&h->st_paths, B * bn::kClrrtPoints * 16)) || (rc = clrrt_alloc(&h->st_ctrl_out, B * 32)) ||
-        (rc = clrrt_alloc(&h->st_tgt, B * S * 4)) || (rc = clrrt_alloc(&h->st_results, B * bn::kClrrtSteerResult * 4))) {
+    bn::DeviceBuffers &t = h->bufs;
+    t.add(&h->map, (size_t)p.G * p.G * 4);
+    t.add(&h->goal, 8);
+    t.add(&h->nodes, nc * 12, BN_CLRRT_BUF_NODES);
+    t.add(&h->edges, nc * 4, BN_CLRRT_BUF_EDGES);
+    t.add(&h->costs, nc * 4, BN_CLRRT_BUF_COSTS);
+    t.add(&h->lens, nc * 4, BN_CLRRT_BUF_SEQ_LENGTHS);
+    t.add(&h->ctrl, nc * 16, BN_CLRRT_BUF_CONTROLLERS);
+    t.add(&h->aseq, nc * S * 8, BN_CLRRT_BUF_ACTION_SEQS);
+    t.add(&h->sseq, nc * (S + 1) * 12, BN_CLRRT_BUF_STATE_SEQS);
+    t.add(&h->counts, B * 4, BN_CLRRT_BUF_COUNTS);
+    t.add(&h->samples, ni * 12, BN_CLRRT_BUF_SAMPLES);
+    t.add(&h->flags, ni * 4, BN_CLRRT_BUF_SAMPLE_FLAGS);
+    t.add(&h->near, ni * 4, BN_CLRRT_BUF_NEAREST);
+    t.add(&h->feasible, ni * 4, BN_CLRRT_BUF_FEASIBLE);
+    t.add(&h->path_actions, B * h->path_cap * 8, BN_CLRRT_BUF_PATH_ACTIONS);
+    t.add(&h->path_states, B * ((size_t)h->path_cap + 1) * 12, BN_CLRRT_BUF_PATH_STATES);
+    t.add(&h->results, B * bn::kClrrtResult * 4, BN_CLRRT_BUF_RESULTS);
+    t.add(&h->state, B * bn::kMtN * 4, BN_CLRRT_BUF_MT_STATE);
+    t.add(&h->pos, B * 4, BN_CLRRT_BUF_MT_POS);
+    t.add(&h->starts, B * 12);
+    t.add(&h->goals, B * 12);
+    t.add(&h->seeds, B * 8);
+    t.add(&h->st_from, B * 12);
+    t.add(&h->st_ctrl, B * 16);
+    t.add(&h->st_targets, B * 12);
+    t.add(&h->st_actions, B * S * 8, BN_CLRRT_BUF_STEER_ACTIONS);
+    t.add(&h->st_states, B * (S + 1) * 12, BN_CLRRT_BUF_STEER_STATES);
+    t.add(&h->st_cost, B * 4, BN_CLRRT_BUF_STEER_COSTS);
+    t.add(&h->st_paths, B * bn::kClrrtPoints * 16, BN_CLRRT_BUF_STEER_PATHS);
+    t.add(&h->st_ctrl_out, B * 32, BN_CLRRT_BUF_STEER_CONTROLLERS);
+    t.add(&h->st_tgt, B * S * 4, BN_CLRRT_BUF_STEER_TARGETS);
+    t.add(&h->st_results, B * bn::kClrrtSteerResult * 4, BN_CLRRT_BUF_STEER_RESULTS);
+    if (int rc = t.alloc_all(clrrt_fail)) {
         std::string keep = bn::g_clrrt_error;
         bn_clrrt_destroy(h);
         bn::g_clrrt_error = keep;
@@ -828,6 +729,7 @@ int bn_clrrt_create(const bn_clrrt_config *cfg, bn_clrrt_t **out)
         bn_clrrt_destroy(h);
         return clrrt_fail(BN_ERR_HIP, "CL-RRT handle initialisation failed");
     }
+    h->pinned_seeds = (uint64_t *)(h->pinned + B * 40);
     *out = h;
     return BN_OK;
 }
@@ -835,14 +737,9 @@ int bn_clrrt_create(const bn_clrrt_config *cfg, bn_clrrt_t **out)
 void bn_clrrt_destroy(bn_clrrt_t *h)
 {
     if (!h) return;
-    ClrrtDeviceGuard guard(h->cfg.device_id);
+    bn::DeviceGuard guard(h->cfg.device_id);
     if (h->ev_recorded && h->ev_done) (void)hipEventSynchronize(h->ev_done);
-    for (void *p : {(void *)h->map, (void *)h->goal, (void *)h->nodes, (void *)h->edges, (void *)h->costs, (void *)h->lens, (void *)h->ctrl,
-                    (void *)h->aseq, (void *)h->sseq, (void *)h->counts, (void *)h->samples, (void *)h->flags, (void *)h->near, (void *)h->feasible,
-                    (void *)h->path_actions, (void *)h->path_states, (void *)h->results, (void *)h->state, (void *)h->pos, (void *)h->starts,
-                    (void *)h->goals, (void *)h->seeds, (void *)h->st_from, (void *)h->st_ctrl, (void *)h->st_targets, (void *)h->st_actions,
-                    (void *)h->st_states, (void *)h->st_cost, (void *)h->st_paths, (void *)h->st_ctrl_out, (void *)h->st_tgt, (void *)h->st_results})
-        if (p) (void)hipFree(p);
+    h->bufs.free_all();
     if (h->pinned) (void)hipHostFree(h->pinned);
     if (h->ev_done) (void)hipEventDestroy(h->ev_done);
     delete h;
@@ -852,7 +749,7 @@ int bn_clrrt_set_map(bn_clrrt_t *h, const float *risk, const float *goal, double
 {
     if (!h || !risk || !goal) return clrrt_fail(BN_ERR_INVALID, "null argument");
     if (!std::isfinite(stuck_threshold) || !std::isfinite(goal[0]) || !std::isfinite(goal[1])) return clrrt_fail(BN_ERR_INVALID, "goal and stuck threshold must be finite");
-    ClrrtDeviceGuard guard(h->cfg.device_id);
+    bn::DeviceGuard guard(h->cfg.device_id);
     if (!guard.ok) return clrrt_fail(BN_ERR_HIP, "hipSetDevice failed");
     if (h->ev_recorded) CLRRT_HIP(hipEventSynchronize(h->ev_done));
     CLRRT_HIP(hipMemcpy(h->map, risk, (size_t)h->c.p.G * h->c.p.G * 4, hipMemcpyHostToDevice));
@@ -866,24 +763,7 @@ int bn_clrrt_plan_async(bn_clrrt_t *h, void *stream, const float *starts, const 
 {
     if (!h || !starts || !goals) return clrrt_fail(BN_ERR_INVALID, "null argument");
     if (!h->have_map) return clrrt_fail(BN_ERR_STATE, "bn_clrrt_set_map has not been called");
-    int rc = clrrt_check_positions(h, starts, goals);
-    if (rc) return rc;
-    if (seeds)
-        for (int b = 0; b < h->B; ++b)
-            if (seeds[b] > 0xFFFFFFFFull) return clrrt_fail(BN_ERR_INVALID, "Seed must be between 0 and 2**32 - 1");
-    ClrrtDeviceGuard guard(h->cfg.device_id);
-    if (!guard.ok) return clrrt_fail(BN_ERR_HIP, "hipSetDevice failed");
-    hipStream_t s = (hipStream_t)stream;
-    if ((rc = clrrt_stage(h, starts, goals, s))) return rc;
-    const bool reseed = seeds || !h->seeded;
-    if (reseed) {
-        uint64_t *ps = (uint64_t *)(h->pinned + (size_t)h->B * 40);
-        for (int b = 0; b < h->B; ++b) ps[b] = seeds ? seeds[b] : h->cfg.seed;
-        CLRRT_HIP(hipMemcpyAsync(h->seeds, ps, (size_t)h->B * 8, hipMemcpyHostToDevice, s));
-    }
-    if ((rc = clrrt_draw_samples(h, s, reseed, nullptr))) return rc;
-    h->seeded = true;
-    return clrrt_grow_and_pick(h, s);
+    return bn::tree_plan<3>(h, stream, starts, goals, seeds, clrrt_fail, [](bn_clrrt_t *hh, hipStream_t s) { return clrrt_grow_and_pick(hh, s); });
 }
 
 int bn_clrrt_grow_from_samples_async(bn_clrrt_t *h, void *stream, const float *starts, const float *goals, const void *samples, int where)
@@ -891,21 +771,8 @@ int bn_clrrt_grow_from_samples_async(bn_clrrt_t *h, void *stream, const float *s
     if (!h || !starts || !goals || !samples) return clrrt_fail(BN_ERR_INVALID, "null argument");
     if (where != BN_MEM_HOST && where != BN_MEM_DEVICE) return clrrt_fail(BN_ERR_INVALID, "where must be BN_MEM_HOST or BN_MEM_DEVICE");
     if (!h->have_map) return clrrt_fail(BN_ERR_STATE, "bn_clrrt_set_map has not been called");
-    int rc = clrrt_check_positions(h, starts, goals);
-    if (rc) return rc;
-    ClrrtDeviceGuard guard(h->cfg.device_id);
-    if (!guard.ok) return clrrt_fail(BN_ERR_HIP, "hipSetDevice failed");
-    hipStream_t s = (hipStream_t)stream;
-    if ((rc = clrrt_stage(h, starts, goals, s))) return rc;
-    const size_t bytes = (size_t)h->B * h->iters * 12;
-    if (where == BN_MEM_HOST) {
-        CLRRT_HIP(hipMemcpyAsync(h->samples, samples, bytes, hipMemcpyHostToDevice, s));
-        CLRRT_HIP(hipStreamSynchronize(s));                                            // the caller's array is consumed before this returns
-    } else {
-        CLRRT_HIP(hipMemcpyAsync(h->samples, samples, bytes, hipMemcpyDeviceToDevice, s));
-    }
-    CLRRT_HIP(hipMemsetAsync(h->flags, 0, (size_t)h->B * h->iters * 4, s));
-    return clrrt_grow_and_pick(h, s);
+    return bn::tree_grow_from_samples<3>(h, stream, starts, goals, samples, where, clrrt_fail,
+                                         [](bn_clrrt_t *hh, hipStream_t s) { return clrrt_grow_and_pick(hh, s); });
 }
 
 int bn_clrrt_steer_async(bn_clrrt_t *h, void *stream, const float *from_states, const float *controller_states, const float *targets)
@@ -916,7 +783,7 @@ int bn_clrrt_steer_async(bn_clrrt_t *h, void *stream, const float *from_states, 
         if (!std::isfinite(from_states[i]) || !std::isfinite(targets[i])) return clrrt_fail(BN_ERR_INVALID, "states and targets must be finite");
     for (int i = 0; i < h->B * 4; ++i)
         if (!std::isfinite(controller_states[i])) return clrrt_fail(BN_ERR_INVALID, "controller states must be finite");
-    ClrrtDeviceGuard guard(h->cfg.device_id);
+    bn::DeviceGuard guard(h->cfg.device_id);
     if (!guard.ok) return clrrt_fail(BN_ERR_HIP, "hipSetDevice failed");
     hipStream_t s = (hipStream_t)stream;
     if (h->ev_recorded) CLRRT_HIP(hipEventSynchronize(h->ev_done));
@@ -933,51 +800,21 @@ int bn_clrrt_steer_async(bn_clrrt_t *h, void *stream, const float *from_states, 
     if (h->geo == bn::kGeoPow2) bn::clrrt_steer_kernel<bn::kGeoPow2><<<h->B, bn::kClrrtThreads, 0, s>>>(a);
     else bn::clrrt_steer_kernel<bn::kGeoPow2Origin0><<<h->B, bn::kClrrtThreads, 0, s>>>(a);
     CLRRT_HIP(hipGetLastError());
-    CLRRT_HIP(hipEventRecord(h->ev_done, s));
-    h->ev_recorded = true;
-    return BN_OK;
+    return bn::tree_mark_done(h, s, clrrt_fail);
 }
 
 int bn_clrrt_sync(bn_clrrt_t *h)
 {
     if (!h) return clrrt_fail(BN_ERR_INVALID, "null handle");
-    ClrrtDeviceGuard guard(h->cfg.device_id);
+    bn::DeviceGuard guard(h->cfg.device_id);
     if (!guard.ok) return clrrt_fail(BN_ERR_HIP, "hipSetDevice failed");
-    if (h->ev_recorded) CLRRT_HIP(hipEventSynchronize(h->ev_done));
-    return BN_OK;
+    return bn::tree_wait_done(h, clrrt_fail);
 }
 
 int bn_clrrt_device_buffer(bn_clrrt_t *h, int which, void **ptr, size_t *bytes)
 {
     if (!h || !ptr || !bytes) return clrrt_fail(BN_ERR_INVALID, "null argument");
-    const size_t B = h->B, nc = B * h->cap, ni = B * h->iters, S = h->S;
-    switch (which) {
-    case BN_CLRRT_BUF_NODES: *ptr = h->nodes; *bytes = nc * 12; break;
-    case BN_CLRRT_BUF_EDGES: *ptr = h->edges; *bytes = nc * 4; break;
-    case BN_CLRRT_BUF_COSTS: *ptr = h->costs; *bytes = nc * 4; break;
-    case BN_CLRRT_BUF_COUNTS: *ptr = h->counts; *bytes = B * 4; break;
-    case BN_CLRRT_BUF_SEQ_LENGTHS: *ptr = h->lens; *bytes = nc * 4; break;
-    case BN_CLRRT_BUF_CONTROLLERS: *ptr = h->ctrl; *bytes = nc * 16; break;
-    case BN_CLRRT_BUF_ACTION_SEQS: *ptr = h->aseq; *bytes = nc * S * 8; break;
-    case BN_CLRRT_BUF_STATE_SEQS: *ptr = h->sseq; *bytes = nc * (S + 1) * 12; break;
-    case BN_CLRRT_BUF_SAMPLES: *ptr = h->samples; *bytes = ni * 12; break;
-    case BN_CLRRT_BUF_SAMPLE_FLAGS: *ptr = h->flags; *bytes = ni * 4; break;
-    case BN_CLRRT_BUF_NEAREST: *ptr = h->near; *bytes = ni * 4; break;
-    case BN_CLRRT_BUF_FEASIBLE: *ptr = h->feasible; *bytes = ni * 4; break;
-    case BN_CLRRT_BUF_PATH_ACTIONS: *ptr = h->path_actions; *bytes = B * h->path_cap * 8; break;
-    case BN_CLRRT_BUF_PATH_STATES: *ptr = h->path_states; *bytes = B * ((size_t)h->path_cap + 1) * 12; break;
-    case BN_CLRRT_BUF_RESULTS: *ptr = h->results; *bytes = B * bn::kClrrtResult * 4; break;
-    case BN_CLRRT_BUF_STEER_ACTIONS: *ptr = h->st_actions; *bytes = B * S * 8; break;
-    case BN_CLRRT_BUF_STEER_STATES: *ptr = h->st_states; *bytes = B * (S + 1) * 12; break;
-    case BN_CLRRT_BUF_STEER_PATHS: *ptr = h->st_paths; *bytes = B * bn::kClrrtPoints * 16; break;
-    case BN_CLRRT_BUF_STEER_TARGETS: *ptr = h->st_tgt; *bytes = B * S * 4; break;
-    case BN_CLRRT_BUF_STEER_RESULTS: *ptr = h->st_results; *bytes = B * bn::kClrrtSteerResult * 4; break;
-    case BN_CLRRT_BUF_STEER_COSTS: *ptr = h->st_cost; *bytes = B * 4; break;
-    case BN_CLRRT_BUF_STEER_CONTROLLERS: *ptr = h->st_ctrl_out; *bytes = B * 32; break;
-    case BN_CLRRT_BUF_MT_STATE: *ptr = h->state; *bytes = B * bn::kMtN * 4; break;
-    case BN_CLRRT_BUF_MT_POS: *ptr = h->pos; *bytes = B * 4; break;
-    default: return clrrt_fail(BN_ERR_INVALID, "unknown CL-RRT buffer id");
-    }
+    if (!h->bufs.find(which, ptr, bytes)) return clrrt_fail(BN_ERR_INVALID, "unknown CL-RRT buffer id");
     return BN_OK;
 }
 

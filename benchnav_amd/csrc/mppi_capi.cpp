@@ -5,6 +5,7 @@
 // fallback: creation fails without a gfx950 device.
 #include "../../include/benchnav_mppi.h"
 #include "mppi_kernels.h"
+#include "bn_host.h"
 #include "astar_dwa.h"
 #include "clrrt_view.h"
 
@@ -309,21 +310,7 @@ namespace {
 
 // Every entry point works on the handle's device and leaves the calling thread's current device as it found it
 // (one process may drive several GPUs; torch tracks its own notion of the current device).
-struct DeviceGuard {
-    int prev = -1;
-    bool changed = false, ok = true;
-    explicit DeviceGuard(int want)
-    {
-        if (hipGetDevice(&prev) != hipSuccess) { ok = false; return; }
-        if (prev != want) {
-            ok = hipSetDevice(want) == hipSuccess;
-            changed = ok;
-        }
-    }
-    ~DeviceGuard() { if (changed) (void)hipSetDevice(prev); }
-    DeviceGuard(const DeviceGuard &) = delete;
-    DeviceGuard &operator=(const DeviceGuard &) = delete;
-};
+using bn::DeviceGuard;                      // bn_host.h
 #define BN_BIND_Q(h) DeviceGuard bn_guard_((h)->cfg.device_id); if (!bn_guard_.ok) return fail(BN_ERR_HIP, "hipSetDevice failed")
 
 // BN_FLAG_UNORDERED_OUTPUTS: the host-paced forward left the handle's stream unordered behind the latest posted solve (a stream-wait on a

@@ -11,6 +11,7 @@
 // mean by one more pass.  Only mean/std in and R out touch HBM (8 B + 4 B per cell instead of 4*num_samples B).
 #include "../../include/benchnav_mppi.h"
 #include "bn_device_math.h"
+#include "bn_host.h"
 
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -143,12 +144,7 @@ int bn_risk_map_infer(int32_t device_id, void *stream, const float *mean, const 
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(BN_ERR_NO_DEVICE, "no HIP device visible: no CPU fallback");
     // work on `device_id`, leave the calling thread's current device as it was
-    struct Guard {
-        int prev = -1; bool changed = false, ok = true;
-        explicit Guard(int want) { if (hipGetDevice(&prev) != hipSuccess) { ok = false; return; }
-                                   if (prev != want) { ok = hipSetDevice(want) == hipSuccess; changed = ok; } }
-        ~Guard() { if (changed) (void)hipSetDevice(prev); }
-    } guard(device_id);
+    bn::DeviceGuard guard(device_id);
     if (!guard.ok) return fail(BN_ERR_HIP, "hipSetDevice failed");
     hipStream_t s = (hipStream_t)stream;
     const size_t cells = (size_t)grid_size * grid_size;

@@ -19,6 +19,8 @@
 //                             thresholds -> the class map (generate_multi_terrain :421-443), and the two per-instance counters
 //   terrain_color_kernel      after it: surface normals of the cropped heights, the light's shade on the class's colour
 // Every index is bounded by the handle's G and B; crater slices are validated on the host and clamped here again.
+// The host side takes its device guard and HIP check from bn_host.h; its buffers are reallocated as the draws and the colouring
+// change size (realloc_dev), so they are not kept in that header's buffer table.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -30,6 +32,7 @@
 
 #include "../../include/benchnav_mppi.h"
 #include "bn_device_math.h"
+#include "bn_host.h"
 #include "mt19937.h"
 
 namespace bn {
@@ -619,14 +622,7 @@ int terrain_fail(int code, const std::string &msg)
     return code;
 }
 
-struct TerrainDeviceGuard {
-    int prev = -1; bool changed = false, ok = true;
-    explicit TerrainDeviceGuard(int want) { if (hipGetDevice(&prev) != hipSuccess) { ok = false; return; }
-                                            if (prev != want) { ok = hipSetDevice(want) == hipSuccess; changed = ok; } }
-    ~TerrainDeviceGuard() { if (changed) (void)hipSetDevice(prev); }
-};
-
-#define TERRAIN_HIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return terrain_fail(BN_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); } while (0)
+#define TERRAIN_HIP(expr) BN_HIP_AS(terrain_fail, expr, #expr)
 
 template <typename P>
 int realloc_dev(P **p, size_t bytes)
@@ -745,7 +741,7 @@ int bn_terrain_create(int32_t device_id, int32_t G, int32_t B, bn_terrain_t **ou
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return terrain_fail(BN_ERR_NO_DEVICE, "no HIP device visible: no CPU fallback");
     if (device_id < 0 || device_id >= ndev) return terrain_fail(BN_ERR_INVALID, "device_id out of range");
-    TerrainDeviceGuard guard(device_id);
+    bn::DeviceGuard guard(device_id);
     if (!guard.ok) return terrain_fail(BN_ERR_HIP, "hipSetDevice failed");
     auto *h = new bn_terrain_t();
     h->device = device_id; h->G = G; h->N = G + 2; h->B = B;
@@ -780,7 +776,7 @@ int bn_terrain_create(int32_t device_id, int32_t G, int32_t B, bn_terrain_t **ou
 void bn_terrain_destroy(bn_terrain_t *h)
 {
     if (!h) return;
-    TerrainDeviceGuard guard(h->device);
+    bn::DeviceGuard guard(h->device);
     if ((h->generated || h->ev_recorded) && h->ev_done) (void)hipEventSynchronize(h->ev_done);
     for (void *p : {(void *)h->hp, (void *)h->S, (void *)h->T, (void *)h->tw, (void *)h->heights, (void *)h->slopes, (void *)h->mean,
                     (void *)h->stddev, (void *)h->classes, (void *)h->phases, (void *)h->cr_count, (void *)h->cr_int,
@@ -821,7 +817,7 @@ int bn_terrain_set_draws(bn_terrain_t *h, const float *phases, const int32_t *cr
                 return terrain_fail(BN_ERR_INVALID, "crater " + std::to_string(c) + " of instance " + std::to_string(b) + " is out of range");
         }
     }
-    TerrainDeviceGuard guard(h->device);
+    bn::DeviceGuard guard(h->device);
     if (!guard.ok) return terrain_fail(BN_ERR_HIP, "hipSetDevice failed");
     int rc = wait_done(h);
     if (rc) return rc;
@@ -859,7 +855,7 @@ int bn_terrain_set_draw_params(bn_terrain_t *h, int32_t is_crater, int32_t num_c
     const double stride = std::ceil(2.0 * std::max(min_radius, max_radius) / h->resolution) + 2.0;
     if (!(stride * slots * h->B <= (double)((int64_t)1 << 30)))
         return terrain_fail(BN_ERR_INVALID, "the crater profiles (B x num_craters x 2 max_radius / resolution) must fit 2^30 values");
-    TerrainDeviceGuard guard(h->device);
+    bn::DeviceGuard guard(h->device);
     if (!guard.ok) return terrain_fail(BN_ERR_HIP, "hipSetDevice failed");
     h->dr_crater = is_crater != 0; h->dr_num = num_craters; h->dr_light = with_light != 0;
     h->dr_margin = crater_margin; h->dr_amin = min_angle; h->dr_amax = max_angle; h->dr_rmin = min_radius; h->dr_rmax = max_radius;
@@ -873,7 +869,7 @@ int bn_terrain_draw_async(bn_terrain_t *h, const uint64_t *seeds, void *stream)
     if (!h || !seeds) return terrain_fail(BN_ERR_INVALID, "null argument");
     if (!h->have_geometry || !h->have_draw_params) return terrain_fail(BN_ERR_STATE, "geometry and draw parameters must be set first");
     if (h->dr_light && !h->light) return terrain_fail(BN_ERR_STATE, "the light source is drawn for the colouring: set it first");
-    TerrainDeviceGuard guard(h->device);
+    bn::DeviceGuard guard(h->device);
     if (!guard.ok) return terrain_fail(BN_ERR_HIP, "hipSetDevice failed");
     int rc = wait_done(h);                   // the last draws or generation: the staging buffer and the tables are free again
     if (rc || (rc = ensure_draw_buffers(h))) return rc;
@@ -915,7 +911,7 @@ int bn_terrain_read_draws(bn_terrain_t *h, int32_t *records, float *centers, dou
     if (!h->drawn) return terrain_fail(BN_ERR_STATE, "no draws made on the device yet");
     if (h->maxc != h->dr_slots) return terrain_fail(BN_ERR_STATE, "the crater tables were replaced by host draws since the device drew");
     if (light && !h->light) return terrain_fail(BN_ERR_STATE, "colouring has not been set");
-    TerrainDeviceGuard guard(h->device);
+    bn::DeviceGuard guard(h->device);
     if (!guard.ok) return terrain_fail(BN_ERR_HIP, "hipSetDevice failed");
     int rc = wait_done(h);
     if (rc) return rc;
@@ -936,7 +932,7 @@ int bn_terrain_set_slip(bn_terrain_t *h, const int32_t *t_classes, const float *
 {
     if (!h || (num_classes > 0 && !class_params)) return terrain_fail(BN_ERR_INVALID, "null argument");
     if (num_classes < 0 || num_classes > (1 << 20)) return terrain_fail(BN_ERR_INVALID, "num_classes out of range");
-    TerrainDeviceGuard guard(h->device);
+    bn::DeviceGuard guard(h->device);
     if (!guard.ok) return terrain_fail(BN_ERR_HIP, "hipSetDevice failed");
     int rc = wait_done(h);
     if (rc) return rc;
@@ -955,7 +951,7 @@ int bn_terrain_generate_async(bn_terrain_t *h, void *stream)
 {
     if (!h) return terrain_fail(BN_ERR_INVALID, "null handle");
     if (!h->have_geometry || !h->have_draws || !h->have_slip) return terrain_fail(BN_ERR_STATE, "geometry, draws and slip models must be set first");
-    TerrainDeviceGuard guard(h->device);
+    bn::DeviceGuard guard(h->device);
     if (!guard.ok) return terrain_fail(BN_ERR_HIP, "hipSetDevice failed");
     hipStream_t s = (hipStream_t)stream;
     const bn::TerrainArgs a = make_args(h);
@@ -998,7 +994,7 @@ int bn_terrain_generate_async(bn_terrain_t *h, void *stream)
 int bn_terrain_sync(bn_terrain_t *h)
 {
     if (!h) return terrain_fail(BN_ERR_INVALID, "null handle");
-    TerrainDeviceGuard guard(h->device);
+    bn::DeviceGuard guard(h->device);
     return wait_done(h);
 }
 
@@ -1013,7 +1009,7 @@ int bn_terrain_copy_out(bn_terrain_t *h, float *heights, float *slopes, float *m
 {
     if (!h) return terrain_fail(BN_ERR_INVALID, "null handle");
     if (!h->generated) return terrain_fail(BN_ERR_STATE, "nothing generated yet");
-    TerrainDeviceGuard guard(h->device);
+    bn::DeviceGuard guard(h->device);
     if (!guard.ok) return terrain_fail(BN_ERR_HIP, "hipSetDevice failed");
     int rc = wait_done(h);
     if (rc) return rc;
@@ -1039,7 +1035,7 @@ int bn_terrain_set_coloring(bn_terrain_t *h, int32_t enable, const float *thresh
         return terrain_fail(BN_ERR_INVALID, "ambient_intensity must be finite and feature_size finite and >= 1e-3");
     for (int b = 0; b < h->B; ++b)
         if (start[b] < 0 || start[b] > num_classes) return terrain_fail(BN_ERR_INVALID, "start class out of range");
-    TerrainDeviceGuard guard(h->device);
+    bn::DeviceGuard guard(h->device);
     if (!guard.ok) return terrain_fail(BN_ERR_HIP, "hipSetDevice failed");
     int rc = wait_done(h);
     if (rc) return rc;
@@ -1064,7 +1060,7 @@ int bn_terrain_colorize(bn_terrain_t *h, const float *heights, const int32_t *t_
     if (num_classes < 1 || num_classes > bn::kMaxColorClasses)
         return terrain_fail(BN_ERR_INVALID, "colouring supports 1 to " + std::to_string(bn::kMaxColorClasses) + " terrain classes");
     if (!std::isfinite(ambient_intensity)) return terrain_fail(BN_ERR_INVALID, "ambient_intensity must be finite");
-    TerrainDeviceGuard guard(h->device);
+    bn::DeviceGuard guard(h->device);
     if (!guard.ok) return terrain_fail(BN_ERR_HIP, "hipSetDevice failed");
     int rc = wait_done(h);
     if (rc) return rc;
@@ -1097,7 +1093,7 @@ int bn_terrain_class_counts(bn_terrain_t *h, int32_t *unassigned, int32_t *beyon
 {
     if (!h || !unassigned || !beyond) return terrain_fail(BN_ERR_INVALID, "null argument");
     if (!h->generated || !h->colored || !h->counts) return terrain_fail(BN_ERR_STATE, "no coloured generation yet");
-    TerrainDeviceGuard guard(h->device);
+    bn::DeviceGuard guard(h->device);
     if (!guard.ok) return terrain_fail(BN_ERR_HIP, "hipSetDevice failed");
     int rc = wait_done(h);
     if (rc) return rc;
@@ -1112,7 +1108,7 @@ int bn_terrain_spectrum(bn_terrain_t *h, int32_t inst, float *out)
     if (!h || !out) return terrain_fail(BN_ERR_INVALID, "null argument");
     if (inst < 0 || inst >= h->B) return terrain_fail(BN_ERR_INVALID, "instance out of range");
     if (!h->have_geometry || !h->have_draws) return terrain_fail(BN_ERR_STATE, "geometry and draws must be set first");
-    TerrainDeviceGuard guard(h->device);
+    bn::DeviceGuard guard(h->device);
     if (!guard.ok) return terrain_fail(BN_ERR_HIP, "hipSetDevice failed");
     int rc = wait_done(h);
     if (rc) return rc;

@@ -18,6 +18,7 @@ import torch
 import torch.nn as nn
 
 from . import _capi
+from ._device import _DevArray  # noqa: F401  (tests and tools import it from here)
 
 
 def _raw_stream(dev_index: int) -> int:
@@ -37,16 +38,6 @@ class _CallState:
 
     def __init__(self):
         self.eps = self.noise_cache = self.rolled = self.state = None
-
-
-class _DevArray:
-    """Library-owned device memory exposed to torch through __cuda_array_interface__."""
-
-    def __init__(self, ptr: int, shape, strides_elems=None):
-        self.__cuda_array_interface__ = {
-            "shape": tuple(int(s) for s in shape), "typestr": "<f4", "data": (int(ptr), False), "version": 2,
-            "strides": None if strides_elems is None else tuple(int(s) * 4 for s in strides_elems),
-        }
 
 
 # Every private attribute of the reference's objects the native planners read (SURVEY.md 8b), by reference class.  The golden

@@ -25,23 +25,7 @@ import torch
 import torch.nn as nn
 
 from . import _capi
-
-_INITIAL_CAPACITY = 1000                     # tree.py:17
-
-
-def _check_seed(seed) -> int:
-    s = int(seed)
-    if s < 0 or s > 0xFFFFFFFF:              # np.random.seed's range (set_randomness)
-        raise ValueError("Seed must be between 0 and 2**32 - 1")
-    return s
-
-
-class _DevArray:
-    """Library-owned device memory exposed to torch through __cuda_array_interface__."""
-
-    def __init__(self, ptr: int, shape, typestr="<f4"):
-        self.__cuda_array_interface__ = {"shape": tuple(int(v) for v in shape), "typestr": typestr, "data": (int(ptr), False),
-                                         "version": 2, "strides": None}
+from ._device import _DevArray, _PlannerHandle, _TreePlanner, _check_seed, check, seed_array, tree_capacity  # noqa: F401
 
 
 class Tree:
@@ -51,9 +35,7 @@ class Tree:
 
     def __init__(self, nodes: torch.Tensor, edges: torch.Tensor, costs: torch.Tensor):
         n = int(nodes.shape[0])
-        cap = _INITIAL_CAPACITY
-        while cap < n:
-            cap *= 2
+        cap = tree_capacity(n)
         dev = nodes.device
         self.nodes = torch.zeros((cap, 2), dtype=torch.float32, device=dev)
         self.edges = -torch.ones(cap, dtype=torch.int64, device=dev)
@@ -64,44 +46,29 @@ class Tree:
         self.nodes_count = n
 
 
-class _Handle:
+class _Handle(_PlannerHandle):
     """One bn_rrt handle: B instances of one parameter set."""
+    family = "rrt"
 
-    def __init__(self, lib, dev: torch.device, B: int, owner: "RRT", flags: int):
+    def __init__(self, lib, dev: torch.device, B: int, owner: "RRT"):
         cfg = _capi.RRTConfig()
         lib.bn_rrt_config_init(C.byref(cfg))
-        cfg.device_id, cfg.num_instances, cfg.max_iterations, cfg.flags = dev.index, B, owner._max_iterations, flags
+        cfg.device_id, cfg.num_instances, cfg.max_iterations, cfg.flags = dev.index, B, owner._max_iterations, owner._flags
         cfg.x_limits[0], cfg.x_limits[1] = float(owner.x_limits[0]), float(owner.x_limits[1])
         cfg.y_limits[0], cfg.y_limits[1] = float(owner.y_limits[0]), float(owner.y_limits[1])
         cfg.delta_distance, cfg.goal_sample_rate = float(owner._delta_distance), float(owner._goal_sample_rate)
         cfg.seed = owner._seed
-        self.lib, self.dev, self.B, self.iters = lib, dev, B, owner._max_iterations
-        self.h = C.c_void_p()
-        _check(lib, lib.bn_rrt_create(C.byref(cfg), C.byref(self.h)))
-
-    def buffer(self, which: int, shape, typestr="<f4") -> torch.Tensor:
-        ptr, nbytes = C.c_void_p(), C.c_size_t()
-        _check(self.lib, self.lib.bn_rrt_device_buffer(self.h, which, C.byref(ptr), C.byref(nbytes)))
-        return torch.as_tensor(_DevArray(ptr.value, shape, typestr), device=self.dev)
-
-    def close(self):
-        if self.h:
-            self.lib.bn_rrt_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self.iters = owner._max_iterations
+        super().__init__(lib, dev, B, cfg)
 
 
 def _check(lib, code: int):
-    if code != _capi.BN_OK:
-        raise _capi.BenchnavError(code, lib.bn_rrt_last_error().decode("utf-8", "replace"))
+    check(lib, "rrt", code)
 
 
-class RRT(nn.Module):
+class RRT(_TreePlanner, nn.Module):
+    _handle_type = _Handle
+
     def __init__(self, grid_map, goal_pos: torch.Tensor, max_iterations: int = 1000, delta_distance: float = 5,
                  goal_sample_rate: float = 0.1, dim_state: int = 2, device: Optional[str] = None, seed: int = 42,
                  node_storage: Optional[str] = None, workgroup: Optional[int] = None) -> None:
@@ -146,8 +113,7 @@ class RRT(nn.Module):
         if not self._is_within_bounds(start) or not self._is_within_bounds(self._goal_host):        # rrt.py:94-97, before any launch
             raise ValueError("Start or goal position is out of bounds.")
         h = self._handle(1)
-        first = not getattr(h, "used", False)
-        self._launch(h, start.numpy()[None], self._goal_host.numpy()[None], np.array([self._seed], np.uint64) if first else None)
+        self._launch(h, start.numpy()[None], self._goal_host.numpy()[None], None if h.used else np.array([self._seed], np.uint64))
         res = h.buffer(_capi.BN_RRT_BUF_RESULTS, (1, 4), "<i4").cpu().numpy()[0]
         self.tree = self._tree(h, 0)
         self._near_goal_count = int(res[3])
@@ -156,10 +122,6 @@ class RRT(nn.Module):
             return None
         path = h.buffer(_capi.BN_RRT_BUF_PATHS, (1, h.iters + 1, 2))[0, :int(res[2])].clone()
         return path.to(self.device)
-
-    def _is_within_bounds(self, node: torch.Tensor) -> bool:
-        x, y = node[:2]
-        return self.x_limits[0] <= x.item() <= self.x_limits[1] and self.y_limits[0] <= y.item() <= self.y_limits[1]
 
     # ---- B planners per launch -------------------------------------------------------------------------------------------
     def plan_batch(self, states, goals=None, seeds=None):
@@ -181,11 +143,7 @@ class RRT(nn.Module):
         for b in range(B):
             if not self._is_within_bounds(starts[b]) or not self._is_within_bounds(g[b]):
                 raise ValueError("Start or goal position is out of bounds.")
-        sd = None
-        if seeds is not None:
-            if len(seeds) != B:
-                raise ValueError("one seed per instance")
-            sd = np.array([_check_seed(s) for s in seeds], np.uint64)
+        sd = None if seeds is None else seed_array(seeds, B)
         h = self._handle(B)
         self._launch(h, starts.numpy(), g.numpy(), sd)
         return self._batch_result(h)
@@ -204,15 +162,7 @@ class RRT(nn.Module):
         if tuple(samples.shape) != (B, self._max_iterations, 2):
             raise ValueError(f"samples must be ({B}, {self._max_iterations}, 2), got {tuple(samples.shape)}")
         h = self._handle(B)
-        if samples.is_cuda:
-            samples = samples.to(self._dev)
-            where, ptr = _capi.BN_MEM_DEVICE, samples.data_ptr()
-        else:
-            keep = samples.numpy()
-            where, ptr = _capi.BN_MEM_HOST, keep.ctypes.data
-        sn, gn = starts.numpy(), g.numpy()
-        _check(self._lib, self._lib.bn_rrt_grow_from_samples_async(h.h, self._stream(), sn.ctypes.data, gn.ctypes.data, ptr, where))
-        torch.cuda.current_stream(self._dev).synchronize()
+        self._grow(h, starts.numpy(), g.numpy(), samples)
         return self._batch_result(h)
 
     def batch_tree(self, b: int) -> Tree:
@@ -233,24 +183,6 @@ class RRT(nn.Module):
         return {0: "global", 1: "lds", 2: "lds+costs"}[int(self._lib.bn_rrt_node_storage(self._handle(B).h))]
 
     # ---- plumbing --------------------------------------------------------------------------------------------------------
-    _last_handle = None
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self._dev).cuda_stream)
-
-    def _handle(self, B: int) -> _Handle:
-        if B not in self._handles:
-            self._handles[B] = _Handle(self._lib, self._dev, B, self, self._flags)
-        return self._handles[B]
-
-    def _launch(self, h: _Handle, starts: np.ndarray, goals: np.ndarray, seeds: Optional[np.ndarray]) -> None:
-        starts, goals = np.ascontiguousarray(starts, np.float32), np.ascontiguousarray(goals, np.float32)
-        sp = seeds.ctypes.data if seeds is not None else None
-        _check(self._lib, self._lib.bn_rrt_plan_async(h.h, self._stream(), starts.ctypes.data, goals.ctypes.data, sp))
-        h.used = True
-        self._last_handle = h
-        torch.cuda.current_stream(self._dev).synchronize()
-
     def _tree(self, h: _Handle, b: int) -> Tree:
         n = h.iters + 1
         return Tree(h.buffer(_capi.BN_RRT_BUF_NODES, (h.B, n, 2))[b], h.buffer(_capi.BN_RRT_BUF_EDGES, (h.B, n), "<i4")[b],

@@ -40,6 +40,7 @@ import numpy as np
 import torch
 
 from . import _capi
+from ._device import _DevArray, stream_ptr
 
 # the dataset script's ranges (scripts/generate_terrain_dataset.py:31-34), the defaults of slip_models()
 SLIP_SENSITIVITY_MINMAX = (1.0, 9.0)
@@ -358,7 +359,7 @@ class TerrainGenerator:
             raise ValueError("The number of terrain classes exceeds the number of slip models.")
         cls32 = np.ascontiguousarray(cls, dtype=np.int32)
         self._check(self._lib.bn_terrain_set_slip(self._handle, cls32.ctypes.data, tab.ctypes.data, tab.shape[0]))
-        self._check(self._lib.bn_terrain_generate_async(self._handle, C.c_void_p(torch.cuda.current_stream(self._dev).cuda_stream)))
+        self._check(self._lib.bn_terrain_generate_async(self._handle, stream_ptr(self._dev)))
         out = self.outputs()
         with torch.cuda.device(self._dev):
             colors = torch.zeros((self.batch, 3, self.grid_size, self.grid_size), device=self._dev)
@@ -444,7 +445,7 @@ class TerrainGenerator:
 
     def _generate_colored(self, draws, is_fractal, slip_models, occupancy, noise, feature_size, ambient_intensity) -> Terrain:
         light = self._set_colored(draws, None, is_fractal, slip_models, occupancy, noise, feature_size, ambient_intensity)
-        self._check(self._lib.bn_terrain_generate_async(self._handle, C.c_void_p(torch.cuda.current_stream(self._dev).cuda_stream)))
+        self._check(self._lib.bn_terrain_generate_async(self._handle, stream_ptr(self._dev)))
         self._check_class_counts()
         out = self.outputs()
         cls, colors, nz = self._color_outputs()
@@ -459,7 +460,7 @@ class TerrainGenerator:
         is_crater, num_craters, crater_margin, min_angle, max_angle, min_radius, max_radius = geometry
         lo, hi = (0.8, 1.0) if coloring is None else coloring
         keys = np.array([s % (1 << 64) for s in seeds], np.uint64)
-        stream = C.c_void_p(torch.cuda.current_stream(self._dev).cuda_stream)
+        stream = stream_ptr(self._dev)
         self._check(self._lib.bn_terrain_set_geometry(self._handle, self.resolution, self.roughness_exponent, self.amplitude_gain,
                                                       int(bool(is_fractal))))
         self._check(self._lib.bn_terrain_set_draw_params(self._handle, int(bool(is_crater)), int(num_craters), float(crater_margin),
@@ -538,7 +539,6 @@ class TerrainGenerator:
 
     def _color_outputs(self):
         """(classes int32 (B, G, G), colours (B, 3, G, G), noise (B, G, G)) device tensors (copies)."""
-        from .astar import _DevArray
         ptrs = [C.c_void_p() for _ in range(3)]
         self._check(self._lib.bn_terrain_color_buffers(self._handle, *[C.byref(p) for p in ptrs]))
         B, G = self.batch, self.grid_size
@@ -568,8 +568,7 @@ class TerrainGenerator:
         L = np.ascontiguousarray(L)
         table = np.ascontiguousarray(_copper_table(num_classes))
         self._check(self._lib.bn_terrain_colorize(self._handle, h.ctypes.data, cls.ctypes.data, table.ctypes.data, int(num_classes),
-                                                  L.ctypes.data, float(ambient_intensity),
-                                                  C.c_void_p(torch.cuda.current_stream(self._dev).cuda_stream)))
+                                                  L.ctypes.data, float(ambient_intensity), stream_ptr(self._dev)))
         return self._color_outputs()[1]
 
     def upload_draws(self, draws: List[Draws], is_fractal: bool) -> None:
@@ -612,7 +611,6 @@ class TerrainGenerator:
 
     def outputs(self):
         """(heights, slopes, latent_mean, latent_std) of the last generate(), (B, G, G) float32 device tensors (copies)."""
-        from .astar import _DevArray
         ptrs = [C.c_void_p() for _ in range(4)]
         self._check(self._lib.bn_terrain_buffers(self._handle, *[C.byref(p) for p in ptrs]))
         shape = (self.batch, self.grid_size, self.grid_size)

@@ -135,3 +135,11 @@ def test_header_is_plain_c_and_the_integration_example_compiles():
         assert r.returncode == 0, r.stderr
     finally:
         os.unlink(f.name)
+
+
+def test_the_wrappers_share_one_device_array_and_keep_their_check_functions():
+    """Tests, tools and the benchmark import _DevArray from mppi, astar and rrt: all three are the one class of _device.py.  The
+    rate tools call rrt._check and clrrt._check."""
+    from benchnav_amd import _device, astar, clrrt, mppi, rrt
+    assert mppi._DevArray is _device._DevArray and astar._DevArray is _device._DevArray and rrt._DevArray is _device._DevArray
+    assert callable(rrt._check) and callable(clrrt._check)
