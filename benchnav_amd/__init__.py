@@ -9,6 +9,7 @@
     from benchnav_amd import RRT           # drop-in for src/planners/global_planners/sampling_based/rrt.py:RRT, B plans per launch
     from benchnav_amd import CLRRT         # drop-in for src/planners/global_planners/sampling_based/cl_rrt.py:CLRRT, B plans per launch
     from benchnav_amd import CLRRTLoop     # test_cl_rrt.py's plan-follow-replan loop on the device, B rovers per launch
+    from benchnav_amd import TraversabilityPredictor, GPSlipRegressor, load_slip_regressors   # the exact-GP slip prediction stage
 """
 from .native import NativeMPPI  # noqa: F401
 
@@ -41,4 +42,7 @@ def __getattr__(name):
     if name == "CLRRTLoop":
         from .clrrt_loop import CLRRTLoop
         return CLRRTLoop
+    if name in ("TraversabilityPredictor", "GPSlipRegressor", "load_slip_regressors"):
+        from . import gp
+        return getattr(gp, name)
     raise AttributeError(name)

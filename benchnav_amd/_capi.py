@@ -210,6 +210,14 @@ SYMBOLS = {
     "bn_clrrt_loop_run": (C.c_int, [_H, _H, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, _FP]),
     "bn_clrrt_loop_log": (C.c_int, [_H] + [C.c_void_p] * 10),
     "bn_clrrt_loop_set_plans": (C.c_int, [_H, _H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),
+    "bn_gp_max_points": (C.c_int32, []),
+    "bn_gp_create": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double,
+                               C.POINTER(_H)]),
+    "bn_gp_destroy": (None, [_H]),
+    "bn_gp_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int32]),
+    "bn_gp_predict_async": (C.c_int, [C.c_int32, C.c_void_p, C.POINTER(_H), C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t]),
+    "bn_gp_last_error": (C.c_char_p, []),
     "bn_device_math_eval": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "bn_device_rng_eval": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "bn_last_error": (C.c_char_p, []),

@@ -1,0 +1,255 @@
+"""Exact-GP slip prediction on the GPU: mirror of TraversabilityPredictor.predict and of the GP slip regressors behind it
+(reference src/prediction_models/traversability_predictors/classifier_and_regressor.py:42-72, slip_regressors/gpr.py,
+trainers/utils.py:65-108).  The stage that fills `distributions["predictions"]` (SURVEY "next" row N4).
+
+The regressor is gpytorch's ExactGP with ConstantMean, ScaleKernel(RBFKernel) and GaussianLikelihood on a 1-D input, evaluated
+from its equations -- gpytorch is not imported:
+
+    k(a, b) = s exp(-(a - b)^2 / (2 l^2)),   K = k(x, x) + noise I = L L^T,   alpha = K^-1 (y - c)
+    mean(phi) = c + k(phi, x) . alpha,       v = L^-1 k(x, phi),              std(phi) = sqrt(max(s - |v|^2, 0) + noise)
+
+The host factorises once per regressor in float64 (NumPy); the device evaluates every cell in float64 and rounds the outputs.
+The UNet terrain classifier is out of scope: any object with `.predict(colors[None]) -> classes` serves, or pass the class maps.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+from typing import Dict, Optional, Tuple
+
+import numpy as np
+import torch
+from torch.distributions import Normal
+
+from . import _capi
+from ._device import stream_ptr
+
+MAX_POINTS = 1024           # bn_gp_max_points(): the k(x, phi) tile of 16 cells x 1024 points fills 128 KB of LDS
+MAX_CLASSES = 32
+_NOISE_LOWER_BOUND = 1e-4   # GaussianLikelihood's default GreaterThan(1e-4) on the noise
+
+
+def _check(lib, code: int):
+    if code != _capi.BN_OK:
+        raise _capi.BenchnavError(code, lib.bn_gp_last_error().decode("utf-8", "replace"))
+
+
+def _scalar(v, name: str) -> float:
+    if isinstance(v, torch.Tensor):
+        v = v.detach().cpu().to(torch.float64).numpy()
+    a = np.asarray(v, dtype=np.float64).reshape(-1)
+    if a.size != 1:
+        raise ValueError(f"{name} must hold one value, got {a.size}")
+    if not np.isfinite(a[0]):
+        raise ValueError(f"{name} must be finite")
+    return float(a[0])
+
+
+def _vector(v, name: str) -> np.ndarray:
+    if isinstance(v, torch.Tensor):
+        v = v.detach().cpu().numpy()
+    a = np.asarray(v)
+    if a.ndim == 2 and a.shape[1] == 1:                  # gpytorch keeps a 1-D input as (N, 1)
+        a = a[:, 0]
+    if a.ndim != 1:
+        raise ValueError(f"{name} must be one-dimensional, got shape {a.shape}")
+    a = a.astype(np.float32).astype(np.float64)          # the reference trains on float32: widened exactly
+    if not np.isfinite(a).all():
+        raise ValueError(f"{name} must be finite")
+    return a
+
+
+def factorize(train_x, train_y, constant: float, outputscale: float, lengthscale: float, noise: float) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """(x, alpha, L^-1) in float64 for the device: K = outputscale exp(-(x - x')^2 / (2 lengthscale^2)) + noise I = L L^T,
+    alpha = K^-1 (y - constant), L^-1 explicit and lower triangular.
+
+    No jitter is added (gpytorch retries a failed Cholesky with 1e-6 ... 1e-4 on the diagonal; here a matrix that is not
+    numerically positive definite raises ValueError).  1 <= N <= MAX_POINTS, else ValueError."""
+    x, y = _vector(train_x, "train_x"), _vector(train_y, "train_y")
+    n = x.shape[0]
+    if y.shape[0] != n:
+        raise ValueError(f"train_x and train_y differ in length: {n} and {y.shape[0]}")
+    if n < 1 or n > MAX_POINTS:
+        raise ValueError(f"the regressor takes 1 to {MAX_POINTS} training points, got {n}")
+    c, s, l, nz = (_scalar(constant, "constant"), _scalar(outputscale, "outputscale"), _scalar(lengthscale, "lengthscale"),
+                   _scalar(noise, "noise"))
+    if not (s > 0.0 and l > 0.0 and nz > 0.0):
+        raise ValueError("outputscale, lengthscale and noise must be > 0")
+    d = x[:, None] - x[None, :]
+    K = s * np.exp(-(d * d) / (2.0 * l * l)) + nz * np.eye(n)
+    try:
+        L = np.linalg.cholesky(K)
+    except np.linalg.LinAlgError as e:
+        raise ValueError(f"k(x, x) + noise I is not numerically positive definite (no jitter is added): {e}") from None
+    linv = np.tril(np.linalg.solve(L, np.eye(n)))
+    alpha = linv.T @ (linv @ (y - c))
+    if not (np.isfinite(linv).all() and np.isfinite(alpha).all()):
+        raise ValueError("the factorisation of k(x, x) + noise I overflowed")
+    return x, alpha, np.ascontiguousarray(linv)
+
+
+def _softplus(v: float) -> float:
+    return float(np.logaddexp(0.0, v))
+
+
+class GPSlipRegressor:
+    """One terrain class's slip regressor on the device: `.predict(slopes)` is GPModel.predict's `likelihood(model(x))`, exact.
+
+    train_x, train_y: (N,) or (N, 1), used as float32 values; constant, outputscale, lengthscale, noise: the ACTUAL (not raw)
+    hyperparameters.  Raises ValueError for invalid inputs and RuntimeError without a GPU (no CPU fallback)."""
+
+    def __init__(self, train_x, train_y, constant: float, outputscale: float, lengthscale: float, noise: float, device=None) -> None:
+        x, alpha, linv = factorize(train_x, train_y, constant, outputscale, lengthscale, noise)
+        self.num_points = int(x.shape[0])
+        self.constant, self.outputscale, self.lengthscale, self.noise = (_scalar(constant, "constant"), _scalar(outputscale, "outputscale"),
+                                                                         _scalar(lengthscale, "lengthscale"), _scalar(noise, "noise"))
+        self._handle = None
+        if not torch.cuda.is_available():
+            raise RuntimeError("benchnav_amd.gp needs an MI355X (gfx950) device; there is no CPU fallback")
+        self._dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        if self._dev.index is None:
+            self._dev = torch.device("cuda", torch.cuda.current_device())
+        self._lib = _capi.load()
+        h = C.c_void_p()
+        _check(self._lib, self._lib.bn_gp_create(self._dev.index, self.num_points, x.ctypes.data, alpha.ctypes.data, linv.ctypes.data,
+                                                 self.constant, self.outputscale, self.lengthscale, self.noise, C.byref(h)))
+        self._handle = h
+
+    @classmethod
+    def from_gpytorch_state_dict(cls, state_dict, train_x, train_y, device=None, noise_lower_bound: Optional[float] = None) -> "GPSlipRegressor":
+        return cls(train_x, train_y, device=device, **hyperparameters_from_state_dict(state_dict, noise_lower_bound))
+
+    def to(self, device) -> "GPSlipRegressor":
+        """The reference moves its regressors with .to(device); this one lives where it was created."""
+        if torch.device(device).type == "cuda" and torch.device(device).index in (None, self._dev.index):
+            return self
+        raise ValueError(f"this regressor lives on {self._dev}; create another one for {device}")
+
+    def predict_tensors(self, x: torch.Tensor, dtype=torch.float32) -> Tuple[torch.Tensor, torch.Tensor]:
+        flat = x.reshape(1, -1)
+        if flat.numel() == 0:
+            e = torch.empty(x.shape, device=self._dev, dtype=dtype)
+            return e, e.clone()
+        cls_map = torch.zeros(flat.shape, device=self._dev, dtype=torch.int32)
+        mean, std = _predict(self._lib, self._dev, [self], flat, cls_map, dtype)
+        return mean.reshape(x.shape), std.reshape(x.shape)
+
+    def predict(self, x: torch.Tensor) -> Normal:
+        """Normal(mean, std) of x's shape: the `.mean` / `.stddev` surface of GPModel.predict, noise included."""
+        return Normal(*self.predict_tensors(x))
+
+    def close(self):
+        if getattr(self, "_handle", None):
+            self._lib.bn_gp_destroy(self._handle)
+            self._handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def hyperparameters_from_state_dict(state_dict, noise_lower_bound: Optional[float] = None) -> Dict[str, float]:
+    """The actual hyperparameters of a GPModel.state_dict() as regressor_trainer.py:172-200 saves it, read without gpytorch:
+    noise = softplus(likelihood.noise_covar.raw_noise) + the stored lower bound (default 1e-4), outputscale and lengthscale =
+    softplus of covar_module.raw_outputscale / covar_module.base_kernel.raw_lengthscale, constant = mean_module.raw_constant
+    (gpytorch >= 1.9) or the older mean_module.constant."""
+    def get(*names):
+        for n in names:
+            if n in state_dict:
+                return _scalar(state_dict[n], n)
+        raise ValueError(f"the state dict has none of {names}")
+    lb = noise_lower_bound
+    if lb is None:
+        key = "likelihood.noise_covar.raw_noise_constraint.lower_bound"
+        lb = _scalar(state_dict[key], key) if key in state_dict else _NOISE_LOWER_BOUND
+    return {"constant": get("mean_module.raw_constant", "mean_module.constant"),
+            "outputscale": _softplus(get("covar_module.raw_outputscale")),
+            "lengthscale": _softplus(get("covar_module.base_kernel.raw_lengthscale")),
+            "noise": _softplus(get("likelihood.noise_covar.raw_noise")) + float(lb)}
+
+
+def load_slip_regressors(num_terrain_classes: int, model_directory: str, train_data_directory: str, device=None) -> Dict[int, GPSlipRegressor]:
+    """trainers/utils.py:65-108 on the reference's file layout: class i's training data from
+    <train_data_directory>/slip_observations/<i:02d>_class.pth ({"train_x", "train_y"}) and its state dict from
+    <model_directory>/models/<i:02d>_class.pth, both read with weights_only=True."""
+    out = {}
+    for i in range(int(num_terrain_classes)):
+        data = torch.load(os.path.join(train_data_directory, f"slip_observations/{i:02d}_class.pth"), map_location="cpu", weights_only=True)
+        state = torch.load(os.path.join(model_directory, f"models/{i:02d}_class.pth"), map_location="cpu", weights_only=True)
+        out[i] = GPSlipRegressor.from_gpytorch_state_dict(state, data["train_x"], data["train_y"], device=device)
+    return out
+
+
+def _predict(lib, dev: torch.device, table, slopes: torch.Tensor, classes: torch.Tensor, dtype) -> Tuple[torch.Tensor, torch.Tensor]:
+    """bn_gp_predict_async on torch's current stream: slopes and classes (B, cells) -> mean, std (B, cells)."""
+    if dtype not in (torch.float32, torch.float64):
+        raise ValueError("dtype must be torch.float32 or torch.float64")
+    B, cells = slopes.shape
+    nc = len(table)
+    with torch.cuda.device(dev):
+        s = slopes.detach().to(dev, torch.float32).contiguous()
+        c = classes.detach().to(dev, torch.int32).contiguous()
+        mean = torch.empty(B, cells, device=dev, dtype=dtype)
+        std = torch.empty(B, cells, device=dev, dtype=dtype)
+        nbytes = lib.bn_gp_workspace_bytes(B, cells, nc)
+        if nbytes == 0:
+            raise ValueError(f"{B} maps of {cells} cells with {nc} classes are out of the library's range")
+        work = torch.empty(nbytes, device=dev, dtype=torch.uint8)     # torch's allocator keeps it alive for the stream
+        handles = (C.c_void_p * nc)(*[(r._handle.value if r is not None else None) for r in table])
+        _check(lib, lib.bn_gp_predict_async(dev.index, stream_ptr(dev), handles, nc, B, cells, C.c_void_p(s.data_ptr()),
+                                            C.c_void_p(c.data_ptr()), C.c_void_p(mean.data_ptr()), C.c_void_p(std.data_ptr()),
+                                            1 if dtype == torch.float64 else 0, C.c_void_p(work.data_ptr()), nbytes))
+    return mean, std
+
+
+class TraversabilityPredictor:
+    """classifier_and_regressor.py's TraversabilityPredictor on the device.
+
+    terrain_classifier: any object with `.predict(colors[None]) -> (1, G, G)` integer classes (the reference's UNet is not part
+    of this package), or None when the class maps are passed to predict_maps.  slip_regressors: {class: GPSlipRegressor}; a
+    class without one predicts mean 0 and std 0 (the reference's zeros_like)."""
+
+    def __init__(self, terrain_classifier, slip_regressors: Dict[int, GPSlipRegressor], device=None) -> None:
+        if not torch.cuda.is_available():
+            raise RuntimeError("benchnav_amd.gp needs an MI355X (gfx950) device; there is no CPU fallback")
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.terrain_classifier = terrain_classifier.to(self.device) if hasattr(terrain_classifier, "to") else terrain_classifier
+        self.slip_regressors = {int(k): r.to(self.device) for k, r in slip_regressors.items()}
+        if any(k < 0 or k >= MAX_CLASSES for k in self.slip_regressors):
+            raise ValueError(f"terrain classes must be in [0, {MAX_CLASSES})")
+        n = max(self.slip_regressors, default=0) + 1
+        self._table = [self.slip_regressors.get(k) for k in range(n)]
+        self._lib = _capi.load()
+
+    def predict_maps(self, slopes: torch.Tensor, t_classes: Optional[torch.Tensor] = None, colors: Optional[torch.Tensor] = None,
+                     dtype=torch.float32) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(mean, std) of slopes' shape, (G, G) or (B, G, G), in one launch pair.  t_classes of the same shape skips the
+        classifier; otherwise colors (3, G, G) or (B, 3, G, G) goes through it map by map."""
+        if slopes.dim() not in (2, 3):
+            raise ValueError(f"slopes must be (G, G) or (B, G, G), got {tuple(slopes.shape)}")
+        batched = slopes.dim() == 3
+        s = slopes if batched else slopes[None]
+        if t_classes is None:
+            if self.terrain_classifier is None or colors is None:
+                raise ValueError("pass t_classes, or colors and a terrain classifier")
+            col = (colors if batched else colors[None]).to(self.device)
+            if col.shape[0] != s.shape[0]:
+                raise ValueError("colors and slopes differ in batch size")
+            t_classes = torch.cat([torch.as_tensor(self.terrain_classifier.predict(col[b:b + 1])).reshape(1, *s.shape[1:])
+                                   for b in range(s.shape[0])])
+        else:
+            t_classes = t_classes if batched else t_classes[None]
+        if tuple(t_classes.shape) != tuple(s.shape):
+            raise ValueError(f"t_classes {tuple(t_classes.shape)} and slopes {tuple(s.shape)} differ in shape")
+        B = s.shape[0]
+        mean, std = _predict(self._lib, self.device, self._table, s.reshape(B, -1), t_classes.reshape(B, -1), dtype)
+        return mean.reshape(slopes.shape), std.reshape(slopes.shape)
+
+    def predict(self, colors: torch.Tensor, slopes: torch.Tensor) -> Normal:
+        """The reference's predict: colors (3, G, G), slopes (G, G) -> Normal(mean (G, G), std (G, G)).  As there, a map with a
+        cell whose class has no regressor has std 0 and Normal's argument check raises."""
+        return Normal(*self.predict_maps(slopes, colors=colors))

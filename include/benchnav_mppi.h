@@ -869,6 +869,42 @@ int bn_clrrt_loop_log(bn_mppi_t *h, float *states, float *rewards, float *action
 int bn_clrrt_loop_set_plans(bn_mppi_t *h, bn_clrrt_t *c, const float *actions, const float *states, const int32_t *lengths,
                             int32_t max_length, int32_t iteration);
 
+/* ------------------------------------------------------------------------------------------------------------------------------
+ * Exact-GP slip prediction (csrc/gp_kernels.hip): the per-class GP regressors behind
+ * TraversabilityPredictor.predict (classifier_and_regressor.py:42-72; slip_regressors/gpr.py: ExactGP, ConstantMean,
+ * ScaleKernel(RBFKernel) with one lengthscale, GaussianLikelihood, 1-D input).  With training inputs x[n], targets y[n],
+ * constant mean c, outputscale s, lengthscale l and noise:
+ *     k(a, b) = s exp(-(a - b)^2 / (2 l^2))          K = k(x, x) + noise I = L L^T (Cholesky, L lower)
+ *     alpha = K^-1 (y - c)                            linv = L^-1 (lower triangular)
+ * and for a cell of slope phi
+ *     mean = c + k(phi, x) . alpha                    v = linv k(x, phi)
+ *     var  = max(s - |v|^2, 0) + noise                std = sqrt(var)            (the likelihood's noise is part of var)
+ * A caller produces alpha and linv with LAPACK (dpotrf, dpotrs, dtrtri) in float64; the library adds no jitter and does not
+ * factorise.  The device evaluates every line above in float64 and rounds only the outputs.
+ * Errors: the gp error string below.
+ * ---------------------------------------------------------------------------------------------------------------------------- */
+typedef struct bn_gp bn_gp_t;
+/* The largest n bn_gp_create takes (1024: the k(x, phi) tile of 16 cells lives in LDS). */
+int32_t bn_gp_max_points(void);
+/* One regressor on device_id from HOST arrays: x (n), alpha (n), linv (n, n) row-major of which the lower triangle is read.
+ * Checked before the device is touched: 1 <= n <= bn_gp_max_points(), every value finite, outputscale, lengthscale and
+ * noise > 0 (BN_ERR_INVALID); without a device BN_ERR_NO_DEVICE ("no CPU fallback").  Synchronous. */
+int bn_gp_create(int32_t device_id, int32_t n, const double *x, const double *alpha, const double *linv, double constant,
+                 double outputscale, double lengthscale, double noise, bn_gp_t **out);
+void bn_gp_destroy(bn_gp_t *h);
+/* Bytes of device workspace bn_gp_predict_async needs: 4 num_maps cells + 4 num_maps (3 num_classes + 1), each part rounded
+ * up to 256.  It does not grow with n.  0 for arguments out of range. */
+size_t bn_gp_workspace_bytes(int32_t num_maps, int64_t cells, int32_t num_classes);
+/* mean and std of num_maps maps of `cells` cells each on `stream`, two launches, no synchronisation: regressors is a HOST table
+ * of num_classes (<= 32) handles of device_id, NULL where a class has none; slopes (num_maps, cells) float32 and classes
+ * (num_maps, cells) int32 on the device; mean and std (num_maps, cells) on the device, float32 or (f64_outputs = 1) float64.  A
+ * cell whose class is outside [0, num_classes) or has no regressor gets mean 0 and std 0.  The workspace and the regressors
+ * must stay alive until the stream has run the launches. */
+int bn_gp_predict_async(int32_t device_id, void *stream, bn_gp_t *const *regressors, int32_t num_classes, int32_t num_maps,
+                        int64_t cells, const float *slopes_device, const int32_t *classes_device, void *mean_device,
+                        void *std_device, int32_t f64_outputs, void *workspace_device, size_t workspace_bytes);
+const char *bn_gp_last_error(void);
+
 /* Test hook: the library's device arithmetic (DESIGN.md "Arithmetic spec") applied elementwise to n device floats:
  * fn 0 = correctly rounded sqrt, 1 / 2 = sin / cos of the spec, 3 = heading wrap (theta + pi) % 2pi - pi with
  * torch.remainder semantics (robot_model.py:90), 4 = its in-loop form, 5 = the sqrt for zero / normal finite arguments.  Lets the tests compare the kernels' building
