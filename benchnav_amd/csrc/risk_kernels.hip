@@ -9,6 +9,10 @@
 // order-preserving integer keys.  The two order statistics torch.quantile interpolates between are found by a
 // radix select over the key bits (32 rounds of compare + ballot + popcount: no sort, no LDS, no barrier), the tail
 // mean by one more pass.  Only mean/std in and R out touch HBM (8 B + 4 B per cell instead of 4*num_samples B).
+// VaR equals torch.quantile by value on the same samples: the selection is exact and the interpolation is at::lerp's
+// fused form (explicit __builtin_fmaf below; this file is built with -ffp-contract=off, so nothing else fuses).  The
+// unfused a + w (b - a) that stood here before agreed with the oracle of the time but not with torch.  CVaR differs
+// from the reference's nanmean by summation order only (tests/test_gpu_risk_edges.py derives the bound).
 #include "../../include/benchnav_mppi.h"
 #include "bn_device_math.h"
 #include "bn_host.h"
@@ -102,8 +106,11 @@ __global__ __launch_bounds__(kRiskWaves * 64) void risk_map_kernel(const float *
         }
     }
     const float below = value_of(klo), above = value_of(khi);
-    // at::lerp: |w| < 0.5 ? a + w (b - a) : b - (b - a)(1 - w)
-    const float var = (fabsf(wgt) < 0.5f) ? below + wgt * (above - below) : above - (above - below) * (1.0f - wgt);
+    // at::lerp, FUSED as torch evaluates it (CPU vector path and GPU compilers alike): |w| < 0.5 ? fma(w, b - a, a)
+    // : fma(w - 1, b - a, b).  One rounding of the product-sum; rounding the product first differs by up to 0.5 ulp
+    // in a few cells per map.  Non-finite cells: an all-NaN / all-inf column gives b - a = NaN, hence NaN (as torch).
+    const float dlt = above - below;
+    const float var = (fabsf(wgt) < 0.5f) ? __builtin_fmaf(wgt, dlt, below) : __builtin_fmaf(wgt - 1.0f, dlt, above);
     if (metric == 1) {
         if (lane == 0) out[cell] = var;
         return;

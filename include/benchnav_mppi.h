@@ -495,7 +495,9 @@ int64_t bn_mppi_algorithmic_bytes_window(const bn_mppi_t *h, bn_noise_kind noise
  * TraversabilityModel._infer_risk_map, traversability_model.py:28-51 (runs once per dynamics object, in
  * UnicycleModel.__init__): the (G,G) risk map from the predicted slip distribution Normal(mean, std).
  *   BN_RISK_EXPECTED  mean                                             (:30-31)
- *   BN_RISK_VAR       torch.quantile(samples, confidence, dim=0)       (:33-36), linear interpolation
+ *   BN_RISK_VAR       torch.quantile(samples, confidence, dim=0)       (:33-36), linear interpolation: exact selection of the
+ *                     two ranks and at::lerp's FUSED form (fma(w, b - a, a) for |w| < 0.5, else fma(w - 1, b - a, b)): equal
+ *                     to torch.quantile by value on the same samples.  A NaN or +-inf mean, or a NaN std, gives NaN.
  *   BN_RISK_CVAR      nanmean of the samples strictly above that       (:37-42)
  * samples_i = mean + std * z_i; z = (num_samples, G, G) standard normals supplied by the caller (the
  * reference's Normal.sample stream, for parity) or NULL: generated in the kernel (Philox, keyed by seed).

@@ -23,7 +23,7 @@ def test_oracle_matches_reference_risk_maps():
     for key, metric, q in _keys(fx):
         got = RO.infer_risk_map(fx["mean"], fx["std"], metric, q, fx["z"])
         if metric == "var":
-            assert np.array_equal(got, fx[key]), key                 # selection + lerp: same arithmetic, bit-exact
+            assert np.array_equal(got, fx[key]), key                 # selection + torch's fused lerp (test_risk_oracle_torch.py)
         else:
             assert np.abs(got - fx[key]).max() <= 5e-7, key          # tail mean: summation order only
     assert np.array_equal(RO.infer_risk_map(fx["mean"], fx["std"], "expected_value"), fx["mean"])
