@@ -8,8 +8,13 @@
 // Two launches per call, no host round trip:
 //   gp_bucket_kernel    one workgroup per map sorts the map's cells by class into an index list, with the count, the list offset
 //                       and the first tile of every class; the cells without a regressor get 0 / 0 here.
-//   gp_predict_kernel   one workgroup per tile of 16 cells of one class: the k(x, phi) columns into LDS, then v = L^-1 k on
-//                       v_mfma_f64_16x16x4_f64 over the blocks on and below the diagonal, |v|^2 and k . alpha reduced per column.
+//   gp_predict_kernel   N <= 1024: one workgroup per tile of 16 cells of one class: the k(x, phi) columns into LDS, then
+//                       v = L^-1 k on v_mfma_f64_16x16x4_f64 over the blocks on and below the diagonal, |v|^2 and k . alpha
+//                       reduced per column.
+//   gp_slab_kernel      N > 1024 (up to 10240): one workgroup per four consecutive tiles (64 cells) of one class walks L^-1 in
+//                       slabs of 32 row blocks and regenerates k(x, phi) in chunks of 128 points per slab (the whole k does not
+//                       fit the LDS); every fragment of L^-1 feeds four MFMAs.
+// A call launches the bucketing and whichever of the two predict kernels its regressors need (two or three launches).
 // Every sum runs in an order fixed by N alone: a cell's result does not depend on the tile, column or map it lands in.
 #include <hip/hip_runtime.h>
 
@@ -24,7 +29,8 @@
 namespace bn {
 namespace {
 
-constexpr int kGpMaxPoints = 1024;       // the k tile of 16 cells x 1024 points x 8 bytes is 128 KB of the CU's 160 KB of LDS
+constexpr int kGpSmallMax = 1024;        // gp_predict_kernel: the k tile of 16 cells x 1024 points x 8 bytes is 128 KB of the CU's 160 KB of LDS
+constexpr int kGpMaxPoints = 10240;      // gp_slab_kernel: 640 row blocks, 420 MB of L^-1 fragments
 constexpr int kGpMaxClasses = 32;
 constexpr int kGpTile = 16;              // cells per tile: the N of the MFMA
 constexpr int kGpWaves = 8;
@@ -145,6 +151,7 @@ __global__ __launch_bounds__(kGpThreads) void gp_predict_kernel(GpPredictArgs a)
     const size_t base = (size_t)b * a.cells;
     const int32_t *idx = a.idx + base + meta[a.C + c] + first;
     const GpRegDev *rp = &a.table.r[c];
+    if (rp->npad > kGpSmallMax) return;  // gp_slab_kernel's class
     const double *x = rp->x, *alpha = rp->alpha, *linv = rp->linv;
     const int n = rp->n, npad = rp->npad;
     const double gc = rp->c, gs = rp->s, gq = rp->q, gnoise = rp->noise;
@@ -224,6 +231,167 @@ __global__ __launch_bounds__(kGpThreads) void gp_predict_kernel(GpPredictArgs a)
     }
 }
 
+// ---- N > 1024 ----
+constexpr int kSlabTiles = 4;                             // tiles per workgroup
+constexpr int kSlabCells = kSlabTiles * kGpTile;          // 64 cells: every fragment of L^-1 feeds four MFMAs
+constexpr int kSlabChunkBlocks = 8;                       // k blocks (of 16 points) per chunk
+constexpr int kSlabChunk = kSlabChunkBlocks * kGpTile;    // 128 points: two chunks of 64 cells are 128 KB of LDS
+constexpr int kSlabRb = 4;                                // row blocks per wave and slab: 16 accumulators of 4 doubles, 128 registers
+constexpr int kSlabBlocks = kGpWaves * kSlabRb;           // 32 row blocks (512 rows) per slab
+
+constexpr size_t gp_slab_lds() { return (size_t)2 * kSlabChunk * kSlabCells * sizeof(double); }
+
+// One workgroup per group of four consecutive tiles of a class with more than kGpSmallMax points (the bucket kernel's tile
+// numbering: the workgroup of the group's first tile works, the other three return).  L^-1 is walked in slabs of 32 row blocks;
+// in slab s wave w owns the row blocks 32 s + w + 8 r, r < 4, with four accumulators (one per tile) each.  For every slab the
+// workgroup walks the k chunks from 0 to the slab's last column in ascending order: chunk ch + 1 is generated into one half of
+// the LDS while chunk ch is consumed from the other (waves 0-3 generate first, waves 4-7 consume first, so that the two waves
+// of a SIMD overlap exp and MFMA work), one barrier per chunk.  A row block's accumulator sums over k in ascending order, as in
+// gp_predict_kernel; at the slab's end every lane folds its 64 values into four running sums of |v|^2 (one per tile) in the
+// order row block, register.  k . alpha is accumulated in the last slab alone, which passes over every chunk.
+// LDS: kt[2][tile][128 points][16 cells]; after the last slab the same memory takes sq_part[wave][tile][64] and mean_part[8][64].
+__global__ __launch_bounds__(kGpThreads) void gp_slab_kernel(GpPredictArgs a)
+{
+    extern __shared__ double gp_lds[];
+    const int t = threadIdx.x, b = blockIdx.y, tile = blockIdx.x;
+    const int32_t *meta = a.meta + (size_t)b * gp_meta_stride(a.C);
+    if (tile >= meta[3 * a.C]) return;
+    int c = 0;
+    for (int k = 0; k < a.C; ++k)
+        if (tile >= meta[2 * a.C + k] && tile < meta[2 * a.C + k + 1]) c = k;
+    const int tl = tile - meta[2 * a.C + c];
+    const GpRegDev *rp = &a.table.r[c];
+    if (rp->npad <= kGpSmallMax || (tl & (kSlabTiles - 1))) return;
+    const int first = tl * kGpTile;
+    const int ncell = min(kSlabCells, meta[c] - first);
+    const size_t base = (size_t)b * a.cells;
+    const int32_t *idx = a.idx + base + meta[a.C + c] + first;
+    const double *x = rp->x, *alpha = rp->alpha, *linv = rp->linv;
+    const int n = rp->n, nb = rp->npad / kGpTile;
+    const double gc = rp->c, gs = rp->s, gq = rp->q, gnoise = rp->noise;
+    const int w = __builtin_amdgcn_readfirstlane(t >> 6), l = t & 63;
+    const int nslabs = (nb + kSlabBlocks - 1) / kSlabBlocks;
+
+    // generation: thread (w, l) takes cell l and the points w, w + 8, ... of the chunk
+    const double phi = l < ncell ? (double)a.slopes[base + idx[l]] : 0.0;
+    double *kcol = gp_lds + (size_t)(l >> 4) * kSlabChunk * kGpTile + (l & 15);
+    double msum = 0.0;
+    auto generate = [&](int ch, int half, bool with_mean) {
+        double *dst = kcol + (size_t)half * kSlabChunk * kSlabCells;
+        const int p0 = ch * kSlabChunk;
+#pragma unroll 4
+        for (int m = 0; m < kSlabChunk / kGpWaves; ++m) {
+            const int pl = w + kGpWaves * m, p = p0 + pl;
+            double kv = 0.0;
+            if (p < n) {
+                const double d = phi - x[p];
+                kv = gs * exp((d * d) * gq);
+                if (with_mean) msum = __builtin_fma(kv, alpha[p], msum);
+            }
+            dst[pl * kGpTile] = kv;
+        }
+    };
+
+    double sq[kSlabTiles] = {0.0, 0.0, 0.0, 0.0};
+    for (int s = 0; s < nslabs; ++s) {
+        const bool last = s == nslabs - 1;
+        int iv[kSlabRb];                 // the wave's row blocks, -1 beyond the matrix
+        const double *A[kSlabRb];
+#pragma unroll
+        for (int r = 0; r < kSlabRb; ++r) {
+            const int i = s * kSlabBlocks + w + kGpWaves * r;
+            iv[r] = i < nb ? i : -1;
+            A[r] = linv + (size_t)128 * (i < nb ? i : 0) * ((i < nb ? i : 0) + 1) + l;
+        }
+        const int imin = iv[kSlabRb - 1] < 0 ? -1 : iv[0];       // k blocks 0 ... imin take all four row blocks
+        const int imax = max(max(iv[0], iv[1]), max(iv[2], iv[3]));
+        const int kbend = min((s + 1) * kSlabBlocks, nb);
+        const int nch = (kbend + kSlabChunkBlocks - 1) / kSlabChunkBlocks;
+        f64x4 acc[kSlabRb][kSlabTiles];
+#pragma unroll
+        for (int r = 0; r < kSlabRb; ++r)
+#pragma unroll
+            for (int q = 0; q < kSlabTiles; ++q) acc[r][q] = f64x4{0.0, 0.0, 0.0, 0.0};
+        // the fragments of the next k block are in flight behind the current ones, across chunks too
+        double an[kSlabRb][4];
+#pragma unroll
+        for (int r = 0; r < kSlabRb; ++r)
+#pragma unroll
+            for (int u = 0; u < 4; ++u) an[r][u] = imin >= 0 ? A[r][64 * u] : 0.0;
+
+        generate(0, 0, last);
+        __syncthreads();
+        for (int ch = 0; ch < nch; ++ch) {
+            const bool more = ch + 1 < nch;
+            if (w < kGpWaves / 2 && more) generate(ch + 1, (ch + 1) & 1, last);
+            {
+                const double *kt = gp_lds + (size_t)(ch & 1) * kSlabChunk * kSlabCells + l;
+                const int kb0 = ch * kSlabChunkBlocks, kb1 = min(kb0 + kSlabChunkBlocks, kbend);
+                const int full1 = min(kb1, imin + 1);
+                for (int kb = kb0; kb < full1; ++kb) {
+                    const int kn = min(kb + 1, imin);    // at the last full k block the reload repeats it: the loads stay unconditional
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        double bk[kSlabTiles];
+#pragma unroll
+                        for (int q = 0; q < kSlabTiles; ++q) bk[q] = kt[q * kSlabChunk * kGpTile + 64 * (4 * (kb - kb0) + u)];
+#pragma unroll
+                        for (int r = 0; r < kSlabRb; ++r)
+#pragma unroll
+                            for (int q = 0; q < kSlabTiles; ++q) acc[r][q] = gp_mfma(an[r][u], bk[q], acc[r][q]);
+                        // step u's fragments of the next k block go into the registers that step u has just read: 48 MFMAs ahead
+#pragma unroll
+                        for (int r = 0; r < kSlabRb; ++r) an[r][u] = A[r][64 * (4 * kn + u)];
+                    }
+                }
+                // around the diagonal (and in a last slab with fewer than four row blocks for the wave): row block by row block
+                const int diag1 = min(kb1, imax + 1);
+                for (int kb = max(kb0, imin + 1); kb < diag1; ++kb) {
+#pragma unroll
+                    for (int r = 0; r < kSlabRb; ++r) {
+                        if (kb > iv[r]) continue;
+                        double ac[4];
+#pragma unroll
+                        for (int u = 0; u < 4; ++u) ac[u] = A[r][64 * (4 * kb + u)];
+#pragma unroll
+                        for (int u = 0; u < 4; ++u)
+#pragma unroll
+                            for (int q = 0; q < kSlabTiles; ++q)
+                                acc[r][q] = gp_mfma(ac[u], kt[q * kSlabChunk * kGpTile + 64 * (4 * (kb - kb0) + u)], acc[r][q]);
+                    }
+                }
+            }
+            if (w >= kGpWaves / 2 && more) generate(ch + 1, (ch + 1) & 1, last);
+            __syncthreads();
+        }
+#pragma unroll
+        for (int r = 0; r < kSlabRb; ++r)
+#pragma unroll
+            for (int q = 0; q < kSlabTiles; ++q)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) sq[q] = __builtin_fma(acc[r][q][e], acc[r][q][e], sq[q]);
+    }
+
+    // every wave is past the last chunk's barrier: the k memory is free
+    double *sq_part = gp_lds, *mean_part = gp_lds + kGpWaves * kSlabTiles * 64;
+#pragma unroll
+    for (int q = 0; q < kSlabTiles; ++q) sq_part[(w * kSlabTiles + q) * 64 + l] = sq[q];
+    mean_part[w * kSlabCells + l] = msum;
+    __syncthreads();
+    if (t < ncell) {
+        const int q = t >> 4, col = t & 15;
+        double tot = 0.0, m = 0.0;
+        for (int k = 0; k < kGpWaves; ++k)
+            for (int g = 0; g < 4; ++g) tot += sq_part[(k * kSlabTiles + q) * 64 + 16 * g + col];
+        for (int g = 0; g < kGpWaves; ++g) m += mean_part[g * kSlabCells + t];
+        const double mean = gc + m;
+        const double sd = sqrt(fmax(gs - tot, 0.0) + gnoise);
+        const size_t o = base + idx[t];
+        if (a.f64) { ((double *)a.mean)[o] = mean; ((double *)a.std)[o] = sd; }
+        else { ((float *)a.mean)[o] = (float)mean; ((float *)a.std)[o] = (float)sd; }
+    }
+}
+
 size_t gp_predict_lds(int npad) { return ((size_t)npad * kGpTile + kGpGroups * kGpTile + kGpThreads) * sizeof(double); }
 
 thread_local std::string g_gp_error;
@@ -268,10 +436,10 @@ int bn_gp_create(int32_t device_id, int32_t n, const double *x, const double *al
     if (!(outputscale > 0.0) || !(lengthscale > 0.0) || !(noise > 0.0)) return gp_fail(BN_ERR_INVALID, "outputscale, lengthscale and noise must be > 0");
     const double q = -1.0 / (2.0 * lengthscale * lengthscale);
     if (!std::isfinite(q) || q == 0.0) return gp_fail(BN_ERR_INVALID, "lengthscale out of range: 1 / (2 l^2) must be finite and non-zero");
-    for (int i = 0; i < n; ++i) {
+    for (size_t i = 0; i < (size_t)n; ++i) {
         if (!std::isfinite(x[i]) || !std::isfinite(alpha[i])) return gp_fail(BN_ERR_INVALID, "x and alpha must be finite");
-        for (int j = 0; j <= i; ++j)
-            if (!std::isfinite(linv[(size_t)i * n + j])) return gp_fail(BN_ERR_INVALID, "the lower triangle of linv must be finite");
+        for (size_t j = 0; j <= i; ++j)
+            if (!std::isfinite(linv[i * (size_t)n + j])) return gp_fail(BN_ERR_INVALID, "the lower triangle of linv must be finite");
     }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return gp_fail(BN_ERR_NO_DEVICE, "no HIP device visible: no CPU fallback");
@@ -344,13 +512,15 @@ int bn_gp_predict_async(int32_t device_id, void *stream, bn_gp_t *const *regress
         return gp_fail(BN_ERR_INVALID, "workspace smaller than bn_gp_workspace_bytes(num_maps, cells, num_classes)");
     bn::GpPredictArgs p{};
     uint32_t present = 0;
-    int npad_max = 0;
+    int npad_small = 0;
+    bool large = false;
     for (int c = 0; c < num_classes; ++c) {
         const bn_gp_t *r = regressors[c];
         if (!r) continue;
         if (r->device != device_id) return gp_fail(BN_ERR_INVALID, "regressor " + std::to_string(c) + " lives on another device");
         present |= 1u << c;
-        npad_max = r->npad > npad_max ? r->npad : npad_max;
+        if (r->npad > bn::kGpSmallMax) large = true;
+        else npad_small = r->npad > npad_small ? r->npad : npad_small;
         bn::GpRegDev &d = p.table.r[c];
         d.x = r->x; d.alpha = r->alpha; d.linv = r->linv; d.n = r->n; d.npad = r->npad;
         d.c = r->c; d.s = r->s; d.q = -1.0 / (2.0 * r->l * r->l); d.noise = r->noise;
@@ -371,12 +541,21 @@ int bn_gp_predict_async(int32_t device_id, void *stream, bn_gp_t *const *regress
     if (!present) return BN_OK;
     p.slopes = slopes_device; p.idx = idx; p.meta = meta; p.mean = mean_device; p.std = std_device;
     p.cells = (int32_t)cells; p.C = num_classes; p.f64 = f64_outputs;
-    const size_t lds = bn::gp_predict_lds(npad_max);
-    GP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(bn::gp_predict_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    // every class of a map ends in at most one partial tile
+    // every class of a map ends in at most one partial tile; both kernels run over the same tile numbering and each leaves the
+    // other's classes alone
     const unsigned tiles = (unsigned)((cells + bn::kGpTile - 1) / bn::kGpTile) + (unsigned)num_classes;
-    bn::gp_predict_kernel<<<dim3(tiles, (unsigned)num_maps), bn::kGpThreads, lds, s>>>(p);
-    GP_HIP(hipGetLastError());
+    if (npad_small) {
+        const size_t lds = bn::gp_predict_lds(npad_small);       // sized by the largest class of this kernel
+        GP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(bn::gp_predict_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        bn::gp_predict_kernel<<<dim3(tiles, (unsigned)num_maps), bn::kGpThreads, lds, s>>>(p);
+        GP_HIP(hipGetLastError());
+    }
+    if (large) {
+        const size_t lds = bn::gp_slab_lds();
+        GP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(bn::gp_slab_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        bn::gp_slab_kernel<<<dim3(tiles, (unsigned)num_maps), bn::kGpThreads, lds, s>>>(p);
+        GP_HIP(hipGetLastError());
+    }
     return BN_OK;
 }
 

@@ -8,7 +8,10 @@ from its equations -- gpytorch is not imported:
     k(a, b) = s exp(-(a - b)^2 / (2 l^2)),   K = k(x, x) + noise I = L L^T,   alpha = K^-1 (y - c)
     mean(phi) = c + k(phi, x) . alpha,       v = L^-1 k(x, phi),              std(phi) = sqrt(max(s - |v|^2, 0) + noise)
 
-The host factorises once per regressor in float64 (NumPy); the device evaluates every cell in float64 and rounds the outputs.
+The host factorises once per regressor in float64 (NumPy; above 1024 points the explicit L^-1 comes from torch's triangular
+solve); the device evaluates every cell in float64 and rounds the outputs.  Up to MAX_POINTS = 10240 training points per class
+(the reference's trainer keeps up to 9999, regressor_trainer.py:91-124): regressors of up to 1024 points run on a kernel that
+holds k(x, phi) in LDS, larger ones on one that regenerates it slab by slab.
 The UNet terrain classifier is out of scope: any object with `.predict(colors[None]) -> classes` serves, or pass the class maps.
 """
 from __future__ import annotations
@@ -24,7 +27,8 @@ from torch.distributions import Normal
 from . import _capi
 from ._device import stream_ptr
 
-MAX_POINTS = 1024           # bn_gp_max_points(): the k(x, phi) tile of 16 cells x 1024 points fills 128 KB of LDS
+MAX_POINTS = 10240          # bn_gp_max_points(): 640 row blocks of 16; L^-1 is 420 MB on the device at this size
+_NUMPY_SOLVE_MAX = 1024     # up to here L^-1 comes from np.linalg.solve(L, I), as it always has; above, from a triangular solve
 MAX_CLASSES = 32
 _NOISE_LOWER_BOUND = 1e-4   # GaussianLikelihood's default GreaterThan(1e-4) on the noise
 
@@ -64,7 +68,8 @@ def factorize(train_x, train_y, constant: float, outputscale: float, lengthscale
     alpha = K^-1 (y - constant), L^-1 explicit and lower triangular.
 
     No jitter is added (gpytorch retries a failed Cholesky with 1e-6 ... 1e-4 on the diagonal; here a matrix that is not
-    numerically positive definite raises ValueError).  1 <= N <= MAX_POINTS, else ValueError."""
+    numerically positive definite raises ValueError).  1 <= N <= MAX_POINTS, else ValueError (raised before K is built: K and
+    L^-1 take 8 N^2 bytes each, 0.8 GB at N = 9999)."""
     x, y = _vector(train_x, "train_x"), _vector(train_y, "train_y")
     n = x.shape[0]
     if y.shape[0] != n:
@@ -76,12 +81,28 @@ def factorize(train_x, train_y, constant: float, outputscale: float, lengthscale
     if not (s > 0.0 and l > 0.0 and nz > 0.0):
         raise ValueError("outputscale, lengthscale and noise must be > 0")
     d = x[:, None] - x[None, :]
-    K = s * np.exp(-(d * d) / (2.0 * l * l)) + nz * np.eye(n)
+    if n <= _NUMPY_SOLVE_MAX:
+        K = s * np.exp(-(d * d) / (2.0 * l * l)) + nz * np.eye(n)
+    else:                                                # the same values, built in place: one N x N array instead of four
+        np.multiply(d, d, out=d)
+        np.negative(d, out=d)
+        np.divide(d, 2.0 * l * l, out=d)
+        np.exp(d, out=d)
+        np.multiply(d, s, out=d)
+        d[np.diag_indices(n)] += nz
+        K = d
+    del d
     try:
         L = np.linalg.cholesky(K)
     except np.linalg.LinAlgError as e:
         raise ValueError(f"k(x, x) + noise I is not numerically positive definite (no jitter is added): {e}") from None
-    linv = np.tril(np.linalg.solve(L, np.eye(n)))
+    del K
+    if n <= _NUMPY_SOLVE_MAX:
+        linv = np.tril(np.linalg.solve(L, np.eye(n)))
+    else:                                                # N^3 / 3 instead of a general solve's LU of L
+        linv = torch.linalg.solve_triangular(torch.from_numpy(L), torch.eye(n, dtype=torch.float64), upper=False).numpy()
+        del L
+        linv = np.tril(linv)
     alpha = linv.T @ (linv @ (y - c))
     if not (np.isfinite(linv).all() and np.isfinite(alpha).all()):
         raise ValueError("the factorisation of k(x, x) + noise I overflowed")
@@ -227,7 +248,8 @@ class TraversabilityPredictor:
 
     def predict_maps(self, slopes: torch.Tensor, t_classes: Optional[torch.Tensor] = None, colors: Optional[torch.Tensor] = None,
                      dtype=torch.float32) -> Tuple[torch.Tensor, torch.Tensor]:
-        """(mean, std) of slopes' shape, (G, G) or (B, G, G), in one launch pair.  t_classes of the same shape skips the
+        """(mean, std) of slopes' shape, (G, G) or (B, G, G), in one call of two or three launches (the bucketing, then one
+        predict kernel for the regressors of up to 1024 points and one for the larger ones) without a host round trip.  t_classes of the same shape skips the
         classifier; otherwise colors (3, G, G) or (B, 3, G, G) goes through it map by map."""
         if slopes.dim() not in (2, 3):
             raise ValueError(f"slopes must be (G, G) or (B, G, G), got {tuple(slopes.shape)}")

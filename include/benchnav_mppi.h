@@ -886,7 +886,9 @@ int bn_clrrt_loop_set_plans(bn_mppi_t *h, bn_clrrt_t *c, const float *actions, c
  * Errors: the gp error string below.
  * ---------------------------------------------------------------------------------------------------------------------------- */
 typedef struct bn_gp bn_gp_t;
-/* The largest n bn_gp_create takes (1024: the k(x, phi) tile of 16 cells lives in LDS). */
+/* The largest n bn_gp_create takes: 10240 (640 row blocks of 16; L^-1 is 420 MB on the device at that size).  Regressors of up to
+ * 1024 points keep the k(x, phi) tile of 16 cells in LDS; larger ones run on a second kernel that walks L^-1 in slabs of 512 rows
+ * and regenerates k(x, phi) per slab, 64 cells per workgroup.  bn_gp_predict_async picks per class; both may serve one call. */
 int32_t bn_gp_max_points(void);
 /* One regressor on device_id from HOST arrays: x (n), alpha (n), linv (n, n) row-major of which the lower triangle is read.
  * Checked before the device is touched: 1 <= n <= bn_gp_max_points(), every value finite, outputscale, lengthscale and
