@@ -1,4 +1,4 @@
-// astar_dwa.h -- launch interface of the fused A* + DWA episode (astar_dwa.hip) for the C ABI (mppi_capi.cpp).
+// astar_dwa.h -- launch interface of the fused A* + DWA episode (astar_dwa.hip) for the C ABI (mppi_loops.cpp).
 #pragma once
 #include "astar_view.h"
 #include "mppi_kernels.h"

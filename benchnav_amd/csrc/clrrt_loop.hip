@@ -1,6 +1,6 @@
 // clrrt_loop.hip -- the follow half of the reference's CL-RRT driver loop (test/test_cl_rrt.py:167-200) on the device, for B rovers
 // (DESIGN.md 4.8).  The planning half is the CL-RRT handle's own kernels (clrrt_kernels.hip) run under a mask; the host only looks
-// at one counter between a round of replans and the next follow launch (bn_clrrt_loop_run, mppi_capi.cpp).
+// at one counter between a round of replans and the next follow launch (bn_clrrt_loop_run, mppi_loops.cpp).
 //
 // clrrt_follow_kernel<GEO>: one workgroup of 256 threads per rover.  It runs the rover's loop iterations from the rover's own
 // counter to the end of the call and stops early where the rover needs a plan: it then writes the rover's state into the planner's

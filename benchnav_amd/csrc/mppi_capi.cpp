@@ -1,13 +1,14 @@
-// mppi_capi.cpp -- host side of the C ABI declared in include/benchnav_mppi.h.
+// mppi_capi.cpp -- host side of the C ABI declared in include/benchnav_mppi.h: the core.
 //
-// Owns the device buffers of one planner handle and enqueues the two kernels of
+// Owns the device buffers of one planner handle (mppi_handle.h) and enqueues the two kernels of
 // a solve (mppi_kernels.hip) on the handle's HIP stream.  No torch types, no CPU
 // fallback: creation fails without a gfx950 device.
-#include "../../include/benchnav_mppi.h"
-#include "mppi_kernels.h"
-#include "bn_host.h"
-#include "astar_dwa.h"
-#include "clrrt_view.h"
+//
+// Here: the error string, the kernel choice, the per-device overlap ownership, the journal and the recovery of expired waits,
+// create / destroy / setters, and everything a solve executes (solve_impl, bn_mppi_solve_n_async).  The other concerns have a
+// file each: mppi_paced.cpp (host-paced loop, forward), mppi_shard.cpp (K-shard exchange), mppi_env.cpp (closed-loop
+// environment, DWA), mppi_loops.cpp (A*+DWA and CL-RRT loops), mppi_query.cpp (getters, profiling, lab hooks).
+#include "mppi_handle.h"
 
 #include <algorithm>
 #include <atomic>
@@ -22,26 +23,21 @@
 #include <fcntl.h>
 #include <sys/file.h>
 #include <unistd.h>
-#include <dlfcn.h>
-#include <hsa/hsa.h>        // types only (as RCCL below): the HSA runtime HIP itself runs on is looked up at run time, and only by a host-paced handle
-#include <hsa/hsa_ext_amd.h>
-#include <rccl/rccl.h>      // types only: the library itself is opened at run time (rccl_api), and only by a K-sharded solve
 #include <map>
 #include <mutex>
-#include <numeric>
 #include <string>
 #include <vector>
 
-namespace {
+namespace bn {
+namespace host {
 
-constexpr int kProfGroup = 10;
 // Role kernel or one-wave throughput kernel for a many-instance launch?  Both give bit-identical results; which one is faster
 // depends on the horizon (the role kernel's skeleton -- prologue, barriers, epilogue -- is a fixed cost per workgroup, the one-wave
 // kernel pays per step), on the workgroups per instance (both re-merge nblk rows per workgroup) and on how full the chip gets.
 // A two-term estimate of either kernel's time per launch, fitted to tools/auto_sweep.py (K 128..2048, T 10..100, 16..300
 // instances, overlapped launches): it picks the faster kernel or one within 10 % of it in 51 of 52 cells (worst: 28 %), where a
 // fixed workgroup-count threshold lost 14-60 % in seven.  K=1024, T=50: crossover between 64 and 128 instances as measured.
-bool wave_kernel_is_faster(const bn::SolveParams &p, size_t resident_role_wgs, int n_cus)
+static bool wave_kernel_is_faster(const bn::SolveParams &p, size_t resident_role_wgs, int n_cus)
 {
     const double W = (double)p.B * (p.nblk + 1), R = (double)std::max<size_t>(resident_role_wgs, 1), rows = std::max(0, p.nblk - 16);
     const double role = (4.5 + 0.19 * p.T + 0.3 * rows) * (1.0 + 0.175 * std::min(W, R) / std::max(n_cus, 1)) * std::max(1.0, W / R);
@@ -52,15 +48,7 @@ bool wave_kernel_is_faster(const bn::SolveParams &p, size_t resident_role_wgs, i
     const double wave = gain * (3.3 + 0.44 * p.T + 0.37 * rows) * (1.0 + 1.5 * W / (24.0 * std::max(n_cus, 1)));
     return wave < role;
 }
-thread_local std::string g_last_error;
-
-// Experiment switches (environment variables read by the measurement tools under tools/): compiled in only with -DBN_EXPERIMENTS
-// (tools/build_variant*.py pass it); the shipped library has none in its entry points.
-#ifdef BN_EXPERIMENTS
-inline const char *exp_env(const char *name) { return std::getenv(name); }
-#else
-inline const char *exp_env(const char *) { return nullptr; }
-#endif
+static thread_local std::string g_last_error;
 
 int fail(int code, const char *fmt, ...)
 {
@@ -73,17 +61,7 @@ int fail(int code, const char *fmt, ...)
     return code;
 }
 
-#define BN_HIP(expr)                                                                         \
-    do {                                                                                     \
-        hipError_t e_ = (expr);                                                              \
-        if (e_ != hipSuccess) {                                                              \
-            (void)hipGetLastError();   /* reported here: do not leave it for the next HIP user of the process (torch) */ \
-            return fail(BN_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_),  \
-                        __FILE__, __LINE__);                                                 \
-        }                                                                                    \
-    } while (0)
-
-bool is_pow2_float(float v)
+static bool is_pow2_float(float v)
 {
     int ex;
     return v > 0.0f && std::isfinite(v) && std::frexp(v, &ex) == 0.5f;
@@ -94,7 +72,7 @@ bool is_pow2_float(float v)
 // (8 handles x 8 instances: seen).  A handle overlaps only while no OTHER handle's overlapped batch is still in flight on its
 // device (its streams still busy); otherwise this batch runs in one stream, which is always safe.
 std::mutex g_overlap_mu;
-std::map<int, bn_mppi *> g_overlap_owner;   // device -> the handle whose overlapped batch was enqueued last
+static std::map<int, bn_mppi *> g_overlap_owner;   // device -> the handle whose overlapped batch was enqueued last
 // ... and nothing ELSE of this process beside it (round 4).  The rule above kept two overlapped batches apart; a differential sweep
 // over pairs of planners (tools/fuzz_features2.py) still saw waits expire: one planner's overlapped batch of latency-kernel
 // launches -- one workgroup per CU, sized for a device it has to itself -- with the other planner's ordinary one-stream launches
@@ -103,14 +81,14 @@ std::map<int, bn_mppi *> g_overlap_owner;   // device -> the handle whose overla
 // overlapped batch is in flight is ordered behind that batch's end by events (order_behind_foreign_overlap): no host blocking,
 // the kernels simply do not share the device with waiting workgroups.
 std::map<int, std::vector<bn_mppi *>> g_handles;   // device -> live handles (guarded by g_overlap_mu)
-std::atomic<int> g_overlap_owners{0};              // devices with an owner: the launch path looks at it without the lock
+static std::atomic<int> g_overlap_owners{0};              // devices with an owner: the launch path looks at it without the lock
 // ... and one PROCESS per device for launches big enough to crowd each other out: two processes with overlapped 64-instance batches
 // on one GPU both ran into expired waits within a second.  An advisory lock on a per-device file in /tmp, taken (non-blocking) by
 // the first process that overlaps big launches there and held until it exits; a process that does not get it runs those batches
 // on one stream and asks again at its next batch.
-std::map<int, int> g_overlap_lock_fd;       // device -> fd holding the lock (-1: not held)
+static std::map<int, int> g_overlap_lock_fd;       // device -> fd holding the lock (-1: not held)
 
-bool own_device_for_big_overlap(int device)
+static bool own_device_for_big_overlap(int device)
 {
     auto it = g_overlap_lock_fd.find(device);
     if (it != g_overlap_lock_fd.end() && it->second >= 0) return true;
@@ -128,204 +106,6 @@ bool own_device_for_big_overlap(int device)
     g_overlap_lock_fd[device] = fd;
     return true;
 }
-
-// Up to this many workgroups per instance every rollout workgroup re-merges the previous solve's partials itself (pipelined mode:
-// no merge launch, no ticket round trips); above, the last workgroup of a launch merges (ticket mode).  64 = what the few-rows
-// merge takes in one wave; measured at K=4096: 17.1 us per solve pipelined against 21.2 with the ticket merge (tools/k_sweep.py).
-constexpr int kPipelinedMaxBlocks = 64;
-constexpr int kEagerTailMinBatch = 16;    // overlapped batches of at least this many solves end with their own tail kernel
-constexpr int kMaxStreams = 3;            // launches of one overlapped batch in flight at most
-constexpr int kSlots = kMaxStreams + 1;   // per-solve buffer slots (see bn_mppi::d_cost)
-
-}  // namespace
-
-struct bn_mppi {
-    bn_mppi_config cfg{};
-    bn::SolveParams p{};
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    int n_maps = 1;
-    uint64_t solves = 0;
-    bool map_set = false, goal_set = false;
-    uint64_t map_epoch = 0, map_epoch_at_solve = 0;   // set_map calls so far / at the latest solve: a re-roll needs the map that solve saw
-    // Pipelined mode (K <= 2048): one launch per solve.  The launch of solve i merges solve i-1's
-    // per-block statistics in every rollout workgroup (warm start) and carries an aux workgroup that
-    // writes solve i-1's tail (U*, X*, weights).  `tail_pending` = the latest solve's tail has not been
-    // written yet; flush() launches the finish kernel for it.
-    bool pipelined = false;
-    bool slow_path = false;          // rollout_wave_kernel + stand-alone tail, two launches per solve: horizons beyond the role kernels' LDS, or the reference-order
-                                     // arithmetic together with sampled slip (the reference order by itself runs on every kernel family, one launch per solve)
-    bool tail_pending = false;
-    // device buffers
-    float *d_map = nullptr, *d_state = nullptr, *d_goal = nullptr, *d_mean = nullptr, *d_eps = nullptr;
-    float *d_X = nullptr, *d_U = nullptr, *d_w = nullptr, *d_cost_out = nullptr;
-    // per-solve buffers rotate over kSlots slots (solve i uses slot i % kSlots): with S launches in flight (see bn_mppi_solve_n_async)
-    // solve i+S may start while solve i+1 -- its merge, its aux workgroup -- still reads solve i's slot: S + 1 slots are enough
-    float *d_cost[kSlots] = {}, *d_part[kSlots] = {}, *d_state_copy[kSlots] = {};
-    float *d_ustar = nullptr, *d_xstar = nullptr, *d_stats = nullptr, *d_scratch = nullptr;
-    float *d_mean_used = nullptr;    // the mean the latest finished solve sampled around (re-rolls)
-    int *d_idx = nullptr;
-    const float *last_eps = nullptr; // noise of the latest solve (caller-owned unless BN_NOISE_HOST_KT2) and its layout
-    bn::EpsMode last_mode = bn::kEpsPhilox;
-    float *d_slip_std = nullptr;     // sampled-slip mode
-    float *d_ustar2[kSlots] = {}, *d_stats2[kSlots] = {};   // ticket-merge outputs, one per slot like the other per-solve buffers (overlapped: S + 1 needed)
-    bool ticket_overlap = false;     // ticket path (deterministic kernel, K > 4096): consecutive launches of a batch overlap too (round 3)
-    std::vector<float> dwa_stage;    // host staging of bn_mppi_dwa_solve's upload
-    int *d_ticket = nullptr;
-    float *d_gpart = nullptr;
-    int n_cus = 256;
-    size_t resident_wgs = 1024;      // role-kernel workgroups the device holds at once (LDS- and wave-limited) x CUs
-    // overlapped launches: consecutive solves of one bn_mppi_solve_n_async call go round the handle's stream and n_streams - 1
-    // extra ones; device counters carry the dependency (SolveParams.flag_part / flag_tail)
-    int n_streams = 1;
-    hipStream_t xstream[kMaxStreams - 1] = {};
-    std::vector<hipStream_t> parked;            // streams that turned out to share the handle's hardware queue (see bn_mppi_create)
-    hipEvent_t ev_fork = nullptr, ev_join[kMaxStreams - 1] = {};
-    hipEvent_t ev_guard[kMaxStreams] = {};      // recorded on this handle's streams BY another handle that must run behind this one's overlapped batch
-    unsigned long long *d_flags = nullptr;      // [kSlots][B] flag_part per slot and instance, [B] flag_tail per instance, then int err
-    bool role_overlap = false;                  // the role kernel's launches of a batch may overlap too (see bn_mppi_solve_n_async)
-    unsigned long long *d_gran[kSlots] = {};   // granule copies of the partial rows per slot (K <= 1024, 2T <= 320)
-    // Second trajectory / control buffers for overlapped batches.  Two launches in flight must not write the same addresses: whose
-    // dirty L2 lines reach memory last is decided by which KERNEL ends last, and a straggling aux workgroup can make the earlier
-    // solve's kernel the later one to end (seen once per cold start: X / U of the last solve partly overwritten by its
-    // predecessor's).  Solves of a batch go round n_streams buffers such that the LAST one writes the exposed buffer.
-    float *d_Xalt[kMaxStreams - 1] = {}, *d_Ualt[kMaxStreams - 1] = {};
-    unsigned long long pub[kSlots] = {};     // host mirror: what flag_part[slot][b] reaches once every launch issued so far has published
-    unsigned long long tails = 0;               // host mirror of flag_tail[b]
-    bool prev_published = false;                // the latest solve counted itself into flag_part (latency kernel): its successor may overlap
-    bool overlap_used = false;                  // a wait could have expired since the last check of the error word
-    bool overlap_off = false;                   // a wait DID expire once: this handle keeps to one stream from then on
-    // The error word of the bounded device-side waits: pinned host memory the kernels write with a system-scope store, so every
-    // entry point can look at it for free.  Journal: the batches enqueued since the word was last found clean at a
-    // synchronisation point, with the mean the first of them started from (kept by that launch itself, SolveParams::mean_snap)
-    // and the solve counter (= Philox position) at that point -- what recover_overlap() needs to run them again on one stream.
-    int *h_err = nullptr, *d_err = nullptr;     // host address / device address of the same word
-    unsigned long long *h_mail = nullptr, *d_mail = nullptr;   // (B, 2) granules {U*[0][d], solve index + 1}: see bn_mppi_first_action
-    float *d_mean_snap = nullptr;
-    float *d_state_snaps = nullptr;             // [snap_cap][B][3]: the states every journalled batch started from, kept by its first launch
-    size_t snap_cap = 0;                        // (SolveParams::state_snap): a re-run reads these, not the caller's buffer
-    size_t snap_slot = 0;                       // slot of the batch being enqueued
-    bool arm_state_snap = false;                // the next launch fills it
-    struct BatchRec { int32_t n; const float *states; const float *eps; bn_noise_kind noise; int32_t eps_ring; int64_t eps_stride; bool episode; const float *z; };
-    std::vector<BatchRec> journal;
-    bool journal_lost = false;                  // something not replayable happened since the last clean check (or too many batches)
-    bool arm_snap = false;                      // the next launch keeps its mean in d_mean_snap
-    bool replaying = false, last_batch_overlapped = false;
-    uint64_t journal_solves0 = 0, recoveries = 0;
-    // Self-protecting overlap (round 6).  Overlapped launches assume the device to themselves: with a co-tenant process on the GPU the
-    // workgroups that wait for their predecessor hold slots the predecessor's stragglers need, and the chain runs at HALF the
-    // one-stream rate (46 k against 80 k solves/s).  The handle watches its own cadence -- the first-action mailbox
-    // counts finished solves, the host clock does the rest: no event, no kernel change -- over windows of 64 launches that found the
-    // device backlogged at both ends, looks at the other mode once, and runs whichever is faster; it looks again when its cadence
-    // degrades by half, and every 256 windows while it runs on one stream (has the co-tenant left?).
-    struct OvTune { double best[2] = {0, 0}, last[2] = {0, 0}, ema[2] = {0, 0}; int chosen = 0, explore = 0, slow_run = 0; uint64_t windows[2] = {0, 0}, since_explore = 0, switches = 0; } tune;
-    struct OvSample { bool valid = false; std::chrono::steady_clock::time_point t{}; uint32_t prog = 0, enq = 0; } ov_sample;
-    int run_mode = 0;                // the mode of the batch being enqueued (0 overlapped, 1 one stream)
-    // One launch per SYNCHRONOUS solve (round 6; bn_mppi_forward_async, bn_mppi_forward_state_async, bn_mppi_solve on the latency kernel):
-    // the solve's own tail rides in its launch as a second aux workgroup (SolveParams::self_tail) -- no stand-alone finish kernel.
-    float *self_out_copy = nullptr;  // the caller's U* | X* block of the forward() being enqueued (consumed by solve_impl)
-    const float *inline_state = nullptr;   // host pointer: the state of the forward() being enqueued travels in the kernel arguments
-    bool self_tail_launched = false; // the latest solve_impl call took the one-launch path (its tail is NOT pending)
-    bool self_used = false;          // a self tail's bounded wait could have expired since the error word was last looked at
-    bool self_off = false;           // ... and one did: two launches per synchronous solve from then on
-    // Host-paced loop (BN_FLAG_HOST_PACED, round 6): bn_mppi_forward_state_async enqueues the NEXT solve's launch one control step ahead,
-    // on one of two private streams; that launch waits on the device for the state the next call posts (rollout_lat.inc, HOSTP).
-    bool hp_enabled = false;
-    hipStream_t hp_stream[2] = {};   // [0] = xstream[0], [1] = xstream[1] (created for this mode); the launches alternate
-    hipEvent_t hp_ev[2] = {};        // recorded behind every prelaunch; the handle's stream waits for it when the request is posted
-    bool hp_unordered = false;       // BN_FLAG_UNORDERED_OUTPUTS: the handle's stream has not been ordered behind the latest posted solve yet ...
-    int hp_unordered_q = 0;          // ... whose launch is the latest one on this private stream (see hp_order_now)
-    unsigned long long *h_req = nullptr, *d_req = nullptr;         // pinned: kSlots x 8 request granules, then 16 status words (acknowledgements, "gave up" per slot)
-    unsigned long long *req_bar = nullptr;                         // the request granules in DEVICE memory the host writes through the BAR (bar_alloc), or null
-    unsigned long long *d_req_dev = nullptr;                       // device: kSlots x 8, republished by the launches' tail workgroups
-    uint32_t hp_seq = 0;             // request tags, unique per prelaunch
-    bool hp_armed = false;           // a prelaunched solve waits for its state
-    uint32_t hp_tag = 0;             // ... its tag, request slot, stream index, trajectory buffer
-    int hp_slot = 0, hp_q = 0, hp_xidx = 0;
-    uint32_t hp_posted_tag = 0;      // the latest request posted (bn_mppi_first_action watches the give-up word for it)
-    float hp_posted_state[3] = {};
-    float *hp_posted_out = nullptr;
-    bool hp_skip_check = false;      // test hook: post without looking whether the launch has given up (exercises the repair in bn_mppi_first_action)
-    int hp_redo_q = -1;              // hp_redo: the private stream its solve runs on (the one the cancelled successor is not on), or -1
-    float hp_prev_state[3] = {};     // the state of the latest forward (the next launch's speculative window is staged around it)
-    bool hp_gran_valid = false;      // the latest solve published its partial rows as granules and nothing has touched the mean since
-    int hp_extra = 2;                // cells the speculative window is wider on each side
-    int x_idx = 0;                   // which trajectory / control buffer holds the latest solve (bn_mppi_states_buffer_index)
-    int hp_next_q = 0;
-    std::chrono::steady_clock::time_point hp_armed_at{};      // when the waiting launch was enqueued (a request is posted only well within its patience)
-    int hp_polls = 25000;            // how long a prelaunched solve waits for its state: looks of ~2 us each (~50 ms); bn_mppi_debug_host_paced
-    bool lat_kernel = false;         // plain pipelined solves of a launch that leaves every workgroup a CU: rollout_lat_kernel
-    bool wave_kernel = false;        // plain pipelined solves use rollout_wave_kernel (episodes keep the role kernel)
-    bool shard_pending = false;      // K-sharded solve: rollouts launched, tail waits for the partials of the other shards
-    void *shard_comm = nullptr;      // ncclComm_t of bn_mppi_shard_comm_init: the exchange is enqueued by the library on the handle's stream
-    int shard_world = 0, shard_rank = 0;
-    bool shard_prepared = false;     // bn_mppi_shard_comm_prepare has run: buffers, events, side stream exist; the communicator may not yet
-    bool shard_inplace = false;               // set around the rollouts of bn_mppi_shard_solve_async
-    float *d_gathered = nullptr;     // (shard_world x nblk, 2 + 2T): every shard's partial rows, rank order
-    float *d_shard_merged = nullptr; // kSlots x [U* (2T) then (max z, sum e)]: what the merge kernel hands to the tail on the side stream
-    hipStream_t shard_side = nullptr;         // the tail of a library-enqueued sharded solve runs here, beside the next solve's rollouts
-    bool shard_side_own = false;
-    hipEvent_t ev_shard_merge = nullptr, ev_shard_tail[kSlots] = {};      // tail events by solve slot (see bn_mppi_shard_solve_async)
-    int shard_tail_slot = 0;                  // slot of the latest tail
-    bool shard_tail_inflight = false;         // the handle's stream has not been ordered behind the latest side-stream tail yet
-    bool ticket_mode = false;        // one launch per solve: ticket merge by the last workgroup + the previous tail as aux
-                                     // workgroup (sampled-slip kernel; deterministic kernel at K > 2048)
-    bool slip_std_set = false;
-    // device-side closed loop (bn_mppi_env_attach / bn_mppi_episode_async)
-    float *d_lat_mean = nullptr, *d_lat_std = nullptr, *d_ep_states = nullptr, *d_ep_reward = nullptr, *d_env_state = nullptr;
-    float *d_ep_action = nullptr;
-    int *d_ep_done = nullptr;
-    bool env_attached = false;
-    int ep_steps = 0;            // capacity of the episode log
-    int ep_len = 0;              // steps enqueued in the current episode
-    const float *ep_z = nullptr; // (n_steps, B) device slip draws of the current episode, or nullptr
-    bool in_episode = false;
-    // fused A* + DWA episode (bn_astar_dwa_episode_async)
-    int32_t *d_ad_i = nullptr;   // (B) root cell | (B) status | (B) status step | (B) done step | error word
-    float *d_ad_state = nullptr; // (B, 3) the environment states the episode advances
-    float *d_ad_log = nullptr;   // (n+1, B, 3) states | (n, B) rewards | (n, B, 2) actions | (n, B, 2) sub-goals
-    int ad_cap = 0, ad_len = 0;  // steps the log holds / the latest call ran
-    uint64_t ad_step = 0;        // episode steps since bn_astar_dwa_reset
-    int ad_walk = 0;             // bn_astar_dwa_set_walk: 0 the serial next-hop walk, 1 the A* handle's jump tables
-    // CL-RRT plan-follow-replan loop (bn_clrrt_loop_run)
-    bn::ClrrtRover *d_cl_rover = nullptr;   // (B)
-    int32_t *d_cl_flags = nullptr;          // (B) the replan mask | the pending counter
-    float *d_cl_goal = nullptr;             // (B, 3) goal nodes
-    float *d_cl_log = nullptr;              // (cap+1, B, 3) states | (cap, B) rewards | (cap, B, 2) actions | (cap, B) deviations | plan index | events
-    int32_t *h_cl_pending = nullptr;        // pinned: the pending counter of the latest round
-    hipEvent_t cl_ev[2] = {};               // around a follow launch (follow_ms)
-    int cl_cap = 0, cl_len = 0;             // iterations the log holds / the latest call ran
-    int32_t cl_iter = 0, cl_limit_steps = 0;   // iterations since the reset; the step count at which elapsed > time_limit
-    bool cl_ready = false;                  // bn_clrrt_loop_reset has run
-    bn_clrrt_t *cl_planner = nullptr;       // ... with this CL-RRT handle: the episode's goals, streams and paths live in it
-    size_t scratch_bytes = 0, eps_bytes = 0, idx_count = 0;
-    float *h_pinned = nullptr;   // pinned staging for (B,3) states
-    // profiling
-    std::vector<hipEvent_t> ev;  // two-launch mode: 3 events per solve (start, after rollout, after finish);
-    size_t ev_used = 0;          // pipelined mode: one event at the start of every group of kProfGroup launches
-    int prof_in_group = 0;
-};
-
-namespace {
-
-// Every entry point works on the handle's device and leaves the calling thread's current device as it found it
-// (one process may drive several GPUs; torch tracks its own notion of the current device).
-using bn::DeviceGuard;                      // bn_host.h
-#define BN_BIND_Q(h) DeviceGuard bn_guard_((h)->cfg.device_id); if (!bn_guard_.ok) return fail(BN_ERR_HIP, "hipSetDevice failed")
-
-// BN_FLAG_UNORDERED_OUTPUTS: the host-paced forward left the handle's stream unordered behind the latest posted solve (a stream-wait on a
-// pending event is 3-5 us of host time per control step, for consumers that mostly are not there).  Every entry point that enqueues on the
-// handle's stream or hands out results makes up for it here, once -- everything except the loop's own two calls.
-static inline void hp_order_now(bn_mppi *h)
-{
-    if (!h->hp_unordered) return;
-    h->hp_unordered = false;
-    if (hipStreamWaitEvent(h->stream, h->hp_ev[h->hp_unordered_q], 0) != hipSuccess) {
-        (void)hipGetLastError();
-        (void)hipStreamSynchronize(h->hp_stream[h->hp_unordered_q]);
-    }
-}
-#define BN_BIND(h) BN_BIND_Q(h); hp_order_now(h)
 
 size_t buffer_bytes(const bn_mppi *h, bn_buffer_id id)
 {
@@ -358,139 +138,8 @@ int ensure_scratch(bn_mppi *h, size_t bytes)
     return BN_OK;
 }
 
-int guard_foreign_overlap(bn_mppi *h);      // (defined with order_behind_foreign_overlap)
-
-// ---- host-paced loop: request words the HOST writes straight into device memory ---------------------------------------------------
-// The waiting launch polls its request.  Pinned host memory makes every look a PCIe read round trip (~3 us on this platform: the
-// state was seen ~4 us after the host's store, a quarter of the control step).  Device memory the CPU can write -- a fine-grained VRAM
-// allocation of the HSA runtime HIP itself runs on, opened to the CPU agent: stores go out through the PCIe BAR as posted writes --
-// turns that around: the host's store travels once, the GPU polls its own memory.  No such allocation (no large BAR, an HSA runtime
-// without the entry points, an agent that cannot be matched to the HIP device): the words stay in pinned host memory, as before.
-struct HsaApi {
-    void *lib = nullptr;
-    decltype(&hsa_iterate_agents) iterate_agents = nullptr;
-    decltype(&hsa_agent_get_info) agent_get_info = nullptr;
-    decltype(&hsa_amd_agent_iterate_memory_pools) iterate_pools = nullptr;
-    decltype(&hsa_amd_memory_pool_get_info) pool_get_info = nullptr;
-    decltype(&hsa_amd_memory_pool_allocate) pool_allocate = nullptr;
-    decltype(&hsa_amd_memory_pool_free) pool_free = nullptr;
-    decltype(&hsa_amd_agents_allow_access) allow_access = nullptr;
-};
-const HsaApi *hsa_api()
-{
-    static const HsaApi api = [] {
-        HsaApi a;
-        for (const char *name : {"libhsa-runtime64.so.1", "libhsa-runtime64.so"}) {
-            a.lib = dlopen(name, RTLD_NOW | RTLD_NOLOAD);      // the copy HIP has loaded, or none
-            if (a.lib) break;
-        }
-        if (!a.lib) return a;
-        a.iterate_agents = reinterpret_cast<decltype(a.iterate_agents)>(dlsym(a.lib, "hsa_iterate_agents"));
-        a.agent_get_info = reinterpret_cast<decltype(a.agent_get_info)>(dlsym(a.lib, "hsa_agent_get_info"));
-        a.iterate_pools = reinterpret_cast<decltype(a.iterate_pools)>(dlsym(a.lib, "hsa_amd_agent_iterate_memory_pools"));
-        a.pool_get_info = reinterpret_cast<decltype(a.pool_get_info)>(dlsym(a.lib, "hsa_amd_memory_pool_get_info"));
-        a.pool_allocate = reinterpret_cast<decltype(a.pool_allocate)>(dlsym(a.lib, "hsa_amd_memory_pool_allocate"));
-        a.pool_free = reinterpret_cast<decltype(a.pool_free)>(dlsym(a.lib, "hsa_amd_memory_pool_free"));
-        a.allow_access = reinterpret_cast<decltype(a.allow_access)>(dlsym(a.lib, "hsa_amd_agents_allow_access"));
-        if (!a.iterate_agents || !a.agent_get_info || !a.iterate_pools || !a.pool_get_info || !a.pool_allocate || !a.pool_free || !a.allow_access) a.lib = nullptr;
-        return a;
-    }();
-    return api.lib ? &api : nullptr;
-}
-
-struct BarFind { const HsaApi *api; uint32_t bdf, domain; hsa_agent_t gpu{}, cpu{}; bool have_gpu = false, have_cpu = false; hsa_amd_memory_pool_t pool{}; int pool_rank = 0; };
-
-hsa_status_t bar_agent_cb(hsa_agent_t agent, void *data)
-{
-    BarFind *f = static_cast<BarFind *>(data);
-    hsa_device_type_t type;
-    if (f->api->agent_get_info(agent, HSA_AGENT_INFO_DEVICE, &type) != HSA_STATUS_SUCCESS) return HSA_STATUS_SUCCESS;
-    if (type == HSA_DEVICE_TYPE_CPU) { if (!f->have_cpu) { f->cpu = agent; f->have_cpu = true; } return HSA_STATUS_SUCCESS; }
-    if (type != HSA_DEVICE_TYPE_GPU) return HSA_STATUS_SUCCESS;
-    uint32_t bdf = 0, dom = 0;
-    if (f->api->agent_get_info(agent, (hsa_agent_info_t)HSA_AMD_AGENT_INFO_BDFID, &bdf) != HSA_STATUS_SUCCESS) return HSA_STATUS_SUCCESS;
-    (void)f->api->agent_get_info(agent, (hsa_agent_info_t)HSA_AMD_AGENT_INFO_DOMAIN, &dom);
-    if (bdf == f->bdf && dom == f->domain) { f->gpu = agent; f->have_gpu = true; }
-    return HSA_STATUS_SUCCESS;
-}
-
-hsa_status_t bar_pool_cb(hsa_amd_memory_pool_t pool, void *data)
-{
-    BarFind *f = static_cast<BarFind *>(data);
-    hsa_amd_segment_t seg;
-    uint32_t flags = 0;
-    bool alloc = false;
-    if (f->api->pool_get_info(pool, HSA_AMD_MEMORY_POOL_INFO_SEGMENT, &seg) != HSA_STATUS_SUCCESS || seg != HSA_AMD_SEGMENT_GLOBAL) return HSA_STATUS_SUCCESS;
-    if (f->api->pool_get_info(pool, HSA_AMD_MEMORY_POOL_INFO_RUNTIME_ALLOC_ALLOWED, &alloc) != HSA_STATUS_SUCCESS || !alloc) return HSA_STATUS_SUCCESS;
-    (void)f->api->pool_get_info(pool, HSA_AMD_MEMORY_POOL_INFO_GLOBAL_FLAGS, &flags);
-    // fine-grained first (coherent with the host by construction), then the extended-scope kind; never the coarse-grained pool
-    const int rank = (flags & HSA_AMD_MEMORY_POOL_GLOBAL_FLAG_FINE_GRAINED) ? 2 : (flags & HSA_AMD_MEMORY_POOL_GLOBAL_FLAG_EXTENDED_SCOPE_FINE_GRAINED) ? 1 : 0;
-    if (rank > f->pool_rank) { f->pool = pool; f->pool_rank = rank; }
-    return HSA_STATUS_SUCCESS;
-}
-
-// `bytes` of device memory the CPU may write; nullptr when the platform does not offer it.
-void *bar_alloc(int device_id, size_t bytes)
-{
-    const HsaApi *a = hsa_api();
-    if (!a) return nullptr;
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device_id) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-    BarFind f;
-    f.api = a;
-    f.bdf = ((uint32_t)prop.pciBusID << 8) | ((uint32_t)prop.pciDeviceID << 3);
-    f.domain = (uint32_t)prop.pciDomainID;
-    if (a->iterate_agents(bar_agent_cb, &f) != HSA_STATUS_SUCCESS || !f.have_gpu || !f.have_cpu) return nullptr;
-    if (a->iterate_pools(f.gpu, bar_pool_cb, &f) != HSA_STATUS_SUCCESS || f.pool_rank == 0) return nullptr;
-    void *ptr = nullptr;
-    if (a->pool_allocate(f.pool, (bytes + 4095) & ~(size_t)4095, 0, &ptr) != HSA_STATUS_SUCCESS || !ptr) return nullptr;
-    if (a->allow_access(1, &f.cpu, nullptr, ptr) != HSA_STATUS_SUCCESS) { (void)a->pool_free(ptr); return nullptr; }
-    return ptr;
-}
-
-void bar_free(void *ptr)
-{
-    if (!ptr) return;
-    if (const HsaApi *a = hsa_api()) (void)a->pool_free(ptr);
-}
-
-// ---- host-paced loop: the request words --------------------------------------------------------------------------------------
-// A request is six {value, tag} granules in pinned memory (x, y, theta, the caller's output block lo / hi, the command); the
-// launch's tail workgroup takes them when all six carry the launch's tag.  Plain 8-byte stores: x86 keeps them in order, and each
-// granule vouches for itself anyway.
-void hp_write_request(bn_mppi *h, int slot, uint32_t tag, const float st[3], const float *out, uint32_t cmd)
-{
-    unsigned long long *r = (h->req_bar ? h->req_bar : h->h_req) + (size_t)slot * 8;
-    uint32_t w[6] = {0, 0, 0, 0, 0, cmd};
-    if (st) std::memcpy(w, st, 12);
-    const unsigned long long o = (unsigned long long)(uintptr_t)out;
-    w[3] = (uint32_t)o; w[4] = (uint32_t)(o >> 32);
-    for (int i = 0; i < 6; ++i) __atomic_store_n(r + i, ((unsigned long long)tag << 32) | w[i], __ATOMIC_RELEASE);
-    if (h->req_bar) __builtin_ia32_sfence();           // device memory through the BAR is write-combining: out with it now
-}
-
-// The tail workgroup of the launch with this tag gave up waiting for the host (~50 ms) and said so: the launch has ended, nothing happened.
-bool hp_gave_up(const bn_mppi *h, uint32_t tag)
-{
-    return tag != 0 && h->h_req && __atomic_load_n(h->h_req + (size_t)kSlots * 8 + 8 + (tag % kSlots), __ATOMIC_ACQUIRE) == (((unsigned long long)tag << 32) | 2ull);
-}
-
-// A launch that still waits for its state is told to leave -- it has touched nothing but its own LDS -- and the host's bookkeeping
-// goes back to where it was before the prelaunch.  No synchronisation: the launch ends by itself within a poll.
-void hp_cancel(bn_mppi *h)
-{
-    if (!h->hp_armed) return;
-    hp_write_request(h, h->hp_slot, h->hp_tag, nullptr, nullptr, 2u);
-    h->hp_armed = false;
-    h->solves -= 1;
-    const int cur3 = (int)(h->solves % kSlots);
-    h->pub[cur3] -= (unsigned long long)h->p.nblk;
-    h->tails -= 1;
-    h->hp_next_q = h->hp_q;                            // (the stream the cancelled launch leaves within a poll)
-}
-
 // Write the tail (U*, next mean, X*, weights, cost copy) of the latest solve if it is still pending.
-int flush_tail(bn_mppi *h, float *out_copy = nullptr)
+int flush_tail(bn_mppi *h, float *out_copy)
 {
     if (h->shard_tail_inflight) {                      // K-sharded solve, library-enqueued: results are ordered on the handle's stream from here on
         BN_HIP(hipStreamWaitEvent(h->stream, h->ev_shard_tail[h->shard_tail_slot], 0));
@@ -529,8 +178,6 @@ int check_instance(const bn_mppi *h, int32_t instance, bool allow_all)
     return BN_OK;
 }
 
-constexpr size_t kJournalCap = 4096;
-
 // Called before the first launch of a batch that journal_push may record: that launch copies the states it reads into the slot
 // the record will point at.  (Costs nothing on the host; one predicated 12-byte store in the kernel.)
 void journal_arm_states(bn_mppi *h)
@@ -558,7 +205,7 @@ void journal_push(bn_mppi *h, bn_mppi::BatchRec r, bool replayable)
 // predecessor from becoming resident (another process on the GPU, most likely) may still be there.
 // BN_OK with a warning in bn_last_error() when the re-run succeeded (bn_mppi_recovery_count counts them: consumers enqueued
 // in stream order BEFORE this synchronisation point have read invalid buffers); BN_ERR_HIP when there was nothing to re-run from.
-int recover_overlap(bn_mppi *h)
+static int recover_overlap(bn_mppi *h)
 {
     for (int q = 0; q < kMaxStreams - 1; ++q)
         if (h->xstream[q]) BN_HIP(hipStreamSynchronize(h->xstream[q]));
@@ -613,7 +260,7 @@ int recover_overlap(bn_mppi *h)
 
 // The handle's stream has just been synchronised (`synced`), or the caller only wants to know what has ALREADY gone wrong:
 // look at the error word, repair if it is set.
-int settle_overlap(bn_mppi *h, bool synced)
+static int settle_overlap(bn_mppi *h, bool synced)
 {
     if (!h->overlap_used || h->replaying) return BN_OK;
     if (__atomic_load_n(h->h_err, __ATOMIC_ACQUIRE) == 0) {
@@ -628,7 +275,7 @@ int settle_overlap(bn_mppi *h, bool synced)
     return recover_overlap(h);
 }
 
-int sync_checked(bn_mppi *h)
+static int sync_checked(bn_mppi *h)
 {
     BN_HIP(hipStreamSynchronize(h->stream));
     // the extra streams of an overlapped batch are not joined into the handle's stream (see bn_mppi_solve_n_async): their last
@@ -698,7 +345,7 @@ void tune_record(bn_mppi *h, int mode, double us)
 
 // Every 64 launches of a batch: how many solves has the device finished (the tails post the first action with the solve's index), and when.
 // Two samples that both found the device behind the host give a cadence; anything else says nothing.
-void tune_sample(bn_mppi *h)
+static void tune_sample(bn_mppi *h)
 {
     if (!h->h_mail || h->in_episode || h->replaying) return;
     bn_mppi::OvSample now;
@@ -714,7 +361,10 @@ void tune_sample(bn_mppi *h)
     h->ov_sample = now;
 }
 
-}  // namespace
+}  // namespace host
+}  // namespace bn
+
+using namespace bn::host;
 
 extern "C" {
 
@@ -1065,62 +715,7 @@ int bn_mppi_create(const bn_mppi_config *cfg, bn_mppi_t **out)
         (void)hipMemset(probe, 0, 2 * sizeof(int));
     }
     // Host-paced loop (BN_FLAG_HOST_PACED): a second private stream that dispatches concurrently with the first, the request words, events
-    if (rc == BN_OK && (cfg->flags & BN_FLAG_HOST_PACED) && p.B == 1 && h->lat_kernel && h->d_gran[0] && may_overlap && !h->overlap_off &&
-        h->n_streams > 1 && h->xstream[0] && !p.slip_on && !(cfg->flags & (BN_FLAG_NO_PIPELINE | BN_FLAG_PROFILE))) {
-        {
-            bn::SolveParams q = p;
-            q.spec_extra = h->hp_extra;
-            if (bn::lat_lds_bytes(q) == 0) h->hp_extra = 0;        // no room for the wider window: every state but the previous one stages again
-        }
-        int *probe = reinterpret_cast<int *>(h->d_flags + ((kSlots + 1) * B + 1) * bn::kFlagStride);      // the spare counter slot
-        bool found = false, ok = hipStreamCreateWithFlags(&h->xstream[1], hipStreamNonBlocking) == hipSuccess;
-        for (int attempt = 0; ok && attempt < 8 && !found; ++attempt) {
-            int seen = 0;
-            ok = hipMemset(probe, 0, 2 * sizeof(int)) == hipSuccess && bn::launch_queue_probe(probe, h->xstream[0], h->xstream[1], h->n_cus) == hipSuccess &&
-                 hipStreamSynchronize(h->xstream[0]) == hipSuccess && hipStreamSynchronize(h->xstream[1]) == hipSuccess &&
-                 hipMemcpy(&seen, probe + 1, sizeof seen, hipMemcpyDeviceToHost) == hipSuccess;
-            if (!ok) break;
-            if (seen) { found = true; break; }
-            if (attempt == 7) break;
-            hipStream_t fresh = nullptr;
-            if (hipStreamCreateWithFlags(&fresh, hipStreamNonBlocking) != hipSuccess) break;
-            h->parked.push_back(h->xstream[1]);
-            h->xstream[1] = fresh;
-        }
-        (void)hipGetLastError();
-        (void)hipMemset(probe, 0, 2 * sizeof(int));
-        if (ok && found) {
-            const size_t words = (size_t)kSlots * 8 + 16;      // request slots | [0] spare, [1..4] acknowledgements, [7] create's echo | [8..11] "gave up" per slot
-            ok = hipHostMalloc((void **)&h->h_req, words * sizeof(unsigned long long), hipHostMallocMapped) == hipSuccess &&
-                 hipHostGetDevicePointer((void **)&h->d_req, h->h_req, 0) == hipSuccess;
-            if (ok) std::memset(h->h_req, 0, words * sizeof(unsigned long long));
-            alloc(&h->d_req_dev, (size_t)kSlots * 8 * sizeof(unsigned long long));
-            for (int q = 0; ok && q < 2; ++q) ok = hipEventCreateWithFlags(&h->hp_ev[q], hipEventDisableTiming) == hipSuccess;
-            if (ok && rc == BN_OK) {
-                h->hp_stream[0] = h->xstream[0]; h->hp_stream[1] = h->xstream[1];
-                h->hp_enabled = true;
-                // request words in device memory the host can write (see bar_alloc) -- taken only if a kernel reads back what the CPU wrote
-                if (!std::getenv("BENCHNAV_NO_BAR_REQUEST")) {
-                    unsigned long long *bar = static_cast<unsigned long long *>(bar_alloc(cfg->device_id, words * sizeof(unsigned long long)));
-                    if (bar) {
-                        bool good = true;
-                        for (size_t i = 0; i < words; ++i) bar[i] = 0;
-                        const unsigned long long magic = 0x5a5a0000c3c30001ull;
-                        __atomic_store_n(bar + 3, magic, __ATOMIC_RELEASE);
-                        __builtin_ia32_sfence();
-                        good = bn::launch_echo64(bar + 3, h->d_req + (size_t)kSlots * 8 + 7, h->xstream[0]) == hipSuccess && hipStreamSynchronize(h->xstream[0]) == hipSuccess &&
-                               __atomic_load_n(h->h_req + (size_t)kSlots * 8 + 7, __ATOMIC_ACQUIRE) == magic;
-                        (void)hipGetLastError();
-                        __atomic_store_n(bar + 3, 0ull, __ATOMIC_RELEASE);
-                        __builtin_ia32_sfence();
-                        h->h_req[(size_t)kSlots * 8 + 7] = 0;
-                        if (good) h->req_bar = bar; else bar_free(bar);
-                    }
-                }
-            }
-        }
-        (void)hipGetLastError();                       // (a handle that cannot pace keeps the one-launch path: bn_mppi_host_paced() tells)
-    }
+    if (rc == BN_OK) rc = paced_setup(h, may_overlap);
     if (rc != BN_OK) {
         bn_mppi_destroy(h);
         return rc;
@@ -1132,8 +727,6 @@ int bn_mppi_create(const bn_mppi_config *cfg, bn_mppi_t **out)
     *out = h;
     return BN_OK;
 }
-
-static void shard_comm_release(bn_mppi *h);      // (with the RCCL loader, further down)
 
 void bn_mppi_destroy(bn_mppi_t *h)
 {
@@ -1151,20 +744,18 @@ void bn_mppi_destroy(bn_mppi_t *h)
     }
     for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
     if (h->shard_comm || h->shard_prepared) shard_comm_release(h);
+    env_release(h);
+    loops_release(h);
+    // what bn_mppi_create and the solve path allocate
     void *bufs[] = {h->d_map, h->d_state, h->d_goal, h->d_mean, h->d_eps, h->d_X, h->d_U, h->d_cost_out,
-                    h->d_w, h->d_ustar /* d_xstar lives in the same block */, h->d_stats, h->d_scratch, h->d_idx, h->d_lat_mean, h->d_lat_std,
-                    h->d_ep_states, h->d_ep_reward, h->d_env_state, h->d_ep_done, h->d_ep_action, h->d_slip_std,
-                    h->d_ustar2[0], h->d_ustar2[1], h->d_ustar2[2], h->d_ustar2[3], h->d_stats2[0], h->d_stats2[1], h->d_stats2[2], h->d_stats2[3],
-                    h->d_ticket, h->d_gpart, h->d_mean_used, h->d_ad_i, h->d_ad_state, h->d_ad_log,
-                    h->d_cl_rover, h->d_cl_flags, h->d_cl_goal, h->d_cl_log};
-    static_assert(kSlots == 4, "the list above names the four slots");
+                    h->d_w, h->d_ustar /* d_xstar lives in the same block */, h->d_stats, h->d_scratch, h->d_idx, h->d_slip_std,
+                    h->d_ticket, h->d_gpart, h->d_mean_used};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (h->d_flags) (void)hipFree(h->d_flags);
-    if (h->h_cl_pending) (void)hipHostFree(h->h_cl_pending);
-    for (hipEvent_t e : h->cl_ev)
-        if (e) (void)hipEventDestroy(e);
     for (int q = 0; q < kSlots; ++q) {
+        if (h->d_ustar2[q]) (void)hipFree(h->d_ustar2[q]);
+        if (h->d_stats2[q]) (void)hipFree(h->d_stats2[q]);
         if (h->d_gran[q]) (void)hipFree(h->d_gran[q]);
         if (h->d_cost[q]) (void)hipFree(h->d_cost[q]);
         if (h->d_part[q]) (void)hipFree(h->d_part[q]);
@@ -1182,10 +773,7 @@ void bn_mppi_destroy(bn_mppi_t *h)
     if (h->h_pinned) (void)hipHostFree(h->h_pinned);
     if (h->h_err) (void)hipHostFree(h->h_err);
     if (h->h_mail) (void)hipHostFree(h->h_mail);
-    if (h->h_req) (void)hipHostFree(h->h_req);
-    if (h->req_bar) bar_free(h->req_bar);
-    if (h->d_req_dev) (void)hipFree(h->d_req_dev);
-    for (hipEvent_t e : h->hp_ev) if (e) (void)hipEventDestroy(e);
+    paced_release(h);
     if (h->d_mean_snap) (void)hipFree(h->d_mean_snap);
     if (h->d_state_snaps) (void)hipFree(h->d_state_snaps);
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
@@ -1267,19 +855,6 @@ int bn_mppi_set_mean(bn_mppi_t *h, int32_t instance, const float *mean_host)
     return BN_OK;
 }
 
-int bn_mppi_get_mean(bn_mppi_t *h, int32_t instance, float *mean_host)
-{
-    if (int rc = check_instance(h, instance, false)) return rc;
-    if (!mean_host) return fail(BN_ERR_INVALID, "null output");
-    BN_BIND(h);
-    if (int rc = settle_point(h)) return rc;
-    if (int rc = flush_tail(h)) return rc;
-    BN_HIP(hipStreamSynchronize(h->stream));
-    const size_t n = (size_t)h->p.T * 2;
-    BN_HIP(hipMemcpy(mean_host, h->d_mean + instance * n, n * 4, hipMemcpyDeviceToHost));
-    return BN_OK;
-}
-
 // A launch of handle h that is not a member of an overlapped batch of its own: if ANOTHER handle's overlapped batch may still be
 // in flight on the device, `st` waits for its end (events recorded on that handle's streams).  See g_handles.
 static int order_behind_foreign_overlap(bn_mppi *h, hipStream_t st)
@@ -1303,15 +878,19 @@ static int order_behind_foreign_overlap(bn_mppi *h, hipStream_t st)
     return BN_OK;
 }
 
+
+}  // extern "C"
+
+namespace bn {
+namespace host {
+
 // Every launch a handle makes on its own stream outside an overlapped batch of its own -- stand-alone tails, re-rolls, environment
 // steps and collision checks, not only solves -- goes behind another handle's overlapped batch the same way.
-namespace {
 int guard_foreign_overlap(bn_mppi *h)
 {
     if (h->last_batch_overlapped || g_overlap_owners.load(std::memory_order_relaxed) == 0) return BN_OK;
     return order_behind_foreign_overlap(h, h->stream);
 }
-}  // namespace
 
 // hp_redo's solve (a lone one-launch solve with its own tail) goes out on a private stream: see hp_redo.
 static inline bool lone_self_redo(const bn_mppi *h, bool self_tail, bool overlap)
@@ -1321,8 +900,8 @@ static inline bool lone_self_redo(const bn_mppi *h, bool self_tail, bool overlap
 }
 
 // shard_rollout: the rollouts of a K-sharded solve only (bn_mppi_shard_rollout_async); the tail follows the exchange.
-static int solve_impl(bn_mppi_t *h, const float *states, bn_mem_kind states_where, const float *eps, bn_noise_kind noise,
-                      bool shard_rollout, bool overlap = false, hipStream_t on_stream = nullptr, int alt_buffers = 0, bool self_tail = false)
+int solve_impl(bn_mppi_t *h, const float *states, bn_mem_kind states_where, const float *eps, bn_noise_kind noise,
+               bool shard_rollout, bool overlap, hipStream_t on_stream, int alt_buffers, bool self_tail)
 {
     if (!h) return fail(BN_ERR_INVALID, "null handle");
     if (!states) return fail(BN_ERR_INVALID, "states is null");
@@ -1575,6 +1154,11 @@ static int solve_impl(bn_mppi_t *h, const float *states, bn_mem_kind states_wher
     return BN_OK;
 }
 
+}  // namespace host
+}  // namespace bn
+
+extern "C" {
+
 int bn_mppi_solve_async(bn_mppi_t *h, const float *states, bn_mem_kind states_where, const float *eps,
                         bn_noise_kind noise)
 {
@@ -1585,466 +1169,6 @@ int bn_mppi_solve_async(bn_mppi_t *h, const float *states, bn_mem_kind states_wh
         journal_push(h, bn_mppi::BatchRec{1, states, eps, noise, 1, 0, false, nullptr}, states_where == BN_MEM_DEVICE && noise != BN_NOISE_HOST_KT2);
     }
     return solve_impl(h, states, states_where, eps, noise, false);
-}
-
-#ifdef BN_TIMING
-// host-side split of the host-paced forward (tools/stamps_forward.py prints it at exit): nanoseconds and calls per piece
-struct HpClock { const char *name; long long ns = 0, n = 0; };
-static HpClock g_hpc[6] = {{"post: request words"}, {"post: hipStreamWaitEvent"}, {"prelaunch: checks + ack"}, {"prelaunch: kernel launch"}, {"prelaunch: hipEventRecord"}, {"self_check + bind"}};
-struct HpTick { int i; std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-                explicit HpTick(int i_) : i(i_) {}
-                ~HpTick() { g_hpc[i].ns += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count(); g_hpc[i].n += 1; } };
-#define BN_HP_TICK(i) HpTick bn_hp_tick_##i(i)
-extern "C" void bn_mppi_debug_hp_clock(void)
-{
-    for (const HpClock &c : g_hpc) if (c.n) std::fprintf(stderr, "[hp host] %-28s %7.2f us x %lld\n", c.name, c.ns / 1e3 / c.n, c.n);
-}
-#else
-#define BN_HP_TICK(i) do { } while (0)
-#endif
-
-// Host-paced loop: enqueue the launch of the solve AFTER the latest one, on a private stream; it waits on the device for its state.
-// Best effort: returns false (and leaves nothing behind) when the handle's state does not allow it.
-static bool hp_prelaunch(bn_mppi *h)
-{
-    if (!h->hp_enabled || h->hp_armed || h->self_off || !h->hp_gran_valid || h->tail_pending || h->shard_pending || h->in_episode || h->replaying ||
-        !h->map_set || !h->goal_set || h->solves == 0)
-        return false;
-    std::chrono::steady_clock::time_point bn_t_pre = std::chrono::steady_clock::now(); (void)bn_t_pre;
-    {   // not beside another handle's launches (the latency kernel is sized for a device it has to itself: see g_handles)
-        std::lock_guard<std::mutex> lock(g_overlap_mu);
-        for (bn_mppi *o : g_handles[h->cfg.device_id]) {
-            if (o == h) continue;
-            for (int q = 0; q < kMaxStreams; ++q) {
-                const hipStream_t os = q ? o->xstream[q - 1] : o->stream;
-                if ((q && !os) || os == h->stream) continue;
-                if (hipStreamQuery(os) != hipSuccess) { (void)hipGetLastError(); return false; }
-            }
-        }
-        (void)hipGetLastError();
-    }
-    bn::SolveParams p = h->p;
-    const size_t B = 1;
-    const int cur3 = (int)(h->solves % kSlots), prev3 = (int)((h->solves + kSlots - 1) % kSlots);
-    p.solve = h->solves; p.tail_solve = p.solve;
-    p.part = h->d_part[cur3]; p.cost = h->d_cost[cur3]; p.state_copy = h->d_state_copy[cur3];
-    p.part_prev = h->d_part[prev3]; p.cost_prev = h->d_cost[prev3]; p.state_prev = h->d_state_copy[prev3];
-    p.have_prev = 0; p.mean_from_part = 1;             // the mean IS the merge of the previous solve's rows (its tail writes the same values)
-    p.lat_kernel = 1; p.wave_kernel = 0;
-    p.flag_tail = h->d_flags + kSlots * B * bn::kFlagStride;
-    p.flag_part = h->d_flags;
-    p.err = h->d_err; p.err_dev = reinterpret_cast<int *>(h->d_flags + ((kSlots + 1) * B + 2) * bn::kFlagStride);
-    p.cur_slot = cur3; p.prev_slot = prev3;
-    p.wait_part = h->pub[prev3];
-    p.gran = h->d_gran[cur3]; p.gran_prev = h->d_gran[prev3];
-    p.overlap = 1;
-    p.self_tail = 1;
-    p.wait_part_self = h->pub[cur3] + (unsigned long long)p.nblk;
-    p.wait_tail_self = h->tails;
-    const int xi = 1 - h->x_idx;                       // the other trajectory / control buffer: two launches in flight never write the same addresses
-    if (xi && h->d_Xalt[0]) p.X = h->d_Xalt[0];
-    if (!p.store_u) p.U = nullptr;
-    else if (xi && h->d_Ualt[0]) p.U = h->d_Ualt[0];
-    p.host_paced = 1;
-    if (exp_env("BN_NO_EARLY_MAIL")) p.no_early_mail = 1;      // (experiment builds)
-    p.sv0 = h->hp_prev_state[0]; p.sv1 = h->hp_prev_state[1]; p.sv2 = h->hp_prev_state[2];
-    p.spec_extra = h->hp_extra;
-    const uint32_t tag = h->hp_seq + 1;
-    const int slot = (int)(tag % kSlots);
-    static_assert(kSlots == 4, "the kernels acknowledge a request in word 1 + (tag & 3)");
-    if (tag > (uint32_t)kSlots) {
-        // The slot's previous user -- the launch four tags back -- must have taken (or given up on) its request before the words are
-        // written again: its tail workgroup says so.  In a loop paced by bn_mppi_first_action that was three solves ago; a caller that
-        // fires forwards back to back is held to the device's pace here (bounded: a launch gives up by itself after ~50 ms).
-        const unsigned long long *ack = h->h_req + (size_t)kSlots * 8 + 1 + slot;
-        const auto t0 = std::chrono::steady_clock::now();
-        for (long it = 0; __atomic_load_n(ack, __ATOMIC_ACQUIRE) != (unsigned long long)(tag - kSlots); ++it)
-            if ((it & 0x3ff) == 0x3ff && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) { h->hp_enabled = false; return false; }
-    }
-    h->hp_seq = tag;
-    p.req_tag = tag;
-    p.req_direct = h->req_bar ? 1 : 0;
-    // the launch's patience, in looks: ~2 us each over PCIe, ~0.7 us in device memory -- at least 50 ms either way; the host stays
-    // below 20 ms (hp_post looks at the clock), so a "go" never meets a "gave up"
-    p.req_polls = (h->req_bar && h->hp_polls == 25000) ? 100000 : h->hp_polls;
-    p.req_host = (h->req_bar ? h->req_bar : h->d_req) + (size_t)slot * 8;
-    p.req_dev = h->d_req_dev + (size_t)slot * 8;
-    p.spec_status = h->d_req + (size_t)kSlots * 8;
-    p.state = h->d_state;                              // (not read: the state comes with the request)
-    const int q = h->hp_next_q;
-#ifdef BN_TIMING
-    g_hpc[2].ns += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - bn_t_pre).count(); g_hpc[2].n += 1;
-#endif
-    hipError_t e;
-    // (the completion event goes out with the launch: one runtime call)
-    { BN_HP_TICK(3); e = p.ref_order ? bn::launch_rollout_lat_host_ref(p, h->hp_stream[q], h->hp_ev[q]) : bn::launch_rollout_lat_host(p, h->hp_stream[q], h->hp_ev[q]); }
-    if (e != hipSuccess) { (void)hipGetLastError(); h->hp_enabled = false; return false; }
-    h->pub[cur3] += (unsigned long long)p.nblk;
-    h->tails += 1;
-    h->solves += 1;
-    h->hp_armed = true; h->hp_tag = tag; h->hp_slot = slot; h->hp_q = q; h->hp_xidx = xi;
-    h->hp_armed_at = std::chrono::steady_clock::now();
-    h->hp_next_q = 1 - q;
-    return true;
-}
-
-// ... and hand the waiting launch its state.
-static int hp_post(bn_mppi *h, const float st[3], float *out_device)
-{
-    // The waiting launch runs on a stream of its own: it is ordered behind the HOST (this store), not behind what the caller enqueued on
-    // the handle's stream before this call.  The contract of the mode (header): work left there that still reads the planner's own
-    // buffers -- weights, trajectory batch, the shared U* | X* block -- or the last users of the memory `out_device` was carved from must
-    // have completed; fresh output blocks per step (what the drop-in class hands out) need nothing.  (Asking the stream -- hipStreamQuery
-    // -- is no way out: the event that orders the previous solve's launch in front of the caller's consumers keeps it "busy" for tens of
-    // microseconds after that launch has ended, and every step would wait for it: 17 -> 39 us, measured.)
-    { BN_HP_TICK(0); hp_write_request(h, h->hp_slot, h->hp_tag, st, out_device, 1u); }
-    h->hp_armed = false;
-    h->hp_posted_tag = h->hp_tag;
-    std::memcpy(h->hp_posted_state, st, 12);
-    h->hp_posted_out = out_device;
-    std::memcpy(h->hp_prev_state, st, 12);
-    h->x_idx = h->hp_xidx;
-    h->map_epoch_at_solve = h->map_epoch;
-    h->last_eps = nullptr; h->last_mode = bn::kEpsPhilox;
-    h->tail_pending = false; h->prev_published = false; h->last_batch_overlapped = false;
-    h->self_used = true;
-    h->hp_gran_valid = true;
-    return BN_OK;
-}
-
-// Whatever the caller enqueues on the handle's stream from here on is ordered behind the posted solve's launch (its outputs).  Issued
-// BEHIND the next solve's prelaunch: that launch needs every microsecond of head start it can get (it has to be through its prologue when
-// the host comes back with the next state), this call only has to be made before the caller gets control back.
-static int hp_order_outputs(bn_mppi *h, int q)
-{
-    if (h->cfg.flags & BN_FLAG_UNORDERED_OUTPUTS) { h->hp_unordered = true; h->hp_unordered_q = q; return BN_OK; }    // made up for by the first call that needs it
-    if (!exp_env("BN_HP_NO_WAIT")) { BN_HP_TICK(1); BN_HIP(hipStreamWaitEvent(h->stream, h->hp_ev[q], 0)); }      // (the switch: experiment builds, tools/stamps_forward.py)
-    return BN_OK;
-}
-
-// MPPI.forward as ONE call -- and, on the latency kernel, ONE launch: the solve's tail (merge -> U* -> first-action mailbox -> X* ->
-// weights) rides in the rollout launch as a second aux workgroup that waits on the device for the rollout workgroups of its own launch.
-static int forward_impl(bn_mppi_t *h, const float *states_device, const float *state_host, const float *eps_device, bn_noise_kind noise,
-                        float *out_device)
-{
-    if (!h) return fail(BN_ERR_INVALID, "null handle");
-    if (!states_device && !state_host) return fail(BN_ERR_INVALID, "states is null");
-    if ((noise == BN_NOISE_PHILOX) != (eps_device == nullptr)) return fail(BN_ERR_INVALID, "eps must be NULL exactly when noise == BN_NOISE_PHILOX");
-    const bool paced = h->hp_enabled && state_host && noise == BN_NOISE_PHILOX && !h->self_off;
-    // (the host took longer than the launch waits -- or, with the request words polled by every workgroup of the launch, may be about
-    // to: a "go" must never meet a "gave up" -- : start over below)
-    if (paced && h->hp_armed && !h->hp_skip_check &&
-        (hp_gave_up(h, h->hp_tag) || std::chrono::steady_clock::now() - h->hp_armed_at > std::chrono::milliseconds(20))) hp_cancel(h);
-    if (paced && h->hp_armed) {                        // the loop's steady state: the launch is there and waits for exactly this
-        BN_BIND_Q(h);
-        if (int rc = self_check(h)) return rc;
-        const int q_posted = h->hp_q;
-        if (int rc = hp_post(h, state_host, out_device)) return rc;
-        (void)hp_prelaunch(h);                         // ... and the next one goes out while this one runs
-        return hp_order_outputs(h, q_posted);
-    }
-    {
-        BN_BIND(h);
-        if (int rc = settle_point(h)) return rc;       // behind overlapped batches: those are checked (one synchronisation) first
-        // a tail still pending (an earlier bn_mppi_solve_async): written by its own kernel first -- the one-launch path carries no other
-        // tail than its own (two tails of one launch would write the outputs from two workgroups with different store scopes)
-        if (h->lat_kernel && h->tail_pending && !h->self_off) { if (int rc = flush_tail(h)) return rc; }
-    }
-    h->self_out_copy = out_device;
-    // by value: one instance on the latency kernel travels in the kernel arguments; anything else is staged and uploaded (bn_mppi_solve_async's host path)
-    const bool by_value = state_host && h->p.B == 1 && h->lat_kernel && !h->self_off && !h->tail_pending && !(h->cfg.flags & BN_FLAG_NO_PIPELINE);
-    h->inline_state = by_value ? state_host : nullptr;
-    const float *st = by_value ? h->d_state : (state_host ? state_host : states_device);
-    const int rc0 = solve_impl(h, st, (state_host && !by_value) ? BN_MEM_HOST : BN_MEM_DEVICE, eps_device, noise, false, false, nullptr, 0, true);
-    h->self_out_copy = nullptr;
-    h->inline_state = nullptr;
-    if (rc0) return rc0;
-    if (h->self_tail_launched) {                       // tail and the caller's copy ride in the launch
-        if (paced && by_value) {
-            BN_BIND(h);
-            std::memcpy(h->hp_prev_state, state_host, 12);
-            (void)hp_prelaunch(h);
-        }
-        return BN_OK;
-    }
-    BN_BIND(h);
-    if (!h->tail_pending && out_device) {              // two-launch modes: the tail has run; one small copy on the stream
-        const size_t n = (size_t)h->p.B * ((size_t)h->p.T * 2 + ((size_t)h->p.T + 1) * 3);
-        BN_HIP(hipMemcpyAsync(out_device, h->d_ustar, n * 4, hipMemcpyDeviceToDevice, h->stream));
-        return BN_OK;
-    }
-    return flush_tail(h, out_device);
-}
-
-// The launch a request was posted to had given up a moment before (its tail workgroup said so after the post): the solve never ran.
-// Take it -- and a successor prelaunched behind it -- out of the books and run it again the ordinary way, from the same state.
-// The successor cancelled here still waits on the device for the rows of exactly the solve that runs again, and leaves only once they are
-// there.  Where the handle's stream shares a hardware queue with that launch's stream (GPU_MAX_HW_QUEUES=2 leaves no other way for three
-// streams), a solve enqueued there could not start before the successor gave up waiting (seconds, and the error word).  So the solve runs
-// on the OTHER private stream -- the create-time queue probe found it runs beside the successor's; the launch that gave up ran there --
-// and the handle's stream is ordered behind it (solve_impl).
-static int hp_redo(bn_mppi *h)
-{
-    const int q_succ = h->hp_armed ? h->hp_q : -1;
-    hp_cancel(h);
-    h->solves -= 1;
-    h->pub[h->solves % kSlots] -= (unsigned long long)h->p.nblk;
-    h->tails -= 1;
-    h->hp_posted_tag = 0;
-    h->hp_gran_valid = false;
-    float st[3];
-    std::memcpy(st, h->hp_posted_state, 12);
-    h->hp_redo_q = q_succ >= 0 ? 1 - q_succ : -1;
-    const int rc = forward_impl(h, nullptr, st, nullptr, BN_NOISE_PHILOX, h->hp_posted_out);
-    h->hp_redo_q = -1;
-    return rc;
-}
-
-int bn_mppi_forward_async(bn_mppi_t *h, const float *states_device, const float *eps_device, bn_noise_kind noise, float *out_device)
-{
-    // MPPI.forward as ONE call for a host loop that consumes every solve's outputs (test_mppi.py:174-183): the solve and
-    // its tail, both only enqueued; U*, X*, weights are in the device buffers in stream order.
-    if (!states_device) return fail(BN_ERR_INVALID, "states is null");
-    return forward_impl(h, states_device, nullptr, eps_device, noise, out_device);
-}
-
-int bn_mppi_forward_state_async(bn_mppi_t *h, const float *states_host, const float *eps_device, bn_noise_kind noise, float *out_device)
-{
-    if (!states_host) return fail(BN_ERR_INVALID, "states is null");
-    return forward_impl(h, nullptr, states_host, eps_device, noise, out_device);
-}
-
-int bn_mppi_set_rollout_offset(bn_mppi_t *h, int64_t first_rollout)
-{
-    if (!h) return fail(BN_ERR_INVALID, "null handle");
-    if (first_rollout < 0 || first_rollout + h->p.K > 0x7fffffffLL) return fail(BN_ERR_INVALID, "first_rollout out of range");
-    BN_BIND(h);
-    if (int rc = settle_point(h)) return rc;
-    if (int rc = flush_tail(h)) return rc;
-    h->p.k0 = (int)first_rollout;
-    return BN_OK;
-}
-
-int bn_mppi_shard_rollout_async(bn_mppi_t *h, const float *states, bn_mem_kind states_where, const float *eps,
-                                bn_noise_kind noise)
-{
-    if (h && h->p.B != 1) return fail(BN_ERR_INVALID, "a K-sharded solve takes one instance per handle");
-    if (h && h->p.slip_on) return fail(BN_ERR_INVALID, "K-sharding is not available in sampled-slip mode");
-    return solve_impl(h, states, states_where, eps, noise, true);
-}
-
-int bn_mppi_shard_partials(bn_mppi_t *h, const float **partials_device, int32_t *workgroups, int32_t *floats_per_workgroup)
-{
-    if (!h) return fail(BN_ERR_INVALID, "null handle");
-    if (!h->shard_pending) return fail(BN_ERR_STATE, "no sharded solve in flight");
-    const int cur = (int)((h->solves - 1) % kSlots);
-    if (partials_device) *partials_device = h->d_part[cur];
-    if (workgroups) *workgroups = h->p.nblk;
-    if (floats_per_workgroup) *floats_per_workgroup = 2 + 2 * h->p.T;
-    return BN_OK;
-}
-
-int bn_mppi_shard_finish_async(bn_mppi_t *h, const float *all_partials_device, int32_t total_workgroups)
-{
-    if (!h) return fail(BN_ERR_INVALID, "null handle");
-    if (!h->shard_pending) return fail(BN_ERR_STATE, "no sharded solve in flight");
-    if (!all_partials_device || total_workgroups < h->p.nblk) return fail(BN_ERR_INVALID, "need the partials of every shard");
-    BN_BIND(h);
-    if (int rc = settle_point(h)) return rc;
-    bn::SolveParams p = h->p;
-    const int cur = (int)((h->solves - 1) % kSlots);
-    p.solve = p.tail_solve = h->solves - 1;
-    p.part = const_cast<float *>(all_partials_device);      // merged in shard order: identical on every rank
-    p.nblk = total_workgroups;
-    p.cost = h->d_cost[cur]; p.state = h->d_state_copy[cur];
-    BN_HIP(bn::launch_finish(p, h->stream));                 // weights of the local rollouts, normalised by the global sum
-    h->shard_pending = false;
-    return BN_OK;
-}
-
-// ---- the exchange of a K-sharded solve enqueued by the library: RCCL on the handle's stream -----------------------------------
-// Round 4's ShardedMPPI drove the three steps from Python -- launch, torch.distributed.all_gather_into_tensor (its own stream, two
-// events to fence it against the planner's), launch: 60 us per solve on one rank against 28 unsharded.  Here the triple is ONE C call
-// and ONE queue: rollout kernel, ncclAllGather, tail kernel, stream-ordered, no host wait, no event.  RCCL is opened with dlopen on
-// first use: the library has no link-time dependency on it, and a process that never shards a solve never loads it.
-namespace {
-struct RcclApi {
-    void *lib = nullptr;
-    decltype(&ncclGetUniqueId) get_unique_id = nullptr;
-    decltype(&ncclCommInitRank) comm_init_rank = nullptr;
-    decltype(&ncclAllGather) all_gather = nullptr;
-    decltype(&ncclCommDestroy) comm_destroy = nullptr;
-    decltype(&ncclGetErrorString) error_string = nullptr;
-};
-const RcclApi *rccl_api()
-{
-    static const RcclApi api = [] {
-        RcclApi a;
-        for (const char *name : {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"}) {
-            a.lib = dlopen(name, RTLD_NOW | RTLD_GLOBAL);
-            if (a.lib) break;
-        }
-        if (!a.lib) return a;
-        a.get_unique_id = reinterpret_cast<decltype(a.get_unique_id)>(dlsym(a.lib, "ncclGetUniqueId"));
-        a.comm_init_rank = reinterpret_cast<decltype(a.comm_init_rank)>(dlsym(a.lib, "ncclCommInitRank"));
-        a.all_gather = reinterpret_cast<decltype(a.all_gather)>(dlsym(a.lib, "ncclAllGather"));
-        a.comm_destroy = reinterpret_cast<decltype(a.comm_destroy)>(dlsym(a.lib, "ncclCommDestroy"));
-        a.error_string = reinterpret_cast<decltype(a.error_string)>(dlsym(a.lib, "ncclGetErrorString"));
-        if (!a.get_unique_id || !a.comm_init_rank || !a.all_gather || !a.comm_destroy || !a.error_string) a.lib = nullptr;
-        return a;
-    }();
-    return api.lib ? &api : nullptr;
-}
-}  // namespace
-
-static void shard_comm_release(bn_mppi *h)
-{
-    if (h->shard_side) (void)hipStreamSynchronize(h->shard_side);
-    if (h->shard_comm) { if (const RcclApi *r = rccl_api()) (void)r->comm_destroy(static_cast<ncclComm_t>(h->shard_comm)); }
-    h->shard_comm = nullptr;
-    h->shard_prepared = false;
-    if (h->d_gathered) (void)hipFree(h->d_gathered);
-    if (h->d_shard_merged) (void)hipFree(h->d_shard_merged);
-    h->d_gathered = h->d_shard_merged = nullptr;
-    if (h->ev_shard_merge) (void)hipEventDestroy(h->ev_shard_merge);
-    for (hipEvent_t &e : h->ev_shard_tail) { if (e) (void)hipEventDestroy(e); e = nullptr; }
-    h->ev_shard_merge = nullptr;
-    if (h->shard_side_own && h->shard_side) (void)hipStreamDestroy(h->shard_side);
-    h->shard_side = nullptr;
-}
-
-int bn_dist_unique_id(uint8_t out[BN_DIST_UNIQUE_ID_BYTES])
-{
-    static_assert(sizeof(ncclUniqueId) == BN_DIST_UNIQUE_ID_BYTES, "ncclUniqueId size");
-    if (!out) return fail(BN_ERR_INVALID, "null output");
-    const RcclApi *r = rccl_api();
-    if (!r) return fail(BN_ERR_HIP, "librccl.so could not be opened: %s", dlerror());
-    ncclUniqueId id;
-    const ncclResult_t e = r->get_unique_id(&id);
-    if (e != ncclSuccess) return fail(BN_ERR_HIP, "ncclGetUniqueId: %s", r->error_string(e));
-    std::memcpy(out, &id, sizeof(id));
-    return BN_OK;
-}
-
-int bn_mppi_shard_comm_prepare(bn_mppi_t *h, int32_t world_size, int32_t rank)
-{
-    // Everything bn_mppi_shard_comm_init can fail on BEFORE it enters the collective (ncclCommInitRank): opening RCCL, the handle's
-    // state, the buffers, events and the side stream.  Local, no communication: the ranks of a job call it, agree on the outcome by
-    // whatever means they have (benchnav_amd.sharding: one all-reduce over the torch group), and enter the collective only if every
-    // rank is ready -- a rank that cannot must not leave the others waiting in ncclCommInitRank's bootstrap.
-    if (!h) return fail(BN_ERR_INVALID, "null argument");
-    if (world_size < 1 || rank < 0 || rank >= world_size) return fail(BN_ERR_INVALID, "rank %d outside a world of %d", rank, world_size);
-    if (h->p.B != 1 || h->p.slip_on) return fail(BN_ERR_INVALID, "a K-sharded solve takes one instance per handle, without sampled slip");
-    if (h->shard_comm) return fail(BN_ERR_STATE, "the handle has a communicator already");
-    if ((size_t)world_size * h->p.nblk > 1024) return fail(BN_ERR_INVALID, "the library's exchange merges at most 1024 workgroups (65536 rollouts)");
-    if (h->shard_prepared) {
-        if (h->shard_world == world_size && h->shard_rank == rank) return BN_OK;
-        return fail(BN_ERR_STATE, "the handle was prepared as rank %d of %d", h->shard_rank, h->shard_world);
-    }
-    const RcclApi *r = rccl_api();
-    if (!r) return fail(BN_ERR_HIP, "librccl.so could not be opened: %s", dlerror());
-    BN_BIND(h);
-    if (int rc = settle_point(h)) return rc;
-    const size_t bytes = (size_t)world_size * h->p.nblk * (2 + 2 * (size_t)h->p.T) * sizeof(float);
-    if (hipMalloc((void **)&h->d_gathered, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        h->d_gathered = nullptr;
-        return fail(BN_ERR_HIP, "hipMalloc of %zu B for the gathered partials failed", bytes);
-    }
-    h->shard_world = world_size;
-    h->shard_rank = rank;
-    // the side stream of the tail: the handle's second stream if it has one (overlapped batches), else one of its own
-    // [ kSlots merged rows | 64 group rows | ticket ]
-    const size_t merged_floats = kSlots * (2 * (size_t)h->p.T + 2) + 64 * (2 + 2 * (size_t)h->p.T) + 4;
-    bool ok = hipMalloc((void **)&h->d_shard_merged, merged_floats * sizeof(float)) == hipSuccess &&
-              hipMemset(h->d_shard_merged, 0, merged_floats * sizeof(float)) == hipSuccess &&
-              hipEventCreateWithFlags(&h->ev_shard_merge, hipEventDisableTiming) == hipSuccess;
-    for (int q = 0; ok && q < kSlots; ++q) ok = hipEventCreateWithFlags(&h->ev_shard_tail[q], hipEventDisableTiming) == hipSuccess;
-    if (ok && h->n_streams > 1 && h->xstream[0]) h->shard_side = h->xstream[0];
-    else if (ok) { ok = hipStreamCreateWithFlags(&h->shard_side, hipStreamNonBlocking) == hipSuccess; h->shard_side_own = ok; }
-    if (!ok) { (void)hipGetLastError(); shard_comm_release(h); return fail(BN_ERR_HIP, "stream / event / buffer creation for the sharded solve failed"); }
-    h->shard_prepared = true;
-    return BN_OK;
-}
-
-int bn_mppi_shard_comm_init(bn_mppi_t *h, const uint8_t unique_id[BN_DIST_UNIQUE_ID_BYTES], int32_t world_size, int32_t rank)
-{
-    if (!h || !unique_id) return fail(BN_ERR_INVALID, "null argument");
-    if (int rc = bn_mppi_shard_comm_prepare(h, world_size, rank)) return rc;      // (a no-op behind the caller's own prepare)
-    const RcclApi *r = rccl_api();
-    BN_BIND(h);
-    ncclUniqueId id;
-    std::memcpy(&id, unique_id, sizeof(id));
-    ncclComm_t comm = nullptr;
-    const ncclResult_t e = r->comm_init_rank(&comm, world_size, id, rank);      // collective: every rank of the solve calls it
-    if (e != ncclSuccess) { shard_comm_release(h); return fail(BN_ERR_HIP, "ncclCommInitRank: %s", r->error_string(e)); }
-    h->shard_comm = comm;
-    return BN_OK;
-}
-
-int bn_mppi_shard_solve_async(bn_mppi_t *h, const float *states, bn_mem_kind states_where, const float *eps, bn_noise_kind noise)
-{
-    if (!h) return fail(BN_ERR_INVALID, "null handle");
-    if (!h->shard_comm) return fail(BN_ERR_STATE, "bn_mppi_shard_comm_init must precede bn_mppi_shard_solve_async");
-    // The rollouts of THIS solve do not wait for the previous solve's tail on the side stream (flush_tail would join it): they read
-    // the mean the merge wrote, on this stream.  And they write their partial rows where the all-gather wants them (in place).
-    // Every per-solve buffer rotates over kSlots solves -- the costs and the start state the rollouts below write, the merged row -- and
-    // the side-stream tail of the solve kSlots back still reads its slot (weights, cost copy, X*).  That tail is done unless something is
-    // badly stuck, so the host LOOKS (hipEventQuery) and only a tail still running puts a cross-queue wait in front of the ROLLOUTS
-    // (the check used to sit behind them and covered the merged row only) -- an event wait between queues costs
-    // microseconds on the handle's stream even when the event has long fired (first cut of this path: 72 us per solve with an
-    // unconditional wait against 47 without the split).
-    {
-        BN_BIND(h);
-        const int next = (int)(h->solves % kSlots);
-        if (h->solves >= (uint64_t)kSlots && h->ev_shard_tail[next] && hipEventQuery(h->ev_shard_tail[next]) != hipSuccess) {
-            (void)hipGetLastError();
-            BN_HIP(hipStreamWaitEvent(h->stream, h->ev_shard_tail[next], 0));
-        }
-    }
-    const bool inflight = h->shard_tail_inflight;
-    h->shard_tail_inflight = false;
-    h->shard_inplace = true;
-    const int rc0 = bn_mppi_shard_rollout_async(h, states, states_where, eps, noise);
-    h->shard_inplace = false;
-    h->shard_tail_inflight = inflight;
-    if (rc0) return rc0;
-    BN_BIND(h);
-    const int cur = (int)((h->solves - 1) % kSlots);
-    const size_t count = (size_t)h->p.nblk * (2 + 2 * (size_t)h->p.T);          // equal shards: every rank contributes the same rows
-    const RcclApi *r = rccl_api();
-    const ncclResult_t e = r->all_gather(h->d_gathered + (size_t)h->shard_rank * count, h->d_gathered, count, ncclFloat,
-                                         static_cast<ncclComm_t>(h->shard_comm), h->stream);
-    if (e != ncclSuccess) {
-        h->shard_pending = false;                            // the solve is lost, the handle is not: the next call starts a new one
-        return fail(BN_ERR_HIP, "ncclAllGather: %s", r->error_string(e));
-    }
-    // Merge on the handle's stream -- U*, the next mean, the softmin statistics: all the next solve's rollouts wait for -- and the
-    // rest of the tail (X* rollout, the shard's weights, the cost copy: ~10 us of one workgroup) on the side stream, beside them.
-    // What the two streams share: the outputs (tails stay in order on their one stream; U* is the merge's alone), the per-solve slots
-    // of costs / states, and the merged row (written by the merge, read by the tail) -- all rotating over kSlots solves and covered by
-    // the look at the tail kSlots back in front of the rollouts, above.
-    if (int rc = settle_point(h)) return rc;
-    bn::SolveParams p = h->p;
-    p.solve = p.tail_solve = h->solves - 1;
-    p.part = h->d_gathered;                                  // merged in shard order: identical on every rank
-    p.nblk = h->shard_world * h->p.nblk;
-    p.cost = h->d_cost[cur]; p.state = h->d_state_copy[cur];
-    float *merged = h->d_shard_merged + (size_t)cur * (2 * (size_t)p.T + 2);
-    p.ustar_cur = merged; p.stats_cur = merged + 2 * (size_t)p.T;
-    float *group_rows = h->d_shard_merged + kSlots * (2 * (size_t)p.T + 2);
-    BN_HIP(bn::launch_shard_merge(p, group_rows, reinterpret_cast<int *>(group_rows + 64 * (2 + 2 * (size_t)p.T)), h->stream));
-    BN_HIP(hipEventRecord(h->ev_shard_merge, h->stream));
-    BN_HIP(hipStreamWaitEvent(h->shard_side, h->ev_shard_merge, 0));
-    p.tail_merged = 1;
-    p.ustar_written = 1;                                     // (the merge kernel above wrote U*: see SolveParams::ustar_written)
-    p.ustar_prev = merged; p.stats_prev = merged + 2 * (size_t)p.T;
-    BN_HIP(bn::launch_finish(p, h->shard_side));            // weights of the local rollouts, normalised by the global sum; X*
-    BN_HIP(hipEventRecord(h->ev_shard_tail[cur], h->shard_side));
-    h->shard_tail_slot = cur;
-    h->shard_tail_inflight = true;
-    h->shard_pending = false;
-    return BN_OK;
 }
 
 int bn_mppi_solve_n_async(bn_mppi_t *h, int32_t n, const float *states, bn_mem_kind states_where, const float *eps,
@@ -2237,545 +1361,6 @@ int bn_mppi_solve_n_async(bn_mppi_t *h, int32_t n, const float *states, bn_mem_k
     return rc;
 }
 
-int bn_mppi_env_attach(bn_mppi_t *h, const float *latent_mean, const float *latent_std, bn_mem_kind where,
-                       float goal_threshold, float delta_t, uint64_t seed)
-{
-    if (!h || !latent_mean || !latent_std) return fail(BN_ERR_INVALID, "null argument");
-    if (!(goal_threshold >= 0.0f) || !(delta_t > 0.0f)) return fail(BN_ERR_INVALID, "goal_threshold >= 0 and delta_t > 0 required");
-    BN_BIND(h);
-    if (int rc = settle_point(h)) return rc;
-    if (int rc = flush_tail(h)) return rc;
-    BN_HIP(hipStreamSynchronize(h->stream));
-    const size_t bytes = (size_t)h->n_maps * h->p.G * h->p.G * 4;
-    if (!h->d_lat_mean) {
-        BN_HIP(hipMalloc((void **)&h->d_lat_mean, bytes));
-        BN_HIP(hipMalloc((void **)&h->d_lat_std, bytes));
-        BN_HIP(hipMalloc((void **)&h->d_env_state, (size_t)h->p.B * 3 * 4));
-        BN_HIP(hipMalloc((void **)&h->d_ep_done, (size_t)h->p.B * sizeof(int)));
-    }
-    const hipMemcpyKind kind = where == BN_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    BN_HIP(hipMemcpy(h->d_lat_mean, latent_mean, bytes, kind));
-    BN_HIP(hipMemcpy(h->d_lat_std, latent_std, bytes, kind));
-    h->p.lat_mean = h->d_lat_mean; h->p.lat_std = h->d_lat_std; h->p.env_state = h->d_env_state; h->p.ep_done = h->d_ep_done;
-    h->p.goal_thr = goal_threshold; h->p.env_dt = delta_t; h->p.env_seed = seed;
-    // latency kernel, overlapped episodes: how far one environment step can move the start cell (see SolveParams::spec_extra)
-    h->p.spec_extra = 0;
-    if (h->lat_kernel && h->d_gran[0] && !exp_env("BN_NO_SPEC_WINDOW")) {
-        const double vmax = std::max(std::fabs((double)h->p.umin0), std::fabs((double)h->p.umax0));
-        const double cells = std::floor(vmax * (double)delta_t / (double)h->p.res) + 1.0;
-        if (cells <= 8.0 && h->p.WN + 2 * (int)cells <= h->p.G + 1) {
-            h->p.spec_extra = (int)cells;
-            if (bn::lat_lds_bytes(h->p) == 0) h->p.spec_extra = 0;      // would not fit the LDS
-        }
-    }
-    h->env_attached = true;
-    return BN_OK;
-}
-
-int bn_mppi_env_set_freeze(bn_mppi_t *h, int32_t freeze_on_goal)
-{
-    if (!h) return fail(BN_ERR_INVALID, "null handle");
-    BN_BIND(h);
-    if (int rc = settle_point(h)) return rc;
-    if (int rc = flush_tail(h)) return rc;
-    h->p.env_freeze = freeze_on_goal ? 1 : 0;
-    return BN_OK;
-}
-
-int bn_mppi_env_step(bn_mppi_t *h, const float *actions_device, float *states_device, float *rewards_device,
-                     int32_t *terminated_device, const float *z_device, uint64_t step_index)
-{
-    if (!h || !actions_device || !states_device || !rewards_device || !terminated_device) return fail(BN_ERR_INVALID, "null argument");
-    if (!h->env_attached) return fail(BN_ERR_STATE, "bn_mppi_env_attach must precede bn_mppi_env_step");
-    BN_BIND(h);
-    if (int rc = settle_point(h)) return rc;
-    if (int rc = guard_foreign_overlap(h)) return rc;
-    BN_HIP(bn::launch_env_step(h->p, actions_device, states_device, rewards_device, terminated_device, z_device, step_index, h->stream));
-    return BN_OK;
-}
-
-int bn_mppi_env_collision_check(bn_mppi_t *h, const float *states_device, int32_t n_positions, float stuck_threshold,
-                                const float *z_device, uint64_t draw_index, uint8_t *out_device)
-{
-    if (!h || !states_device || !out_device) return fail(BN_ERR_INVALID, "null argument");
-    if (n_positions < 1) return fail(BN_ERR_INVALID, "n_positions must be >= 1");
-    if (!h->env_attached) return fail(BN_ERR_STATE, "bn_mppi_env_attach must precede bn_mppi_env_collision_check");
-    BN_BIND(h);
-    if (int rc = settle_point(h)) return rc;
-    if (int rc = guard_foreign_overlap(h)) return rc;
-    BN_HIP(bn::launch_env_collision(h->p, states_device, n_positions, stuck_threshold, z_device, draw_index, out_device, h->stream));
-    return BN_OK;
-}
-
-int bn_mppi_episode_async(bn_mppi_t *h, int32_t n_steps, const float *states0, bn_mem_kind states_where, const float *eps,
-                          bn_noise_kind noise, int32_t eps_ring, int64_t eps_stride, const float *z_device)
-{
-    if (!h) return fail(BN_ERR_INVALID, "null handle");
-    if (!h->env_attached) return fail(BN_ERR_STATE, "bn_mppi_env_attach must precede bn_mppi_episode_async");
-    if (h->slow_path) return fail(BN_ERR_INVALID, "the fused device-side closed loop is not available on the slow path (a horizon beyond the role kernels' LDS, or the "
-                                                   "reference-order arithmetic together with sampled slip): drive bn_mppi_forward_async + bn_mppi_env_step instead");
-    if (!h->pipelined) return fail(BN_ERR_INVALID, "the device-side closed loop needs the pipelined mode (num_samples <= 4096)");
-    if (n_steps < 1) return fail(BN_ERR_INVALID, "n_steps must be >= 1");
-    BN_BIND(h);
-    if (int rc = flush_tail(h)) return rc;            // anything pending belongs to the pre-episode state
-    const size_t B = h->p.B;
-    if (n_steps > h->ep_steps) {
-        BN_HIP(hipStreamSynchronize(h->stream));
-        if (h->d_ep_states) BN_HIP(hipFree(h->d_ep_states));
-        if (h->d_ep_reward) BN_HIP(hipFree(h->d_ep_reward));
-        if (h->d_ep_action) BN_HIP(hipFree(h->d_ep_action));
-        h->d_ep_states = h->d_ep_reward = h->d_ep_action = nullptr;
-        BN_HIP(hipMalloc((void **)&h->d_ep_states, (size_t)(n_steps + 1) * B * 3 * 4));
-        BN_HIP(hipMalloc((void **)&h->d_ep_reward, (size_t)n_steps * B * 4));
-        BN_HIP(hipMalloc((void **)&h->d_ep_action, (size_t)n_steps * B * 2 * 4));
-        h->ep_steps = n_steps;
-    }
-    h->p.ep_states = h->d_ep_states; h->p.ep_reward = h->d_ep_reward; h->p.ep_action = h->d_ep_action;
-    BN_HIP(hipMemsetAsync(h->d_ep_done, 0xff, B * sizeof(int), h->stream));        // -1: goal not reached
-    if (!states0) return fail(BN_ERR_INVALID, "states0 is null");
-    if (states_where == BN_MEM_HOST) {                 // one upload; the loop below must not touch the host again
-        BN_HIP(hipStreamSynchronize(h->stream));
-        BN_HIP(hipMemcpy(h->d_state, states0, B * 3 * 4, hipMemcpyHostToDevice));
-        states0 = h->d_state;
-        states_where = BN_MEM_DEVICE;
-    }
-    journal_arm_states(h);                            // the first step's launch keeps states0 for a re-run
-    h->in_episode = true;
-    h->ep_len = 0;
-    h->ep_z = z_device;
-    int rc = bn_mppi_solve_n_async(h, n_steps, states0, states_where, eps, noise, eps_ring, eps_stride);
-    if (rc == BN_OK) rc = flush_tail(h);              // the last solve's tail and the last environment step
-    h->in_episode = false;
-    if (rc == BN_OK) journal_push(h, bn_mppi::BatchRec{n_steps, states0, eps, noise, eps_ring, eps_stride, true, z_device}, noise != BN_NOISE_HOST_KT2);
-    return rc;
-}
-
-int bn_mppi_episode_log(bn_mppi_t *h, float *states_host, float *rewards_host, float *actions_host, int32_t *done_step_host)
-{
-    if (!h) return fail(BN_ERR_INVALID, "null handle");
-    if (!h->d_ep_states || h->ep_len < 1) return fail(BN_ERR_STATE, "no episode has been run");
-    BN_BIND(h);
-    if (int rc = settle_point(h)) return rc;
-    BN_HIP(hipStreamSynchronize(h->stream));
-    const size_t B = h->p.B, n = (size_t)h->ep_len;
-    if (states_host) BN_HIP(hipMemcpy(states_host, h->d_ep_states, (n + 1) * B * 3 * 4, hipMemcpyDeviceToHost));
-    if (rewards_host) BN_HIP(hipMemcpy(rewards_host, h->d_ep_reward, n * B * 4, hipMemcpyDeviceToHost));
-    if (actions_host) BN_HIP(hipMemcpy(actions_host, h->d_ep_action, n * B * 2 * 4, hipMemcpyDeviceToHost));
-    if (done_step_host) BN_HIP(hipMemcpy(done_step_host, h->d_ep_done, B * sizeof(int), hipMemcpyDeviceToHost));
-    return BN_OK;
-}
-
-int bn_mppi_dwa_solve(bn_mppi_t *h, const float *states_host, const float *actions_host, int32_t num_actions,
-                      const float *stage_goal_host, float *best_action_host, float *best_states_host,
-                      float *costs_host, float *weights_host, float *states_all_host, int32_t *best_index_host)
-{
-    if (!h || !states_host || !actions_host) return fail(BN_ERR_INVALID, "null argument");
-    if (num_actions < 1 || num_actions > 1024) return fail(BN_ERR_INVALID, "num_actions must be in [1, 1024]");
-    if (!h->map_set || !h->goal_set) return fail(BN_ERR_STATE, "set_map and set_goal must precede dwa_solve");
-    BN_BIND(h);
-    if (int rc = settle_point(h)) return rc;
-    if (int rc = flush_tail(h)) return rc;
-    const size_t B = h->p.B, NA = num_actions, T1 = h->p.T + 1;
-    // scratch layout: actions | stage goal | X | cost | w | best | best states | states
-    const size_t n_act = B * NA * 2, n_goal = B * 2, n_X = B * NA * T1 * 3, n_c = B * NA, n_bs = B * T1 * 3;
-    const size_t floats = n_act + n_goal + n_X + 2 * n_c + B + n_bs + B * 3;
-    if (int rc = ensure_scratch(h, floats * 4)) return rc;
-    float *d_act = h->d_scratch, *d_goal = d_act + n_act, *d_X = d_goal + n_goal, *d_c = d_X + n_X, *d_w = d_c + n_c;
-    int *d_best = reinterpret_cast<int *>(d_w + n_c);
-    float *d_bs = d_w + n_c + B, *d_st = d_bs + n_bs;
-    // one staged upload (actions | stage goal) + the states, one launch, the downloads queued behind it, one wait
-    h->dwa_stage.resize(n_act + n_goal);
-    std::memcpy(h->dwa_stage.data(), actions_host, n_act * 4);
-    if (stage_goal_host) std::memcpy(h->dwa_stage.data() + n_act, stage_goal_host, n_goal * 4);
-    BN_HIP(hipStreamSynchronize(h->stream));            // the staging vector and the scratch may still feed a previous call
-    BN_HIP(hipMemcpyAsync(d_act, h->dwa_stage.data(), (n_act + (stage_goal_host ? n_goal : 0)) * 4, hipMemcpyHostToDevice, h->stream));
-    if (!stage_goal_host) BN_HIP(hipMemcpyAsync(d_goal, h->d_goal, n_goal * 4, hipMemcpyDeviceToDevice, h->stream));   // no reference path: the goal (dwa.py:243-247)
-    BN_HIP(hipMemcpyAsync(d_st, states_host, B * 3 * 4, hipMemcpyHostToDevice, h->stream));
-    bn::SolveParams p = h->p;
-    p.state = d_st;
-    BN_HIP(bn::launch_dwa(p, d_act, d_goal, num_actions, d_X, d_c, d_w, d_best, d_bs, nullptr, h->stream));
-    std::vector<int> best(B);
-    BN_HIP(hipMemcpyAsync(best.data(), d_best, B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    if (best_states_host) BN_HIP(hipMemcpyAsync(best_states_host, d_bs, n_bs * 4, hipMemcpyDeviceToHost, h->stream));
-    if (costs_host) BN_HIP(hipMemcpyAsync(costs_host, d_c, n_c * 4, hipMemcpyDeviceToHost, h->stream));
-    if (weights_host) BN_HIP(hipMemcpyAsync(weights_host, d_w, n_c * 4, hipMemcpyDeviceToHost, h->stream));
-    if (states_all_host) BN_HIP(hipMemcpyAsync(states_all_host, d_X, n_X * 4, hipMemcpyDeviceToHost, h->stream));
-    BN_HIP(hipStreamSynchronize(h->stream));
-    for (size_t b = 0; b < B; ++b) {
-        if (best_index_host) best_index_host[b] = best[b];
-        if (best_action_host) std::memcpy(best_action_host + b * 2, actions_host + (b * NA + best[b]) * 2, 8);
-    }
-    return BN_OK;
-}
-
-int bn_mppi_dwa_forward_async(bn_mppi_t *h, const float *states_device, float *prev_action_device, const float a_lim_host[2],
-                              float dwa_delta_t, int32_t num_lin_vel, int32_t num_ang_vel, const float *path_device, int32_t num_path,
-                              float lookahead, float *best_states_device)
-{
-    if (!h || !states_device || !prev_action_device || !a_lim_host) return fail(BN_ERR_INVALID, "null argument");
-    const int64_t NA = (int64_t)num_lin_vel * num_ang_vel;
-    if (num_lin_vel < 1 || num_ang_vel < 1 || NA > 1024) return fail(BN_ERR_INVALID, "num_lin_vel * num_ang_vel must be in [1, 1024]");
-    if (path_device && num_path < 1) return fail(BN_ERR_INVALID, "a reference path needs at least one point");
-    if (!h->map_set || !h->goal_set) return fail(BN_ERR_STATE, "set_map and set_goal must precede dwa_forward");
-    BN_BIND(h);
-    if (int rc = settle_point(h)) return rc;
-    if (int rc = flush_tail(h)) return rc;
-    const size_t B = h->p.B, T1 = h->p.T + 1;
-    // the scratch layout of bn_mppi_dwa_solve: actions | stage goal | X | cost | w | best | best states | states
-    const size_t n_act = B * NA * 2, n_goal = B * 2, n_X = B * NA * T1 * 3, n_c = B * NA, n_bs = B * T1 * 3;
-    const size_t floats = n_act + n_goal + n_X + 2 * n_c + B + n_bs + B * 3;
-    if (floats * 4 > h->scratch_bytes) BN_HIP(hipStreamSynchronize(h->stream));      // growing frees the old block: nothing may still use it
-    if (int rc = ensure_scratch(h, floats * 4)) return rc;
-    float *d_act = h->d_scratch, *d_goal = d_act + n_act, *d_X = d_goal + n_goal, *d_c = d_X + n_X, *d_w = d_c + n_c;
-    int *d_best = reinterpret_cast<int *>(d_w + n_c);
-    float *d_bs = best_states_device ? best_states_device : d_w + n_c + B;
-    bn::SolveParams p = h->p;
-    p.state = states_device;
-    BN_HIP(bn::launch_dwa_window(p, prev_action_device, a_lim_host, dwa_delta_t, num_lin_vel, num_ang_vel, path_device, num_path, lookahead,
-                                 d_act, d_goal, h->stream));
-    BN_HIP(bn::launch_dwa(p, d_act, d_goal, (int)NA, d_X, d_c, d_w, d_best, d_bs, prev_action_device, h->stream));
-    return BN_OK;
-}
-
-int bn_mppi_dwa_buffers(bn_mppi_t *h, int32_t num_actions, const float **states_all_device, const float **costs_device,
-                        const float **weights_device)
-{
-    if (!h) return fail(BN_ERR_INVALID, "null handle");
-    if (num_actions < 1 || num_actions > 1024) return fail(BN_ERR_INVALID, "num_actions must be in [1, 1024]");
-    const size_t B = h->p.B, NA = num_actions, T1 = h->p.T + 1;
-    const size_t n_act = B * NA * 2, n_goal = B * 2, n_X = B * NA * T1 * 3, n_c = B * NA;
-    if (!h->d_scratch || h->scratch_bytes < (n_act + n_goal + n_X + 2 * n_c + B + B * T1 * 3 + B * 3) * 4)
-        return fail(BN_ERR_STATE, "no bn_mppi_dwa_solve with this num_actions has run");
-    const float *d_X = h->d_scratch + n_act + n_goal;          // the scratch layout of bn_mppi_dwa_solve
-    if (states_all_device) *states_all_device = d_X;
-    if (costs_device) *costs_device = d_X + n_X;
-    if (weights_device) *weights_device = d_X + n_X + n_c;
-    return BN_OK;
-}
-
-int bn_mppi_dwa_candidates(bn_mppi_t *h, int32_t num_actions, const float **actions_device, const float **stage_goal_device)
-{
-    if (!h) return fail(BN_ERR_INVALID, "null handle");
-    if (num_actions < 1 || num_actions > 1024) return fail(BN_ERR_INVALID, "num_actions must be in [1, 1024]");
-    if (!h->d_scratch) return fail(BN_ERR_STATE, "no DWA solve has run");
-    if (actions_device) *actions_device = h->d_scratch;                                                    // (B, num_actions, 2)
-    if (stage_goal_device) *stage_goal_device = h->d_scratch + (size_t)h->p.B * num_actions * 2;            // (B, 2)
-    return BN_OK;
-}
-
-// ---- the A* + DWA closed loop (astar_dwa.hip) ----
-
-// root cells -1, statuses BN_AD_OK, status / done steps -1, error word 0 (allocates on first use)
-static int astar_dwa_clear(bn_mppi *h)
-{
-    const size_t B = h->p.B;
-    if (!h->d_ad_i) {
-        BN_HIP(hipMalloc((void **)&h->d_ad_i, (4 * B + 1) * sizeof(int32_t)));
-        BN_HIP(hipMalloc((void **)&h->d_ad_state, B * 3 * sizeof(float)));
-    }
-    BN_HIP(hipMemsetAsync(h->d_ad_i, 0xff, B * sizeof(int32_t), h->stream));
-    BN_HIP(hipMemsetAsync(h->d_ad_i + B, 0, B * sizeof(int32_t), h->stream));
-    BN_HIP(hipMemsetAsync(h->d_ad_i + 2 * B, 0xff, 2 * B * sizeof(int32_t), h->stream));
-    BN_HIP(hipMemsetAsync(h->d_ad_i + 4 * B, 0, sizeof(int32_t), h->stream));
-    h->ad_step = 0;
-    return BN_OK;
-}
-
-int bn_astar_dwa_reset(bn_mppi_t *h)
-{
-    if (!h) return fail(BN_ERR_INVALID, "null handle");
-    BN_BIND(h);
-    if (int rc = settle_point(h)) return rc;
-    return astar_dwa_clear(h);
-}
-
-int bn_astar_dwa_set_root(bn_mppi_t *h, int32_t instance, int32_t ix, int32_t iy)
-{
-    if (!h) return fail(BN_ERR_INVALID, "null handle");
-    if (instance < 0 || instance >= h->p.B) return fail(BN_ERR_INVALID, "instance out of range");
-    if (ix >= 0 && (ix >= h->p.G || iy < 0 || iy >= h->p.G)) return fail(BN_ERR_INVALID, "root cell out of bounds");
-    BN_BIND(h);
-    if (int rc = settle_point(h)) return rc;
-    if (!h->d_ad_i)
-        if (int rc = astar_dwa_clear(h)) return rc;
-    const int32_t cell = ix < 0 ? -1 : iy * h->p.G + ix;
-    BN_HIP(hipStreamSynchronize(h->stream));
-    BN_HIP(hipMemcpy(h->d_ad_i + instance, &cell, sizeof(int32_t), hipMemcpyHostToDevice));
-    return BN_OK;
-}
-
-int bn_astar_dwa_set_walk(bn_mppi_t *h, int32_t mode)
-{
-    if (!h) return fail(BN_ERR_INVALID, "null handle");
-    if (mode != 0 && mode != 1) return fail(BN_ERR_INVALID, "walk mode must be 0 (serial) or 1 (jump tables)");
-    h->ad_walk = mode;
-    return BN_OK;
-}
-
-int bn_astar_dwa_episode_async(bn_mppi_t *h, bn_astar_t *a, int32_t n_steps, const float *states0, bn_mem_kind where,
-                               float *prev_action_device, const float a_lim[2], float dwa_delta_t, int32_t num_lin_vel,
-                               int32_t num_ang_vel, float lookahead, const float *z_device)
-{
-    if (!h || !a || !states0 || !prev_action_device || !a_lim) return fail(BN_ERR_INVALID, "null argument");
-    if (n_steps < 1) return fail(BN_ERR_INVALID, "n_steps must be >= 1");
-    const int64_t NA = (int64_t)num_lin_vel * num_ang_vel;
-    if (num_lin_vel < 1 || num_ang_vel < 1 || NA > 1024) return fail(BN_ERR_INVALID, "num_lin_vel * num_ang_vel must be in [1, 1024]");
-    if (where != BN_MEM_HOST && where != BN_MEM_DEVICE) return fail(BN_ERR_INVALID, "unknown memory kind");
-    if (!h->env_attached) return fail(BN_ERR_STATE, "bn_mppi_env_attach must precede bn_astar_dwa_episode_async");
-    if (!h->map_set || !h->goal_set) return fail(BN_ERR_STATE, "set_map and set_goal must precede bn_astar_dwa_episode_async");
-    bn::AStarView v;
-    if (bn::astar_view(a, &v) != BN_OK) return fail(BN_ERR_STATE, "the A* handle has no solve: bn_astar_solve_async must precede the episode");
-    if (v.device != h->cfg.device_id) return fail(BN_ERR_INVALID, "the A* handle is on device %d, the planner on device %d", v.device, h->cfg.device_id);
-    if (v.B != h->p.B) return fail(BN_ERR_INVALID, "the A* handle has %d instances, the planner %d", v.B, h->p.B);
-    if (v.H != h->p.G || v.W != h->p.G) return fail(BN_ERR_INVALID, "the A* maps are %d x %d, the planner's grid is %d x %d", v.H, v.W, h->p.G, h->p.G);
-    if (h->ad_walk == 1 && !v.jump_current)
-        return fail(BN_ERR_STATE, "walk mode 1 needs current jump tables: bn_astar_jump_build_async must follow the A* handle's latest solve");
-    BN_BIND(h);
-    if (int rc = settle_point(h)) return rc;
-    if (int rc = flush_tail(h)) return rc;
-    if (int rc = guard_foreign_overlap(h)) return rc;
-    const size_t B = h->p.B, n = (size_t)n_steps;
-    if (!h->d_ad_i)
-        if (int rc = astar_dwa_clear(h)) return rc;
-    if (n_steps > h->ad_cap) {
-        BN_HIP(hipStreamSynchronize(h->stream));       // the log of the previous call may still be written
-        if (h->d_ad_log) BN_HIP(hipFree(h->d_ad_log));
-        h->d_ad_log = nullptr;
-        BN_HIP(hipMalloc((void **)&h->d_ad_log, ((n + 1) * 3 + n * 5) * B * sizeof(float)));
-        h->ad_cap = n_steps;
-    }
-    const hipMemcpyKind kind = where == BN_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    BN_HIP(hipMemcpyAsync(h->d_ad_state, states0, B * 3 * sizeof(float), kind, h->stream));
-    if (where == BN_MEM_HOST) BN_HIP(hipStreamSynchronize(h->stream));   // (pageable source: one upload, before the loop)
-    BN_HIP(hipStreamWaitEvent(h->stream, v.solved, 0));                 // behind a's latest solve, without the host
-    if (h->ad_walk == 1) BN_HIP(hipStreamWaitEvent(h->stream, v.jump_built, 0));   // ... and its table build
-    float *lg = h->d_ad_log;
-    const size_t cap = (size_t)h->ad_cap;                                 // the log's layout is by capacity (bn_astar_dwa_episode_log)
-    bn::AstarDwaArgs x{};
-    x.next = v.next; x.arisk = v.risk; x.ainst = v.inst; x.aerr = v.err; x.H = v.H; x.W = v.W;
-    if (h->ad_walk == 1) { x.hops = v.hops; x.jump = v.jump; x.jerr = v.jerr; x.levels = v.levels; }
-    x.state = h->d_ad_state; x.prev = prev_action_device;
-    x.root = h->d_ad_i; x.status = h->d_ad_i + B; x.status_step = h->d_ad_i + 2 * B; x.done = h->d_ad_i + 3 * B; x.err = h->d_ad_i + 4 * B;
-    x.log_states = lg; x.log_reward = lg + (cap + 1) * B * 3; x.log_action = x.log_reward + cap * B; x.log_subgoal = x.log_action + cap * B * 2;
-    x.z = z_device;
-    x.alim0 = a_lim[0]; x.alim1 = a_lim[1]; x.dwa_dt = dwa_delta_t; x.lookahead = lookahead;
-    x.nv = num_lin_vel; x.nw = num_ang_vel;
-    x.step0 = h->ad_step;
-    // chained launches on one stream.  A step walks the path twice at most (2 H W hops): the node budget keeps one launch short
-    // on large maps with long paths (64^2: 256 steps, 256^2: 16, 512^2: 4)
-    const int per_launch = (int)std::max<int64_t>(1, std::min<int64_t>(bn::kAstarDwaStepsPerLaunch,
-                                                                          bn::kAstarDwaNodesPerLaunch / ((int64_t)v.H * v.W)));
-    for (int s0 = 0; s0 < n_steps; s0 += per_launch) {
-        x.s0 = s0;
-        x.ns = std::min(per_launch, n_steps - s0);
-        BN_HIP(bn::launch_astar_dwa(h->p, x, h->stream));
-    }
-    if (bn::astar_add_reader(a, h->stream) != BN_OK) return fail(BN_ERR_HIP, "%s", bn_astar_last_error());
-    h->ad_step += n;
-    h->ad_len = n_steps;
-    return BN_OK;
-}
-
-int bn_astar_dwa_episode_log(bn_mppi_t *h, float *states, float *rewards, float *actions, float *sub_goals,
-                             int32_t *done_step, int32_t *status, int32_t *status_step)
-{
-    if (!h) return fail(BN_ERR_INVALID, "null handle");
-    if (!h->d_ad_log || h->ad_len < 1) return fail(BN_ERR_STATE, "no A* + DWA episode has been run");
-    BN_BIND(h);
-    if (int rc = settle_point(h)) return rc;
-    BN_HIP(hipStreamSynchronize(h->stream));
-    const size_t B = h->p.B, n = (size_t)h->ad_len, cap = (size_t)h->ad_cap;
-    const float *lg = h->d_ad_log, *rw = lg + (cap + 1) * B * 3, *ac = rw + cap * B, *sg = ac + cap * B * 2;
-    if (states) BN_HIP(hipMemcpy(states, lg, (n + 1) * B * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    if (rewards) BN_HIP(hipMemcpy(rewards, rw, n * B * sizeof(float), hipMemcpyDeviceToHost));
-    if (actions) BN_HIP(hipMemcpy(actions, ac, n * B * 2 * sizeof(float), hipMemcpyDeviceToHost));
-    if (sub_goals) BN_HIP(hipMemcpy(sub_goals, sg, n * B * 2 * sizeof(float), hipMemcpyDeviceToHost));
-    if (status) BN_HIP(hipMemcpy(status, h->d_ad_i + B, B * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (status_step) BN_HIP(hipMemcpy(status_step, h->d_ad_i + 2 * B, B * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (done_step) BN_HIP(hipMemcpy(done_step, h->d_ad_i + 3 * B, B * sizeof(int32_t), hipMemcpyDeviceToHost));
-    int32_t err = 0;
-    BN_HIP(hipMemcpy(&err, h->d_ad_i + 4 * B, sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (err) return fail(BN_ERR_STATE, "a next-hop walk broke (more than H*W nodes, or onto an unreachable cell): the A* field is not a valid solve");
-    return BN_OK;
-}
-
-// ---- the CL-RRT plan-follow-replan loop (clrrt_loop.hip) ----
-
-// what bn_clrrt_loop_reset verified once: the CL-RRT handle plans on the environment's grid
-static int clrrt_loop_view(bn_mppi *h, bn_clrrt_t *c, bn::ClrrtView *v)
-{
-    if (bn::clrrt_view(c, v) != BN_OK) return fail(BN_ERR_INVALID, "%s", bn_clrrt_last_error());
-    const bn_clrrt_config &k = v->cfg;
-    const bn::SolveParams &p = h->p;
-    if (v->device != h->cfg.device_id) return fail(BN_ERR_INVALID, "the CL-RRT handle is on device %d, the environment on device %d", v->device, h->cfg.device_id);
-    if (v->B != p.B) return fail(BN_ERR_INVALID, "the CL-RRT handle has %d instances, the environment %d", v->B, p.B);
-    if (k.grid_size != p.G || (float)k.resolution != p.res) return fail(BN_ERR_INVALID, "the CL-RRT handle's grid (%d cells of %g) is not the environment's (%d of %g)", k.grid_size, k.resolution, p.G, (double)p.res);
-    if ((float)k.x_limits[0] != p.x0 || (float)k.x_limits[1] != p.x_hi || (float)k.y_limits[0] != p.y0 || (float)k.y_limits[1] != p.y_hi)
-        return fail(BN_ERR_INVALID, "the CL-RRT handle's limits are not the environment's");
-    if ((float)k.u_min[0] != p.umin0 || (float)k.u_min[1] != p.umin1 || (float)k.u_max[0] != p.umax0 || (float)k.u_max[1] != p.umax1)
-        return fail(BN_ERR_INVALID, "the CL-RRT handle's action bounds are not the environment's");
-    if (!v->have_map) return fail(BN_ERR_STATE, "bn_clrrt_set_map must precede the loop");
-    return BN_OK;
-}
-
-int bn_clrrt_loop_reset(bn_mppi_t *h, bn_clrrt_t *c, const float *goal_nodes, const uint64_t *seeds, double delta_t, double time_limit)
-{
-    if (!h || !c || !goal_nodes || !seeds) return fail(BN_ERR_INVALID, "null argument");
-    if (!std::isfinite(time_limit)) return fail(BN_ERR_INVALID, "time_limit must be finite");
-    if (!h->env_attached) return fail(BN_ERR_STATE, "bn_mppi_env_attach must precede bn_clrrt_loop_reset");
-    if ((float)delta_t != h->p.env_dt) return fail(BN_ERR_INVALID, "delta_t (%g) is not the environment's (%g)", delta_t, (double)h->p.env_dt);
-    bn::ClrrtView v;
-    if (int rc = clrrt_loop_view(h, c, &v)) return rc;
-    BN_BIND(h);
-    if (int rc = settle_point(h)) return rc;
-    if (int rc = flush_tail(h)) return rc;
-    const size_t B = h->p.B;
-    if (!h->d_cl_rover) {
-        BN_HIP(hipMalloc((void **)&h->d_cl_rover, B * sizeof(bn::ClrrtRover)));
-        BN_HIP(hipMalloc((void **)&h->d_cl_flags, (B + 1) * sizeof(int32_t)));
-        BN_HIP(hipMalloc((void **)&h->d_cl_goal, B * 3 * sizeof(float)));
-        BN_HIP(hipHostMalloc((void **)&h->h_cl_pending, sizeof(int32_t), hipHostMallocDefault));
-        BN_HIP(hipEventCreate(&h->cl_ev[0]));
-        BN_HIP(hipEventCreate(&h->cl_ev[1]));
-    }
-    BN_HIP(hipStreamSynchronize(h->stream));                               // a previous episode's launches are done with the words below
-    std::vector<bn::ClrrtRover> r0(B, bn::ClrrtRover{0, BN_CL_RUNNING, 1, 0, 0, 0, 0, -1});
-    BN_HIP(hipMemcpy(h->d_cl_rover, r0.data(), B * sizeof(bn::ClrrtRover), hipMemcpyHostToDevice));
-    BN_HIP(hipMemset(h->d_cl_flags, 0, (B + 1) * sizeof(int32_t)));
-    BN_HIP(hipMemcpy(h->d_cl_goal, goal_nodes, B * 3 * sizeof(float), hipMemcpyHostToDevice));
-    if (bn::clrrt_loop_reset(c, h->stream, goal_nodes, seeds) != BN_OK) return fail(BN_ERR_INVALID, "%s", bn_clrrt_last_error());
-    // PlanetaryEnv: elapsed += delta_t in float64, elapsed > time_limit after the step: the first step count at which that holds
-    double elapsed = 0.0;
-    int32_t k = 0;
-    const double dt = delta_t;                     // the Python float, not its float32 rounding: 5 x 0.1 is exactly 0.5, 5 x 0.1f is above it
-    if (dt > 0.0) {
-        while (!(elapsed > time_limit) && k < INT32_MAX) { elapsed += dt; ++k; }
-    } else {
-        k = INT32_MAX;
-    }
-    h->cl_limit_steps = k;
-    h->cl_iter = 0;
-    h->cl_len = 0;
-    h->cl_ready = true;
-    h->cl_planner = c;
-    return BN_OK;
-}
-
-int bn_clrrt_loop_run(bn_mppi_t *h, bn_clrrt_t *c, int32_t n, float *states_device, const float *z_device,
-                      const float *samples_device, int32_t num_tables, uint32_t flags, float *follow_ms)
-{
-    if (!h || !c || !states_device) return fail(BN_ERR_INVALID, "null argument");
-    if (n < 1 || n > (1 << 24)) return fail(BN_ERR_INVALID, "n must be in [1, 2^24]");
-    if (num_tables < 0) return fail(BN_ERR_INVALID, "num_tables must be >= 0");
-    if (!h->cl_ready) return fail(BN_ERR_STATE, "bn_clrrt_loop_reset must precede bn_clrrt_loop_run");
-    if (c != h->cl_planner) return fail(BN_ERR_INVALID, "this is not the CL-RRT handle bn_clrrt_loop_reset was given: the episode's goals, streams and plans live in that one");
-    if (!h->env_attached || !h->goal_set) return fail(BN_ERR_STATE, "bn_mppi_env_attach and the goals must precede bn_clrrt_loop_run");
-    if ((int64_t)h->cl_iter + n > INT32_MAX) return fail(BN_ERR_INVALID, "the episode's iteration count exceeds 2^31 - 1");
-    bn::ClrrtView v;
-    if (int rc = clrrt_loop_view(h, c, &v)) return rc;
-    BN_BIND(h);
-    if (int rc = settle_point(h)) return rc;
-    if (int rc = flush_tail(h)) return rc;
-    if (int rc = guard_foreign_overlap(h)) return rc;
-    const size_t B = h->p.B, N = (size_t)n;
-    if (n > h->cl_cap) {
-        BN_HIP(hipStreamSynchronize(h->stream));
-        if (h->d_cl_log) BN_HIP(hipFree(h->d_cl_log));
-        h->d_cl_log = nullptr;
-        BN_HIP(hipMalloc((void **)&h->d_cl_log, ((N + 1) * 3 + N * 6) * B * sizeof(float)));
-        h->cl_cap = n;
-    }
-    const size_t cap = (size_t)h->cl_cap;
-    bn::ClrrtFollowArgs x{};
-    x.rover = h->d_cl_rover; x.state = states_device; x.starts = v.starts; x.goal_nodes = h->d_cl_goal;
-    x.path_actions = v.path_actions; x.path_states = v.path_states; x.results = v.results;
-    x.active = h->d_cl_flags; x.pending = h->d_cl_flags + B; x.psamples = v.samples;
-    x.inj = samples_device; x.P = samples_device ? num_tables : 0; x.iters = v.iters; x.path_cap = v.path_cap;
-    float *lg = h->d_cl_log;
-    x.log_states = lg; x.log_reward = lg + (cap + 1) * B * 3; x.log_action = x.log_reward + cap * B; x.log_dev = x.log_action + cap * B * 2;
-    x.log_plan = reinterpret_cast<int32_t *>(x.log_dev + cap * B); x.log_event = x.log_plan + cap * B;
-    x.z = z_device; x.iter0 = h->cl_iter; x.n = n; x.limit_steps = h->cl_limit_steps; x.use_lds = (flags & 1u) ? 0 : 1;
-    x.xlo = v.cfg.x_limits[0]; x.xhi = v.cfg.x_limits[1]; x.ylo = v.cfg.y_limits[0]; x.yhi = v.cfg.y_limits[1];
-    float ms_total = 0.0f;
-    // One host round trip per ROUND of replans: every pending rover takes its plan and at least one iteration (or a status) in the
-    // next follow launch, so n + 2 rounds bound the loop.
-    for (int64_t round = 0; round < (int64_t)n + 2; ++round) {
-        if (follow_ms) BN_HIP(hipEventRecord(h->cl_ev[0], h->stream));
-        BN_HIP(bn::launch_clrrt_follow(h->p, x, h->stream));
-        if (follow_ms) BN_HIP(hipEventRecord(h->cl_ev[1], h->stream));
-        BN_HIP(hipMemcpyAsync(h->h_cl_pending, h->d_cl_flags + B, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-        BN_HIP(hipStreamSynchronize(h->stream));
-        if (follow_ms) {
-            float ms = 0.0f;
-            BN_HIP(hipEventElapsedTime(&ms, h->cl_ev[0], h->cl_ev[1]));
-            ms_total += ms;
-        }
-        if (*h->h_cl_pending == 0) break;
-        if (bn::clrrt_plan_masked(c, h->stream, h->d_cl_flags, samples_device ? 0 : 1) != BN_OK) return fail(BN_ERR_HIP, "%s", bn_clrrt_last_error());
-        BN_HIP(hipMemsetAsync(h->d_cl_flags + B, 0, sizeof(int32_t), h->stream));     // (the follow kernel clears the mask words it takes)
-    }
-    if (follow_ms) *follow_ms = ms_total;
-    h->cl_iter += n;
-    h->cl_len = n;
-    return BN_OK;
-}
-
-int bn_clrrt_loop_log(bn_mppi_t *h, float *states, float *rewards, float *actions, float *deviations, int32_t *plan_index,
-                      int32_t *events, int32_t *done_iter, int32_t *status, int32_t *plans, int32_t *steps)
-{
-    if (!h) return fail(BN_ERR_INVALID, "null handle");
-    if (!h->d_cl_log || h->cl_len < 1) return fail(BN_ERR_STATE, "no CL-RRT loop has been run");
-    BN_BIND(h);
-    if (int rc = settle_point(h)) return rc;
-    BN_HIP(hipStreamSynchronize(h->stream));
-    const size_t B = h->p.B, n = (size_t)h->cl_len, cap = (size_t)h->cl_cap;
-    const float *lg = h->d_cl_log, *rw = lg + (cap + 1) * B * 3, *ac = rw + cap * B, *dv = ac + cap * B * 2, *pl = dv + cap * B, *ev = pl + cap * B;
-    if (states) BN_HIP(hipMemcpy(states, lg, (n + 1) * B * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    if (rewards) BN_HIP(hipMemcpy(rewards, rw, n * B * sizeof(float), hipMemcpyDeviceToHost));
-    if (actions) BN_HIP(hipMemcpy(actions, ac, n * B * 2 * sizeof(float), hipMemcpyDeviceToHost));
-    if (deviations) BN_HIP(hipMemcpy(deviations, dv, n * B * sizeof(float), hipMemcpyDeviceToHost));
-    if (plan_index) BN_HIP(hipMemcpy(plan_index, pl, n * B * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (events) BN_HIP(hipMemcpy(events, ev, n * B * sizeof(int32_t), hipMemcpyDeviceToHost));
-    std::vector<bn::ClrrtRover> r(B);
-    BN_HIP(hipMemcpy(r.data(), h->d_cl_rover, B * sizeof(bn::ClrrtRover), hipMemcpyDeviceToHost));
-    for (size_t b = 0; b < B; ++b) {
-        if (done_iter) done_iter[b] = r[b].done_iter;
-        if (status) status[b] = r[b].status;
-        if (plans) plans[b] = r[b].plans;
-        if (steps) steps[b] = r[b].steps;
-    }
-    return BN_OK;
-}
-
-int bn_clrrt_loop_set_plans(bn_mppi_t *h, bn_clrrt_t *c, const float *actions, const float *states, const int32_t *lengths,
-                            int32_t max_length, int32_t iteration)
-{
-    if (!h || !c || !actions || !states || !lengths) return fail(BN_ERR_INVALID, "null argument");
-    if (!h->cl_ready) return fail(BN_ERR_STATE, "bn_clrrt_loop_reset must precede bn_clrrt_loop_set_plans");
-    if (c != h->cl_planner) return fail(BN_ERR_INVALID, "this is not the CL-RRT handle bn_clrrt_loop_reset was given: the episode's goals, streams and plans live in that one");
-    bn::ClrrtView v;
-    if (int rc = clrrt_loop_view(h, c, &v)) return rc;
-    if (max_length < 1 || max_length > v.path_cap) return fail(BN_ERR_INVALID, "max_length must be in [1, path_cap = %d]", v.path_cap);
-    const size_t B = h->p.B, Lm = (size_t)max_length;
-    for (size_t b = 0; b < B; ++b)
-        if (lengths[b] < 1 || lengths[b] > max_length) return fail(BN_ERR_INVALID, "lengths must be in [1, max_length]");
-    BN_BIND(h);
-    if (int rc = settle_point(h)) return rc;
-    BN_HIP(hipStreamSynchronize(h->stream));
-    std::vector<bn::ClrrtRover> r(B);
-    BN_HIP(hipMemcpy(r.data(), h->d_cl_rover, B * sizeof(bn::ClrrtRover), hipMemcpyDeviceToHost));
-    for (size_t b = 0; b < B; ++b) {
-        BN_HIP(hipMemcpy(v.path_actions + b * (size_t)v.path_cap * 2, actions + b * Lm * 2, (size_t)lengths[b] * 2 * sizeof(float), hipMemcpyHostToDevice));
-        BN_HIP(hipMemcpy(v.path_states + b * ((size_t)v.path_cap + 1) * 3, states + b * (Lm + 1) * 3, ((size_t)lengths[b] + 1) * 3 * sizeof(float), hipMemcpyHostToDevice));
-        r[b].need = 0; r[b].aidx = 0; r[b].length = lengths[b];
-        if (iteration >= 0) r[b].iter = iteration;
-    }
-    BN_HIP(hipMemcpy(h->d_cl_rover, r.data(), B * sizeof(bn::ClrrtRover), hipMemcpyHostToDevice));
-    BN_HIP(hipMemset(h->d_cl_flags, 0, (B + 1) * sizeof(int32_t)));
-    if (iteration >= 0) h->cl_iter = iteration;
-    return BN_OK;
-}
-
 int bn_mppi_sync(bn_mppi_t *h)
 {
     if (!h) return fail(BN_ERR_INVALID, "null handle");
@@ -2802,94 +1387,6 @@ int32_t bn_mppi_overlap_mode(const bn_mppi_t *h)
     if (!capable) return 3;
     if (h->overlap_off) return 2;
     return h->tune.chosen ? 1 : 0;
-}
-
-int bn_mppi_debug_cadence(bn_mppi_t *h, int32_t mode, double us_per_launch)
-{
-    if (!h || mode < 0 || mode > 1 || !(us_per_launch > 0)) return fail(BN_ERR_INVALID, "bad argument");
-    tune_record(h, mode, us_per_launch);
-    return h->tune.explore ? 1 : 0;
-}
-
-int bn_mppi_first_action(bn_mppi_t *h, int32_t instance, float action_host[2])
-{
-    if (int rc = check_instance(h, instance, false)) return rc;
-    if (!action_host) return fail(BN_ERR_INVALID, "null output");
-    if (h->solves == 0) return fail(BN_ERR_STATE, "no solve has run");
-    if (h->shard_pending) return fail(BN_ERR_STATE, "a sharded solve waits for bn_mppi_shard_finish_async");
-    BN_BIND_Q(h);                                           // (the mailbox lives on the host: nothing of the handle's stream is touched, nothing to order)
-    if (int rc = flush_tail(h)) return rc;                  // the tail is what posts it
-    // The tail writes U*[0] to pinned host memory as soon as its merge is done -- two {value, tag} granules, tag = solve index + 1
-    // -- and goes on with X* and the weights; the host polls the granules: no stream synchronisation, no copy.
-    uint32_t want = (uint32_t)(h->solves - (h->hp_armed ? 1 : 0));      // (a launch that waits for the NEXT state is not the latest solve)
-    const volatile unsigned long long *m = h->h_mail + 2 * (size_t)instance;
-    for (long it = 0;; ++it) {
-        if ((it & 0xff) == 0xff && h->hp_posted_tag && hp_gave_up(h, h->hp_posted_tag)) {      // host-paced: the request went to a launch that had just given up
-            if (int rc = hp_redo(h)) return rc;
-            want = (uint32_t)(h->solves - (h->hp_armed ? 1 : 0));
-        }
-
-        const unsigned long long a = m[0], b = m[1];
-        if ((uint32_t)(a >> 32) == want && (uint32_t)(b >> 32) == want) {
-            const uint32_t ua = (uint32_t)a, ub = (uint32_t)b;
-            std::memcpy(action_host, &ua, 4); std::memcpy(action_host + 1, &ub, 4);
-            break;
-        }
-        if ((it & 0xfff) == 0xfff) {                        // every few microseconds: is the stream still working on it?
-            const hipError_t q = hipStreamQuery(h->stream);
-            (void)hipGetLastError();
-            if (q == hipSuccess && it > (1L << 22)) return fail(BN_ERR_HIP, "the stream is idle but the first action of solve %llu never arrived",
-                                                                 (unsigned long long)h->solves - 1);
-            if (q != hipSuccess && q != hipErrorNotReady) return fail(BN_ERR_HIP, "the stream failed while waiting for the first action");
-        }
-    }
-    if (int rc = self_check(h)) return rc;                  // (a one-launch solve: its tail's wait ended before it posted)
-    if (h->overlap_used && __atomic_load_n(h->h_err, __ATOMIC_ACQUIRE)) {   // an expired wait upstream: repair, then read the repaired value
-        if (int rc = settle_point(h)) return rc;
-        const unsigned long long a = m[0], b = m[1];
-        const uint32_t ua = (uint32_t)a, ub = (uint32_t)b;
-        std::memcpy(action_host, &ua, 4); std::memcpy(action_host + 1, &ub, 4);
-    }
-    return BN_OK;
-}
-
-int bn_mppi_debug_expire_wait(bn_mppi_t *h)
-{
-    // Test hook: behave as if a wait had expired in the batches enqueued since the last synchronisation point -- the error word is
-    // set and everything those batches wrote (mean, U* | X*, weights, costs, trajectories) is overwritten with NaN patterns, so a
-    // caller that gets valid results afterwards got them from the re-run.
-    if (!h) return fail(BN_ERR_INVALID, "null handle");
-    BN_BIND(h);
-    hp_cancel(h);
-    if (int rc = flush_tail(h)) return rc;
-    BN_HIP(hipStreamSynchronize(h->stream));
-    const size_t B = h->p.B, K = h->p.K, T = h->p.T;
-    BN_HIP(hipMemset(h->d_mean, 0xff, B * T * 2 * 4));
-    BN_HIP(hipMemset(h->d_ustar, 0xff, (B * T * 2 + B * (T + 1) * 3) * 4));
-    BN_HIP(hipMemset(h->d_w, 0xff, B * K * 4));
-    BN_HIP(hipMemset(h->d_cost_out, 0xff, B * K * 4));
-    if (h->d_X) BN_HIP(hipMemset(h->d_X, 0xff, B * (T + 1) * 3 * (size_t)h->p.Kp * 4));
-    if (h->d_ticket) BN_HIP(hipMemset(h->d_ticket, 0x01, B * 65 * 4));      // what two launches drawing tickets at once leave behind (recover_overlap)
-    if (h->d_ep_states && h->ep_len > 0) {
-        BN_HIP(hipMemset(h->d_ep_states, 0xff, (size_t)(h->ep_len + 1) * B * 3 * 4));
-        BN_HIP(hipMemset(h->d_ep_reward, 0xff, (size_t)h->ep_len * B * 4));
-        BN_HIP(hipMemset(h->d_ep_action, 0xff, (size_t)h->ep_len * B * 2 * 4));
-    }
-    *h->h_err = 1;
-    h->overlap_used = true;
-    return BN_OK;
-}
-
-int bn_mppi_debug_host_paced(bn_mppi_t *h, int32_t polls, int32_t post_unchecked)
-{
-    // Test hook: how many looks (~2 us each) a prelaunched solve waits for its state before it gives up (default 25000), and whether the
-    // host posts without checking that the launch is still there -- with one look the launch is gone before any host can answer, and
-    // an unchecked post lands in the repair path of bn_mppi_first_action.
-    if (!h) return fail(BN_ERR_INVALID, "null handle");
-    if (polls < 1) return fail(BN_ERR_INVALID, "polls must be >= 1");
-    h->hp_polls = polls;
-    h->hp_skip_check = post_unchecked != 0;
-    return BN_OK;
 }
 
 int bn_mppi_flush(bn_mppi_t *h)
@@ -2920,293 +1417,7 @@ int bn_mppi_solve(bn_mppi_t *h, const float *states, bn_mem_kind states_where, c
     return self_check(h);
 }
 
-// Rows of the latest solve's trajectory batch, regenerated (launch_reroll).  The tail of that solve must have run
-// (mean_used, state copy); the caller's eps block of that solve must still be alive when the noise was injected.
-static int reroll_rows(bn_mppi_t *h, int32_t instance, const int *idx_device, int32_t n, float *out_device)
-{
-    if (h->p.slip_on) return fail(BN_ERR_INVALID, "re-rolling is not available in sampled-slip mode");
-    if (h->solves == 0) return fail(BN_ERR_STATE, "no solve has run");
-    if (h->shard_pending) return fail(BN_ERR_STATE, "a sharded solve waits for bn_mppi_shard_finish_async");
-    // The rows are rolled out again on the map as it is NOW: after a bn_mppi_set_map they would not be the latest solve's rollouts
-    // (the reference's get_top_samples returns the batch forward() stored, mppi.py:221-240) -- refuse instead of answering for another map.
-    if (h->map_epoch != h->map_epoch_at_solve)
-        return fail(BN_ERR_STATE, "the map changed since the latest solve: its rollouts cannot be regenerated (read them before bn_mppi_set_map, or solve again)");
-    if (int rc = flush_tail(h)) return rc;
-    bn::SolveParams p = h->p;
-    const int cur = (int)((h->solves - 1) % kSlots);
-    p.solve = h->solves - 1;
-    p.state = h->d_state_copy[cur];
-    p.eps = h->last_eps;
-    if (int rc = guard_foreign_overlap(h)) return rc;
-    BN_HIP(bn::launch_reroll(p, h->last_mode, instance, idx_device, n, out_device, h->stream));
-    return BN_OK;
-}
-
-int bn_mppi_reroll_async(bn_mppi_t *h, int32_t instance, const int32_t *idx_device, int32_t n, float *out_device)
-{
-    if (int rc = check_instance(h, instance, false)) return rc;
-    if (n < 0 || (!idx_device && n > h->p.K)) return fail(BN_ERR_INVALID, "n=%d out of range", n);
-    if (n == 0) return BN_OK;
-    if (!out_device) return fail(BN_ERR_INVALID, "null output");
-    BN_BIND(h);
-    if (int rc = settle_point(h)) return rc;
-    return reroll_rows(h, instance, idx_device, n, out_device);
-}
-
-static int copy_out(bn_mppi_t *h, int32_t instance, const float *dev, size_t per_instance, float *out_host)
-{
-    if (int rc = check_instance(h, instance, false)) return rc;
-    if (!out_host) return fail(BN_ERR_INVALID, "null output");
-    BN_BIND(h);
-    if (int rc = settle_point(h)) return rc;
-    if (int rc = flush_tail(h)) return rc;
-    BN_HIP(hipStreamSynchronize(h->stream));
-    BN_HIP(hipMemcpy(out_host, dev + (size_t)instance * per_instance, per_instance * 4, hipMemcpyDeviceToHost));
-    return BN_OK;
-}
-
-int bn_mppi_get_weights(bn_mppi_t *h, int32_t instance, float *out_host)
-{
-    return h ? copy_out(h, instance, h->d_w, h->p.K, out_host) : fail(BN_ERR_INVALID, "null handle");
-}
-
-int bn_mppi_get_costs(bn_mppi_t *h, int32_t instance, float *out_host)
-{
-    return h ? copy_out(h, instance, h->d_cost_out, h->p.K, out_host) : fail(BN_ERR_INVALID, "null handle");
-}
-
-int bn_mppi_get_states(bn_mppi_t *h, int32_t instance, float *out_host)
-{
-    if (int rc = check_instance(h, instance, false)) return rc;
-    if (!out_host) return fail(BN_ERR_INVALID, "null output");
-    BN_BIND(h);
-    if (int rc = settle_point(h)) return rc;
-    const size_t K = h->p.K, Kp = h->p.Kp, T1 = h->p.T + 1, n = K * T1 * 3;
-    if (int rc = ensure_scratch(h, n * 4)) return rc;
-    if (h->p.lean) {                                   // not materialised: regenerate all K rows
-        if (int rc = reroll_rows(h, instance, nullptr, (int32_t)K, h->d_scratch)) return rc;
-    } else
-    BN_HIP(bn::launch_states_to_reference((h->x_idx && h->d_Xalt[0] ? h->d_Xalt[0] : h->d_X) + (size_t)instance * Kp * T1 * 3, h->d_scratch, (int)K, (int)Kp, (int)T1,
-                                          h->stream));
-    BN_HIP(hipMemcpyAsync(out_host, h->d_scratch, n * 4, hipMemcpyDeviceToHost, h->stream));
-    BN_HIP(hipStreamSynchronize(h->stream));
-    return BN_OK;
-}
-
-int bn_mppi_get_controls(bn_mppi_t *h, int32_t instance, float *out_host)
-{
-    if (int rc = check_instance(h, instance, false)) return rc;
-    if (!out_host) return fail(BN_ERR_INVALID, "null output");
-    if (!h->d_U || !h->p.store_u) return fail(BN_ERR_STATE, "controls are only stored with BN_FLAG_STORE_CONTROLS");
-    BN_BIND(h);
-    if (int rc = settle_point(h)) return rc;
-    const size_t K = h->p.K, Kp = h->p.Kp, T = h->p.T, n = K * T * 2;
-    if (int rc = ensure_scratch(h, n * 4)) return rc;
-    BN_HIP(bn::launch_controls_to_reference((h->x_idx && h->d_Ualt[0] ? h->d_Ualt[0] : h->d_U) + (size_t)instance * Kp * T * 2, h->d_scratch, (int)K, (int)Kp, (int)T,
-                                            h->stream));
-    BN_HIP(hipMemcpyAsync(out_host, h->d_scratch, n * 4, hipMemcpyDeviceToHost, h->stream));
-    BN_HIP(hipStreamSynchronize(h->stream));
-    return BN_OK;
-}
-
-int bn_mppi_get_philox_noise(bn_mppi_t *h, int32_t instance, uint64_t solve_index, float *out_host)
-{
-    if (int rc = check_instance(h, instance, false)) return rc;
-    if (!out_host) return fail(BN_ERR_INVALID, "null output");
-    BN_BIND(h);
-    if (int rc = settle_point(h)) return rc;
-    const size_t n = (size_t)h->p.K * h->p.T * 2;
-    if (int rc = ensure_scratch(h, n * 4)) return rc;
-    BN_HIP(bn::launch_philox_noise(h->d_scratch, h->p.seed, solve_index, instance, h->p.K, h->p.T, h->p.k0, h->stream));
-    BN_HIP(hipMemcpyAsync(out_host, h->d_scratch, n * 4, hipMemcpyDeviceToHost, h->stream));
-    BN_HIP(hipStreamSynchronize(h->stream));
-    return BN_OK;
-}
-
-int bn_mppi_get_slip_noise(bn_mppi_t *h, int32_t instance, uint64_t solve_index, float *zt_host, float *zc_host, float *zo_host)
-{
-    if (int rc = check_instance(h, instance, false)) return rc;
-    if (!zt_host || !zc_host || !zo_host) return fail(BN_ERR_INVALID, "null output");
-    if (!h->p.slip_on) return fail(BN_ERR_STATE, "handle was created without BN_FLAG_SAMPLED_SLIP");
-    BN_BIND(h);
-    const size_t K = h->p.K, T = h->p.T, nt = K * T, nc = K * (T + 1);
-    if (int rc = ensure_scratch(h, (nt + nc + T) * 4)) return rc;
-    float *zt = h->d_scratch, *zc = zt + nt, *zo = zc + nc;
-    BN_HIP(bn::launch_philox_slip(zt, zc, zo, h->p.seed, solve_index, instance, (int)K, (int)T, h->p.k0, h->stream));
-    BN_HIP(hipMemcpyAsync(zt_host, zt, nt * 4, hipMemcpyDeviceToHost, h->stream));
-    BN_HIP(hipMemcpyAsync(zc_host, zc, nc * 4, hipMemcpyDeviceToHost, h->stream));
-    BN_HIP(hipMemcpyAsync(zo_host, zo, T * 4, hipMemcpyDeviceToHost, h->stream));
-    BN_HIP(hipStreamSynchronize(h->stream));
-    return BN_OK;
-}
-
-int bn_mppi_get_top_samples(bn_mppi_t *h, int32_t instance, int32_t n, float *states_host, float *weights_host)
-{
-    if (int rc = check_instance(h, instance, false)) return rc;
-    if (n < 0 || n > h->p.K) return fail(BN_ERR_INVALID, "n=%d must satisfy 0 <= n <= K=%d", n, h->p.K);  // mppi.py:229
-    if (n == 0) return BN_OK;
-    if (!states_host || !weights_host) return fail(BN_ERR_INVALID, "null output");
-    BN_BIND(h);
-    if (int rc = settle_point(h)) return rc;
-    const size_t K = h->p.K, T1 = h->p.T + 1;
-    std::vector<float> w(K);
-    if (int rc = flush_tail(h)) return rc;
-    BN_HIP(hipStreamSynchronize(h->stream));
-    BN_HIP(hipMemcpy(w.data(), h->d_w + (size_t)instance * K, K * 4, hipMemcpyDeviceToHost));
-    std::vector<int> idx(K);
-    std::iota(idx.begin(), idx.end(), 0);
-    // topk + descending sort (mppi.py:232-238); ties resolved by the lower rollout index
-    std::partial_sort(idx.begin(), idx.begin() + n, idx.end(),
-                      [&](int a, int b) { return w[a] > w[b] || (w[a] == w[b] && a < b); });
-    if ((size_t)n > h->idx_count) {
-        if (h->d_idx) BN_HIP(hipFree(h->d_idx));
-        h->d_idx = nullptr; h->idx_count = 0;
-        BN_HIP(hipMalloc((void **)&h->d_idx, (size_t)n * sizeof(int)));
-        h->idx_count = n;
-    }
-    if (int rc = ensure_scratch(h, (size_t)n * T1 * 3 * 4)) return rc;
-    BN_HIP(hipMemcpyAsync(h->d_idx, idx.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    if (h->p.lean) {                                   // the n winners are re-rolled, bit-identical to a stored batch
-        if (int rc = reroll_rows(h, instance, h->d_idx, n, h->d_scratch)) return rc;
-    } else
-    BN_HIP(bn::launch_gather_states((h->x_idx && h->d_Xalt[0] ? h->d_Xalt[0] : h->d_X) + (size_t)instance * h->p.Kp * T1 * 3, h->d_idx, h->d_scratch, n, h->p.Kp,
-                                    (int)T1, h->stream));
-    BN_HIP(hipMemcpyAsync(states_host, h->d_scratch, (size_t)n * T1 * 3 * 4, hipMemcpyDeviceToHost, h->stream));
-    BN_HIP(hipStreamSynchronize(h->stream));
-    for (int i = 0; i < n; ++i) weights_host[i] = w[idx[i]];
-    return BN_OK;
-}
-
-int bn_mppi_device_buffer(bn_mppi_t *h, bn_buffer_id id, void **device_ptr, size_t *bytes)
-{
-    if (!h || !device_ptr) return fail(BN_ERR_INVALID, "null argument");
-    if (h->shard_tail_inflight) {                     // a library-enqueued sharded solve: order the handle's stream behind its tail first
-        BN_BIND(h);
-        if (int rc = flush_tail(h)) return rc;
-    }
-    void *ptrs[BN_BUF_COUNT_] = {h->d_X, h->d_w, h->d_cost_out, h->d_U, h->d_ustar, h->d_xstar, h->d_mean, h->d_map, h->d_goal, h->d_ustar,
-                                 h->d_Xalt[0], h->d_Ualt[0]};
-    if ((int)id < 0 || id >= BN_BUF_COUNT_) return fail(BN_ERR_INVALID, "unknown buffer id %d", (int)id);
-    *device_ptr = ptrs[id];
-    if (bytes) *bytes = buffer_bytes(h, id);
-    if (!ptrs[id]) return fail(BN_ERR_STATE, "buffer %d is not allocated in this configuration", (int)id);
-    return BN_OK;
-}
-
 uint64_t bn_mppi_solve_count(const bn_mppi_t *h) { return h ? h->solves - (h->hp_armed ? 1 : 0) : 0; }
-int32_t bn_mppi_host_paced(const bn_mppi_t *h) { return h ? (h->hp_enabled ? (h->req_bar ? 2 : 1) : 0) : -1; }
-int32_t bn_mppi_states_buffer_index(const bn_mppi_t *h) { return h ? h->x_idx : -1; }
-
-int32_t bn_mppi_arithmetic(const bn_mppi_t *h) { return h ? h->p.ref_order : -1; }
-int32_t bn_mppi_fast_quotient(const bn_mppi_t *h) { return h ? (h->p.pow2 ? 2 : h->p.fast_div) : -1; }
-int32_t bn_mppi_launches_per_solve(const bn_mppi_t *h) { return h ? ((h->pipelined || h->ticket_mode) ? 1 : 2) : -1; }
-int32_t bn_mppi_launches_per_forward(const bn_mppi_t *h)
-{
-    return h ? ((h->lat_kernel && h->pipelined && !h->self_off && !(h->cfg.flags & BN_FLAG_NO_PIPELINE)) ? 1 : 2) : -1;
-}
-
-int32_t bn_mppi_row_pitch(const bn_mppi_t *h) { return h ? h->p.Kp : 0; }
-
-int bn_mppi_kernel_ms(bn_mppi_t *h, float *rollout_ms, float *finish_ms, int32_t *n_solves)
-{
-    if (!h) return fail(BN_ERR_INVALID, "null handle");
-    if (!(h->cfg.flags & BN_FLAG_PROFILE)) return fail(BN_ERR_STATE, "handle was created without BN_FLAG_PROFILE");
-    BN_BIND(h);
-    if (int rc = settle_point(h)) return rc;
-    if (h->pipelined || h->ticket_mode) {
-        // close the open group with one more event *before* the flush, then average complete groups only
-        const int open = h->prof_in_group;
-        if (h->ev_used + 1 > h->ev.size()) {
-            hipEvent_t e;
-            BN_HIP(hipEventCreate(&e));
-            h->ev.push_back(e);
-        }
-        BN_HIP(hipEventRecord(h->ev[h->ev_used++], h->stream));
-        if (int rc = flush_tail(h)) return rc;
-        BN_HIP(hipStreamSynchronize(h->stream));
-        const size_t marks = h->ev_used;                  // marks-1 intervals; the last one holds `open` launches (or a full group)
-        double tot = 0.0;
-        size_t launches = 0;
-        for (size_t i = 0; i + 1 < marks; ++i) {
-            const bool last = (i + 2 == marks);
-            const int in_this = (last && open != 0) ? open : kProfGroup;
-            if (last && open != 0) break;                 // skip the ragged last group
-            float a = 0.0f;
-            BN_HIP(hipEventElapsedTime(&a, h->ev[i], h->ev[i + 1]));
-            tot += a;
-            launches += in_this;
-        }
-        if (rollout_ms) *rollout_ms = launches ? (float)(tot / launches) : 0.0f;
-        if (finish_ms) *finish_ms = 0.0f;
-        if (n_solves) *n_solves = (int32_t)launches;
-        h->ev_used = 0;
-        h->prof_in_group = 0;
-        return BN_OK;
-    }
-    if (int rc = flush_tail(h)) return rc;
-    BN_HIP(hipStreamSynchronize(h->stream));
-    double r = 0.0, f = 0.0;
-    const size_t n = h->ev_used / 3;
-    for (size_t i = 0; i < n; ++i) {
-        float a = 0.0f, b = 0.0f;
-        BN_HIP(hipEventElapsedTime(&a, h->ev[3 * i], h->ev[3 * i + 1]));
-        BN_HIP(hipEventElapsedTime(&b, h->ev[3 * i + 1], h->ev[3 * i + 2]));
-        r += a; f += b;
-    }
-    if (rollout_ms) *rollout_ms = n ? (float)(r / n) : 0.0f;
-    if (finish_ms) *finish_ms = n ? (float)(f / n) : 0.0f;
-    if (n_solves) *n_solves = (int32_t)n;
-    h->ev_used = 0;
-    return BN_OK;
-}
-
-int64_t bn_mppi_algorithmic_bytes(const bn_mppi_t *h, bn_noise_kind noise)
-{
-    if (!h) return 0;
-    const int64_t K = h->p.K, T = h->p.T, G = h->p.G;
-    int64_t bytes = 4 * G * G            // risk map read once
-                    + (8 * T + 12)       // mean, state
-                    + (h->p.lean ? 0 : 12 * K * (T + 1))   // _state_seq_batch write (not in lean mode)
-                    + 4 * K              // weights write
-                    + 8 * T + 12 * (T + 1);   // U*, X* write
-    if (noise != BN_NOISE_PHILOX) bytes += 8 * K * T;   // injected noise read
-    if (h->p.store_u) bytes += 8 * K * T;               // _perturbed_action_seqs write
-    return bytes;
-}
-
-/* The same with the map term replaced by what a solve can reach: the LDS window of (WN x WN) cells around the start state, staged
- * once per instance in the best case (every rollout workgroup stages its own copy; the copies hit in L2).  With BN_FLAG_LEAN the
- * map read is most of SURVEY 8d's lean formula, and a kernel that reads the window only would be credited for bytes it never
- * moves: bench.py reports both fractions. */
-int64_t bn_mppi_algorithmic_bytes_window(const bn_mppi_t *h, bn_noise_kind noise)
-{
-    if (!h) return 0;
-    const int64_t G = h->p.G, W = h->p.WN > 0 ? h->p.WN : G;
-    return bn_mppi_algorithmic_bytes(h, noise) - 4 * G * G + 4 * W * W;
-}
-
-#ifdef BN_TIMING
-int bn_mppi_debug_blocks_per_cu(bn_mppi_t *h) { return bn::rollout_blocks_per_cu(h->p); }
-/* tools/ablate.py only: device buffer of >= 16 uint64 for the in-kernel cycle stamps */
-void bn_mppi_debug_set_stamps(bn_mppi_t *h, void *device_ptr) { h->p.stamps = (unsigned long long *)device_ptr; }
-void bn_mppi_debug_trace_by_parity(bn_mppi_t *h, int on) { h->p.trace_by_parity = on; }
-#endif
-
-int bn_device_math_eval(int32_t fn, const float *in_device, float *out_device, int64_t n, void *stream)
-{
-    if (fn < 0 || fn > 6 || !in_device || !out_device || n < 0) return fail(BN_ERR_INVALID, "bad argument");
-    if (n == 0) return BN_OK;
-    BN_HIP(bn::launch_math_eval(fn, in_device, out_device, (size_t)n, (hipStream_t)stream));
-    return BN_OK;
-}
-
-int bn_device_rng_eval(int32_t fn, const uint32_t *in_device, uint32_t *out_device, int64_t n, void *stream)
-{
-    if (fn < 0 || fn > 2 || !in_device || !out_device || n < 0) return fail(BN_ERR_INVALID, "bad argument");
-    if (n == 0) return BN_OK;
-    BN_HIP(bn::launch_rng_eval(fn, in_device, out_device, (size_t)n, (hipStream_t)stream));
-    return BN_OK;
-}
 
 const char *bn_last_error(void) { return g_last_error.c_str(); }
 int bn_mppi_abi_version(void) { return BN_MPPI_ABI_VERSION; }

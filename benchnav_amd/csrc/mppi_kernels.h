@@ -1,4 +1,4 @@
-// mppi_kernels.h -- launch interface between the C ABI (mppi_capi.cpp) and the
+// mppi_kernels.h -- launch interface between the C ABI (the host files behind mppi_handle.h) and the
 // gfx950 kernels (mppi_kernels.hip).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -103,7 +103,7 @@ struct SolveParams {
     const float *ustar_prev, *stats_prev;   // merge outputs of the solve whose tail this launch / the stand-alone tail writes
     int tail_merged;                   // the tail reads (ustar_prev, stats_prev) instead of merging `part`
     uint64_t tail_solve;               // index of the solve whose tail is written (its X* draws)
-    // ---- overlapped launches (solve_n_overlapped in mppi_capi.cpp): consecutive solves alternate between two streams, so a launch
+    // ---- overlapped launches (bn_mppi_solve_n_async in mppi_capi.cpp): consecutive solves alternate between two streams, so a launch
     // may start while its predecessor still runs; what stream order used to guarantee is carried by monotonic device counters ----
     int overlap;                         // this launch must WAIT on the counters (its predecessor is on the other stream)
     int cur_slot, prev_slot;             // slots (0..2) of this solve's and the previous solve's per-solve buffers

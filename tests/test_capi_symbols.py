@@ -143,3 +143,19 @@ def test_the_wrappers_share_one_device_array_and_keep_their_check_functions():
     from benchnav_amd import _device, astar, clrrt, mppi, rrt
     assert mppi._DevArray is _device._DevArray and astar._DevArray is _device._DevArray and rrt._DevArray is _device._DevArray
     assert callable(rrt._check) and callable(clrrt._check)
+
+
+# What the toolchain itself exports from a HIP shared library (one __hip_cuid_<hash> per translation unit with kernels; the linker's
+# own section marks where it emits them): looked up on the library as it was before the host file was split, where the only other
+# unmangled export was the RCCL loader's `rccl_api` (an anonymous namespace inside an extern "C" block).
+TOOLCHAIN_EXPORTS = re.compile(r"^(__hip_cuid_[0-9a-f]+|_init|_fini|__bss_start|_edata|_end)$")
+
+
+def test_only_the_headers_functions_are_exported_unmangled():
+    path = build.build_library()
+    out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
+    names = [line.split()[-1] for line in out.splitlines() if line.strip()]
+    assert len(names) > 100
+    plain = sorted(n for n in names if not n.startswith("_Z"))
+    stray = [n for n in plain if n not in set(declared_functions()) and not TOOLCHAIN_EXPORTS.match(n)]
+    assert not stray, f"unmangled exports the public header does not declare: {stray}"

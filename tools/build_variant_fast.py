@@ -30,10 +30,12 @@ if timing:
         assert pr.wait() == 0
 obj = os.path.join(out_dir, f"{os.path.splitext(SRC)[0]}_{name}.o")
 subprocess.check_call([b.hipcc(), *compile_flags, *b.EXTRA_FLAGS.get(SRC, []), *flags, "-x", "hip", "-c", os.path.join(b.CSRC, SRC), "-o", obj])
-# the host side as well: its experiment switches (environment variables) exist only with -DBN_EXPERIMENTS
-capi = os.path.join(out_dir, f"capi_{name}.o")
-subprocess.check_call([b.hipcc(), *compile_flags, *flags, "-x", "hip", "-c", os.path.join(b.CSRC, "mppi_capi.cpp"), "-o", capi])
-others = [capi] + [os.path.join(base_dir, os.path.splitext(s)[0] + ".o") for s in b.SOURCES if s not in (SRC, "mppi_capi.cpp")]
+# the host side as well, every file of it: its experiment switches (environment variables) exist only with -DBN_EXPERIMENTS
+host = [os.path.join(out_dir, f"{os.path.splitext(s)[0]}_{name}.o") for s in b.HOST_SOURCES]
+procs = [subprocess.Popen([b.hipcc(), *compile_flags, *flags, "-x", "hip", "-c", os.path.join(b.CSRC, s), "-o", o]) for s, o in zip(b.HOST_SOURCES, host)]
+for pr in procs:
+    assert pr.wait() == 0
+others = host + [os.path.join(base_dir, os.path.splitext(s)[0] + ".o") for s in b.SOURCES if s != SRC and s not in b.HOST_SOURCES]
 out = os.path.join(out_dir, f"lib_{name}.so")
 subprocess.check_call([b.hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", obj, *others, "-o", out])
 print("built", out)

@@ -11,7 +11,7 @@ out_dir = os.path.join(ROOT, "tools", "_ablate")
 os.makedirs(out_dir, exist_ok=True)
 compile_flags = [f for f in b.HIPCC_FLAGS if f != "-shared"] + ["-DBN_EXPERIMENTS"]
 base_dir = os.path.join(b.LIB_DIR, "obj")
-mine = ("rollout_wave.hip", "rollout_wave_ref.hip", "mppi_kernels.hip", "mppi_capi.cpp")
+mine = ("rollout_wave.hip", "rollout_wave_ref.hip", "mppi_kernels.hip", *b.HOST_SOURCES)      # every host file: each reads experiment switches
 procs = []
 for s in mine:
     obj = os.path.join(out_dir, f"{os.path.splitext(s)[0]}_{name}.o")
