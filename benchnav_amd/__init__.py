@@ -10,6 +10,7 @@
     from benchnav_amd import CLRRT         # drop-in for src/planners/global_planners/sampling_based/cl_rrt.py:CLRRT, B plans per launch
     from benchnav_amd import CLRRTLoop     # test_cl_rrt.py's plan-follow-replan loop on the device, B rovers per launch
     from benchnav_amd import TraversabilityPredictor, GPSlipRegressor, load_slip_regressors   # the exact-GP slip prediction stage
+    from benchnav_amd import SlipRegressorTrainer   # RegressorTrainer: fits the slip regressors on the GPU (GPSlipRegressor.fit)
 """
 from .native import NativeMPPI  # noqa: F401
 
@@ -42,7 +43,7 @@ def __getattr__(name):
     if name == "CLRRTLoop":
         from .clrrt_loop import CLRRTLoop
         return CLRRTLoop
-    if name in ("TraversabilityPredictor", "GPSlipRegressor", "load_slip_regressors"):
+    if name in ("TraversabilityPredictor", "GPSlipRegressor", "load_slip_regressors", "SlipRegressorTrainer"):
         from . import gp
         return getattr(gp, name)
     raise AttributeError(name)

@@ -218,6 +218,18 @@ SYMBOLS = {
     "bn_gp_predict_async": (C.c_int, [C.c_int32, C.c_void_p, C.POINTER(_H), C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t]),
     "bn_gp_last_error": (C.c_char_p, []),
+    "bn_gp_fit_workspace_bytes": (C.c_size_t, [C.c_int32]),
+    "bn_gp_fit_create": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_double, C.POINTER(_H)]),
+    "bn_gp_fit_destroy": (None, [_H]),
+    "bn_gp_fit_set_raw": (C.c_int, [_H, C.c_void_p]),
+    "bn_gp_fit_set_hyperparameters": (C.c_int, [_H, C.c_double, C.c_double, C.c_double, C.c_double]),
+    "bn_gp_fit_evaluate_async": (C.c_int, [_H, C.c_void_p]),
+    "bn_gp_fit_run_async": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double]),
+    "bn_gp_fit_read": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "bn_gp_fit_hyperparameters": (C.c_int, [_H, C.c_void_p]),
+    "bn_gp_fit_history": (C.c_int32, [_H, C.c_void_p, C.c_int32]),
+    "bn_gp_fit_finish": (C.c_int, [_H, C.c_void_p, C.POINTER(_H)]),
+    "bn_gp_fit_last_error": (C.c_char_p, []),
     "bn_device_math_eval": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "bn_device_rng_eval": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "bn_last_error": (C.c_char_p, []),

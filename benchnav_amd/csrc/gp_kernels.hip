@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "bn_host.h"
+#include "gp_handle.h"
 
 namespace bn {
 namespace {
@@ -39,14 +40,6 @@ constexpr int kGpGroups = kGpThreads / kGpTile;   // point groups of the generat
 constexpr int kGpBucketThreads = 1024;
 
 using f64x4 = __attribute__((ext_vector_type(4))) double;
-
-// one class's regressor as the predict kernel reads it
-struct GpRegDev {
-    const double *x, *alpha;             // (npad), zero beyond n
-    const double *linv;                  // L^-1 in fragment order: row block i, k step j (j < 4 (i + 1)), lane
-    int32_t n, npad;                     // npad: n rounded up to 16
-    double c, s, q, noise;               // q = -1 / (2 l^2)
-};
 
 struct GpTable {
     GpRegDev r[kGpMaxClasses];
@@ -408,13 +401,6 @@ size_t gp_align(size_t v) { return (v + 255) & ~(size_t)255; }
 
 }  // namespace
 }  // namespace bn
-
-struct bn_gp {
-    int device = 0, n = 0, npad = 0;
-    double c = 0, s = 0, l = 0, noise = 0;
-    bn::DeviceBuffers bufs;
-    double *x = nullptr, *alpha = nullptr, *linv = nullptr;
-};
 
 using bn::gp_fail;
 

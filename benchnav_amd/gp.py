@@ -13,6 +13,11 @@ solve); the device evaluates every cell in float64 and rounds the outputs.  Up t
 (the reference's trainer keeps up to 9999, regressor_trainer.py:91-124): regressors of up to 1024 points run on a kernel that
 holds k(x, phi) in LDS, larger ones on one that regenerates it slab by slab.
 The UNet terrain classifier is out of scope: any object with `.predict(colors[None]) -> classes` serves, or pass the class maps.
+
+The step that makes the regressors is here too (csrc/gp_fit_kernels.hip): `GPSlipRegressor.fit` runs
+RegressorTrainer.train's Adam on the exact marginal log-likelihood in float64 on the device and hands its factorisation to the
+predict kernels; `GPSlipRegressor(..., factorization="device")` factorises given hyperparameters there instead of on the host;
+`SlipRegressorTrainer` keeps the reference trainer's interface and file layout, which `load_slip_regressors` reads back.
 """
 from __future__ import annotations
 
@@ -113,28 +118,176 @@ def _softplus(v: float) -> float:
     return float(np.logaddexp(0.0, v))
 
 
+def _train_pair(train_x, train_y) -> Tuple[np.ndarray, np.ndarray]:
+    x, y = _vector(train_x, "train_x"), _vector(train_y, "train_y")
+    n = x.shape[0]
+    if y.shape[0] != n:
+        raise ValueError(f"train_x and train_y differ in length: {n} and {y.shape[0]}")
+    if n < 1 or n > MAX_POINTS:
+        raise ValueError(f"the regressor takes 1 to {MAX_POINTS} training points, got {n}")
+    return np.ascontiguousarray(x), np.ascontiguousarray(y)
+
+
+def _check_fit(lib, code: int):
+    if code == _capi.BN_ERR_STATE:
+        raise ValueError(lib.bn_gp_fit_last_error().decode("utf-8", "replace"))
+    if code != _capi.BN_OK:
+        raise _capi.BenchnavError(code, lib.bn_gp_fit_last_error().decode("utf-8", "replace"))
+
+
+class _Fit:
+    """One bn_gp_fit_t: the device workspace of a fit (two N x N float64 buffers), released on exit.  Launches go to torch's
+    current stream of the device."""
+
+    def __init__(self, lib, dev: torch.device, x: np.ndarray, y: np.ndarray, noise_lower_bound: float) -> None:
+        self.lib, self.dev, self.handle = lib, dev, None
+        h = C.c_void_p()
+        _check_fit(lib, lib.bn_gp_fit_create(dev.index, x.shape[0], x.ctypes.data, y.ctypes.data, float(noise_lower_bound), C.byref(h)))
+        self.handle = h
+
+    def __enter__(self) -> "_Fit":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+    def close(self) -> None:
+        if self.handle:
+            self.lib.bn_gp_fit_destroy(self.handle)
+            self.handle = None
+
+    def set_raw(self, raw) -> None:
+        r = np.ascontiguousarray(raw, dtype=np.float64)
+        _check_fit(self.lib, self.lib.bn_gp_fit_set_raw(self.handle, r.ctypes.data))
+
+    def evaluate(self) -> None:
+        _check_fit(self.lib, self.lib.bn_gp_fit_evaluate_async(self.handle, stream_ptr(self.dev)))
+
+    def run(self, iterations: int, lr: float, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8) -> None:
+        _check_fit(self.lib, self.lib.bn_gp_fit_run_async(self.handle, stream_ptr(self.dev), int(iterations), lr, beta1, beta2, eps))
+
+    def read(self):
+        """(raw (4,), grad (4,), loss, status, failed iteration) after a synchronisation"""
+        raw, grad = np.zeros(4), np.zeros(4)
+        loss, status, failed = C.c_double(), C.c_int32(), C.c_int32()
+        _check_fit(self.lib, self.lib.bn_gp_fit_read(self.handle, raw.ctypes.data, grad.ctypes.data, C.byref(loss), C.byref(status), C.byref(failed)))
+        return raw, grad, loss.value, status.value, failed.value
+
+    def hyperparameters(self):
+        hyp = np.zeros(4)
+        _check_fit(self.lib, self.lib.bn_gp_fit_hyperparameters(self.handle, hyp.ctypes.data))
+        return tuple(float(v) for v in hyp)
+
+    def history(self) -> np.ndarray:
+        done = self.lib.bn_gp_fit_history(self.handle, None, 0)
+        if done < 0:
+            _check_fit(self.lib, done)
+        out = np.zeros(done)
+        if done:
+            self.lib.bn_gp_fit_history(self.handle, out.ctypes.data, done)
+        return out
+
+    def finish(self) -> C.c_void_p:
+        g = C.c_void_p()
+        _check_fit(self.lib, self.lib.bn_gp_fit_finish(self.handle, stream_ptr(self.dev), C.byref(g)))
+        return g
+
+
 class GPSlipRegressor:
     """One terrain class's slip regressor on the device: `.predict(slopes)` is GPModel.predict's `likelihood(model(x))`, exact.
 
     train_x, train_y: (N,) or (N, 1), used as float32 values; constant, outputscale, lengthscale, noise: the ACTUAL (not raw)
     hyperparameters.  Raises ValueError for invalid inputs and RuntimeError without a GPU (no CPU fallback)."""
 
-    def __init__(self, train_x, train_y, constant: float, outputscale: float, lengthscale: float, noise: float, device=None) -> None:
+    raw_parameters = None                # (constant, raw_outputscale, raw_lengthscale, raw_noise) float64 after fit(), else None
+    loss_history = None                  # float64, one loss per iteration, after fit()
+    noise_lower_bound = _NOISE_LOWER_BOUND
+
+    def __init__(self, train_x, train_y, constant: float, outputscale: float, lengthscale: float, noise: float, device=None,
+                 factorization: str = "host") -> None:
+        """factorization="host" (the default): gp.factorize on the host and an upload of L^-1.  "device": the same
+        hyperparameters factorised by the fit kernels, no N x N host array and no upload of L^-1."""
+        if factorization not in ("host", "device"):
+            raise ValueError(f'factorization must be "host" or "device", got {factorization!r}')
+        self._handle = None
+        if factorization == "device":
+            x, y = _train_pair(train_x, train_y)
+            c, s, l, nz = (_scalar(constant, "constant"), _scalar(outputscale, "outputscale"), _scalar(lengthscale, "lengthscale"),
+                           _scalar(noise, "noise"))
+            if not (s > 0.0 and l > 0.0 and nz > 0.0):
+                raise ValueError("outputscale, lengthscale and noise must be > 0")
+            self.num_points = int(x.shape[0])
+            self.constant, self.outputscale, self.lengthscale, self.noise = c, s, l, nz
+            self._open(device)
+            with _Fit(self._lib, self._dev, x, y, _NOISE_LOWER_BOUND) as fit:
+                _check_fit(self._lib, self._lib.bn_gp_fit_set_hyperparameters(fit.handle, c, s, l, nz))
+                self._handle = fit.finish()
+            return
         x, alpha, linv = factorize(train_x, train_y, constant, outputscale, lengthscale, noise)
         self.num_points = int(x.shape[0])
         self.constant, self.outputscale, self.lengthscale, self.noise = (_scalar(constant, "constant"), _scalar(outputscale, "outputscale"),
                                                                          _scalar(lengthscale, "lengthscale"), _scalar(noise, "noise"))
-        self._handle = None
+        self._open(device)
+        h = C.c_void_p()
+        _check(self._lib, self._lib.bn_gp_create(self._dev.index, self.num_points, x.ctypes.data, alpha.ctypes.data, linv.ctypes.data,
+                                                 self.constant, self.outputscale, self.lengthscale, self.noise, C.byref(h)))
+        self._handle = h
+
+    def _open(self, device) -> None:
         if not torch.cuda.is_available():
             raise RuntimeError("benchnav_amd.gp needs an MI355X (gfx950) device; there is no CPU fallback")
         self._dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         if self._dev.index is None:
             self._dev = torch.device("cuda", torch.cuda.current_device())
         self._lib = _capi.load()
-        h = C.c_void_p()
-        _check(self._lib, self._lib.bn_gp_create(self._dev.index, self.num_points, x.ctypes.data, alpha.ctypes.data, linv.ctypes.data,
-                                                 self.constant, self.outputscale, self.lengthscale, self.noise, C.byref(h)))
-        self._handle = h
+
+    @classmethod
+    def fit(cls, train_x, train_y, learning_rate: float = 0.1, num_iterations: int = 100, device=None, initial_raw=None,
+            noise_lower_bound: float = _NOISE_LOWER_BOUND) -> "GPSlipRegressor":
+        """RegressorTrainer.train (regressor_trainer.py:128-170) on the device: num_iterations steps of Adam (torch.optim.Adam's
+        defaults, learning_rate) on the exact negative marginal log-likelihood over N in float64, from initial_raw = (constant,
+        raw_outputscale, raw_lengthscale, raw_noise) (default: gpytorch's zeros), enqueued without a host round trip; then the
+        factorisation at the final parameters.  The result carries .raw_parameters and .loss_history (the loss BEFORE each
+        step).  A factorisation that fails raises ValueError with the iteration: no jitter is added."""
+        x, y = _train_pair(train_x, train_y)
+        n_it = int(num_iterations)
+        if n_it < 0:
+            raise ValueError("num_iterations must be >= 0")
+        if not (float(learning_rate) > 0.0 and np.isfinite(float(learning_rate))):
+            raise ValueError("learning_rate must be finite and > 0")
+        raw0 = np.zeros(4) if initial_raw is None else np.ascontiguousarray(np.asarray(initial_raw, dtype=np.float64).reshape(-1))
+        if raw0.shape != (4,) or not np.isfinite(raw0).all():
+            raise ValueError("initial_raw must hold four finite values: constant, raw_outputscale, raw_lengthscale, raw_noise")
+        self = cls.__new__(cls)
+        self._handle = None
+        self.num_points = int(x.shape[0])
+        self.noise_lower_bound = float(noise_lower_bound)
+        self._open(device)
+        with _Fit(self._lib, self._dev, x, y, self.noise_lower_bound) as fit:
+            fit.set_raw(raw0)
+            fit.run(n_it, float(learning_rate))
+            raw, _, _, status, failed = fit.read()
+            if status:
+                raise ValueError(f"k(x, x) + noise I is not numerically positive definite at iteration {failed} (no jitter is added)")
+            self.raw_parameters = raw
+            self.loss_history = fit.history()
+            self.constant, self.outputscale, self.lengthscale, self.noise = fit.hyperparameters()
+            self._handle = fit.finish()
+        return self
+
+    def state_dict(self) -> Dict[str, torch.Tensor]:
+        """The fitted raw parameters in gpytorch's key layout as float32 tensors, for the reference's load_slip_regressors and
+        this module's hyperparameters_from_state_dict.  The layout is gpytorch's as documented; it has not been checked against
+        gpytorch itself.  Only a regressor that came from fit() has raw parameters."""
+        if self.raw_parameters is None:
+            raise ValueError("this regressor was built from actual hyperparameters: it has no raw parameters to save")
+        c, ro, rl, rn = (float(v) for v in self.raw_parameters)
+        return {"likelihood.noise_covar.raw_noise": torch.tensor([rn], dtype=torch.float32),
+                "likelihood.noise_covar.raw_noise_constraint.lower_bound": torch.tensor(self.noise_lower_bound, dtype=torch.float32),
+                "likelihood.noise_covar.raw_noise_constraint.upper_bound": torch.tensor(float("inf"), dtype=torch.float32),
+                "mean_module.raw_constant": torch.tensor(c, dtype=torch.float32),
+                "covar_module.raw_outputscale": torch.tensor(ro, dtype=torch.float32),
+                "covar_module.base_kernel.raw_lengthscale": torch.tensor([[rl]], dtype=torch.float32)}
 
     @classmethod
     def from_gpytorch_state_dict(cls, state_dict, train_x, train_y, device=None, noise_lower_bound: Optional[float] = None) -> "GPSlipRegressor":
@@ -201,6 +354,62 @@ def load_slip_regressors(num_terrain_classes: int, model_directory: str, train_d
         state = torch.load(os.path.join(model_directory, f"models/{i:02d}_class.pth"), map_location="cpu", weights_only=True)
         out[i] = GPSlipRegressor.from_gpytorch_state_dict(state, data["train_x"], data["train_y"], device=device)
     return out
+
+
+class SlipRegressorTrainer:
+    """RegressorTrainer's interface and on-disk layout (trainers/regressor_trainer.py:22-200) around GPSlipRegressor.fit: plain
+    host Python.  params_model_training: any object with .batch_size, .learning_rate and .num_iterations; train_dataset: any
+    dataset that yields (slopes, slips, t_classes).  Class i's regressor goes to
+    <model_directory>/lr<lr:.0e>_iters<n:03d>/models/<i:02d>_class.pth (GPSlipRegressor.state_dict()) and its observations to
+    <data_directory>/slip_observations/<i:02d>_class.pth ({"train_x", "train_y"}); load_slip_regressors(num_terrain_classes,
+    trainer.model_directory, data_directory) reads both back."""
+
+    def __init__(self, device, model_directory: str, data_directory: str, num_terrain_classes: int, params_model_training, train_dataset) -> None:
+        from torch.utils.data import DataLoader
+        self.device = device
+        self.train_dataset = train_dataset
+        self.train_loader = DataLoader(train_dataset, batch_size=params_model_training.batch_size, shuffle=True)
+        self.num_terrain_classes = int(num_terrain_classes)
+        self.params_model_training = params_model_training
+        self.model_directory = os.path.join(model_directory, f"lr{params_model_training.learning_rate:.0e}_iters{params_model_training.num_iterations:03d}")
+        self.learned_models_directory = os.path.join(self.model_directory, "models")
+        self.data_directory = os.path.join(data_directory, "slip_observations")
+        os.makedirs(self.learned_models_directory, exist_ok=True)
+        os.makedirs(self.data_directory, exist_ok=True)
+        self.regressors: Dict[int, GPSlipRegressor] = {}
+
+    def train_all_models(self) -> None:
+        phis, slips = self.load_data()
+        for k in range(self.num_terrain_classes):
+            self.train(k, phis[k], slips[k])
+
+    def load_data(self, num_samples: int = 9999) -> Tuple[Dict[int, torch.Tensor], Dict[int, torch.Tensor]]:
+        """Per class the slopes and slips of its cells in the loader's order, cut at num_samples."""
+        phis = {k: [] for k in range(self.num_terrain_classes)}
+        slips = {k: [] for k in range(self.num_terrain_classes)}
+        for slope_b, slip_b, class_b in self.train_loader:
+            for k in range(self.num_terrain_classes):
+                sel = class_b == k
+                if bool(sel.any()):
+                    phis[k].append(slope_b[sel])
+                    slips[k].append(slip_b[sel])
+        for k in range(self.num_terrain_classes):
+            if not phis[k]:
+                raise ValueError(f"the dataset holds no cell of terrain class {k}")
+            phis[k] = torch.cat(phis[k], dim=0)[:num_samples]
+            slips[k] = torch.cat(slips[k], dim=0)[:num_samples]
+        return phis, slips
+
+    def train(self, terrain_class: int, phis: torch.Tensor, slips: torch.Tensor) -> GPSlipRegressor:
+        p = self.params_model_training
+        model = GPSlipRegressor.fit(phis, slips, learning_rate=p.learning_rate, num_iterations=p.num_iterations, device=self.device)
+        self.regressors[int(terrain_class)] = model
+        self.save(phis, slips, model, terrain_class)
+        return model
+
+    def save(self, train_x: torch.Tensor, train_y: torch.Tensor, model: GPSlipRegressor, terrain_class: int) -> None:
+        torch.save({"train_x": train_x, "train_y": train_y}, os.path.join(self.data_directory, f"{terrain_class:02d}_class.pth"))
+        torch.save(model.state_dict(), os.path.join(self.learned_models_directory, f"{terrain_class:02d}_class.pth"))
 
 
 def _predict(lib, dev: torch.device, table, slopes: torch.Tensor, classes: torch.Tensor, dtype) -> Tuple[torch.Tensor, torch.Tensor]:

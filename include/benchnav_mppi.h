@@ -881,8 +881,9 @@ int bn_clrrt_loop_set_plans(bn_mppi_t *h, bn_clrrt_t *c, const float *actions, c
  * and for a cell of slope phi
  *     mean = c + k(phi, x) . alpha                    v = linv k(x, phi)
  *     var  = max(s - |v|^2, 0) + noise                std = sqrt(var)            (the likelihood's noise is part of var)
- * A caller produces alpha and linv with LAPACK (dpotrf, dpotrs, dtrtri) in float64; the library adds no jitter and does not
- * factorise.  The device evaluates every line above in float64 and rounds only the outputs.
+ * A caller produces alpha and linv with LAPACK (dpotrf, dpotrs, dtrtri) in float64 for bn_gp_create, or lets the library
+ * factorise on the device (bn_gp_fit_create, bn_gp_fit_set_hyperparameters, bn_gp_fit_finish below); no jitter is added either
+ * way.  The device evaluates every line above in float64 and rounds only the outputs.
  * Errors: the gp error string below.
  * ---------------------------------------------------------------------------------------------------------------------------- */
 typedef struct bn_gp bn_gp_t;
@@ -908,6 +909,56 @@ int bn_gp_predict_async(int32_t device_id, void *stream, bn_gp_t *const *regress
                         int64_t cells, const float *slopes_device, const int32_t *classes_device, void *mean_device,
                         void *std_device, int32_t f64_outputs, void *workspace_device, size_t workspace_bytes);
 const char *bn_gp_last_error(void);
+
+/* ------------------------------------------------------------------------------------------------------------------------------
+ * Fitting the GP slip regressors on the device (csrc/gp_fit_kernels.hip): RegressorTrainer.train's Adam on the
+ * exact marginal log-likelihood (trainers/regressor_trainer.py:128-170), in float64, and the factorisation behind a bn_gp_t
+ * without host LAPACK.  Raw parameters theta = (constant, raw_outputscale, raw_lengthscale, raw_noise), all 0 at creation as in
+ * gpytorch; c = constant, s = softplus(raw_outputscale), l = softplus(raw_lengthscale), noise = softplus(raw_noise) +
+ * noise_lower_bound;
+ *     K = s exp(-(x - x')^2 / (2 l^2)) + noise I = L L^T      r = y - c      alpha = K^-1 r
+ *     loss = [ r . alpha + 2 sum log L_ii + n log 2 pi ] / (2 n)               (the negative marginal log-likelihood over n)
+ *     dloss/dc = -sum alpha / n        dloss/dpsi = tr((K^-1 - alpha alpha^T) dK/dpsi) / (2 n),  psi in {s, l, noise}
+ * and the gradient with respect to the raw parameters by dpsi/draw = sigmoid(raw).  No jitter is added anywhere: a pivot that is
+ * not positive and finite sets the handle's status to 1 with the iteration number, and every launch enqueued behind it returns
+ * at once.  Every sum runs in an order fixed by n alone (no floating-point atomics): equal inputs give equal bits.
+ * Errors: the gp fit error string below.
+ * ---------------------------------------------------------------------------------------------------------------------------- */
+typedef struct bn_gp_fit bn_gp_fit_t;
+/* Bytes of device memory a fit handle of n points holds: with np = n rounded up to 32 and T = np / 32,
+ *     2 np^2 8 (K then L, and L^-1) + 8192 T (the inverses of L's diagonal tiles) + 32 np (x, y, z, alpha)
+ *     + 12 T (T + 1) (three gradient partials per tile of K^-1) + 131072 (the loss history) + the state block,
+ * 1.68 GB at n = 10240.  0 for n outside [1, bn_gp_max_points()]. */
+size_t bn_gp_fit_workspace_bytes(int32_t n);
+/* A fit handle on device_id from HOST arrays x (n) and y (n).  Checked before the device is touched: 1 <= n <= bn_gp_max_points(),
+ * x and y finite, noise_lower_bound finite and >= 0 (gpytorch's default is 1e-4) (BN_ERR_INVALID); without a device
+ * BN_ERR_NO_DEVICE ("no CPU fallback").  theta = 0.  Synchronous. */
+int bn_gp_fit_create(int32_t device_id, int32_t n, const double *x, const double *y, double noise_lower_bound, bn_gp_fit_t **out);
+void bn_gp_fit_destroy(bn_gp_fit_t *h);
+/* theta = raw[4]; clears Adam's moments, the history, the status and the iteration count.  Synchronises. */
+int bn_gp_fit_set_raw(bn_gp_fit_t *h, const double *raw);
+/* The ACTUAL hyperparameters directly (all finite, the last three > 0), for bn_gp_fit_finish alone: the raw parameters and the
+ * gradient are NaN afterwards.  Clears what bn_gp_fit_set_raw clears.  Synchronises. */
+int bn_gp_fit_set_hyperparameters(bn_gp_fit_t *h, double constant, double outputscale, double lengthscale, double noise);
+/* Loss and gradient at the current theta on `stream`, no update, no synchronisation. */
+int bn_gp_fit_evaluate_async(bn_gp_fit_t *h, void *stream);
+/* `iterations` (>= 0) steps of torch.optim.Adam's update (lr > 0, betas in [0, 1), eps >= 0; bias-corrected, no weight decay) on
+ * `stream` without a host round trip: per step one evaluation, the loss appended to the history, theta and the moments updated.
+ * A handle records up to 16384 iterations. */
+int bn_gp_fit_run_async(bn_gp_fit_t *h, void *stream, int32_t iterations, double lr, double beta1, double beta2, double eps);
+/* Synchronises the last stream used and reads theta, the gradient and loss of the last evaluation, the status (0, or 1: a
+ * factorisation failed) and the iteration it failed in (-1 if none).  Any output pointer may be NULL. */
+int bn_gp_fit_read(bn_gp_fit_t *h, double *raw, double *grad, double *loss, int32_t *status, int32_t *failed_iteration);
+/* Synchronises; hyp[4] = (constant, outputscale, lengthscale, noise) as the next evaluation will use them. */
+int bn_gp_fit_hyperparameters(bn_gp_fit_t *h, double *hyp);
+/* Synchronises; copies min(completed iterations, capacity) losses, oldest first, and returns the number of completed iterations
+ * (or a negative error code). */
+int32_t bn_gp_fit_history(bn_gp_fit_t *h, double *losses, int32_t capacity);
+/* Factorises at the current hyperparameters on `stream` and hands back an ordinary regressor for bn_gp_predict_async: alpha and
+ * L^-1 are written on the device in the handle's own order, nothing of size n^2 crosses the bus.  Synchronises.  BN_ERR_STATE
+ * when the matrix is not numerically positive definite ("no jitter is added").  The regressor outlives the fit handle. */
+int bn_gp_fit_finish(bn_gp_fit_t *h, void *stream, bn_gp_t **out);
+const char *bn_gp_fit_last_error(void);
 
 /* Test hook: the library's device arithmetic (DESIGN.md "Arithmetic spec") applied elementwise to n device floats:
  * fn 0 = correctly rounded sqrt, 1 / 2 = sin / cos of the spec, 3 = heading wrap (theta + pi) % 2pi - pi with
