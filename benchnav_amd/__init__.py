@@ -11,6 +11,7 @@
     from benchnav_amd import CLRRTLoop     # test_cl_rrt.py's plan-follow-replan loop on the device, B rovers per launch
     from benchnav_amd import TraversabilityPredictor, GPSlipRegressor, load_slip_regressors   # the exact-GP slip prediction stage
     from benchnav_amd import SlipRegressorTrainer   # RegressorTrainer: fits the slip regressors on the GPU (GPSlipRegressor.fit)
+    from benchnav_amd import TerrainClassifier, load_terrain_classifier, fold_state_dict   # the U-Net terrain classifier (unet.py)
 """
 from .native import NativeMPPI  # noqa: F401
 
@@ -46,4 +47,7 @@ def __getattr__(name):
     if name in ("TraversabilityPredictor", "GPSlipRegressor", "load_slip_regressors", "SlipRegressorTrainer"):
         from . import gp
         return getattr(gp, name)
+    if name in ("TerrainClassifier", "load_terrain_classifier", "fold_state_dict"):
+        from . import unet
+        return getattr(unet, name)
     raise AttributeError(name)

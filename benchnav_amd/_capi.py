@@ -230,6 +230,20 @@ SYMBOLS = {
     "bn_gp_fit_history": (C.c_int32, [_H, C.c_void_p, C.c_int32]),
     "bn_gp_fit_finish": (C.c_int, [_H, C.c_void_p, C.POINTER(_H)]),
     "bn_gp_fit_last_error": (C.c_char_p, []),
+    "bn_unet_param_count": (C.c_int64, [C.c_int32]),
+    "bn_unet_create": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.POINTER(_H)]),
+    "bn_unet_destroy": (None, [_H]),
+    "bn_unet_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "bn_unet_forward_async": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_size_t]),
+    "bn_unet_feature_layout": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_size_t), C.POINTER(C.c_int32),
+                                         C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "bn_unet_conv2d_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "bn_unet_conv2d_async": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                       C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
+                                       C.c_void_p, C.c_void_p, C.c_size_t]),
+    "bn_unet_maxpool_async": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
+    "bn_unet_last_error": (C.c_char_p, []),
     "bn_device_math_eval": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "bn_device_rng_eval": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "bn_last_error": (C.c_char_p, []),

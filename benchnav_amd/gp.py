@@ -12,7 +12,8 @@ The host factorises once per regressor in float64 (NumPy; above 1024 points the 
 solve); the device evaluates every cell in float64 and rounds the outputs.  Up to MAX_POINTS = 10240 training points per class
 (the reference's trainer keeps up to 9999, regressor_trainer.py:91-124): regressors of up to 1024 points run on a kernel that
 holds k(x, phi) in LDS, larger ones on one that regenerates it slab by slab.
-The UNet terrain classifier is out of scope: any object with `.predict(colors[None]) -> classes` serves, or pass the class maps.
+The UNet terrain classifier is unet.TerrainClassifier; any object with `.predict(colors[None]) -> classes` serves
+too, or pass the class maps.
 
 The step that makes the regressors is here too (csrc/gp_fit_kernels.hip): `GPSlipRegressor.fit` runs
 RegressorTrainer.train's Adam on the exact marginal log-likelihood in float64 on the device and hands its factorisation to the
@@ -437,9 +438,11 @@ def _predict(lib, dev: torch.device, table, slopes: torch.Tensor, classes: torch
 class TraversabilityPredictor:
     """classifier_and_regressor.py's TraversabilityPredictor on the device.
 
-    terrain_classifier: any object with `.predict(colors[None]) -> (1, G, G)` integer classes (the reference's UNet is not part
-    of this package), or None when the class maps are passed to predict_maps.  slip_regressors: {class: GPSlipRegressor}; a
-    class without one predicts mean 0 and std 0 (the reference's zeros_like)."""
+    terrain_classifier: unet.TerrainClassifier (the reference's UNet on the device: it has `batched = True`, and predict_maps
+    classifies the whole batch in one call and hands the int32 device class maps straight to the GP kernels), or any other
+    object with `.predict(colors[None]) -> (1, G, G)` integer classes, called map by map, or None when the class maps are passed
+    to predict_maps.  slip_regressors: {class: GPSlipRegressor}; a class without one predicts mean 0 and std 0 (the reference's
+    zeros_like)."""
 
     def __init__(self, terrain_classifier, slip_regressors: Dict[int, GPSlipRegressor], device=None) -> None:
         if not torch.cuda.is_available():
@@ -459,7 +462,7 @@ class TraversabilityPredictor:
                      dtype=torch.float32) -> Tuple[torch.Tensor, torch.Tensor]:
         """(mean, std) of slopes' shape, (G, G) or (B, G, G), in one call of two or three launches (the bucketing, then one
         predict kernel for the regressors of up to 1024 points and one for the larger ones) without a host round trip.  t_classes of the same shape skips the
-        classifier; otherwise colors (3, G, G) or (B, 3, G, G) goes through it map by map."""
+        classifier; otherwise colors (3, G, G) or (B, 3, G, G) goes through it: in one call when it is `batched`, else map by map."""
         if slopes.dim() not in (2, 3):
             raise ValueError(f"slopes must be (G, G) or (B, G, G), got {tuple(slopes.shape)}")
         batched = slopes.dim() == 3
@@ -470,8 +473,11 @@ class TraversabilityPredictor:
             col = (colors if batched else colors[None]).to(self.device)
             if col.shape[0] != s.shape[0]:
                 raise ValueError("colors and slopes differ in batch size")
-            t_classes = torch.cat([torch.as_tensor(self.terrain_classifier.predict(col[b:b + 1])).reshape(1, *s.shape[1:])
-                                   for b in range(s.shape[0])])
+            if getattr(self.terrain_classifier, "batched", False):   # unet.TerrainClassifier: one call, int32 classes on the device
+                t_classes = self.terrain_classifier.predict_classes(col).reshape(s.shape)
+            else:
+                t_classes = torch.cat([torch.as_tensor(self.terrain_classifier.predict(col[b:b + 1])).reshape(1, *s.shape[1:])
+                                       for b in range(s.shape[0])])
         else:
             t_classes = t_classes if batched else t_classes[None]
         if tuple(t_classes.shape) != tuple(s.shape):

@@ -960,6 +960,64 @@ int32_t bn_gp_fit_history(bn_gp_fit_t *h, double *losses, int32_t capacity);
 int bn_gp_fit_finish(bn_gp_fit_t *h, void *stream, bn_gp_t **out);
 const char *bn_gp_fit_last_error(void);
 
+/* ------------------------------------------------------------------------------------------------------------------------------
+ * The U-Net terrain classifier (csrc/unet_kernels.hip, csrc/unet_host.cpp): the first half of
+ * TraversabilityPredictor.predict, colours (num_maps, 3, H, W) in [0, 1] -> logits, softmax probabilities and class maps.  The
+ * network is terrain_classifiers/unet.py's Unet(encoder "resnet18", classes): a ResNet-18 encoder, five decoder blocks (2x
+ * nearest upsample, concatenation with the skip feature, two 3x3 convolutions) and a 3x3 head, in eval mode: every BatchNorm is
+ * folded into its convolution BEFORE upload, so the library sees 31 convolutions with a bias each.  Float32 throughout, on the
+ * exact float32 MFMA; an output's bits depend on the parameters and on that map's pixels only.
+ *
+ * The packed parameters, float32: per convolution its weights (cout, cin, k, k) row-major, then its bias (cout), in this order:
+ *     encoder.conv1 (64, 3, 7, 7);
+ *     encoder.layer1 ... layer4 with widths 64, 128, 256, 512, per layer: block 0 conv1, block 0 conv2, [layers 2-4: block 0
+ *         downsample (1x1)], block 1 conv1, block 1 conv2;
+ *     decoder.blocks.0 ... 4: conv1 (cout, cin + cskip, 3, 3), conv2 (cout, cout, 3, 3), with cin = 512, 256, 128, 64, 32, cskip =
+ *         256, 128, 64, 64, 0 and cout = 256, 128, 64, 32, 16; the input channels are [upsampled, skip] in that order;
+ *     segmentation_head.0 (classes, 16, 3, 3).
+ * Range: H and W multiples of 32 in [32, 2048], num_maps in [1, 4096], num_maps H W <= 2^24.
+ * Errors: the unet error string below.
+ * ---------------------------------------------------------------------------------------------------------------------------- */
+typedef struct bn_unet bn_unet_t;
+/* Floats of packed parameters for `classes` terrain classes (14 323 722 at 10); 0 for classes outside [1, 32]. */
+int64_t bn_unet_param_count(int32_t classes);
+/* A classifier on device_id from the HOST array of packed parameters.  Checked before the device is touched: 1 <= classes <= 32,
+ * count == bn_unet_param_count(classes), every value finite (BN_ERR_INVALID); without a device BN_ERR_NO_DEVICE ("no CPU
+ * fallback").  Re-lays every convolution out as the kernel reads it ([k][cout], padded with zeros).  Synchronous. */
+int bn_unet_create(int32_t device_id, int32_t classes, const float *params_host, int64_t count, bn_unet_t **out);
+void bn_unet_destroy(bn_unet_t *h);
+/* Bytes of device workspace one forward of num_maps maps of H x W needs: every activation of the network, each rounded up to
+ * 256 bytes, and room for the logits of 32 classes (used when the caller passes none).  0 for arguments out of range or H, W not
+ * multiples of 32. */
+size_t bn_unet_workspace_bytes(int32_t num_maps, int32_t H, int32_t W);
+/* One forward on `stream`: 32 launches (33 with probabilities or classes), no synchronisation, no allocation.  colors_device
+ * (num_maps, 3, H, W) float32; any of logits_device (num_maps, classes, H, W) float32, probabilities_device (same shape, softmax
+ * over the classes) and classes_device (num_maps, H, W) int32 (argmax of the logits, the lowest index wins a tie) may be NULL.  The
+ * handle and the workspace must stay alive until the stream has run the launches. */
+int bn_unet_forward_async(bn_unet_t *h, void *stream, int32_t num_maps, int32_t H, int32_t W, const float *colors_device,
+                          float *logits_device, float *probabilities_device, int32_t *classes_device, void *workspace_device,
+                          size_t workspace_bytes);
+/* Where a forward of this shape leaves feature `index` in its workspace: 0 the stem (after bn1 + ReLU), 1-4 layer1 ... layer4,
+ * 5-9 decoder blocks 0 ... 4; each (num_maps, channels, height, width) float32 at offset_bytes. */
+int bn_unet_feature_layout(int32_t num_maps, int32_t H, int32_t W, int32_t index, size_t *offset_bytes, int32_t *channels,
+                           int32_t *height, int32_t *width);
+/* Bytes of workspace bn_unet_conv2d_async needs for the re-laid weights; 0 unless 1 <= cin, cout <= 4096 and ksize is 1, 3 or 7. */
+size_t bn_unet_conv2d_workspace_bytes(int32_t cin, int32_t cout, int32_t ksize);
+/* The network's one fused convolution on caller tensors, all on the device (two launches: the weight re-layout, the convolution):
+ *     out = [relu]( conv2d([up2x](a) ++ skip, weights, stride, pad) + bias [+ residual] )
+ * a (num_maps, ca, hin, win), or (num_maps, ca, hin / 2, win / 2) with upsample = 1 (2x nearest); skip (num_maps, cb, hin, win) or
+ * NULL with cb = 0; weights (cout, ca + cb, ksize, ksize); bias (cout) or NULL; residual of out's shape or NULL; ksize 1, 3 or 7,
+ * stride 1 or 2, pad 0 ... 3, zero padding; out (num_maps, cout, (hin + 2 pad - ksize) / stride + 1, likewise for win). */
+int bn_unet_conv2d_async(int32_t device_id, void *stream, const float *a_device, int32_t ca, const float *skip_device, int32_t cb,
+                         int32_t upsample, int32_t num_maps, int32_t hin, int32_t win, const float *weights_device,
+                         const float *bias_device, int32_t cout, int32_t ksize, int32_t stride, int32_t pad,
+                         const float *residual_device, int32_t relu, float *out_device, void *workspace_device, size_t workspace_bytes);
+/* The network's max-pool (3x3, stride 2, pad 1, padding counts as -inf) on `planes` device images of hin x win:
+ * out (planes, (hin - 1) / 2 + 1, (win - 1) / 2 + 1). */
+int bn_unet_maxpool_async(int32_t device_id, void *stream, const float *in_device, int64_t planes, int32_t hin, int32_t win,
+                          float *out_device);
+const char *bn_unet_last_error(void);
+
 /* Test hook: the library's device arithmetic (DESIGN.md "Arithmetic spec") applied elementwise to n device floats:
  * fn 0 = correctly rounded sqrt, 1 / 2 = sin / cos of the spec, 3 = heading wrap (theta + pi) % 2pi - pi with
  * torch.remainder semantics (robot_model.py:90), 4 = its in-loop form, 5 = the sqrt for zero / normal finite arguments.  Lets the tests compare the kernels' building
