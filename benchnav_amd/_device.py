@@ -1,6 +1,6 @@
-"""What the planner wrappers share on the Python side: the view of library-owned device memory, torch's current stream as the
-library takes it, the seed checks, the reference Tree's capacity rule, and the handle and plumbing of the two tree planners
-(rrt.py, clrrt.py)."""
+"""What the wrappers share on the Python side: the view of library-owned device memory, torch's current stream as the library
+takes it, the device a `device` argument names, the error check, the base of every class that owns a library handle, the seed
+checks, the reference Tree's capacity rule, and the plumbing of the two tree planners (rrt.py, clrrt.py)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -47,36 +47,69 @@ def tree_capacity(n: int) -> int:
 
 
 def check(lib, family: str, code: int):
-    if code != _capi.BN_OK:
+    """Raise the family's last error for a negative code (some entry points return a count)."""
+    if code < 0:
         raise _capi.BenchnavError(code, getattr(lib, f"bn_{family}_last_error")().decode("utf-8", "replace"))
 
 
-class _PlannerHandle:
-    """One handle of the library's `family` ("rrt", "clrrt": bn_<family>_create / _destroy / _device_buffer / _last_error): B
-    instances of one parameter set.  A subclass fills the family's config struct."""
+def resolve_device(device, who: str, lenient: bool = False) -> torch.device:
+    """The CUDA device, with its index, that `device` names for benchnav_amd.<who>.  None or an index-less CUDA device is the
+    current device.  Any other kind of device is an error, or with `lenient` (the planners that receive the reference's
+    `device` argument) the current device too.  Without a GPU nothing resolves: there is no CPU fallback."""
+    if not torch.cuda.is_available():
+        raise RuntimeError(f"benchnav_amd.{who} needs an MI355X (gfx950) device; there is no CPU fallback")
+    dev = torch.device(device) if device is not None else torch.device("cuda")
+    if dev.type != "cuda":
+        if not lenient:
+            raise RuntimeError(f"benchnav_amd.{who} runs on the GPU only (device={device!r})")
+        dev = torch.device("cuda")
+    return dev if dev.index is not None else torch.device("cuda", torch.cuda.current_device())
+
+
+class Handle:
+    """One handle of the library's `family` (bn_<family>_destroy / _last_error).  The owner sets `_lib` and, from the family's
+    create call, `_handle` (a c_void_p); it is destroyed once -- by close(), by leaving a `with` block, or when the object goes."""
     family = ""
+    _lib = None
+    _handle = None
 
-    def __init__(self, lib, dev: torch.device, B: int, cfg):
-        self.lib, self.dev, self.B = lib, dev, B
-        self.used = False                    # a plan has run: its streams are seeded
-        self.h = C.c_void_p()
-        check(lib, self.family, getattr(lib, f"bn_{self.family}_create")(C.byref(cfg), C.byref(self.h)))
+    def _check(self, code: int) -> None:
+        check(self._lib, self.family, code)
 
-    def buffer(self, which: int, shape, typestr="<f4") -> torch.Tensor:
-        ptr, nbytes = C.c_void_p(), C.c_size_t()
-        check(self.lib, self.family, getattr(self.lib, f"bn_{self.family}_device_buffer")(self.h, which, C.byref(ptr), C.byref(nbytes)))
-        return torch.as_tensor(_DevArray(ptr.value, shape, typestr), device=self.dev)
+    def close(self) -> None:
+        if self._handle:
+            getattr(self._lib, f"bn_{self.family}_destroy")(self._handle)
+        self._handle = None
 
-    def close(self):
-        if self.h:
-            getattr(self.lib, f"bn_{self.family}_destroy")(self.h)
-            self.h = C.c_void_p()
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
 
     def __del__(self):
         try:
             self.close()
         except Exception:
             pass
+
+
+class _PlannerHandle(Handle):
+    """One handle of a tree planner's `family` ("rrt", "clrrt": bn_<family>_create / _device_buffer): B instances of one
+    parameter set.  A subclass fills the family's config struct."""
+    h = property(lambda self: self._handle)
+
+    def __init__(self, lib, dev: torch.device, B: int, cfg):
+        self._lib, self.dev, self.B = lib, dev, B
+        self.used = False                    # a plan has run: its streams are seeded
+        h = C.c_void_p()
+        self._check(getattr(lib, f"bn_{self.family}_create")(C.byref(cfg), C.byref(h)))
+        self._handle = h
+
+    def buffer(self, which: int, shape, typestr="<f4") -> torch.Tensor:
+        ptr, nbytes = C.c_void_p(), C.c_size_t()
+        self._check(getattr(self._lib, f"bn_{self.family}_device_buffer")(self._handle, which, C.byref(ptr), C.byref(nbytes)))
+        return torch.as_tensor(_DevArray(ptr.value, shape, typestr), device=self.dev)
 
 
 class _TreePlanner:

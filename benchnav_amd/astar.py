@@ -21,10 +21,12 @@ import torch
 import torch.nn as nn
 
 from . import _capi
-from ._device import _DevArray, stream_ptr
+from ._device import Handle, _DevArray, resolve_device, stream_ptr
 
 
-class AStar(nn.Module):
+class AStar(Handle, nn.Module):
+    family = "astar"
+
     def __init__(self, grid_map, goal_pos: torch.Tensor, dynamics, stuck_threshold: float, device: Optional[str] = None) -> None:
         super().__init__()
         heights = grid_map.tensors["heights"].detach()                            # astar.py:53-58
@@ -37,10 +39,7 @@ class AStar(nn.Module):
         assert risks.shape == heights.shape, "Traversability and height maps must have the same shape."
         self._h, self._w = heights.shape
         self._goal_node = self._pos_to_index(goal_pos)                             # astar.py:71
-        if not torch.cuda.is_available():
-            raise RuntimeError("benchnav_amd.AStar needs an MI355X (gfx950) device; there is no CPU fallback")
-        dev = torch.device(self.device)
-        self._dev = dev if dev.type == "cuda" and dev.index is not None else torch.device("cuda", torch.cuda.current_device())
+        self._dev = resolve_device(self.device, "AStar", lenient=True)
         heights = heights.to(torch.float32).contiguous()
         risks = risks.to(torch.float32).contiguous()
         # the goal checks of forward() (astar.py:88-94), decided once: the goal never changes
@@ -163,18 +162,3 @@ class AStar(nn.Module):
     def _is_within_bounds(self, node: tuple[int, int]) -> bool:                   # astar.py:169-180
         return 0 <= node[0] < self._w and 0 <= node[1] < self._h
 
-    def _check(self, code):
-        if code < 0:
-            raise _capi.BenchnavError(code, self._lib.bn_astar_last_error().decode("utf-8", "replace"))
-
-    def close(self):
-        h = getattr(self, "_handle", None)
-        if h is not None and h.value:
-            self._lib.bn_astar_destroy(h)
-            self._handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

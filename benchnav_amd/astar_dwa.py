@@ -27,7 +27,7 @@ import numpy as np
 import torch
 
 from . import _capi
-from ._device import stream_ptr
+from ._device import Handle, stream_ptr
 
 _MESSAGES = {
     _capi.BN_AD_OUT_OF_BOUNDS: "Start or goal position is out of bounds.",       # astar.py:88-92
@@ -44,7 +44,10 @@ def _per_instance(a, B: int, G: int, what: str) -> np.ndarray:
     return np.ascontiguousarray(a)
 
 
-class AStarDWALoop:
+class AStarDWALoop(Handle):
+    family = "astar"                         # the handle the loop owns; the planner's (`_h`) is the environment's
+    _astar = property(lambda self: self._handle)
+
     def __init__(self, env, heights, risks, stuck_threshold: float, a_lim, delta_t: float, num_lin_vel: int = 10,
                  num_ang_vel: int = 10, lookahead_distance: float = 1.0, walk: str = "serial"):
         """env: a BatchedPlanetaryEnv; its planner (NativeMPPI, horizon = DWA's horizon) rolls out the candidates on `risks` and
@@ -81,18 +84,18 @@ class AStarDWALoop:
         # the A* planner of every instance: one goal-rooted solve, goal = the environment's goal (astar.py:71)
         self.resolution = planner.resolution
         self._x0, self._y0 = planner.x_limits[0], planner.y_limits[0]
-        self._astar = C.c_void_p()
-        self._check_astar(self._lib.bn_astar_create(planner.device_id, G, G, B, C.byref(self._astar)))
+        self._handle = C.c_void_p()
+        self._check(self._lib.bn_astar_create(planner.device_id, G, G, B, C.byref(self._handle)))
         goals = env._goal_pos.detach().cpu().numpy().astype(np.float32)
         for b in range(B):
-            self._check_astar(self._lib.bn_astar_set_map(self._astar, b, C.c_void_p(self._heights[b].ctypes.data),
+            self._check(self._lib.bn_astar_set_map(self._astar, b, C.c_void_p(self._heights[b].ctypes.data),
                                                          C.c_void_p(self._risks[b].ctypes.data), _capi.BN_MEM_HOST,
                                                          self.stuck_threshold, self.resolution))
             gx, gy = self.pos_to_index(goals[b])
-            self._check_astar(self._lib.bn_astar_set_goal(self._astar, b, gx, gy))
-        self._check_astar(self._lib.bn_astar_solve_async(self._astar, stream_ptr(self._dev)))
+            self._check(self._lib.bn_astar_set_goal(self._astar, b, gx, gy))
+        self._check(self._lib.bn_astar_solve_async(self._astar, stream_ptr(self._dev)))
         if walk == "jump":
-            self._check_astar(self._lib.bn_astar_jump_build_async(self._astar, stream_ptr(self._dev)))
+            self._check(self._lib.bn_astar_jump_build_async(self._astar, stream_ptr(self._dev)))
         self._prev = torch.zeros(B, 2, device=self._dev)          # the window centre: DWA's _previous_action_seq[0] (zeros, dwa.py:59)
         self._steps = 0
         self.status = np.zeros(B, np.int32)
@@ -105,10 +108,6 @@ class AStarDWALoop:
         p = np.asarray(pos, np.float32)
         return (int((p[0] - np.float32(self._x0)) / np.float32(self.resolution)),
                 int((p[1] - np.float32(self._y0)) / np.float32(self.resolution)))
-
-    def _check_astar(self, code):
-        if code < 0:
-            raise _capi.BenchnavError(code, self._lib.bn_astar_last_error().decode("utf-8", "replace"))
 
     def reset(self):
         """A new episode: forget the root cells, the statuses and the step count, and re-centre the window on zero.  env.reset()
@@ -180,15 +179,3 @@ class AStarDWALoop:
             if s in _MESSAGES:
                 raise ValueError(_MESSAGES[s])
             raise RuntimeError(f"instance {b}: the A* field solve failed (status {s})")
-
-    def close(self):
-        h = getattr(self, "_astar", None)
-        if h is not None and h.value:
-            self._lib.bn_astar_destroy(h)
-            self._astar = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -25,7 +25,7 @@ import torch
 import torch.nn as nn
 
 from . import _capi
-from ._device import _PlannerHandle, _TreePlanner, _check_seed, check, seed_array, tree_capacity
+from ._device import _PlannerHandle, _TreePlanner, _check_seed, check, resolve_device, seed_array, tree_capacity
 
 WORDS = ("LSL", "RSR", "RSL", "LSR", "RLR", "LRL")
 _POINTS = 64
@@ -82,7 +82,7 @@ class _Handle(_PlannerHandle):
         super().__init__(lib, dev, B, cfg)
         self.path_cap = int(lib.bn_clrrt_path_cap(self.h))
         goal = np.ascontiguousarray(owner._goal_host.numpy()[:2], np.float32)
-        _check(lib, lib.bn_clrrt_set_map(self.h, owner._risk.ctypes.data, goal.ctypes.data, float(owner._stuck_threshold)))
+        self._check(lib.bn_clrrt_set_map(self.h, owner._risk.ctypes.data, goal.ctypes.data, float(owner._stuck_threshold)))
 
 
 class CLRRT(_TreePlanner, nn.Module):
@@ -129,10 +129,7 @@ class CLRRT(_TreePlanner, nn.Module):
         self.tree = None
         self._planner_name = "cl_rrt"
         self._start_node = None
-        if not torch.cuda.is_available():
-            raise RuntimeError("benchnav_amd.CLRRT needs an MI355X (gfx950) device; there is no CPU fallback")
-        dev = torch.device(self.device)
-        self._dev = dev if dev.type == "cuda" and dev.index is not None else torch.device("cuda", torch.cuda.current_device())
+        self._dev = resolve_device(self.device, "CLRRT", lenient=True)
         self._goal_node = self._goal_host.clone()                 # grows by one heading per forward(), as the reference's does
         self._lib = _capi.load()
         self._handles = {}

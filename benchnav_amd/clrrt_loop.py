@@ -181,10 +181,4 @@ class CLRRTLoop:
         h = getattr(self, "_handle", None)
         if h is not None:
             h.close()
-            self._handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+            self._handle = None                             # (a loop that just goes leaves the closing to its _Handle)

@@ -439,6 +439,7 @@ struct bn_astar {
     size_t starts_cap = 0;
     hipEvent_t ev_jump_start = nullptr, ev_jump_kernels = nullptr, ev_jump_done = nullptr;
     bool jump_valid = false, jump_pending = false;   // built behind the latest solve and not stale; error word not yet read
+    bn::DeviceBuffers bufs, jumps;              // the table of all of the above (bn_host.h); `jumps` is built by the first table build
 };
 
 namespace {
@@ -449,9 +450,8 @@ int astar_fail(int code, const std::string &msg)
     return code;
 }
 
-using bn::DeviceGuard;
-
 #define ASTAR_HIP(expr) BN_HIP_AS(astar_fail, expr, #expr)
+#define ASTAR_ON_DEVICE(h) BN_ON_DEVICE(astar_fail, (h)->device)
 
 // an enqueued episode still reads the buffers: wait for it before they are rewritten or freed
 void wait_readers(bn_astar_t *h)
@@ -463,29 +463,6 @@ void wait_readers(bn_astar_t *h)
     if (!h->reader_pending) return;
     (void)hipEventSynchronize(h->ev_reader);
     h->reader_pending = false;
-}
-
-// the tables' buffers and events, allocated together by the first build; h->jump is set last, so it stands for all of them
-void jump_free(bn_astar_t *h)
-{
-    for (int32_t **p : {&h->jump, &h->hopbuf[0], &h->hopbuf[1], &h->jerr})
-        if (*p) { (void)hipFree(*p); *p = nullptr; }
-    if (h->jerr_host) { (void)hipHostFree(h->jerr_host); h->jerr_host = nullptr; }
-    for (hipEvent_t *e : {&h->ev_jump_start, &h->ev_jump_kernels, &h->ev_jump_done})
-        if (*e) { (void)hipEventDestroy(*e); *e = nullptr; }
-}
-
-hipError_t jump_alloc(bn_astar_t *h, size_t total)
-{
-    hipError_t e;
-    if ((e = hipMalloc((void **)&h->hopbuf[0], total * 4)) != hipSuccess) return e;
-    if ((e = hipMalloc((void **)&h->hopbuf[1], total * 4)) != hipSuccess) return e;
-    if ((e = hipMalloc((void **)&h->jerr, 2 * 4)) != hipSuccess) return e;
-    if ((e = hipHostMalloc((void **)&h->jerr_host, 2 * 4, hipHostMallocDefault)) != hipSuccess) return e;
-    if ((e = hipEventCreate(&h->ev_jump_start)) != hipSuccess) return e;
-    if ((e = hipEventCreate(&h->ev_jump_kernels)) != hipSuccess) return e;
-    if ((e = hipEventCreate(&h->ev_jump_done)) != hipSuccess) return e;
-    return hipMalloc((void **)&h->jump, total * h->levels * 4);
 }
 
 // BN_OK when the tables are current and their build found next valid (waits for a pending build)
@@ -525,6 +502,31 @@ int astar_wait(bn_astar_t *h)
     return BN_OK;
 }
 
+// What bn_astar_create builds: every buffer, pinned block and event of the handle entered in its tables, the solve's allocated.
+int astar_init(bn_astar_t *h)
+{
+    const int B = h->B;
+    const size_t cells = (size_t)h->H * h->W * B;
+    h->inst.assign(B, bn::InstParams{-1, -1, 0.0f, 0});
+    h->have_map.assign(B, 0);
+    bn::DeviceBuffers &m = h->bufs, &j = h->jumps;
+    m.add(&h->heights, cells * 4); m.add(&h->risk, cells * 4); m.add(&h->D, cells * 4); m.add(&h->next, cells);
+    m.add(&h->flags, (size_t)B * h->TX * h->TY * 4); m.add(&h->ctl, 4 * 4); m.add(&h->inst_dev, sizeof(bn::InstParams) * B);
+    m.add_later(&h->starts_dev);                // grows with the largest n of host starts (starts_cap)
+    m.add_pinned(&h->inst_pinned, sizeof(bn::InstParams) * B); m.add_pinned(&h->next_host, cells); m.add_pinned(&h->ctl_host, 4 * 4);
+    m.add_event(&h->ev_start); m.add_event(&h->ev_kernels); m.add_event(&h->ev_done);
+    m.add_event(&h->ev_reader, hipEventDisableTiming);
+    j.add(&h->hopbuf[0], cells * 4); j.add(&h->hopbuf[1], cells * 4); j.add(&h->jerr, 2 * 4); j.add_pinned(&h->jerr_host, 2 * 4);
+    j.add_event(&h->ev_jump_start); j.add_event(&h->ev_jump_kernels); j.add_event(&h->ev_jump_done);
+    j.add(&h->jump, cells * h->levels * 4);
+    if (int rc = m.alloc_all(astar_fail)) return rc;
+    int clock_khz = 0;
+    ASTAR_HIP(hipDeviceGetAttribute(&clock_khz, hipDeviceAttributeWallClockRate, h->device));
+    std::memset(h->ctl_host, 0, 16);
+    h->deadline_ticks = (uint64_t)(clock_khz > 0 ? clock_khz : 100000) * 1000ull * 5ull;    // 5 s
+    return BN_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -538,46 +540,17 @@ int bn_astar_create(int32_t device_id, int32_t H, int32_t W, int32_t B, bn_astar
     *out = nullptr;
     if (H < 1 || W < 1 || B < 1 || (int64_t)H * W > (1 << 26) || (int64_t)H * W * B > ((int64_t)1 << 31))
         return astar_fail(BN_ERR_INVALID, "H, W, B must be >= 1 and the field must fit 2^31 cells");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return astar_fail(BN_ERR_NO_DEVICE, "no HIP device visible: no CPU fallback");
-    if (device_id < 0 || device_id >= ndev) return astar_fail(BN_ERR_INVALID, "device_id out of range");
-    DeviceGuard guard(device_id);
-    if (!guard.ok) return astar_fail(BN_ERR_HIP, "hipSetDevice failed");
+    if (int rc = bn::open_device(device_id, astar_fail)) return rc;
+    BN_ON_DEVICE(astar_fail, device_id);
     auto *h = new bn_astar_t();
     h->device = device_id; h->H = H; h->W = W; h->B = B;
     h->TX = (W + bn::kTile - 1) / bn::kTile;
     h->TY = (H + bn::kTile - 1) / bn::kTile;
     while (((int64_t)1 << h->levels) < (int64_t)H * W) ++h->levels;
-    const size_t cells = (size_t)H * W * B;
-    h->inst.assign(B, bn::InstParams{-1, -1, 0.0f, 0});
-    h->have_map.assign(B, 0);
-    int clock_khz = 0;
-    auto bad = [&](hipError_t e, const char *what) {
-        if (e == hipSuccess) return false;
-        astar_fail(BN_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
-        return true;
-    };
-    if (bad(hipMalloc((void **)&h->heights, cells * 4), "hipMalloc heights") ||
-        bad(hipMalloc((void **)&h->risk, cells * 4), "hipMalloc risk") ||
-        bad(hipMalloc((void **)&h->D, cells * 4), "hipMalloc D") ||
-        bad(hipMalloc((void **)&h->next, cells), "hipMalloc next") ||
-        bad(hipMalloc((void **)&h->flags, (size_t)B * h->TX * h->TY * 4), "hipMalloc flags") ||
-        bad(hipMalloc((void **)&h->ctl, 4 * 4), "hipMalloc ctl") ||
-        bad(hipMalloc((void **)&h->inst_dev, sizeof(bn::InstParams) * B), "hipMalloc inst") ||
-        bad(hipHostMalloc((void **)&h->inst_pinned, sizeof(bn::InstParams) * B, hipHostMallocDefault), "hipHostMalloc inst") ||
-        bad(hipHostMalloc((void **)&h->next_host, cells, hipHostMallocDefault), "hipHostMalloc next") ||
-        bad(hipHostMalloc((void **)&h->ctl_host, 4 * 4, hipHostMallocDefault), "hipHostMalloc ctl") ||
-        bad(hipEventCreate(&h->ev_start), "hipEventCreate") || bad(hipEventCreate(&h->ev_kernels), "hipEventCreate") ||
-        bad(hipEventCreate(&h->ev_done), "hipEventCreate") ||
-        bad(hipDeviceGetAttribute(&clock_khz, hipDeviceAttributeWallClockRate, device_id), "wall clock rate") ||
-        bad(hipMemset(h->heights, 0, cells * 4), "hipMemset") || bad(hipMemset(h->risk, 0, cells * 4), "hipMemset")) {
-        std::string keep = bn::g_astar_error;
-        bn_astar_destroy(h);
-        bn::g_astar_error = keep;
-        return BN_ERR_HIP;
+    if (int rc = astar_init(h)) {
+        bn_astar_destroy(h);                    // leaves the error text as astar_init set it
+        return rc;
     }
-    std::memset(h->ctl_host, 0, 16);
-    h->deadline_ticks = (uint64_t)(clock_khz > 0 ? clock_khz : 100000) * 1000ull * 5ull;    // 5 s
     *out = h;
     return BN_OK;
 }
@@ -585,16 +558,11 @@ int bn_astar_create(int32_t device_id, int32_t H, int32_t W, int32_t B, bn_astar
 void bn_astar_destroy(bn_astar_t *h)
 {
     if (!h) return;
-    DeviceGuard guard(h->device);
+    bn::DeviceGuard guard(h->device);
     if (h->pending_check) (void)hipEventSynchronize(h->ev_done);
     wait_readers(h);
-    for (void *p : {(void *)h->heights, (void *)h->risk, (void *)h->D, (void *)h->next, (void *)h->flags, (void *)h->ctl, (void *)h->inst_dev,
-                    (void *)h->jump, (void *)h->hopbuf[0], (void *)h->hopbuf[1], (void *)h->jerr, (void *)h->starts_dev})
-        if (p) (void)hipFree(p);
-    for (void *p : {(void *)h->inst_pinned, (void *)h->next_host, (void *)h->ctl_host, (void *)h->jerr_host})
-        if (p) (void)hipHostFree(p);
-    for (hipEvent_t e : {h->ev_start, h->ev_kernels, h->ev_done, h->ev_reader, h->ev_jump_start, h->ev_jump_kernels, h->ev_jump_done})
-        if (e) (void)hipEventDestroy(e);
+    h->jumps.free_all();
+    h->bufs.free_all();
     delete h;
 }
 
@@ -609,8 +577,7 @@ int bn_astar_set_map(bn_astar_t *h, int32_t inst, const float *heights, const fl
     if (!(resolution > 0.0) || !std::isfinite(resolution)) return astar_fail(BN_ERR_INVALID, "resolution must be finite and > 0");
     if (h->resolution > 0.0 && resolution != h->resolution) return astar_fail(BN_ERR_INVALID, "every instance must share one resolution");
     if (where != BN_MEM_HOST && where != BN_MEM_DEVICE) return astar_fail(BN_ERR_INVALID, "unknown memory kind");
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return astar_fail(BN_ERR_HIP, "hipSetDevice failed");
+    ASTAR_ON_DEVICE(h);
     if (h->pending_check) { ASTAR_HIP(hipEventSynchronize(h->ev_done)); h->pending_check = false; }
     wait_readers(h);
     const size_t cells = (size_t)h->H * h->W, off = cells * inst;
@@ -649,8 +616,7 @@ int bn_astar_solve_async(bn_astar_t *h, void *stream)
     if (!h) return astar_fail(BN_ERR_INVALID, "null handle");
     for (int b = 0; b < h->B; ++b)
         if (!h->have_map[b]) return astar_fail(BN_ERR_STATE, "instance " + std::to_string(b) + " has no map");
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return astar_fail(BN_ERR_HIP, "hipSetDevice failed");
+    ASTAR_ON_DEVICE(h);
     if (h->pending_check) { ASTAR_HIP(hipEventSynchronize(h->ev_done)); h->pending_check = false; }   // pinned buffers are reused
     wait_readers(h);
     hipStream_t s = (hipStream_t)stream;
@@ -687,7 +653,7 @@ int bn_astar_solve_async(bn_astar_t *h, void *stream)
 int bn_astar_sync(bn_astar_t *h)
 {
     if (!h) return astar_fail(BN_ERR_INVALID, "null handle");
-    DeviceGuard guard(h->device);
+    ASTAR_ON_DEVICE(h);
     int rc = astar_wait(h);
     if (rc != BN_OK || !h->jump_valid) return rc;
     return jump_ready(h);
@@ -697,7 +663,7 @@ int bn_astar_sync(bn_astar_t *h)
 int bn_astar_kernel_ms(bn_astar_t *h, float *ms)
 {
     if (!h || !ms) return astar_fail(BN_ERR_INVALID, "null argument");
-    DeviceGuard guard(h->device);
+    ASTAR_ON_DEVICE(h);
     int rc = astar_wait(h);
     if (rc != BN_OK) return rc;
     ASTAR_HIP(hipEventElapsedTime(ms, h->ev_start, h->ev_kernels));
@@ -714,7 +680,7 @@ int bn_astar_path(bn_astar_t *h, int32_t inst, int32_t ix, int32_t iy, int32_t *
     if (inst < 0 || inst >= h->B) return astar_fail(BN_ERR_INVALID, "instance out of range");
     if (ix < 0 || ix >= h->W || iy < 0 || iy >= h->H) return astar_fail(BN_ERR_INVALID, "start out of bounds");
     if (max_len > 0 && !out_xy) return astar_fail(BN_ERR_INVALID, "null output");
-    DeviceGuard guard(h->device);
+    ASTAR_ON_DEVICE(h);
     int rc = astar_wait(h);
     if (rc != BN_OK) return rc;
     const uint8_t *nx = h->next_host + (size_t)h->H * h->W * inst;
@@ -750,18 +716,11 @@ int bn_astar_jump_build_async(bn_astar_t *h, void *stream)
 {
     if (!h) return astar_fail(BN_ERR_INVALID, "null handle");
     if (!h->solved) return astar_fail(BN_ERR_STATE, "no solve has been enqueued: bn_astar_solve_async must precede the table build");
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return astar_fail(BN_ERR_HIP, "hipSetDevice failed");
+    ASTAR_ON_DEVICE(h);
     wait_readers(h);                              // an earlier build (its pinned word), episodes and paths reading the old tables
     const size_t cells = (size_t)h->H * h->W, total = cells * h->B;
     h->jump_valid = false;                        // until this build is enqueued whole: a failure below leaves no current tables
-    if (!h->jump) {
-        const hipError_t e = jump_alloc(h, total);
-        if (e != hipSuccess) {
-            jump_free(h);                         // all or nothing: the next build allocates again
-            return astar_fail(BN_ERR_HIP, std::string("jump table allocation: ") + hipGetErrorString(e));
-        }
-    }
+    if (int rc = h->jumps.ensure(astar_fail)) return rc;      // all or nothing: after a failure the next build allocates again
     hipStream_t s = (hipStream_t)stream;
     ASTAR_HIP(hipStreamWaitEvent(s, h->ev_kernels, 0));
     ASTAR_HIP(hipEventRecord(h->ev_jump_start, s));
@@ -792,7 +751,7 @@ int bn_astar_jump_build_async(bn_astar_t *h, void *stream)
 int bn_astar_jump_ms(bn_astar_t *h, float *ms)
 {
     if (!h || !ms) return astar_fail(BN_ERR_INVALID, "null argument");
-    DeviceGuard guard(h->device);
+    ASTAR_ON_DEVICE(h);
     int rc = jump_ready(h);
     if (rc != BN_OK) return rc;
     ASTAR_HIP(hipEventElapsedTime(ms, h->ev_jump_start, h->ev_jump_kernels));
@@ -806,8 +765,7 @@ int bn_astar_paths_async(bn_astar_t *h, int32_t inst, const int32_t *starts_xy, 
     if (inst < 0 || inst >= h->B) return astar_fail(BN_ERR_INVALID, "instance out of range");
     if (n < 0 || max_len < 0) return astar_fail(BN_ERR_INVALID, "n and max_len must be >= 0");
     if (where != BN_MEM_HOST && where != BN_MEM_DEVICE) return astar_fail(BN_ERR_INVALID, "unknown memory kind");
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return astar_fail(BN_ERR_HIP, "hipSetDevice failed");
+    ASTAR_ON_DEVICE(h);
     int rc = jump_ready(h);
     if (rc != BN_OK) return rc;
     if (n == 0) return BN_OK;
@@ -819,9 +777,8 @@ int bn_astar_paths_async(bn_astar_t *h, int32_t inst, const int32_t *starts_xy, 
     if (where == BN_MEM_HOST) {
         wait_readers(h);                          // an earlier call's kernel may still read the staging buffer
         if ((size_t)n > h->starts_cap) {
-            if (h->starts_dev) ASTAR_HIP(hipFree(h->starts_dev));
-            h->starts_dev = nullptr; h->starts_cap = 0;
-            ASTAR_HIP(hipMalloc((void **)&h->starts_dev, (size_t)n * 2 * 4));
+            h->starts_cap = 0;
+            if ((rc = h->bufs.resize(&h->starts_dev, (size_t)n * 2 * 4, astar_fail))) return rc;
             h->starts_cap = (size_t)n;
         }
         ASTAR_HIP(hipMemcpyAsync(h->starts_dev, starts_xy, (size_t)n * 2 * 4, hipMemcpyHostToDevice, s));
@@ -867,8 +824,7 @@ int astar_view(bn_astar_t *h, AStarView *v)
 
 int astar_add_reader(bn_astar_t *h, hipStream_t s)
 {
-    DeviceGuard guard(h->device);
-    if (!h->ev_reader) ASTAR_HIP(hipEventCreateWithFlags(&h->ev_reader, hipEventDisableTiming));
+    ASTAR_ON_DEVICE(h);
     // one event stands for every reader: `s` waits, on the device, for the readers another stream enqueued before it is re-recorded
     if (h->reader_pending && h->reader_stream != s) ASTAR_HIP(hipStreamWaitEvent(s, h->ev_reader, 0));
     ASTAR_HIP(hipEventRecord(h->ev_reader, s));

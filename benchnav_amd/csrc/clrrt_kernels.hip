@@ -583,8 +583,7 @@ int clrrt_loop_reset(bn_clrrt *h, hipStream_t s, const float *goal_nodes, const 
         if (!std::isfinite(goal_nodes[3 * b]) || !std::isfinite(goal_nodes[3 * b + 1]) || !std::isfinite(goal_nodes[3 * b + 2]))
             return clrrt_fail(BN_ERR_INVALID, "goal nodes must be finite");
     }
-    bn::DeviceGuard guard(h->cfg.device_id);
-    if (!guard.ok) return clrrt_fail(BN_ERR_HIP, "hipSetDevice failed");
+    BN_ON_DEVICE(clrrt_fail, h->cfg.device_id);
     if (h->ev_recorded) CLRRT_HIP(hipEventSynchronize(h->ev_done));                    // the staging block is free again
     const size_t B = h->B;
     std::memcpy(h->pinned + B * 12, goal_nodes, B * 12);
@@ -603,8 +602,7 @@ int clrrt_plan_masked(bn_clrrt *h, hipStream_t s, const int32_t *active, int dra
 {
     if (!h || !active) return clrrt_fail(BN_ERR_INVALID, "null argument");
     if (!h->have_map) return clrrt_fail(BN_ERR_STATE, "bn_clrrt_set_map has not been called");
-    bn::DeviceGuard guard(h->cfg.device_id);
-    if (!guard.ok) return clrrt_fail(BN_ERR_HIP, "hipSetDevice failed");
+    BN_ON_DEVICE(clrrt_fail, h->cfg.device_id);
     if (draw)
         if (int rc = tree_draw_samples<3>(h, s, false, active, clrrt_fail)) return rc;
     return clrrt_grow_and_pick(h, s, active);
@@ -665,11 +663,8 @@ int bn_clrrt_create(const bn_clrrt_config *cfg, bn_clrrt_t **out)
     if (!(cfg->delta_t > 0.0) || !(cfg->transit_dt > 0.0)) return clrrt_fail(BN_ERR_INVALID, "time steps must be positive");
     if (!(cfg->u_min[0] <= cfg->u_max[0]) || !(cfg->u_min[1] <= cfg->u_max[1])) return clrrt_fail(BN_ERR_INVALID, "action bounds must be ordered");
     if (cfg->seed > 0xFFFFFFFFull) return clrrt_fail(BN_ERR_INVALID, "Seed must be between 0 and 2**32 - 1");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return clrrt_fail(BN_ERR_NO_DEVICE, "no HIP device visible: no CPU fallback");
-    if (cfg->device_id < 0 || cfg->device_id >= ndev) return clrrt_fail(BN_ERR_INVALID, "device_id out of range");
-    bn::DeviceGuard guard(cfg->device_id);
-    if (!guard.ok) return clrrt_fail(BN_ERR_HIP, "hipSetDevice failed");
+    if (int rc = bn::open_device(cfg->device_id, clrrt_fail)) return rc;
+    BN_ON_DEVICE(clrrt_fail, cfg->device_id);
     auto *h = new bn_clrrt_t();
     h->cfg = *cfg;
     h->B = cfg->num_instances; h->iters = cfg->max_iterations; h->cap = h->iters + 1; h->S = cfg->max_seqs;
@@ -718,17 +713,13 @@ int bn_clrrt_create(const bn_clrrt_config *cfg, bn_clrrt_t **out)
     t.add(&h->st_ctrl_out, B * 32, BN_CLRRT_BUF_STEER_CONTROLLERS);
     t.add(&h->st_tgt, B * S * 4, BN_CLRRT_BUF_STEER_TARGETS);
     t.add(&h->st_results, B * bn::kClrrtSteerResult * 4, BN_CLRRT_BUF_STEER_RESULTS);
+    t.add_pinned(&h->pinned, B * 48);
+    t.add_event(&h->ev_done);
     if (int rc = t.alloc_all(clrrt_fail)) {
-        std::string keep = bn::g_clrrt_error;
-        bn_clrrt_destroy(h);
-        bn::g_clrrt_error = keep;
+        bn_clrrt_destroy(h);                 // leaves the error text alone
         return rc;
     }
     p.map = h->map;
-    if (hipHostMalloc((void **)&h->pinned, B * 48, hipHostMallocDefault) != hipSuccess || hipEventCreate(&h->ev_done) != hipSuccess) {
-        bn_clrrt_destroy(h);
-        return clrrt_fail(BN_ERR_HIP, "CL-RRT handle initialisation failed");
-    }
     h->pinned_seeds = (uint64_t *)(h->pinned + B * 40);
     *out = h;
     return BN_OK;
@@ -740,8 +731,6 @@ void bn_clrrt_destroy(bn_clrrt_t *h)
     bn::DeviceGuard guard(h->cfg.device_id);
     if (h->ev_recorded && h->ev_done) (void)hipEventSynchronize(h->ev_done);
     h->bufs.free_all();
-    if (h->pinned) (void)hipHostFree(h->pinned);
-    if (h->ev_done) (void)hipEventDestroy(h->ev_done);
     delete h;
 }
 
@@ -749,8 +738,7 @@ int bn_clrrt_set_map(bn_clrrt_t *h, const float *risk, const float *goal, double
 {
     if (!h || !risk || !goal) return clrrt_fail(BN_ERR_INVALID, "null argument");
     if (!std::isfinite(stuck_threshold) || !std::isfinite(goal[0]) || !std::isfinite(goal[1])) return clrrt_fail(BN_ERR_INVALID, "goal and stuck threshold must be finite");
-    bn::DeviceGuard guard(h->cfg.device_id);
-    if (!guard.ok) return clrrt_fail(BN_ERR_HIP, "hipSetDevice failed");
+    BN_ON_DEVICE(clrrt_fail, h->cfg.device_id);
     if (h->ev_recorded) CLRRT_HIP(hipEventSynchronize(h->ev_done));
     CLRRT_HIP(hipMemcpy(h->map, risk, (size_t)h->c.p.G * h->c.p.G * 4, hipMemcpyHostToDevice));
     CLRRT_HIP(hipMemcpy(h->goal, goal, 8, hipMemcpyHostToDevice));
@@ -783,8 +771,7 @@ int bn_clrrt_steer_async(bn_clrrt_t *h, void *stream, const float *from_states, 
         if (!std::isfinite(from_states[i]) || !std::isfinite(targets[i])) return clrrt_fail(BN_ERR_INVALID, "states and targets must be finite");
     for (int i = 0; i < h->B * 4; ++i)
         if (!std::isfinite(controller_states[i])) return clrrt_fail(BN_ERR_INVALID, "controller states must be finite");
-    bn::DeviceGuard guard(h->cfg.device_id);
-    if (!guard.ok) return clrrt_fail(BN_ERR_HIP, "hipSetDevice failed");
+    BN_ON_DEVICE(clrrt_fail, h->cfg.device_id);
     hipStream_t s = (hipStream_t)stream;
     if (h->ev_recorded) CLRRT_HIP(hipEventSynchronize(h->ev_done));
     const size_t B = h->B;
@@ -806,8 +793,7 @@ int bn_clrrt_steer_async(bn_clrrt_t *h, void *stream, const float *from_states, 
 int bn_clrrt_sync(bn_clrrt_t *h)
 {
     if (!h) return clrrt_fail(BN_ERR_INVALID, "null handle");
-    bn::DeviceGuard guard(h->cfg.device_id);
-    if (!guard.ok) return clrrt_fail(BN_ERR_HIP, "hipSetDevice failed");
+    BN_ON_DEVICE(clrrt_fail, h->cfg.device_id);
     return bn::tree_wait_done(h, clrrt_fail);
 }
 

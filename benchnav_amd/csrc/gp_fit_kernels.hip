@@ -539,11 +539,8 @@ int bn_gp_fit_create(int32_t device_id, int32_t n, const double *x, const double
     if (!std::isfinite(noise_lower_bound) || noise_lower_bound < 0.0) return fit_fail(BN_ERR_INVALID, "noise_lower_bound must be finite and >= 0");
     for (int i = 0; i < n; ++i)
         if (!std::isfinite(x[i]) || !std::isfinite(y[i])) return fit_fail(BN_ERR_INVALID, "x and y must be finite");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fit_fail(BN_ERR_NO_DEVICE, "no HIP device visible: no CPU fallback");
-    if (device_id < 0 || device_id >= ndev) return fit_fail(BN_ERR_INVALID, "device_id out of range");
-    bn::DeviceGuard guard(device_id);
-    if (!guard.ok) return fit_fail(BN_ERR_HIP, "hipSetDevice failed");
+    if (int rc = bn::open_device(device_id, fit_fail)) return rc;
+    BN_ON_DEVICE(fit_fail, device_id);
     auto *h = new bn_gp_fit_t();
     h->device = device_id; h->n = n; h->npad = bn::fit_npad(n); h->T = h->npad / bn::kFitNB;
     const size_t np = (size_t)h->npad, T = (size_t)h->T;
@@ -570,9 +567,7 @@ int bn_gp_fit_create(int32_t device_id, int32_t n, const double *x, const double
         if (rc == BN_OK) rc = bn::fit_upload_state(h, st);
     }
     if (rc != BN_OK) {
-        std::string keep = bn::g_fit_error;
-        bn_gp_fit_destroy(h);
-        bn::g_fit_error = keep;
+        bn_gp_fit_destroy(h);                // leaves the error text alone
         return rc;
     }
     *out = h;
@@ -593,8 +588,7 @@ int bn_gp_fit_set_raw(bn_gp_fit_t *h, const double *raw)
     if (!h || !raw) return fit_fail(BN_ERR_INVALID, "null argument");
     for (int p = 0; p < 4; ++p)
         if (!std::isfinite(raw[p])) return fit_fail(BN_ERR_INVALID, "the raw parameters must be finite");
-    bn::DeviceGuard guard(h->device);
-    if (!guard.ok) return fit_fail(BN_ERR_HIP, "hipSetDevice failed");
+    BN_ON_DEVICE(fit_fail, h->device);
     bn::GpFitState old{}, st{};
     if (int rc = bn::fit_download_state(h, &old)) return rc;
     if (int rc = bn::fit_state_from_raw(raw, old.lower_bound, &st)) return rc;
@@ -610,8 +604,7 @@ int bn_gp_fit_set_hyperparameters(bn_gp_fit_t *h, double constant, double output
     if (!(outputscale > 0.0) || !(lengthscale > 0.0) || !(noise > 0.0)) return fit_fail(BN_ERR_INVALID, "outputscale, lengthscale and noise must be > 0");
     const double q = -1.0 / (2.0 * lengthscale * lengthscale);
     if (!std::isfinite(q) || q == 0.0) return fit_fail(BN_ERR_INVALID, "lengthscale out of range: 1 / (2 l^2) must be finite and non-zero");
-    bn::DeviceGuard guard(h->device);
-    if (!guard.ok) return fit_fail(BN_ERR_HIP, "hipSetDevice failed");
+    BN_ON_DEVICE(fit_fail, h->device);
     bn::GpFitState old{}, st{};
     if (int rc = bn::fit_download_state(h, &old)) return rc;
     st.lower_bound = old.lower_bound;
@@ -624,8 +617,7 @@ int bn_gp_fit_set_hyperparameters(bn_gp_fit_t *h, double constant, double output
 int bn_gp_fit_evaluate_async(bn_gp_fit_t *h, void *stream)
 {
     if (!h) return fit_fail(BN_ERR_INVALID, "null argument");
-    bn::DeviceGuard guard(h->device);
-    if (!guard.ok) return fit_fail(BN_ERR_HIP, "hipSetDevice failed");
+    BN_ON_DEVICE(fit_fail, h->device);
     return bn::fit_enqueue(h, (hipStream_t)stream, true);
 }
 
@@ -638,8 +630,7 @@ int bn_gp_fit_run_async(bn_gp_fit_t *h, void *stream, int32_t iterations, double
     if (!h) return fit_fail(BN_ERR_INVALID, "null argument");
     if (h->enqueued + (int64_t)iterations > bn::kFitHistory)
         return fit_fail(BN_ERR_INVALID, "a handle records at most " + std::to_string(bn::kFitHistory) + " iterations");
-    bn::DeviceGuard guard(h->device);
-    if (!guard.ok) return fit_fail(BN_ERR_HIP, "hipSetDevice failed");
+    BN_ON_DEVICE(fit_fail, h->device);
     hipStream_t s = (hipStream_t)stream;
     for (int it = 0; it < iterations; ++it) {
         if (int rc = bn::fit_enqueue(h, s, true)) return rc;
@@ -654,8 +645,7 @@ int bn_gp_fit_run_async(bn_gp_fit_t *h, void *stream, int32_t iterations, double
 int bn_gp_fit_read(bn_gp_fit_t *h, double *raw, double *grad, double *loss, int32_t *status, int32_t *failed_iteration)
 {
     if (!h) return fit_fail(BN_ERR_INVALID, "null argument");
-    bn::DeviceGuard guard(h->device);
-    if (!guard.ok) return fit_fail(BN_ERR_HIP, "hipSetDevice failed");
+    BN_ON_DEVICE(fit_fail, h->device);
     bn::GpFitState st{};
     if (int rc = bn::fit_download_state(h, &st)) return rc;
     if (raw) std::memcpy(raw, st.raw, sizeof(st.raw));
@@ -669,8 +659,7 @@ int bn_gp_fit_read(bn_gp_fit_t *h, double *raw, double *grad, double *loss, int3
 int bn_gp_fit_hyperparameters(bn_gp_fit_t *h, double *hyp)
 {
     if (!h || !hyp) return fit_fail(BN_ERR_INVALID, "null argument");
-    bn::DeviceGuard guard(h->device);
-    if (!guard.ok) return fit_fail(BN_ERR_HIP, "hipSetDevice failed");
+    BN_ON_DEVICE(fit_fail, h->device);
     bn::GpFitState st{};
     if (int rc = bn::fit_download_state(h, &st)) return rc;
     std::memcpy(hyp, st.hyp, 4 * sizeof(double));
@@ -680,8 +669,7 @@ int bn_gp_fit_hyperparameters(bn_gp_fit_t *h, double *hyp)
 int32_t bn_gp_fit_history(bn_gp_fit_t *h, double *losses, int32_t capacity)
 {
     if (!h || (!losses && capacity > 0) || capacity < 0) return fit_fail(BN_ERR_INVALID, "null argument or negative capacity");
-    bn::DeviceGuard guard(h->device);
-    if (!guard.ok) return fit_fail(BN_ERR_HIP, "hipSetDevice failed");
+    BN_ON_DEVICE(fit_fail, h->device);
     bn::GpFitState st{};
     if (int rc = bn::fit_download_state(h, &st)) return rc;
     const int done = st.iteration < bn::kFitHistory ? st.iteration : bn::kFitHistory;
@@ -695,8 +683,7 @@ int bn_gp_fit_finish(bn_gp_fit_t *h, void *stream, bn_gp_t **out)
     if (!out) return fit_fail(BN_ERR_INVALID, "null handle pointer");
     *out = nullptr;
     if (!h) return fit_fail(BN_ERR_INVALID, "null argument");
-    bn::DeviceGuard guard(h->device);
-    if (!guard.ok) return fit_fail(BN_ERR_HIP, "hipSetDevice failed");
+    BN_ON_DEVICE(fit_fail, h->device);
     hipStream_t s = (hipStream_t)stream;
     if (int rc = bn::fit_enqueue(h, s, false)) return rc;
     bn::GpFitState st{};
@@ -705,12 +692,10 @@ int bn_gp_fit_finish(bn_gp_fit_t *h, void *stream, bn_gp_t **out)
         return fit_fail(BN_ERR_STATE, "k(x, x) + noise I is not numerically positive definite at iteration " + std::to_string(st.failed_iteration) +
                                           " (no jitter is added)");
     auto *g = new bn_gp_t();
-    g->device = h->device; g->n = h->n; g->npad = (h->n + 15) / 16 * 16;
+    g->device = h->device; g->n = h->n;
     g->c = st.hyp[0]; g->s = st.hyp[1]; g->l = st.hyp[2]; g->noise = st.hyp[3];
+    bn::gp_layout(g);
     const int nb = g->npad / 16;
-    g->bufs.add(&g->x, (size_t)g->npad * 8);
-    g->bufs.add(&g->alpha, (size_t)g->npad * 8);
-    g->bufs.add(&g->linv, (size_t)128 * nb * (nb + 1) * 8);
     int rc = g->bufs.alloc_all(fit_fail);
     if (rc == BN_OK) {
         // the padded x and alpha of the fit are zero beyond n, and npad of the handle is <= the fit's

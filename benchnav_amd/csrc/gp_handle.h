@@ -25,3 +25,21 @@ struct bn_gp {
     bn::DeviceBuffers bufs;
     double *x = nullptr, *alpha = nullptr, *linv = nullptr;
 };
+
+namespace bn {
+namespace {
+
+// The layout of a regressor of g->n points, written once: npad, and the three buffers entered in the table.  Returns the
+// number of doubles of L^-1 in fragment order (nb (nb + 1) fragments of 128, nb = npad / 16).
+size_t gp_layout(bn_gp *g)
+{
+    g->npad = (g->n + 15) / 16 * 16;
+    const size_t nb = (size_t)g->npad / 16, frag = 128 * nb * (nb + 1);
+    g->bufs.add(&g->x, (size_t)g->npad * 8);
+    g->bufs.add(&g->alpha, (size_t)g->npad * 8);
+    g->bufs.add(&g->linv, frag * 8);
+    return frag;
+}
+
+}  // namespace
+}  // namespace bn

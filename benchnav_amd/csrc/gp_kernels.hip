@@ -427,17 +427,15 @@ int bn_gp_create(int32_t device_id, int32_t n, const double *x, const double *al
         for (size_t j = 0; j <= i; ++j)
             if (!std::isfinite(linv[i * (size_t)n + j])) return gp_fail(BN_ERR_INVALID, "the lower triangle of linv must be finite");
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return gp_fail(BN_ERR_NO_DEVICE, "no HIP device visible: no CPU fallback");
-    if (device_id < 0 || device_id >= ndev) return gp_fail(BN_ERR_INVALID, "device_id out of range");
-    bn::DeviceGuard guard(device_id);
-    if (!guard.ok) return gp_fail(BN_ERR_HIP, "hipSetDevice failed");
+    if (int rc = bn::open_device(device_id, gp_fail)) return rc;
+    BN_ON_DEVICE(gp_fail, device_id);
     auto *h = new bn_gp_t();
-    h->device = device_id; h->n = n; h->npad = (n + bn::kGpTile - 1) / bn::kGpTile * bn::kGpTile;
+    h->device = device_id; h->n = n;
     h->c = constant; h->s = outputscale; h->l = lengthscale; h->noise = noise;
+    const size_t nfrag = bn::gp_layout(h);
     const int npad = h->npad, nb = npad / bn::kGpTile;
     // L^-1 in the order the MFMA's A operand is read: row block i, k step j, lane -> L^-1[16 i + (lane & 15)][4 j + (lane >> 4)]
-    std::vector<double> xs(npad, 0.0), as(npad, 0.0), frag((size_t)128 * nb * (nb + 1), 0.0);
+    std::vector<double> xs(npad, 0.0), as(npad, 0.0), frag(nfrag, 0.0);
     std::memcpy(xs.data(), x, (size_t)n * 8);
     std::memcpy(as.data(), alpha, (size_t)n * 8);
     for (int i = 0; i < nb; ++i)
@@ -448,9 +446,6 @@ int bn_gp_create(int32_t device_id, int32_t n, const double *x, const double *al
                 f[l] = (row < n && col <= row) ? linv[(size_t)row * n + col] : 0.0;
             }
         }
-    h->bufs.add(&h->x, (size_t)npad * 8);
-    h->bufs.add(&h->alpha, (size_t)npad * 8);
-    h->bufs.add(&h->linv, frag.size() * 8);
     int rc = h->bufs.alloc_all(gp_fail);
     if (rc == BN_OK) {
         auto up = [&](void *dst, const std::vector<double> &src) {
@@ -460,9 +455,7 @@ int bn_gp_create(int32_t device_id, int32_t n, const double *x, const double *al
         if ((rc = up(h->x, xs)) == BN_OK && (rc = up(h->alpha, as)) == BN_OK) rc = up(h->linv, frag);
     }
     if (rc != BN_OK) {
-        std::string keep = bn::g_gp_error;
-        bn_gp_destroy(h);
-        bn::g_gp_error = keep;
+        bn_gp_destroy(h);                    // leaves the error text alone
         return rc;
     }
     *out = h;
@@ -511,11 +504,8 @@ int bn_gp_predict_async(int32_t device_id, void *stream, bn_gp_t *const *regress
         d.x = r->x; d.alpha = r->alpha; d.linv = r->linv; d.n = r->n; d.npad = r->npad;
         d.c = r->c; d.s = r->s; d.q = -1.0 / (2.0 * r->l * r->l); d.noise = r->noise;
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return gp_fail(BN_ERR_NO_DEVICE, "no HIP device visible: no CPU fallback");
-    if (device_id < 0 || device_id >= ndev) return gp_fail(BN_ERR_INVALID, "device_id out of range");
-    bn::DeviceGuard guard(device_id);
-    if (!guard.ok) return gp_fail(BN_ERR_HIP, "hipSetDevice failed");
+    if (int rc = bn::open_device(device_id, gp_fail)) return rc;
+    BN_ON_DEVICE(gp_fail, device_id);
     hipStream_t s = (hipStream_t)stream;
     int32_t *idx = (int32_t *)workspace_device;
     int32_t *meta = (int32_t *)((char *)workspace_device + bn::gp_align((size_t)num_maps * (size_t)cells * 4));

@@ -149,10 +149,8 @@ int bn_risk_map_infer(int32_t device_id, void *stream, const float *mean, const 
     if (metric != BN_RISK_EXPECTED && !(confidence >= 0.0f && confidence <= 1.0f))
         return fail(BN_ERR_INVALID, "confidence must be in [0, 1]");       // ModelConfig asserts the same (utils.py:27-33)
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(BN_ERR_NO_DEVICE, "no HIP device visible: no CPU fallback");
-    // work on `device_id`, leave the calling thread's current device as it was
-    bn::DeviceGuard guard(device_id);
-    if (!guard.ok) return fail(BN_ERR_HIP, "hipSetDevice failed");
+    if (int rc = bn::count_devices(&ndev, fail)) return rc;
+    BN_ON_DEVICE(fail, device_id);
     hipStream_t s = (hipStream_t)stream;
     const size_t cells = (size_t)grid_size * grid_size;
 #define RISK_HIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { free_all(); return fail(BN_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); } } while (0)

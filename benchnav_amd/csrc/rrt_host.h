@@ -80,8 +80,7 @@ int tree_plan(H *h, void *stream, const float *starts, const float *goals, const
     if (seeds)
         for (int b = 0; b < h->B; ++b)
             if (seeds[b] > 0xFFFFFFFFull) return fail(BN_ERR_INVALID, "Seed must be between 0 and 2**32 - 1");
-    DeviceGuard guard(h->cfg.device_id);
-    if (!guard.ok) return fail(BN_ERR_HIP, "hipSetDevice failed");
+    BN_ON_DEVICE(fail, h->cfg.device_id);
     hipStream_t s = (hipStream_t)stream;
     if (int rc = tree_stage<DIM>(h, starts, goals, s, fail)) return rc;
     const bool reseed = seeds || !h->seeded;                  // the first plan without seeds starts every stream from the config's seed
@@ -100,8 +99,7 @@ template <int DIM, typename H, typename Fail, typename Grow>
 int tree_grow_from_samples(H *h, void *stream, const float *starts, const float *goals, const void *samples, int where, Fail fail, Grow grow)
 {
     if (int rc = tree_check_positions<DIM>(h, starts, goals, fail)) return rc;
-    DeviceGuard guard(h->cfg.device_id);
-    if (!guard.ok) return fail(BN_ERR_HIP, "hipSetDevice failed");
+    BN_ON_DEVICE(fail, h->cfg.device_id);
     hipStream_t s = (hipStream_t)stream;
     if (int rc = tree_stage<DIM>(h, starts, goals, s, fail)) return rc;                // waits for the handle's last launch
     const size_t bytes = (size_t)h->B * h->iters * DIM * 4;

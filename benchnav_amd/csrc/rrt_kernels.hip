@@ -239,11 +239,8 @@ int bn_rrt_create(const bn_rrt_config *cfg, bn_rrt_t **out)
     if (!(cfg->x_limits[1] >= cfg->x_limits[0]) || !(cfg->y_limits[1] >= cfg->y_limits[0])) return rrt_fail(BN_ERR_INVALID, "limits must be ordered");
     if (cfg->seed > 0xFFFFFFFFull) return rrt_fail(BN_ERR_INVALID, "Seed must be between 0 and 2**32 - 1");
     if ((cfg->flags & BN_RRT_FLAG_ONE_WAVE) && (cfg->flags & BN_RRT_FLAG_FOUR_WAVES)) return rrt_fail(BN_ERR_INVALID, "one workgroup size at a time");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return rrt_fail(BN_ERR_NO_DEVICE, "no HIP device visible: no CPU fallback");
-    if (cfg->device_id < 0 || cfg->device_id >= ndev) return rrt_fail(BN_ERR_INVALID, "device_id out of range");
-    bn::DeviceGuard guard(cfg->device_id);
-    if (!guard.ok) return rrt_fail(BN_ERR_HIP, "hipSetDevice failed");
+    if (int rc = bn::open_device(cfg->device_id, rrt_fail)) return rc;
+    BN_ON_DEVICE(rrt_fail, cfg->device_id);
     auto *h = new bn_rrt_t();
     h->cfg = *cfg;
     h->B = cfg->num_instances; h->iters = cfg->max_iterations; h->cap = h->iters + 1;
@@ -267,15 +264,11 @@ int bn_rrt_create(const bn_rrt_config *cfg, bn_rrt_t **out)
     t.add(&h->starts, B * 8);
     t.add(&h->goals, B * 8);
     t.add(&h->seeds, B * 8);
+    t.add_pinned(&h->pinned, B * 24);
+    t.add_event(&h->ev_done);
     if (int rc = t.alloc_all(rrt_fail)) {
-        std::string keep = bn::g_rrt_error;
-        bn_rrt_destroy(h);
-        bn::g_rrt_error = keep;
+        bn_rrt_destroy(h);                   // leaves the error text alone
         return rc;
-    }
-    if (hipHostMalloc((void **)&h->pinned, B * 24, hipHostMallocDefault) != hipSuccess || hipEventCreate(&h->ev_done) != hipSuccess) {
-        bn_rrt_destroy(h);
-        return rrt_fail(BN_ERR_HIP, "RRT handle initialisation failed");
     }
     h->pinned_seeds = (uint64_t *)(h->pinned + B * 16);
     *out = h;
@@ -288,8 +281,6 @@ void bn_rrt_destroy(bn_rrt_t *h)
     bn::DeviceGuard guard(h->cfg.device_id);
     if (h->ev_recorded && h->ev_done) (void)hipEventSynchronize(h->ev_done);
     h->bufs.free_all();
-    if (h->pinned) (void)hipHostFree(h->pinned);
-    if (h->ev_done) (void)hipEventDestroy(h->ev_done);
     delete h;
 }
 
@@ -309,8 +300,7 @@ int bn_rrt_grow_from_samples_async(bn_rrt_t *h, void *stream, const float *start
 int bn_rrt_sync(bn_rrt_t *h)
 {
     if (!h) return rrt_fail(BN_ERR_INVALID, "null handle");
-    bn::DeviceGuard guard(h->cfg.device_id);
-    if (!guard.ok) return rrt_fail(BN_ERR_HIP, "hipSetDevice failed");
+    BN_ON_DEVICE(rrt_fail, h->cfg.device_id);
     return bn::tree_wait_done(h, rrt_fail);
 }
 

@@ -595,7 +595,7 @@ struct bn_terrain {
     double2 *T = nullptr, *tw = nullptr;
     int32_t *classes = nullptr, *cr_count = nullptr, *cr_int = nullptr;
     float *cr_val = nullptr, *lin = nullptr, *cparams = nullptr;
-    int maxc = 0, lin_len = 0, nclass = 0;
+    int maxc = 0, lin_len = 0, nclass = -1;  // what cr_int / cr_val, lin and cparams are sized for (nothing yet)
     hipEvent_t ev_done = nullptr;
     // colouring (allocated by the first bn_terrain_set_coloring / bn_terrain_colorize)
     bool coloring = false, own_noise = false, colored = false, ev_recorded = false;
@@ -612,6 +612,8 @@ struct bn_terrain {
     int32_t *drec = nullptr;
     float *dcenters = nullptr, *dlight_u = nullptr;
     double *dangles = nullptr;
+    // the table of all of the above (bn_host.h): `bufs` from bn_terrain_create on, the groups from their first use
+    bn::DeviceBuffers bufs, color, draw, stage;
 };
 
 namespace {
@@ -624,13 +626,7 @@ int terrain_fail(int code, const std::string &msg)
 
 #define TERRAIN_HIP(expr) BN_HIP_AS(terrain_fail, expr, #expr)
 
-template <typename P>
-int realloc_dev(P **p, size_t bytes)
-{
-    if (*p) { (void)hipFree(*p); *p = nullptr; }
-    TERRAIN_HIP(hipMalloc((void **)p, bytes ? bytes : 4));
-    return BN_OK;
-}
+#define TERRAIN_ON_DEVICE(h) BN_ON_DEVICE(terrain_fail, (h)->device)
 
 int wait_done(bn_terrain_t *h)
 {
@@ -667,19 +663,37 @@ bn::ColorArgs make_color_args(bn_terrain_t *h)
 // the colouring buffers whose size depends on G and B alone (the first use allocates them), and the (C, 3) table
 int ensure_color_buffers(bn_terrain_t *h, int C)
 {
-    const size_t oc = (size_t)h->G * h->G * h->B;
-    int rc = BN_OK;
-    if (!h->colors) {
-        if ((rc = realloc_dev(&h->noise, oc * 4)) || (rc = realloc_dev(&h->colors, oc * 12)) || (rc = realloc_dev(&h->light, (size_t)h->B * 12)) ||
-            (rc = realloc_dev(&h->cstart, (size_t)h->B * 4)) || (rc = realloc_dev(&h->counts, (size_t)h->B * 8)) ||
-            (rc = realloc_dev(&h->cseeds, (size_t)h->B * 8)))
+    int rc = h->color.ensure(terrain_fail);
+    if (rc) return rc;
+    if (C != h->ncolor) {
+        h->ncolor = 0;
+        if ((rc = h->color.resize(&h->thr, (size_t)h->B * C * 4, terrain_fail)) || (rc = h->color.resize(&h->ctable, (size_t)C * 12, terrain_fail)))
             return rc;
-        TERRAIN_HIP(hipMemset(h->counts, 0, (size_t)h->B * 8));
-    }
-    if (C != h->ncolor || !h->ctable) {
-        if ((rc = realloc_dev(&h->thr, (size_t)h->B * C * 4)) || (rc = realloc_dev(&h->ctable, (size_t)C * 12))) return rc;
         h->ncolor = C;
     }
+    return BN_OK;
+}
+
+// The crater tables for `slots` craters an instance, and the profile table for `len` values (it only grows; lin_len is the
+// length in use).  Both size fields are void while their buffers are being replaced: a failure leaves them asking for the
+// replacement again.
+int resize_craters(bn_terrain_t *h, int slots)
+{
+    int rc = BN_OK;
+    h->maxc = 0;
+    if ((rc = h->bufs.resize(&h->cr_int, (size_t)h->B * slots * 32, terrain_fail)) || (rc = h->bufs.resize(&h->cr_val, (size_t)h->B * slots * 8, terrain_fail)))
+        return rc;
+    h->maxc = slots;
+    return BN_OK;
+}
+
+int fit_lin(bn_terrain_t *h, int64_t len)
+{
+    if (len > h->lin_len) {
+        h->lin_len = 0;
+        if (int rc = h->bufs.resize(&h->lin, (size_t)len * 4, terrain_fail)) return rc;
+    }
+    h->lin_len = (int)len;
     return BN_OK;
 }
 
@@ -698,31 +712,47 @@ int ensure_draw_buffers(bn_terrain_t *h)
     const int64_t need = (int64_t)h->B * slots * draw_stride(h);
     if (need > ((int64_t)1 << 30)) return terrain_fail(BN_ERR_INVALID, "the crater profiles (B x num_craters x 2 max_radius / resolution) must fit 2^30 values");
     int rc = BN_OK;
-    if (slots != h->maxc || slots != h->dr_slots || need > h->lin_len || !h->drec) {
+    if (slots != h->maxc || slots != h->dr_slots || need > h->lin_len || !h->draw.live) {
         if ((rc = wait_done(h))) return rc;
     }
-    if (slots != h->maxc) {
-        if ((rc = realloc_dev(&h->cr_int, (size_t)h->B * slots * 32)) || (rc = realloc_dev(&h->cr_val, (size_t)h->B * slots * 8))) return rc;
-        TERRAIN_HIP(hipMemset(h->cr_int, 0, (size_t)h->B * slots * 32));
-        TERRAIN_HIP(hipMemset(h->cr_val, 0, (size_t)h->B * slots * 8));
-        h->maxc = slots;
-    }
+    if ((rc = h->draw.ensure(terrain_fail))) return rc;
+    if (slots != h->maxc && (rc = resize_craters(h, slots))) return rc;
     if (slots != h->dr_slots) {
-        if ((rc = realloc_dev(&h->dcenters, (size_t)h->B * slots * 8)) || (rc = realloc_dev(&h->dangles, (size_t)h->B * slots * 8))) return rc;
-        TERRAIN_HIP(hipMemset(h->dcenters, 0, (size_t)h->B * slots * 8));
-        TERRAIN_HIP(hipMemset(h->dangles, 0, (size_t)h->B * slots * 8));
+        h->dr_slots = 0;
+        if ((rc = h->draw.resize(&h->dcenters, (size_t)h->B * slots * 8, terrain_fail)) || (rc = h->draw.resize(&h->dangles, (size_t)h->B * slots * 8, terrain_fail)))
+            return rc;
         h->dr_slots = slots;
     }
-    if (need > h->lin_len) {
-        if ((rc = realloc_dev(&h->lin, (size_t)need * 4))) return rc;
+    return fit_lin(h, need);
+}
+
+// What bn_terrain_create builds on the device: every buffer of the handle entered in its table, the ones every generation needs
+// allocated, and the DFT's twiddle factors.
+int terrain_init(bn_terrain_t *h)
+{
+    const size_t pc = (size_t)h->N * h->N * h->B, oc = (size_t)h->G * h->G * h->B, sB = (size_t)h->B;
+    std::vector<double2> tw(h->N);
+    for (int m = 0; m < h->N; ++m) {
+        const double t = 2.0 * M_PI * (double)m / (double)h->N;
+        tw[m] = make_double2(std::cos(t), std::sin(t));
     }
-    h->lin_len = (int)need;
-    if (!h->drec) {
-        if ((rc = realloc_dev(&h->dseeds, (size_t)h->B * 8)) || (rc = realloc_dev(&h->drec, (size_t)h->B * bn::kDrawRecord * 4)) ||
-            (rc = realloc_dev(&h->dlight_u, (size_t)h->B * 8)))
-            return rc;
-        if (!h->dseeds_pinned) TERRAIN_HIP(hipHostMalloc((void **)&h->dseeds_pinned, (size_t)h->B * 8, hipHostMallocDefault));
-    }
+    bn::DeviceBuffers &m = h->bufs, &c = h->color, &d = h->draw, &z = h->stage;
+    m.add(&h->hp, pc * 4); m.add(&h->S, pc * 8); m.add(&h->T, pc * 16); m.add(&h->tw, (size_t)h->N * 16);
+    m.add(&h->heights, oc * 4); m.add(&h->slopes, oc * 4); m.add(&h->mean, oc * 4); m.add(&h->stddev, oc * 4);
+    m.add(&h->classes, oc * 4); m.add(&h->phases, (size_t)h->nph * sB * 4); m.add(&h->cr_count, sB * 4);
+    // sized by the draws and the slip models as they are set (maxc, lin_len and nclass say for what)
+    m.add_later(&h->cr_int); m.add_later(&h->cr_val); m.add_later(&h->lin); m.add_later(&h->cparams);
+    m.add_event(&h->ev_done);
+    // the colouring: sized by G and B alone, and the two tables that follow the number of classes (ncolor)
+    c.add(&h->noise, oc * 4); c.add(&h->colors, oc * 12); c.add(&h->light, sB * 12); c.add(&h->cstart, sB * 4);
+    c.add(&h->counts, sB * 8); c.add(&h->cseeds, sB * 8); c.add_later(&h->thr); c.add_later(&h->ctable);
+    // the device draws: the records, and the two tables that follow the crater slots (dr_slots)
+    d.add(&h->dseeds, sB * 8); d.add_pinned(&h->dseeds_pinned, sB * 8); d.add(&h->drec, sB * bn::kDrawRecord * 4);
+    d.add(&h->dlight_u, sB * 8); d.add_later(&h->dcenters); d.add_later(&h->dangles);
+    // bn_terrain_colorize's copies of the caller's maps
+    z.add(&h->cz_heights, oc * 4); z.add(&h->cz_classes, oc * 4);
+    if (int rc = m.alloc_all(terrain_fail)) return rc;
+    TERRAIN_HIP(hipMemcpy(h->tw, tw.data(), (size_t)h->N * 16, hipMemcpyHostToDevice));
     return BN_OK;
 }
 
@@ -738,36 +768,15 @@ int bn_terrain_create(int32_t device_id, int32_t G, int32_t B, bn_terrain_t **ou
     *out = nullptr;
     if (G < 2 || G + 2 > bn::kMaxN || B < 1 || (int64_t)(G + 2) * (G + 2) * B > ((int64_t)1 << 31))
         return terrain_fail(BN_ERR_INVALID, "G must be in [2, 1024], B >= 1, and B (G+2)^2 must fit 2^31 cells");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return terrain_fail(BN_ERR_NO_DEVICE, "no HIP device visible: no CPU fallback");
-    if (device_id < 0 || device_id >= ndev) return terrain_fail(BN_ERR_INVALID, "device_id out of range");
-    bn::DeviceGuard guard(device_id);
-    if (!guard.ok) return terrain_fail(BN_ERR_HIP, "hipSetDevice failed");
+    if (int rc = bn::open_device(device_id, terrain_fail)) return rc;
+    BN_ON_DEVICE(terrain_fail, device_id);
     auto *h = new bn_terrain_t();
     h->device = device_id; h->G = G; h->N = G + 2; h->B = B;
     const int hN = h->N / 2;
     h->nph = (hN + 1) * (hN + 1) + (hN - 1) * (hN - 1);
-    const size_t pc = (size_t)h->N * h->N * B, oc = (size_t)G * G * B;
-    std::vector<double2> tw(h->N);
-    for (int m = 0; m < h->N; ++m) {
-        const double t = 2.0 * M_PI * (double)m / (double)h->N;
-        tw[m] = make_double2(std::cos(t), std::sin(t));
-    }
-    int rc = BN_OK;
-    if ((rc = realloc_dev(&h->hp, pc * 4)) || (rc = realloc_dev(&h->S, pc * 8)) || (rc = realloc_dev(&h->T, pc * 16)) ||
-        (rc = realloc_dev(&h->tw, (size_t)h->N * 16)) || (rc = realloc_dev(&h->heights, oc * 4)) ||
-        (rc = realloc_dev(&h->slopes, oc * 4)) || (rc = realloc_dev(&h->mean, oc * 4)) || (rc = realloc_dev(&h->stddev, oc * 4)) ||
-        (rc = realloc_dev(&h->classes, oc * 4)) || (rc = realloc_dev(&h->phases, (size_t)h->nph * B * 4)) ||
-        (rc = realloc_dev(&h->cr_count, (size_t)B * 4))) {
-        std::string keep = bn::g_terrain_error;
-        bn_terrain_destroy(h);
-        bn::g_terrain_error = keep;
+    if (int rc = terrain_init(h)) {
+        bn_terrain_destroy(h);               // leaves the error text as terrain_init set it
         return rc;
-    }
-    if (hipMemcpy(h->tw, tw.data(), (size_t)h->N * 16, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemset(h->cr_count, 0, (size_t)B * 4) != hipSuccess || hipEventCreate(&h->ev_done) != hipSuccess) {
-        bn_terrain_destroy(h);
-        return terrain_fail(BN_ERR_HIP, "terrain handle initialisation failed");
     }
     *out = h;
     return BN_OK;
@@ -778,15 +787,7 @@ void bn_terrain_destroy(bn_terrain_t *h)
     if (!h) return;
     bn::DeviceGuard guard(h->device);
     if ((h->generated || h->ev_recorded) && h->ev_done) (void)hipEventSynchronize(h->ev_done);
-    for (void *p : {(void *)h->hp, (void *)h->S, (void *)h->T, (void *)h->tw, (void *)h->heights, (void *)h->slopes, (void *)h->mean,
-                    (void *)h->stddev, (void *)h->classes, (void *)h->phases, (void *)h->cr_count, (void *)h->cr_int,
-                    (void *)h->cr_val, (void *)h->lin, (void *)h->cparams, (void *)h->noise, (void *)h->colors, (void *)h->thr,
-                    (void *)h->ctable, (void *)h->light, (void *)h->cz_heights, (void *)h->cstart, (void *)h->counts,
-                    (void *)h->cz_classes, (void *)h->cseeds, (void *)h->dseeds, (void *)h->drec, (void *)h->dcenters,
-                    (void *)h->dlight_u, (void *)h->dangles})
-        if (p) (void)hipFree(p);
-    if (h->dseeds_pinned) (void)hipHostFree(h->dseeds_pinned);
-    if (h->ev_done) (void)hipEventDestroy(h->ev_done);
+    for (bn::DeviceBuffers *t : {&h->stage, &h->draw, &h->color, &h->bufs}) t->free_all();
     delete h;
 }
 
@@ -817,19 +818,11 @@ int bn_terrain_set_draws(bn_terrain_t *h, const float *phases, const int32_t *cr
                 return terrain_fail(BN_ERR_INVALID, "crater " + std::to_string(c) + " of instance " + std::to_string(b) + " is out of range");
         }
     }
-    bn::DeviceGuard guard(h->device);
-    if (!guard.ok) return terrain_fail(BN_ERR_HIP, "hipSetDevice failed");
+    TERRAIN_ON_DEVICE(h);
     int rc = wait_done(h);
     if (rc) return rc;
-    if (max_craters != h->maxc) {
-        if ((rc = realloc_dev(&h->cr_int, (size_t)h->B * max_craters * 32)) || (rc = realloc_dev(&h->cr_val, (size_t)h->B * max_craters * 8)))
-            return rc;
-        h->maxc = max_craters;
-    }
-    if (lin_len > h->lin_len) {
-        if ((rc = realloc_dev(&h->lin, (size_t)lin_len * 4))) return rc;
-    }
-    h->lin_len = (int)lin_len;
+    if (max_craters != h->maxc && (rc = resize_craters(h, max_craters))) return rc;
+    if ((rc = fit_lin(h, lin_len))) return rc;
     TERRAIN_HIP(hipMemcpy(h->phases, phases, (size_t)h->nph * h->B * 4, hipMemcpyHostToDevice));
     TERRAIN_HIP(hipMemcpy(h->cr_count, crater_count, (size_t)h->B * 4, hipMemcpyHostToDevice));
     TERRAIN_HIP(hipMemcpy(h->cr_int, crater_int, (size_t)h->B * max_craters * 32, hipMemcpyHostToDevice));
@@ -855,8 +848,7 @@ int bn_terrain_set_draw_params(bn_terrain_t *h, int32_t is_crater, int32_t num_c
     const double stride = std::ceil(2.0 * std::max(min_radius, max_radius) / h->resolution) + 2.0;
     if (!(stride * slots * h->B <= (double)((int64_t)1 << 30)))
         return terrain_fail(BN_ERR_INVALID, "the crater profiles (B x num_craters x 2 max_radius / resolution) must fit 2^30 values");
-    bn::DeviceGuard guard(h->device);
-    if (!guard.ok) return terrain_fail(BN_ERR_HIP, "hipSetDevice failed");
+    TERRAIN_ON_DEVICE(h);
     h->dr_crater = is_crater != 0; h->dr_num = num_craters; h->dr_light = with_light != 0;
     h->dr_margin = crater_margin; h->dr_amin = min_angle; h->dr_amax = max_angle; h->dr_rmin = min_radius; h->dr_rmax = max_radius;
     h->dr_llo = lower_threshold; h->dr_lhi = upper_threshold;
@@ -869,8 +861,7 @@ int bn_terrain_draw_async(bn_terrain_t *h, const uint64_t *seeds, void *stream)
     if (!h || !seeds) return terrain_fail(BN_ERR_INVALID, "null argument");
     if (!h->have_geometry || !h->have_draw_params) return terrain_fail(BN_ERR_STATE, "geometry and draw parameters must be set first");
     if (h->dr_light && !h->light) return terrain_fail(BN_ERR_STATE, "the light source is drawn for the colouring: set it first");
-    bn::DeviceGuard guard(h->device);
-    if (!guard.ok) return terrain_fail(BN_ERR_HIP, "hipSetDevice failed");
+    TERRAIN_ON_DEVICE(h);
     int rc = wait_done(h);                   // the last draws or generation: the staging buffer and the tables are free again
     if (rc || (rc = ensure_draw_buffers(h))) return rc;
     hipStream_t s = (hipStream_t)stream;
@@ -911,8 +902,7 @@ int bn_terrain_read_draws(bn_terrain_t *h, int32_t *records, float *centers, dou
     if (!h->drawn) return terrain_fail(BN_ERR_STATE, "no draws made on the device yet");
     if (h->maxc != h->dr_slots) return terrain_fail(BN_ERR_STATE, "the crater tables were replaced by host draws since the device drew");
     if (light && !h->light) return terrain_fail(BN_ERR_STATE, "colouring has not been set");
-    bn::DeviceGuard guard(h->device);
-    if (!guard.ok) return terrain_fail(BN_ERR_HIP, "hipSetDevice failed");
+    TERRAIN_ON_DEVICE(h);
     int rc = wait_done(h);
     if (rc) return rc;
     const size_t B = (size_t)h->B, slots = (size_t)h->dr_slots;
@@ -932,12 +922,12 @@ int bn_terrain_set_slip(bn_terrain_t *h, const int32_t *t_classes, const float *
 {
     if (!h || (num_classes > 0 && !class_params)) return terrain_fail(BN_ERR_INVALID, "null argument");
     if (num_classes < 0 || num_classes > (1 << 20)) return terrain_fail(BN_ERR_INVALID, "num_classes out of range");
-    bn::DeviceGuard guard(h->device);
-    if (!guard.ok) return terrain_fail(BN_ERR_HIP, "hipSetDevice failed");
+    TERRAIN_ON_DEVICE(h);
     int rc = wait_done(h);
     if (rc) return rc;
-    if (num_classes != h->nclass || !h->cparams) {
-        if ((rc = realloc_dev(&h->cparams, (size_t)(num_classes > 0 ? num_classes : 1) * bn::kClassParams * 4))) return rc;
+    if (num_classes != h->nclass) {
+        h->nclass = -1;
+        if ((rc = h->bufs.resize(&h->cparams, (size_t)num_classes * bn::kClassParams * 4, terrain_fail))) return rc;
         h->nclass = num_classes;
     }
     if (t_classes) TERRAIN_HIP(hipMemcpy(h->classes, t_classes, (size_t)h->G * h->G * h->B * 4, hipMemcpyHostToDevice));
@@ -951,8 +941,7 @@ int bn_terrain_generate_async(bn_terrain_t *h, void *stream)
 {
     if (!h) return terrain_fail(BN_ERR_INVALID, "null handle");
     if (!h->have_geometry || !h->have_draws || !h->have_slip) return terrain_fail(BN_ERR_STATE, "geometry, draws and slip models must be set first");
-    bn::DeviceGuard guard(h->device);
-    if (!guard.ok) return terrain_fail(BN_ERR_HIP, "hipSetDevice failed");
+    TERRAIN_ON_DEVICE(h);
     hipStream_t s = (hipStream_t)stream;
     const bn::TerrainArgs a = make_args(h);
     const size_t pc = (size_t)h->N * h->N * h->B, oc = (size_t)h->G * h->G * h->B;
@@ -994,7 +983,7 @@ int bn_terrain_generate_async(bn_terrain_t *h, void *stream)
 int bn_terrain_sync(bn_terrain_t *h)
 {
     if (!h) return terrain_fail(BN_ERR_INVALID, "null handle");
-    bn::DeviceGuard guard(h->device);
+    TERRAIN_ON_DEVICE(h);
     return wait_done(h);
 }
 
@@ -1009,8 +998,7 @@ int bn_terrain_copy_out(bn_terrain_t *h, float *heights, float *slopes, float *m
 {
     if (!h) return terrain_fail(BN_ERR_INVALID, "null handle");
     if (!h->generated) return terrain_fail(BN_ERR_STATE, "nothing generated yet");
-    bn::DeviceGuard guard(h->device);
-    if (!guard.ok) return terrain_fail(BN_ERR_HIP, "hipSetDevice failed");
+    TERRAIN_ON_DEVICE(h);
     int rc = wait_done(h);
     if (rc) return rc;
     const size_t bytes = (size_t)h->G * h->G * h->B * 4;
@@ -1035,8 +1023,7 @@ int bn_terrain_set_coloring(bn_terrain_t *h, int32_t enable, const float *thresh
         return terrain_fail(BN_ERR_INVALID, "ambient_intensity must be finite and feature_size finite and >= 1e-3");
     for (int b = 0; b < h->B; ++b)
         if (start[b] < 0 || start[b] > num_classes) return terrain_fail(BN_ERR_INVALID, "start class out of range");
-    bn::DeviceGuard guard(h->device);
-    if (!guard.ok) return terrain_fail(BN_ERR_HIP, "hipSetDevice failed");
+    TERRAIN_ON_DEVICE(h);
     int rc = wait_done(h);
     if (rc) return rc;
     if ((rc = ensure_color_buffers(h, num_classes))) return rc;
@@ -1060,13 +1047,12 @@ int bn_terrain_colorize(bn_terrain_t *h, const float *heights, const int32_t *t_
     if (num_classes < 1 || num_classes > bn::kMaxColorClasses)
         return terrain_fail(BN_ERR_INVALID, "colouring supports 1 to " + std::to_string(bn::kMaxColorClasses) + " terrain classes");
     if (!std::isfinite(ambient_intensity)) return terrain_fail(BN_ERR_INVALID, "ambient_intensity must be finite");
-    bn::DeviceGuard guard(h->device);
-    if (!guard.ok) return terrain_fail(BN_ERR_HIP, "hipSetDevice failed");
+    TERRAIN_ON_DEVICE(h);
     int rc = wait_done(h);
     if (rc) return rc;
     if ((rc = ensure_color_buffers(h, num_classes))) return rc;
     const size_t oc = (size_t)h->G * h->G * h->B;
-    if (!h->cz_heights && ((rc = realloc_dev(&h->cz_heights, oc * 4)) || (rc = realloc_dev(&h->cz_classes, oc * 4)))) return rc;
+    if ((rc = h->stage.ensure(terrain_fail))) return rc;
     TERRAIN_HIP(hipMemcpy(h->cz_heights, heights, oc * 4, hipMemcpyHostToDevice));
     TERRAIN_HIP(hipMemcpy(h->cz_classes, t_classes, oc * 4, hipMemcpyHostToDevice));
     TERRAIN_HIP(hipMemcpy(h->ctable, color_table, (size_t)num_classes * 12, hipMemcpyHostToDevice));
@@ -1093,8 +1079,7 @@ int bn_terrain_class_counts(bn_terrain_t *h, int32_t *unassigned, int32_t *beyon
 {
     if (!h || !unassigned || !beyond) return terrain_fail(BN_ERR_INVALID, "null argument");
     if (!h->generated || !h->colored || !h->counts) return terrain_fail(BN_ERR_STATE, "no coloured generation yet");
-    bn::DeviceGuard guard(h->device);
-    if (!guard.ok) return terrain_fail(BN_ERR_HIP, "hipSetDevice failed");
+    TERRAIN_ON_DEVICE(h);
     int rc = wait_done(h);
     if (rc) return rc;
     std::vector<int32_t> c((size_t)h->B * 2);
@@ -1108,8 +1093,7 @@ int bn_terrain_spectrum(bn_terrain_t *h, int32_t inst, float *out)
     if (!h || !out) return terrain_fail(BN_ERR_INVALID, "null argument");
     if (inst < 0 || inst >= h->B) return terrain_fail(BN_ERR_INVALID, "instance out of range");
     if (!h->have_geometry || !h->have_draws) return terrain_fail(BN_ERR_STATE, "geometry and draws must be set first");
-    bn::DeviceGuard guard(h->device);
-    if (!guard.ok) return terrain_fail(BN_ERR_HIP, "hipSetDevice failed");
+    TERRAIN_ON_DEVICE(h);
     int rc = wait_done(h);
     if (rc) return rc;
     const int cells = h->N * h->N;

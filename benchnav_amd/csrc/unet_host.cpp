@@ -65,10 +65,7 @@ UnetPlan unet_plan(int64_t n, int64_t H, int64_t W)
 
 int unet_open_device(int32_t device_id)
 {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return unet_fail(BN_ERR_NO_DEVICE, "no HIP device visible: no CPU fallback");
-    if (device_id < 0 || device_id >= ndev) return unet_fail(BN_ERR_INVALID, "device_id out of range");
-    return BN_OK;
+    return open_device(device_id, unet_fail);
 }
 
 }  // namespace
@@ -99,8 +96,7 @@ int bn_unet_create(int32_t device_id, int32_t classes, const float *params_host,
     for (int64_t i = 0; i < count; ++i)
         if (!std::isfinite(params_host[i])) return unet_fail(BN_ERR_INVALID, "every parameter must be finite (index " + std::to_string(i) + ")");
     if (int rc = bn::unet_open_device(device_id)) return rc;
-    bn::DeviceGuard guard(device_id);
-    if (!guard.ok) return unet_fail(BN_ERR_HIP, "hipSetDevice failed");
+    BN_ON_DEVICE(unet_fail, device_id);
 
     bn_unet *h = new bn_unet();
     h->device = device_id;
@@ -177,8 +173,7 @@ int bn_unet_forward_async(bn_unet_t *h, void *stream, int32_t num_maps, int32_t 
         return unet_fail(BN_ERR_INVALID, "H and W must be multiples of 32 in [32, 2048], num_maps in [1, 4096], num_maps H W <= 2^24");
     const bn::UnetPlan p = bn::unet_plan(num_maps, H, W);
     if (workspace_bytes < p.total) return unet_fail(BN_ERR_INVALID, "workspace smaller than bn_unet_workspace_bytes(num_maps, H, W)");
-    bn::DeviceGuard guard(h->device);
-    if (!guard.ok) return unet_fail(BN_ERR_HIP, "hipSetDevice failed");
+    BN_ON_DEVICE(unet_fail, h->device);
     hipStream_t s = (hipStream_t)stream;
     char *ws = (char *)workspace_device;
     auto buf = [&](size_t off) { return (float *)(ws + off); };
@@ -265,8 +260,7 @@ int bn_unet_conv2d_async(int32_t device_id, void *stream, const float *a_device,
     if ((int64_t)num_maps * (ca + cb) * hin * win >= ((int64_t)1 << 31) || (int64_t)num_maps * cout * hout * wout >= ((int64_t)1 << 31))
         return unet_fail(BN_ERR_INVALID, "a tensor must hold fewer than 2^31 elements");
     if (int rc = bn::unet_open_device(device_id)) return rc;
-    bn::DeviceGuard guard(device_id);
-    if (!guard.ok) return unet_fail(BN_ERR_HIP, "hipSetDevice failed");
+    BN_ON_DEVICE(unet_fail, device_id);
     hipStream_t s = (hipStream_t)stream;
     const bn::UnetConvDesc d{ca + cb, cout, ksize, stride, pad};
     float *wt = (float *)workspace_device, *bias = wt + (size_t)d.kpad() * d.coutpad();
@@ -286,8 +280,7 @@ int bn_unet_maxpool_async(int32_t device_id, void *stream, const float *in_devic
     if (planes < 1 || hin < 1 || hin > bn::kUnetMaxSide || win < 1 || win > bn::kUnetMaxSide || planes * hin * win > ((int64_t)1 << 30))
         return unet_fail(BN_ERR_INVALID, "planes must be >= 1, the sides in [1, 2048] and planes x hin x win <= 2^30");
     if (int rc = bn::unet_open_device(device_id)) return rc;
-    bn::DeviceGuard guard(device_id);
-    if (!guard.ok) return unet_fail(BN_ERR_HIP, "hipSetDevice failed");
+    BN_ON_DEVICE(unet_fail, device_id);
     UNET_HIP(bn::unet_launch_maxpool((hipStream_t)stream, in_device, out_device, planes, hin, win, (hin - 1) / 2 + 1, (win - 1) / 2 + 1));
     return BN_OK;
 }

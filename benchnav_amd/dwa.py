@@ -19,6 +19,7 @@ import torch.nn as nn
 import ctypes as C
 
 from . import _capi
+from ._device import resolve_device
 from .mppi import MPPI as _MPPI, _DevArray, _planner_inputs
 from .native import NativeMPPI
 
@@ -34,12 +35,7 @@ class DWA(nn.Module):
         assert a_lim.shape == (dim_control,), "acceleration limits must be a tensor of shape (dim_control,)"
         if dim_state != 3 or dim_control != 2 or dtype != torch.float32:
             raise ValueError("the native planner implements the float32 unicycle model: dim_state=3, dim_control=2")
-        if not torch.cuda.is_available():
-            raise RuntimeError("benchnav_amd.DWA needs an MI355X (gfx950) device; there is no CPU fallback")
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise RuntimeError(f"benchnav_amd.DWA runs on the GPU only (device={device!r})")
-        self._device = torch.device("cuda", torch.cuda.current_device()) if dev.index is None else dev
+        self._device = resolve_device(device, "DWA")
         self._dtype = dtype
         self._horizon, self._dim_state, self._dim_control = horizon, dim_state, dim_control
         self._dynamics = dynamics

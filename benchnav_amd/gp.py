@@ -31,17 +31,12 @@ import torch
 from torch.distributions import Normal
 
 from . import _capi
-from ._device import stream_ptr
+from ._device import Handle, check, resolve_device, stream_ptr
 
 MAX_POINTS = 10240          # bn_gp_max_points(): 640 row blocks of 16; L^-1 is 420 MB on the device at this size
 _NUMPY_SOLVE_MAX = 1024     # up to here L^-1 comes from np.linalg.solve(L, I), as it always has; above, from a triangular solve
 MAX_CLASSES = 32
 _NOISE_LOWER_BOUND = 1e-4   # GaussianLikelihood's default GreaterThan(1e-4) on the noise
-
-
-def _check(lib, code: int):
-    if code != _capi.BN_OK:
-        raise _capi.BenchnavError(code, lib.bn_gp_last_error().decode("utf-8", "replace"))
 
 
 def _scalar(v, name: str) -> float:
@@ -132,74 +127,67 @@ def _train_pair(train_x, train_y) -> Tuple[np.ndarray, np.ndarray]:
 def _check_fit(lib, code: int):
     if code == _capi.BN_ERR_STATE:
         raise ValueError(lib.bn_gp_fit_last_error().decode("utf-8", "replace"))
-    if code != _capi.BN_OK:
-        raise _capi.BenchnavError(code, lib.bn_gp_fit_last_error().decode("utf-8", "replace"))
+    check(lib, "gp_fit", code)
 
 
-class _Fit:
+class _Fit(Handle):
     """One bn_gp_fit_t: the device workspace of a fit (two N x N float64 buffers), released on exit.  Launches go to torch's
     current stream of the device."""
+    family = "gp_fit"
+    handle = property(lambda self: self._handle)
 
     def __init__(self, lib, dev: torch.device, x: np.ndarray, y: np.ndarray, noise_lower_bound: float) -> None:
-        self.lib, self.dev, self.handle = lib, dev, None
+        self._lib, self.dev = lib, dev
         h = C.c_void_p()
-        _check_fit(lib, lib.bn_gp_fit_create(dev.index, x.shape[0], x.ctypes.data, y.ctypes.data, float(noise_lower_bound), C.byref(h)))
-        self.handle = h
+        self._check(lib.bn_gp_fit_create(dev.index, x.shape[0], x.ctypes.data, y.ctypes.data, float(noise_lower_bound), C.byref(h)))
+        self._handle = h
 
-    def __enter__(self) -> "_Fit":
-        return self
-
-    def __exit__(self, *exc) -> None:
-        self.close()
-
-    def close(self) -> None:
-        if self.handle:
-            self.lib.bn_gp_fit_destroy(self.handle)
-            self.handle = None
+    def _check(self, code: int) -> None:
+        _check_fit(self._lib, code)
 
     def set_raw(self, raw) -> None:
         r = np.ascontiguousarray(raw, dtype=np.float64)
-        _check_fit(self.lib, self.lib.bn_gp_fit_set_raw(self.handle, r.ctypes.data))
+        self._check(self._lib.bn_gp_fit_set_raw(self._handle, r.ctypes.data))
 
     def evaluate(self) -> None:
-        _check_fit(self.lib, self.lib.bn_gp_fit_evaluate_async(self.handle, stream_ptr(self.dev)))
+        self._check(self._lib.bn_gp_fit_evaluate_async(self._handle, stream_ptr(self.dev)))
 
     def run(self, iterations: int, lr: float, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8) -> None:
-        _check_fit(self.lib, self.lib.bn_gp_fit_run_async(self.handle, stream_ptr(self.dev), int(iterations), lr, beta1, beta2, eps))
+        self._check(self._lib.bn_gp_fit_run_async(self._handle, stream_ptr(self.dev), int(iterations), lr, beta1, beta2, eps))
 
     def read(self):
         """(raw (4,), grad (4,), loss, status, failed iteration) after a synchronisation"""
         raw, grad = np.zeros(4), np.zeros(4)
         loss, status, failed = C.c_double(), C.c_int32(), C.c_int32()
-        _check_fit(self.lib, self.lib.bn_gp_fit_read(self.handle, raw.ctypes.data, grad.ctypes.data, C.byref(loss), C.byref(status), C.byref(failed)))
+        self._check(self._lib.bn_gp_fit_read(self._handle, raw.ctypes.data, grad.ctypes.data, C.byref(loss), C.byref(status), C.byref(failed)))
         return raw, grad, loss.value, status.value, failed.value
 
     def hyperparameters(self):
         hyp = np.zeros(4)
-        _check_fit(self.lib, self.lib.bn_gp_fit_hyperparameters(self.handle, hyp.ctypes.data))
+        self._check(self._lib.bn_gp_fit_hyperparameters(self._handle, hyp.ctypes.data))
         return tuple(float(v) for v in hyp)
 
     def history(self) -> np.ndarray:
-        done = self.lib.bn_gp_fit_history(self.handle, None, 0)
-        if done < 0:
-            _check_fit(self.lib, done)
+        done = self._lib.bn_gp_fit_history(self._handle, None, 0)
+        self._check(done)
         out = np.zeros(done)
         if done:
-            self.lib.bn_gp_fit_history(self.handle, out.ctypes.data, done)
+            self._lib.bn_gp_fit_history(self._handle, out.ctypes.data, done)
         return out
 
     def finish(self) -> C.c_void_p:
         g = C.c_void_p()
-        _check_fit(self.lib, self.lib.bn_gp_fit_finish(self.handle, stream_ptr(self.dev), C.byref(g)))
+        self._check(self._lib.bn_gp_fit_finish(self._handle, stream_ptr(self.dev), C.byref(g)))
         return g
 
 
-class GPSlipRegressor:
+class GPSlipRegressor(Handle):
     """One terrain class's slip regressor on the device: `.predict(slopes)` is GPModel.predict's `likelihood(model(x))`, exact.
 
     train_x, train_y: (N,) or (N, 1), used as float32 values; constant, outputscale, lengthscale, noise: the ACTUAL (not raw)
     hyperparameters.  Raises ValueError for invalid inputs and RuntimeError without a GPU (no CPU fallback)."""
 
+    family = "gp"
     raw_parameters = None                # (constant, raw_outputscale, raw_lengthscale, raw_noise) float64 after fit(), else None
     loss_history = None                  # float64, one loss per iteration, after fit()
     noise_lower_bound = _NOISE_LOWER_BOUND
@@ -221,7 +209,7 @@ class GPSlipRegressor:
             self.constant, self.outputscale, self.lengthscale, self.noise = c, s, l, nz
             self._open(device)
             with _Fit(self._lib, self._dev, x, y, _NOISE_LOWER_BOUND) as fit:
-                _check_fit(self._lib, self._lib.bn_gp_fit_set_hyperparameters(fit.handle, c, s, l, nz))
+                fit._check(self._lib.bn_gp_fit_set_hyperparameters(fit.handle, c, s, l, nz))
                 self._handle = fit.finish()
             return
         x, alpha, linv = factorize(train_x, train_y, constant, outputscale, lengthscale, noise)
@@ -230,16 +218,12 @@ class GPSlipRegressor:
                                                                          _scalar(lengthscale, "lengthscale"), _scalar(noise, "noise"))
         self._open(device)
         h = C.c_void_p()
-        _check(self._lib, self._lib.bn_gp_create(self._dev.index, self.num_points, x.ctypes.data, alpha.ctypes.data, linv.ctypes.data,
-                                                 self.constant, self.outputscale, self.lengthscale, self.noise, C.byref(h)))
+        self._check(self._lib.bn_gp_create(self._dev.index, self.num_points, x.ctypes.data, alpha.ctypes.data, linv.ctypes.data,
+                                           self.constant, self.outputscale, self.lengthscale, self.noise, C.byref(h)))
         self._handle = h
 
     def _open(self, device) -> None:
-        if not torch.cuda.is_available():
-            raise RuntimeError("benchnav_amd.gp needs an MI355X (gfx950) device; there is no CPU fallback")
-        self._dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        if self._dev.index is None:
-            self._dev = torch.device("cuda", torch.cuda.current_device())
+        self._dev = resolve_device(device, "gp")
         self._lib = _capi.load()
 
     @classmethod
@@ -312,17 +296,6 @@ class GPSlipRegressor:
     def predict(self, x: torch.Tensor) -> Normal:
         """Normal(mean, std) of x's shape: the `.mean` / `.stddev` surface of GPModel.predict, noise included."""
         return Normal(*self.predict_tensors(x))
-
-    def close(self):
-        if getattr(self, "_handle", None):
-            self._lib.bn_gp_destroy(self._handle)
-            self._handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def hyperparameters_from_state_dict(state_dict, noise_lower_bound: Optional[float] = None) -> Dict[str, float]:
@@ -429,7 +402,7 @@ def _predict(lib, dev: torch.device, table, slopes: torch.Tensor, classes: torch
             raise ValueError(f"{B} maps of {cells} cells with {nc} classes are out of the library's range")
         work = torch.empty(nbytes, device=dev, dtype=torch.uint8)     # torch's allocator keeps it alive for the stream
         handles = (C.c_void_p * nc)(*[(r._handle.value if r is not None else None) for r in table])
-        _check(lib, lib.bn_gp_predict_async(dev.index, stream_ptr(dev), handles, nc, B, cells, C.c_void_p(s.data_ptr()),
+        check(lib, "gp", lib.bn_gp_predict_async(dev.index, stream_ptr(dev), handles, nc, B, cells, C.c_void_p(s.data_ptr()),
                                             C.c_void_p(c.data_ptr()), C.c_void_p(mean.data_ptr()), C.c_void_p(std.data_ptr()),
                                             1 if dtype == torch.float64 else 0, C.c_void_p(work.data_ptr()), nbytes))
     return mean, std
@@ -445,11 +418,7 @@ class TraversabilityPredictor:
     zeros_like)."""
 
     def __init__(self, terrain_classifier, slip_regressors: Dict[int, GPSlipRegressor], device=None) -> None:
-        if not torch.cuda.is_available():
-            raise RuntimeError("benchnav_amd.gp needs an MI355X (gfx950) device; there is no CPU fallback")
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = resolve_device(device, "gp")
         self.terrain_classifier = terrain_classifier.to(self.device) if hasattr(terrain_classifier, "to") else terrain_classifier
         self.slip_regressors = {int(k): r.to(self.device) for k, r in slip_regressors.items()}
         if any(k < 0 or k >= MAX_CLASSES for k in self.slip_regressors):

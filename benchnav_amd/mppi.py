@@ -18,7 +18,7 @@ import torch
 import torch.nn as nn
 
 from . import _capi
-from ._device import _DevArray  # noqa: F401  (tests and tools import it from here)
+from ._device import _DevArray, resolve_device  # noqa: F401  (tests and tools import _DevArray from here)
 
 
 def _raw_stream(dev_index: int) -> int:
@@ -137,14 +137,7 @@ class MPPI(nn.Module):
             raise ValueError("the native planner computes in float32")
         if noise not in ("torch", "torch_device", "philox"):
             raise ValueError(f"unknown noise mode {noise!r}")
-        if not torch.cuda.is_available():
-            raise RuntimeError("benchnav_amd.MPPI needs an MI355X (gfx950) device; there is no CPU fallback")
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise RuntimeError(f"benchnav_amd.MPPI runs on the GPU only (device={device!r})")
-        if dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
-        self._device = dev
+        self._device = dev = resolve_device(device, "MPPI")
         self._dtype = dtype
 
         self._horizon = horizon

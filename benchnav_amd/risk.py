@@ -8,6 +8,7 @@ from typing import Optional
 import torch
 
 from . import _capi
+from ._device import check, resolve_device
 
 _METRICS = {"expected_value": _capi.BN_RISK_EXPECTED, "var": _capi.BN_RISK_VAR, "cvar": _capi.BN_RISK_CVAR}
 
@@ -27,9 +28,7 @@ def infer_risk_map(mean: torch.Tensor, std: torch.Tensor, inference_metric: str,
     if inference_metric != "expected_value":
         assert confidence_value is not None and 0.0 <= confidence_value <= 1.0, \
             "confidence_value must be set between 0 and 1 when inference_metric is 'var' or 'cvar'."
-    if not torch.cuda.is_available():
-        raise RuntimeError("benchnav_amd.risk needs an MI355X (gfx950) device; there is no CPU fallback")
-    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    dev = resolve_device(device, "risk")
     G = mean.shape[0]
     assert mean.shape == (G, G) and std.shape == (G, G)
     m = mean.detach().to(dev, torch.float32).contiguous()
@@ -46,6 +45,5 @@ def infer_risk_map(mean: torch.Tensor, std: torch.Tensor, inference_metric: str,
                                    _METRICS[inference_metric], float(confidence_value or 0.0), int(num_samples),
                                    C.c_void_p(zd.data_ptr() if zd is not None else None), _capi.BN_MEM_DEVICE, seed,
                                    C.c_void_p(out.data_ptr()), _capi.BN_MEM_DEVICE)
-    if rc != _capi.BN_OK:
-        raise _capi.BenchnavError(rc, lib.bn_risk_last_error().decode())
+    check(lib, "risk", rc)
     return out

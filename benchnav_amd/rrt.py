@@ -25,7 +25,7 @@ import torch
 import torch.nn as nn
 
 from . import _capi
-from ._device import _DevArray, _PlannerHandle, _TreePlanner, _check_seed, check, seed_array, tree_capacity  # noqa: F401
+from ._device import _DevArray, _PlannerHandle, _TreePlanner, _check_seed, check, resolve_device, seed_array, tree_capacity  # noqa: F401
 
 
 class Tree:
@@ -96,10 +96,7 @@ class RRT(_TreePlanner, nn.Module):
         self._flags = (_capi.BN_RRT_FLAG_GLOBAL_NODES if node_storage == "global" else 0) | \
             {None: 0, 64: _capi.BN_RRT_FLAG_ONE_WAVE, 256: _capi.BN_RRT_FLAG_FOUR_WAVES}[workgroup]
         self._goal_host = goal_pos.detach().to("cpu", torch.float32)[:2].contiguous()
-        if not torch.cuda.is_available():
-            raise RuntimeError("benchnav_amd.RRT needs an MI355X (gfx950) device; there is no CPU fallback")
-        dev = torch.device(self.device)
-        self._dev = dev if dev.type == "cuda" and dev.index is not None else torch.device("cuda", torch.cuda.current_device())
+        self._dev = resolve_device(self.device, "RRT", lenient=True)
         self._goal_node = self._goal_host.to(self.device)
         self._lib = _capi.load()
         self._handles = {}                   # B -> _Handle: forward() is the B = 1 handle, whose stream continues across calls

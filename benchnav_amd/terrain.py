@@ -40,7 +40,7 @@ import numpy as np
 import torch
 
 from . import _capi
-from ._device import _DevArray, stream_ptr
+from ._device import Handle, _DevArray, resolve_device, stream_ptr
 
 # the dataset script's ranges (scripts/generate_terrain_dataset.py:31-34), the defaults of slip_models()
 SLIP_SENSITIVITY_MINMAX = (1.0, 9.0)
@@ -281,7 +281,7 @@ class Terrain:
     light: Optional[np.ndarray] = None         # (B, 3) float32
 
 
-class TerrainGenerator:
+class TerrainGenerator(Handle):
     """B map instances of one grid size per launch.
 
         gen = TerrainGenerator(64, 0.5, batch=8)
@@ -290,14 +290,13 @@ class TerrainGenerator:
         t = gen.generate(seeds=range(8), occupancy=occ[0], slip_models=slip_models(10))
         insts = gen.to_instances()                  # io.MapInstance: io.save_instance / io.planner_inputs take them
     """
+    family = "terrain"
 
     def __init__(self, grid_size: int, resolution: float, batch: int = 1, roughness_exponent: float = 0.75,
                  amplitude_gain: float = 10, device_id: Optional[int] = None) -> None:
-        if not torch.cuda.is_available():
-            raise RuntimeError("benchnav_amd.TerrainGenerator needs an MI355X (gfx950) device; there is no CPU fallback")
+        self._dev = resolve_device(None if device_id is None else torch.device("cuda", device_id), "TerrainGenerator")
         self.grid_size, self.resolution, self.batch = int(grid_size), float(resolution), int(batch)
         self.roughness_exponent, self.amplitude_gain = float(roughness_exponent), float(amplitude_gain)
-        self._dev = torch.device("cuda", torch.cuda.current_device() if device_id is None else device_id)
         self._lib = _capi.load()
         h = C.c_void_p()
         self._check(self._lib.bn_terrain_create(self._dev.index, self.grid_size, self.batch, C.byref(h)))
@@ -639,25 +638,3 @@ class TerrainGenerator:
             out.append(MapInstance(grid_size=G, tensors=tensors, latent_mean=t.latent_mean[b].cpu(),
                                    latent_std=t.latent_std[b].cpu(), extra={"craters": t.craters[b]}))
         return out
-
-    def _check(self, code):
-        if code < 0:
-            raise _capi.BenchnavError(code, self._lib.bn_terrain_last_error().decode("utf-8", "replace"))
-
-    def close(self):
-        h = getattr(self, "_handle", None)
-        if h is not None and h.value:
-            self._lib.bn_terrain_destroy(h)
-            self._handle = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

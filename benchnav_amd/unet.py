@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import _capi
-from ._device import stream_ptr
+from ._device import Handle, check, resolve_device, stream_ptr
 
 MAX_CLASSES = 32
 BN_EPS = 1e-5
@@ -109,21 +109,17 @@ def fold_state_dict(state_dict, classes: int = 10, dtype=np.float32) -> np.ndarr
     return np.ascontiguousarray(out)
 
 
-def _check(lib, code: int):
-    if code != _capi.BN_OK:
-        raise _capi.BenchnavError(code, lib.bn_unet_last_error().decode("utf-8", "replace"))
-
-
 def _ptr(t: Optional[torch.Tensor]):
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
-class TerrainClassifier:
+class TerrainClassifier(Handle):
     """smp.Unet(encoder_name="resnet18", classes=C) in eval mode on the device.  state_dict: the model's state dict (tensors or
     arrays).  Inputs are (B, 3, H, W) colours in [0, 1] with H and W multiples of 32, on the host or the device; every call is
     enqueued on torch's current stream of the device without a synchronisation.  Raises ValueError for invalid inputs and
     RuntimeError without a GPU (no CPU fallback)."""
 
+    family = "unet"
     batched = True                       # predict_classes takes a whole batch: TraversabilityPredictor classifies it in one call
     training = False
 
@@ -131,14 +127,10 @@ class TerrainClassifier:
         self._handle = None
         self.classes = _check_classes(classes)
         params = fold_state_dict(state_dict, self.classes)
-        if not torch.cuda.is_available():
-            raise RuntimeError("benchnav_amd.unet needs an MI355X (gfx950) device; there is no CPU fallback")
-        self._dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        if self._dev.index is None:
-            self._dev = torch.device("cuda", torch.cuda.current_device())
+        self._dev = resolve_device(device, "unet")
         self._lib = _capi.load()
         h = C.c_void_p()
-        _check(self._lib, self._lib.bn_unet_create(self._dev.index, self.classes, params.ctypes.data, params.size, C.byref(h)))
+        self._check(self._lib.bn_unet_create(self._dev.index, self.classes, params.ctypes.data, params.size, C.byref(h)))
         self._handle = h
 
     # ---- the nn.Module surface the reference touches ----
@@ -149,17 +141,6 @@ class TerrainClassifier:
 
     def eval(self) -> "TerrainClassifier":
         return self
-
-    def close(self) -> None:
-        if getattr(self, "_handle", None):
-            self._lib.bn_unet_destroy(self._handle)
-            self._handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     # ---- the forward ----
     def _input(self, x) -> torch.Tensor:
@@ -184,7 +165,7 @@ class TerrainClassifier:
             cl = torch.empty(B, H, W, device=self._dev, dtype=torch.int32) if classes else None
             nbytes = self._lib.bn_unet_workspace_bytes(B, H, W)
             work = torch.empty(nbytes, device=self._dev, dtype=torch.uint8)       # torch's allocator keeps it alive for the stream
-            _check(self._lib, self._lib.bn_unet_forward_async(self._handle, stream_ptr(self._dev), B, H, W, _ptr(x), _ptr(lo), _ptr(pr),
+            self._check(self._lib.bn_unet_forward_async(self._handle, stream_ptr(self._dev), B, H, W, _ptr(x), _ptr(lo), _ptr(pr),
                                                               _ptr(cl), _ptr(work), nbytes))
         return lo, pr, cl, work
 
@@ -213,7 +194,7 @@ class TerrainClassifier:
         out = []
         for i in range(10):
             off, ch, fh, fw = C.c_size_t(), C.c_int32(), C.c_int32(), C.c_int32()
-            _check(self._lib, self._lib.bn_unet_feature_layout(B, H, W, i, C.byref(off), C.byref(ch), C.byref(fh), C.byref(fw)))
+            self._check(self._lib.bn_unet_feature_layout(B, H, W, i, C.byref(off), C.byref(ch), C.byref(fh), C.byref(fw)))
             n = B * ch.value * fh.value * fw.value
             out.append(work[off.value:off.value + 4 * n].view(torch.float32).reshape(B, ch.value, fh.value, fw.value).clone())
         return out[:5], out[5:]
@@ -228,18 +209,11 @@ class TerrainClassifier:
         return maxpool(x, device=self._dev)
 
 
-def _device(device) -> torch.device:
-    if not torch.cuda.is_available():
-        raise RuntimeError("benchnav_amd.unet needs an MI355X (gfx950) device; there is no CPU fallback")
-    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-    return dev if dev.index is not None else torch.device("cuda", torch.cuda.current_device())
-
-
 def conv2d(a, weight, bias=None, stride: int = 1, padding: int = 0, skip=None, upsample: bool = False, residual=None, relu: bool = False,
            device=None) -> torch.Tensor:
     """bn_unet_conv2d_async on torch's current stream: a (B, Ca, h, w) (half-size with upsample=True), skip (B, Cb, H, W) or None,
     weight (Cout, Ca + Cb, k, k) with k in {1, 3, 7}, bias (Cout) or None, residual of the output's shape or None."""
-    dev = _device(device)
+    dev = resolve_device(device, "unet")
     lib = _capi.load()
     f = lambda t: None if t is None else torch.as_tensor(t).detach().to(dev, torch.float32).contiguous()
     a, weight, bias, skip, residual = f(a), f(weight), f(bias), f(skip), f(residual)
@@ -271,13 +245,13 @@ def conv2d(a, weight, bias=None, stride: int = 1, padding: int = 0, skip=None, u
                                         _ptr(work), nbytes)
     if code == _capi.BN_ERR_INVALID:
         raise ValueError(lib.bn_unet_last_error().decode("utf-8", "replace"))
-    _check(lib, code)
+    check(lib, "unet", code)
     return out
 
 
 def maxpool(x, device=None) -> torch.Tensor:
     """bn_unet_maxpool_async: the network's 3x3 stride-2 pad-1 max-pool of (B, C, h, w), padding counting as -inf."""
-    dev = _device(device)
+    dev = resolve_device(device, "unet")
     lib = _capi.load()
     x = torch.as_tensor(x).detach().to(dev, torch.float32).contiguous()
     if x.dim() != 4 or x.numel() == 0:
@@ -288,7 +262,7 @@ def maxpool(x, device=None) -> torch.Tensor:
         code = lib.bn_unet_maxpool_async(dev.index, stream_ptr(dev), _ptr(x), B * ch, h, w, _ptr(out))
     if code == _capi.BN_ERR_INVALID:
         raise ValueError(lib.bn_unet_last_error().decode("utf-8", "replace"))
-    _check(lib, code)
+    check(lib, "unet", code)
     return out
 
 

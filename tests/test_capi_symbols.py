@@ -5,6 +5,7 @@ import os
 import re
 import subprocess
 
+import numpy as np
 import pytest
 
 from benchnav_amd import _capi, build
@@ -92,6 +93,25 @@ def test_no_cpu_fallback_without_gpu():
     h = C.c_void_p()
     assert lib.bn_mppi_create(C.byref(cfg), C.byref(h)) == _capi.BN_ERR_NO_DEVICE
     assert b"no CPU fallback" in lib.bn_last_error()
+    # every other family whose create reaches the device check with a few bytes of valid arguments, each with its own error string
+    one = np.ones(1)
+    rrt, clrrt = _capi.RRTConfig(), _capi.CLRRTConfig()
+    lib.bn_rrt_config_init(C.byref(rrt))
+    lib.bn_clrrt_config_init(C.byref(clrrt))
+    f32 = np.ones(1, np.float32)
+    calls = {
+        "astar": lambda: lib.bn_astar_create(0, 4, 4, 1, C.byref(h)),
+        "terrain": lambda: lib.bn_terrain_create(0, 8, 1, C.byref(h)),
+        "rrt": lambda: lib.bn_rrt_create(C.byref(rrt), C.byref(h)),
+        "clrrt": lambda: lib.bn_clrrt_create(C.byref(clrrt), C.byref(h)),
+        "gp": lambda: lib.bn_gp_create(0, 1, one.ctypes.data, one.ctypes.data, one.ctypes.data, 0.0, 1.0, 1.0, 1.0, C.byref(h)),
+        "gp_fit": lambda: lib.bn_gp_fit_create(0, 1, one.ctypes.data, one.ctypes.data, 1e-4, C.byref(h)),
+        "risk": lambda: lib.bn_risk_map_infer(0, None, f32.ctypes.data, f32.ctypes.data, _capi.BN_MEM_HOST, 1, _capi.BN_RISK_EXPECTED,
+                                              0.0, 0, None, _capi.BN_MEM_HOST, 0, f32.ctypes.data, _capi.BN_MEM_HOST),
+    }
+    for family, call in calls.items():
+        assert call() == _capi.BN_ERR_NO_DEVICE, (family, getattr(lib, f"bn_{family}_last_error")())
+        assert b"no CPU fallback" in getattr(lib, f"bn_{family}_last_error")(), family
     import torch
     from benchnav_amd.mppi import MPPI
 
