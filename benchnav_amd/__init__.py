@@ -12,6 +12,7 @@
     from benchnav_amd import TraversabilityPredictor, GPSlipRegressor, load_slip_regressors   # the exact-GP slip prediction stage
     from benchnav_amd import SlipRegressorTrainer   # RegressorTrainer: fits the slip regressors on the GPU (GPSlipRegressor.fit)
     from benchnav_amd import TerrainClassifier, load_terrain_classifier, fold_state_dict   # the U-Net terrain classifier (unet.py)
+    from benchnav_amd import TrainableTerrainClassifier, ClassifierTrainer, init_state_dict   # ... and its training (unet_train.py)
 """
 from .native import NativeMPPI  # noqa: F401
 
@@ -50,4 +51,7 @@ def __getattr__(name):
     if name in ("TerrainClassifier", "load_terrain_classifier", "fold_state_dict"):
         from . import unet
         return getattr(unet, name)
+    if name in ("TrainableTerrainClassifier", "ClassifierTrainer", "init_state_dict", "pack_state_dict", "unpack_params"):
+        from . import unet_train
+        return getattr(unet_train, name)
     raise AttributeError(name)

@@ -244,6 +244,29 @@ SYMBOLS = {
                                        C.c_void_p, C.c_void_p, C.c_size_t]),
     "bn_unet_maxpool_async": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
     "bn_unet_last_error": (C.c_char_p, []),
+    "bn_segtrain_param_count": (C.c_int64, [C.c_int32]),
+    "bn_segtrain_create": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.POINTER(_H)]),
+    "bn_segtrain_destroy": (None, [_H]),
+    "bn_segtrain_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "bn_segtrain_grad_async": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "bn_segtrain_step_async": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double,
+                                         C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "bn_segtrain_read": (C.c_int, [_H, C.c_int32, C.c_void_p, C.c_int64]),
+    "bn_segtrain_steps": (C.c_int64, [_H]),
+    "bn_segtrain_conv2d_backward_workspace_bytes": (C.c_size_t, [C.c_int32] * 8),
+    "bn_segtrain_conv2d_backward_async": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                    C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t]),
+    "bn_segtrain_batchnorm_forward_async": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p,
+                                                      C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bn_segtrain_batchnorm_backward_async": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                                       C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bn_segtrain_maxpool_backward_async": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int32]),
+    "bn_segtrain_cross_entropy_async": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_size_t]),
+    "bn_segtrain_adam_async": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_double,
+                                         C.c_double, C.c_double, C.c_double, C.c_double]),
+    "bn_segtrain_last_error": (C.c_char_p, []),
     "bn_device_math_eval": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "bn_device_rng_eval": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "bn_last_error": (C.c_char_p, []),

@@ -1018,6 +1018,81 @@ int bn_unet_maxpool_async(int32_t device_id, void *stream, const float *in_devic
                           float *out_device);
 const char *bn_unet_last_error(void);
 
+/* ------------------------------------------------------------------------------------------------------------------------------
+ * Training the U-Net terrain classifier (csrc/segtrain_kernels.hip, csrc/segtrain_host.cpp): the reference's
+ * trainers/classifier_trainer.py on the device -- the network above in TRAINING mode (BatchNorm on batch statistics), the mean
+ * cross-entropy over all cells, the backward pass and Adam.  Float32 tensors; convolutions (forward, backward-data,
+ * backward-weight) on the exact float32 MFMA; every reduction and every elementwise formula of BatchNorm, the loss and Adam in
+ * float64 from the float32 operands, rounded once.  No atomics: two runs from the same state give the same bits.
+ *
+ * The packed UNFOLDED parameters, float32, in the order of the convolutions above: per convolution its weights (cout, cin, k, k),
+ * then its BatchNorm's gamma, beta, running mean and running variance (cout each); the head has its bias (classes) instead of
+ * those four.  Gradients, m and v are read in the same layout with zeros in the place of the running statistics.
+ * Range: that of bn_unet_workspace_bytes, and num_maps (H / 32) (W / 32) > 1 (more than one value per channel at the bottleneck).
+ * Errors: the segtrain error string below.
+ * ---------------------------------------------------------------------------------------------------------------------------- */
+typedef struct bn_segtrain bn_segtrain_t;
+/* Floats of packed unfolded parameters for `classes` classes; 0 for classes outside [1, 32]. */
+int64_t bn_segtrain_param_count(int32_t classes);
+/* A trainer on device_id from the HOST array of packed parameters: it holds the parameters, their gradients, Adam's m and v (zero)
+ * and the step count (zero).  Checked before the device is touched like bn_unet_create; BN_ERR_NO_DEVICE ("no CPU fallback"). */
+int bn_segtrain_create(int32_t device_id, int32_t classes, const float *params_host, int64_t count, bn_segtrain_t **out);
+void bn_segtrain_destroy(bn_segtrain_t *h);
+/* Bytes of device workspace one step on num_maps maps of H x W needs (every activation is kept for the backward pass); 0 out of
+ * range. */
+size_t bn_segtrain_workspace_bytes(int32_t num_maps, int32_t H, int32_t W);
+/* Training-mode forward, loss and backward on `stream`, no synchronisation: colors_device (num_maps, 3, H, W) float32,
+ * targets_device (num_maps, H, W) int64 in [0, classes) (the caller checks the range; a value outside contributes nothing),
+ * loss_device one float.  The gradients stay in the handle; no parameter, running statistic or step count changes. */
+int bn_segtrain_grad_async(bn_segtrain_t *h, void *stream, int32_t num_maps, int32_t H, int32_t W, const float *colors_device,
+                           const int64_t *targets_device, float *loss_device, void *workspace_device, size_t workspace_bytes);
+/* The same, then the running statistics (momentum 0.1, unbiased variance) and one step of torch.optim.Adam on every trainable
+ * parameter; the step count goes up by one.  Fully enqueued on `stream`; loss_device may point into an array of slots. */
+int bn_segtrain_step_async(bn_segtrain_t *h, void *stream, int32_t num_maps, int32_t H, int32_t W, const float *colors_device,
+                           const int64_t *targets_device, double lr, double beta1, double beta2, double eps, double weight_decay,
+                           float *loss_device, void *workspace_device, size_t workspace_bytes);
+/* Copies to the host, after a device synchronise: what = 0 the parameters, 1 the gradients, 2 Adam's m, 3 Adam's v; count ==
+ * bn_segtrain_param_count(classes). */
+int bn_segtrain_read(bn_segtrain_t *h, int32_t what, float *host, int64_t count);
+/* Steps taken so far (BatchNorm's num_batches_tracked grows by the same number); -1 for a null handle. */
+int64_t bn_segtrain_steps(bn_segtrain_t *h);
+/* Single layers on caller tensors, all on the device, for the layer-level tests.
+ * conv2d_backward: the gradients of bn_unet_conv2d_async's convolution (no bias, residual or ReLU) given grad_out (num_maps, cout,
+ * hout, wout): grad_weight (cout, ca + cb, ksize, ksize), grad_a of a's shape (the 2 x 2 sum with upsample = 1), grad_skip of the
+ * skip's shape; any of the three may be NULL.  accumulate = 1 adds grad_a and grad_skip to what the destinations hold.  pad <=
+ * ksize - 1.  The workspace size takes cin = ca + cb; 0 for arguments out of range. */
+size_t bn_segtrain_conv2d_backward_workspace_bytes(int32_t num_maps, int32_t cin, int32_t hin, int32_t win, int32_t cout, int32_t ksize,
+                                                   int32_t stride, int32_t pad);
+int bn_segtrain_conv2d_backward_async(int32_t device_id, void *stream, const float *a_device, int32_t ca, const float *skip_device, int32_t cb,
+                                      int32_t upsample, int32_t num_maps, int32_t hin, int32_t win, const float *weights_device, int32_t cout,
+                                      int32_t ksize, int32_t stride, int32_t pad, const float *grad_out_device, float *grad_weight_device,
+                                      float *grad_a_device, float *grad_skip_device, int32_t accumulate, void *workspace_device,
+                                      size_t workspace_bytes);
+/* y = [relu]((x - mean) gamma / sqrt(var + 1e-5) + beta [+ residual]) on the batch statistics of x (num_maps, channels, cells);
+ * stats_device receives 2 channels doubles (mean, 1 / sqrt(var + eps)); the running statistics, if given, are updated in place. */
+int bn_segtrain_batchnorm_forward_async(int32_t device_id, void *stream, const float *x_device, int32_t num_maps, int32_t channels, int64_t cells,
+                                        const float *gamma_device, const float *beta_device, const float *residual_device, int32_t relu,
+                                        float *running_mean_device, float *running_var_device, float *y_device, double *stats_device);
+/* Its backward from the saved x, y and stats: grad_x (may be grad_out's buffer), grad_residual (the gradient behind the ReLU mask,
+ * or NULL), grad_gamma, grad_beta; sums_device is scratch of 2 channels doubles. */
+int bn_segtrain_batchnorm_backward_async(int32_t device_id, void *stream, const float *grad_out_device, const float *y_device,
+                                         const float *x_device, const double *stats_device, const float *gamma_device, int32_t relu,
+                                         int32_t num_maps, int32_t channels, int64_t cells, float *grad_x_device, float *grad_residual_device,
+                                         float *grad_gamma_device, float *grad_beta_device, double *sums_device);
+/* The backward of bn_unet_maxpool_async: a cell receives a window's gradient iff it is the window's first maximum in row-major
+ * order. */
+int bn_segtrain_maxpool_backward_async(int32_t device_id, void *stream, const float *x_device, const float *grad_out_device, int64_t planes,
+                                       int32_t hin, int32_t win, float *grad_x_device, int32_t accumulate);
+/* loss = -mean log softmax(logits)[target] over num_maps x cells cells and, unless NULL, grad_logits = (softmax - onehot) / (num_maps
+ * cells); the workspace holds 8 bytes per cell. */
+int bn_segtrain_cross_entropy_async(int32_t device_id, void *stream, const float *logits_device, const int64_t *targets_device, int32_t num_maps,
+                                    int32_t classes, int64_t cells, float *loss_device, float *grad_logits_device, void *workspace_device,
+                                    size_t workspace_bytes);
+/* Step number `step` (from 1) of torch.optim.Adam on n parameters in place. */
+int bn_segtrain_adam_async(int32_t device_id, void *stream, float *params_device, const float *grads_device, float *m_device, float *v_device,
+                           int64_t n, int64_t step, double lr, double beta1, double beta2, double eps, double weight_decay);
+const char *bn_segtrain_last_error(void);
+
 /* Test hook: the library's device arithmetic (DESIGN.md "Arithmetic spec") applied elementwise to n device floats:
  * fn 0 = correctly rounded sqrt, 1 / 2 = sin / cos of the spec, 3 = heading wrap (theta + pi) % 2pi - pi with
  * torch.remainder semantics (robot_model.py:90), 4 = its in-loop form, 5 = the sqrt for zero / normal finite arguments.  Lets the tests compare the kernels' building
