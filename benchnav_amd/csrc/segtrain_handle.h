@@ -1,6 +1,6 @@
 // segtrain_handle.h -- training the U-Net terrain classifier: the argument blocks and launchers of
-// csrc/segtrain_kernels.hip and the handle of csrc/segtrain_host.cpp.  The layer table, the tile sizes and the forward convolution
-// are unet_handle.h's.  Private to csrc/.
+// csrc/segtrain_kernels.hip and the handle of csrc/segtrain_host.cpp.  The network's graph and the tile sizes are unet_graph.h's,
+// the forward convolution unet_handle.h's, the gather and the staging constants unet_conv_tile.h's.  Private to csrc/.
 #pragma once
 #include "unet_handle.h"
 

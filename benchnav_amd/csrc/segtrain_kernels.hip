@@ -17,30 +17,10 @@
 //   per-channel and whole-tensor reductions: float64; thread t adds elements t, t + 256, ... in ascending order, then a binary tree
 //     over the 256 threads.  Elementwise arithmetic: float64 from the float32 operands, rounded once.
 #include "segtrain_handle.h"
+#include "unet_conv_tile.h"
 
 namespace bn {
 namespace {
-
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-
-constexpr int kPitch = 80, kStage = 64, kRows = kStage / 4, kSlabStages = 2;      // the forward's staging (unet_kernels.hip)
-
-// One element of the forward's (virtual) input matrix: row k (wave-uniform), this lane's pixel.  unet_kernels.hip's gather.
-template <int KS>
-__device__ __forceinline__ float seg_gather(const SegConvGrad &p, int k, bool pixel_valid, const float *map_a, const float *map_b, int iy0, int ix0)
-{
-    const int ci = k / (KS * KS), tap = k - ci * (KS * KS), ky = tap / KS, kx = tap - ky * KS;
-    const int iy = iy0 + ky, ix = ix0 + kx;
-    if (!pixel_valid || k >= p.k || iy < 0 || iy >= p.hin || ix < 0 || ix >= p.win) return 0.0f;
-    if (ci < p.ca) {
-        if (p.upsample) {
-            const int ha = p.hin >> 1, wa = p.win >> 1;
-            return map_a[ci * (ha * wa) + (iy >> 1) * wa + (ix >> 1)];
-        }
-        return map_a[ci * (p.hin * p.win) + iy * p.win + ix];
-    }
-    return map_b[(ci - p.ca) * (p.hin * p.win) + iy * p.win + ix];
-}
 
 template <int KS>
 __global__ __launch_bounds__(256) void segtrain_wgrad_kernel(const SegConvGrad p)
@@ -75,7 +55,7 @@ __global__ __launch_bounds__(256) void segtrain_wgrad_kernel(const SegConvGrad p
         for (int j = 0; j < kRows; ++j) {
             const int r = wave + 4 * j + again;
             ra[j] = (valid && co0 + r < p.cout) ? dy[(int64_t)(co0 + r) * cells] : 0.0f;
-            rb[j] = seg_gather<KS>(p, k0 + r, valid, map_a, map_b, iy0, ix0);
+            rb[j] = unet_gather<KS>(p, k0 + r, valid, map_a, map_b, iy0, ix0);
         }
     };
     load(0);

@@ -1,57 +1,14 @@
-// unet_handle.h -- the U-Net terrain classifier's layer table, its handle and the launchers of csrc/unet_kernels.hip, shared with
-// the host file that drives them (unet_host.cpp).  Private to csrc/.
+// unet_handle.h -- the U-Net terrain classifier's handle, the convolution's argument block and the launchers of
+// csrc/unet_kernels.hip, shared with the host file that drives them (unet_host.cpp).  The network itself -- the layer table, the
+// nodes and their geometry -- is unet_graph.h's.  Private to csrc/.
 #pragma once
-#include <cstdint>
-#include <vector>
-
 #include "bn_host.h"
+#include "unet_graph.h"
 
 namespace bn {
 
-constexpr int kUnetMaxClasses = 32;
-constexpr int kUnetTile = 64;                // the convolution's block tile: 64 output channels x 64 output pixels
-constexpr int kUnetKStep = 16;               // the k rows of a convolution are padded to a multiple of this (four MFMA steps)
 constexpr int kUnetMinSide = 32, kUnetMaxSide = 2048, kUnetMaxMaps = 4096;
 constexpr int64_t kUnetMaxPixels = (int64_t)1 << 24;      // num_maps * H * W
-
-inline int unet_round_up(int v, int m) { return (v + m - 1) / m * m; }
-
-// one convolution of the network, in the order of the packed parameters (include/benchnav_mppi.h)
-struct UnetConvDesc {
-    int cin, cout, ksize, stride, pad;
-    int K() const { return cin * ksize * ksize; }
-    int kpad() const { return unet_round_up(K(), kUnetKStep); }
-    int coutpad() const { return unet_round_up(cout, kUnetTile); }
-    size_t host_floats() const { return (size_t)cout * K() + cout; }                // weights, then bias
-    size_t device_floats() const { return (size_t)kpad() * coutpad() + coutpad(); }   // wt[kpad][coutpad], then bias[coutpad]
-};
-
-// indices into the table below
-enum { kUnetStem = 0, kUnetLayer1 = 1, kUnetLayer2 = 5, kUnetLayer3 = 10, kUnetLayer4 = 15, kUnetDecoder = 20, kUnetHead = 30, kUnetConvs = 31 };
-
-inline std::vector<UnetConvDesc> unet_layers(int classes)
-{
-    std::vector<UnetConvDesc> v;
-    v.push_back({3, 64, 7, 2, 3});
-    const int width[4] = {64, 128, 256, 512};
-    int cin = 64;
-    for (int l = 0; l < 4; ++l) {
-        const int w = width[l], s = l ? 2 : 1;
-        v.push_back({cin, w, 3, s, 1});                   // block 0: conv1, conv2, (downsample)
-        v.push_back({w, w, 3, 1, 1});
-        if (l) v.push_back({cin, w, 1, 2, 0});
-        v.push_back({w, w, 3, 1, 1});                     // block 1: conv1, conv2
-        v.push_back({w, w, 3, 1, 1});
-        cin = w;
-    }
-    const int din[5] = {512, 256, 128, 64, 32}, dskip[5] = {256, 128, 64, 64, 0}, dout[5] = {256, 128, 64, 32, 16};
-    for (int b = 0; b < 5; ++b) {
-        v.push_back({din[b] + dskip[b], dout[b], 3, 1, 1});
-        v.push_back({dout[b], dout[b], 3, 1, 1});
-    }
-    v.push_back({16, classes, 3, 1, 1});
-    return v;
-}
 
 // One fused convolution as the kernel reads it.  The input is tensor a (ca channels), optionally 2x nearest-upsampled, followed
 // along channels by tensor b (cb channels, may be 0); hin x win is the size of that (virtual) input.
@@ -62,6 +19,38 @@ struct UnetConvArgs {
     float *out;
     int32_t num_maps, ca, cb, hin, win, hout, wout, cout, coutpad, k, kpad, stride, pad, upsample, relu;
 };
+
+// the argument block of convolution d at geometry geo: a holds ca of d.cin channels, b the rest; the bias follows wt's kpad rows
+inline UnetConvArgs unet_conv_args(const UnetConvDesc &d, const UnetGeo &geo, int num_maps, const float *a, int ca, const float *b, int upsample,
+                                   const float *wt, const float *residual, int relu, float *out)
+{
+    UnetConvArgs g{};
+    g.a = a; g.b = b; g.wt = wt; g.bias = wt + (size_t)d.kpad() * d.coutpad(); g.residual = residual; g.out = out;
+    g.num_maps = num_maps; g.ca = ca; g.cb = d.cin - ca; g.hin = geo.hin; g.win = geo.win; g.hout = geo.hout; g.wout = geo.wout;
+    g.cout = d.cout; g.coutpad = d.coutpad(); g.k = d.K(); g.kpad = d.kpad(); g.stride = d.stride; g.pad = d.pad;
+    g.upsample = upsample; g.relu = relu;
+    return g;
+}
+
+// The single-convolution entry points' range checks: nullptr, or why the arguments are refused.  The backward also needs
+// pad <= ksize - 1 (its stride-1 data gradient is a convolution with pad ksize - 1 - pad).
+inline const char *unet_conv_check(int ca, int cb, int cout, int ksize, int stride, int pad, int upsample, int num_maps, int hin, int win, bool backward)
+{
+    if (ca < 1 || cb < 0 || ca + cb > 4096 || cout < 1 || cout > 4096) return "ca must be >= 1, cb >= 0, and input and output channels in [1, 4096]";
+    if (ksize != 1 && ksize != 3 && ksize != 7) return "ksize must be 1, 3 or 7";
+    if (stride < 1 || stride > 2 || pad < 0 || pad > 3) return "stride must be 1 or 2 and pad in [0, 3]";
+    if (backward && pad > ksize - 1) return "the backward needs pad <= ksize - 1";
+    if (upsample != 0 && upsample != 1) return "upsample must be 0 or 1";
+    if (num_maps < 1 || num_maps > kUnetMaxMaps || hin < 1 || hin > kUnetMaxSide || win < 1 || win > kUnetMaxSide)
+        return "num_maps must be in [1, 4096] and the input sides in [1, 2048]";
+    if (upsample && ((hin | win) & 1)) return "an upsampled input has even sides";
+    if (hin + 2 * pad < ksize || win + 2 * pad < ksize) return "the kernel does not fit the padded input";
+    const int64_t hout = (hin + 2 * pad - ksize) / stride + 1, wout = (win + 2 * pad - ksize) / stride + 1;
+    if ((int64_t)num_maps * hin * win > kUnetMaxPixels || num_maps * hout * wout > kUnetMaxPixels) return "num_maps x pixels must be <= 2^24";
+    if ((int64_t)num_maps * (ca + cb) * hin * win >= ((int64_t)1 << 31) || num_maps * cout * hout * wout >= ((int64_t)1 << 31))
+        return "a tensor must hold fewer than 2^31 elements";
+    return nullptr;
+}
 
 // launchers (unet_kernels.hip); every one enqueues on `stream` and returns hipGetLastError()
 hipError_t unet_launch_conv(hipStream_t stream, int ksize, const UnetConvArgs &args);

@@ -1,5 +1,6 @@
 // unet_kernels.hip -- the U-Net terrain classifier's kernels: one fused convolution family on the exact float32
-// MFMA, the max-pool, the head's softmax / argmax and the weight re-layout.  Host side: unet_host.cpp, shared types: unet_handle.h.
+// MFMA, the max-pool, the head's softmax / argmax and the weight re-layout.  Host side: unet_host.cpp, shared types: unet_handle.h;
+// the staging constants and the gather, shared with the training kernels: unet_conv_tile.h.
 //
 // The convolution is an implicit GEMM  out[co][pixel] = sum_k wt[k][co] * x[k][pixel]  with k = ci * ksize^2 + ky * ksize + kx
 // (the order of a PyTorch weight row) and pixel = (map, oy, ox).  A workgroup of four waves owns 64 output channels x 64 pixels;
@@ -11,36 +12,11 @@
 // Summation order (what makes the bits a function of the weights and the map's own pixels alone): an output element is the sum over
 // slabs of 128 consecutive k of one k-ordered fmaf chain each (the MFMA's own order), the slab sums added in ascending order.  The
 // partition depends on k only -- not on the tile, the batch or the launch -- there is no split over workgroups and no atomic.
+#include "unet_conv_tile.h"
 #include "unet_handle.h"
 
 namespace bn {
 namespace {
-
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-
-constexpr int kPitch = 80;                   // floats per LDS row: 64 + 16
-constexpr int kStage = 64;                   // k rows staged through LDS per main-loop step (the last step may hold fewer)
-constexpr int kRows = kStage / 4;            // rows of each operand a thread stages: one column, every fourth row
-constexpr int kSlabStages = 2;               // 2 stages of 64 k = one slab of 128
-
-// One element of the (virtual) input matrix: row k, this lane's pixel.  k is the same for the 64 lanes of a wave (wave-uniform,
-// see row0 below), so its split into channel and tap, the choice between the two tensors and the channel's offset run on the
-// scalar unit; a lane adds its pixel's 32-bit offset inside the map (a map's tensor holds fewer than 2^31 elements).
-template <int KS>
-__device__ __forceinline__ float unet_gather(const UnetConvArgs &p, int k, bool pixel_valid, const float *map_a, const float *map_b, int iy0, int ix0)
-{
-    const int ci = k / (KS * KS), tap = k - ci * (KS * KS), ky = tap / KS, kx = tap - ky * KS;
-    const int iy = iy0 + ky, ix = ix0 + kx;
-    if (!pixel_valid || k >= p.k || iy < 0 || iy >= p.hin || ix < 0 || ix >= p.win) return 0.0f;    // zero padding, the K tail
-    if (ci < p.ca) {
-        if (p.upsample) {
-            const int ha = p.hin >> 1, wa = p.win >> 1;
-            return map_a[ci * (ha * wa) + (iy >> 1) * wa + (ix >> 1)];
-        }
-        return map_a[ci * (p.hin * p.win) + iy * p.win + ix];
-    }
-    return map_b[(ci - p.ca) * (p.hin * p.win) + iy * p.win + ix];
-}
 
 template <int KS>
 __global__ __launch_bounds__(256) void unet_conv_kernel(const UnetConvArgs p)

@@ -50,6 +50,23 @@ def conv_table(classes: int) -> List[Tuple[str, Optional[str], Tuple[int, int, i
     return t
 
 
+def conv_inputs(classes: int, side: int) -> List[Tuple[int, int, bool]]:
+    """Per convolution of conv_table, for maps of side x side: (side of its input, channels of the skip tensor concatenated behind
+    it or 0, whether the input's first tensor is 2x-upsampled to that side) -- the graph of csrc/unet_graph.h seen from Python."""
+    out, cur, block_in = [], int(side), int(side)
+    for i, (key, _, shape, stride, pad) in enumerate(conv_table(classes)):
+        first, up = key.endswith(".0.conv1.weight") and key.startswith("encoder.layer"), key.startswith("decoder") and ".conv1." in key
+        if first:
+            block_in = cur
+        src = block_in if ".downsample." in key else 2 * cur if up else cur
+        out.append((src, _DEC_SKIP[int(key.split(".")[2])] if up else 0, up))
+        if ".downsample." not in key:
+            cur = (src + 2 * pad - shape[2]) // stride + 1
+        if i == 0:
+            cur = (cur - 1) // 2 + 1                    # the max-pool behind the stem
+    return out
+
+
 def param_count(classes: int) -> int:
     """Floats of folded parameters: bn_unet_param_count(classes) without the library."""
     return sum(int(np.prod(shape)) + shape[0] for _, _, shape, _, _ in conv_table(classes))

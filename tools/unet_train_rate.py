@@ -32,27 +32,11 @@ from unet_rate import alternate, sample  # noqa: E402
 
 def layer_shapes(classes, B, G):
     """per convolution of unet.conv_table: (a shape, skip shape or None, upsample, weight shape, stride, pad)"""
-    from benchnav_amd.unet import _DEC_IN, _DEC_SKIP, conv_table
+    from benchnav_amd.unet import conv_inputs, conv_table
     out = []
-    for i, (_, _, shape, stride, pad) in enumerate(conv_table(classes)):
-        if i == 0:
-            side = G
-        elif i < 20:
-            l = 0 if i < 5 else 1 if i < 10 else 2 if i < 15 else 3
-            first = (1, 5, 10, 15)[l]
-            side = G >> (2 + l)
-            if l and i in (first, first + 2):
-                side *= 2
-        elif i < 30:
-            side = G >> (4 - (i - 20) // 2)
-        else:
-            side = G
-        if 20 <= i < 30 and (i - 20) % 2 == 0:
-            b = (i - 20) // 2
-            skip = (B, _DEC_SKIP[b], side, side) if _DEC_SKIP[b] else None
-            out.append(((B, _DEC_IN[b], side // 2, side // 2), skip, True, shape, stride, pad))
-        else:
-            out.append(((B, shape[1], side, side), None, False, shape, stride, pad))
+    for (_, _, shape, stride, pad), (side, cb, up) in zip(conv_table(classes), conv_inputs(classes, G)):
+        a_side = side // 2 if up else side
+        out.append(((B, shape[1] - cb, a_side, a_side), (B, cb, side, side) if cb else None, up, shape, stride, pad))
     return out
 
 
