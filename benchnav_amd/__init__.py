@@ -13,6 +13,8 @@
     from benchnav_amd import SlipRegressorTrainer   # RegressorTrainer: fits the slip regressors on the GPU (GPSlipRegressor.fit)
     from benchnav_amd import TerrainClassifier, load_terrain_classifier, fold_state_dict   # the U-Net terrain classifier (unet.py)
     from benchnav_amd import TrainableTerrainClassifier, ClassifierTrainer, init_state_dict   # ... and its training (unet_train.py)
+    from benchnav_amd import DatasetGenerator, TerrainDataset   # the dataset stage: splits on the device, the reference's files (dataset.py)
+    from benchnav_amd import TerrainClassificationDataset, SlipRegressionDataset, TraversabilityPredictionDataset   # ... and its three views
 """
 from .native import NativeMPPI  # noqa: F401
 
@@ -54,4 +56,7 @@ def __getattr__(name):
     if name in ("TrainableTerrainClassifier", "ClassifierTrainer", "init_state_dict", "pack_state_dict", "unpack_params"):
         from . import unet_train
         return getattr(unet_train, name)
+    if name in ("DatasetGenerator", "TerrainDataset", "TerrainClassificationDataset", "SlipRegressionDataset", "TraversabilityPredictionDataset"):
+        from . import dataset
+        return getattr(dataset, name)
     raise AttributeError(name)

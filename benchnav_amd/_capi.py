@@ -267,7 +267,14 @@ SYMBOLS = {
     "bn_segtrain_adam_async": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_double,
                                          C.c_double, C.c_double, C.c_double, C.c_double]),
     "bn_segtrain_last_error": (C.c_char_p, []),
-    "bn_device_math_eval": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "bn_dataset_sample_slips_async": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_uint64,
+                                                C.c_uint32, C.c_void_p]),
+    "bn_dataset_gather_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
+    "bn_dataset_gather_async": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                          C.c_int64, C.c_int32, C.c_int32, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_size_t]),
+    "bn_dataset_last_error": (C.c_char_p, []),
+    "bn_device_math_eval": (C.c_int,[C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "bn_device_rng_eval": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "bn_last_error": (C.c_char_p, []),
     "bn_mppi_abi_version": (C.c_int, []),

@@ -357,8 +357,23 @@ class SlipRegressorTrainer:
         for k in range(self.num_terrain_classes):
             self.train(k, phis[k], slips[k])
 
-    def load_data(self, num_samples: int = 9999) -> Tuple[Dict[int, torch.Tensor], Dict[int, torch.Tensor]]:
-        """Per class the slopes and slips of its cells in the loader's order, cut at num_samples."""
+    def load_data(self, num_samples: int = 9999, order=None) -> Tuple[Dict[int, torch.Tensor], Dict[int, torch.Tensor]]:
+        """Per class the slopes and slips of its cells in the loader's order, cut at num_samples.
+
+        A dataset with `gather_observations` (dataset.SlipRegressionDataset) is gathered on the device in one call instead: the
+        maps are visited in `order` (a permutation of the maps; default torch.randperm(len(dataset)) from torch's global
+        generator).  That is a shuffled order, but not the order DataLoader(shuffle=True) would have visited them in under the
+        same seed (its sampler draws a seed first).  Every other dataset goes through the loader, and `order` must stay None."""
+        if hasattr(self.train_dataset, "gather_observations"):
+            if order is None:
+                order = torch.randperm(len(self.train_dataset))
+            phis, slips, _, totals = self.train_dataset.gather_observations(self.num_terrain_classes, num_samples, order=order)
+            for k in range(self.num_terrain_classes):
+                if int(totals[k]) == 0:
+                    raise ValueError(f"the dataset holds no cell of terrain class {k}")
+            return phis, slips
+        if order is not None:
+            raise ValueError("order= applies to datasets with gather_observations; this one is read through its DataLoader")
         phis = {k: [] for k in range(self.num_terrain_classes)}
         slips = {k: [] for k in range(self.num_terrain_classes)}
         for slope_b, slip_b, class_b in self.train_loader:

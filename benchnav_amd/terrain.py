@@ -279,6 +279,7 @@ class Terrain:
     colors: Optional[torch.Tensor] = None      # (B, 3, G, G) float32, device
     noise: Optional[torch.Tensor] = None       # (B, G, G) float32, device
     light: Optional[np.ndarray] = None         # (B, 3) float32
+    classes_device: Optional[torch.Tensor] = None   # (B, G, G) int32, device: the class buffer t_classes was copied from (colouring only)
 
 
 class TerrainGenerator(Handle):
@@ -449,7 +450,7 @@ class TerrainGenerator(Handle):
         out = self.outputs()
         cls, colors, nz = self._color_outputs()
         self._last = Terrain(*out, t_classes=cls.cpu().to(torch.int64), craters=self._crater_tables(draws), draws=draws,
-                             colors=colors, noise=nz, light=light)
+                             colors=colors, noise=nz, light=light, classes_device=cls)
         return self._last
 
     def _generate_device(self, seeds, is_fractal, geometry, coloring, t_classes, slip_models, occupancy, noise, feature_size,
@@ -490,7 +491,7 @@ class TerrainGenerator(Handle):
         if coloring is not None:
             cls_t, colors, nz = self._color_outputs()
             self._last = Terrain(*out, t_classes=cls_t.cpu().to(torch.int64), craters=self._crater_tables(drawn), draws=drawn,
-                                 colors=colors, noise=nz, light=np.stack([d.light for d in drawn]))
+                                 colors=colors, noise=nz, light=np.stack([d.light for d in drawn]), classes_device=cls_t)
         else:
             with torch.cuda.device(self._dev):
                 colors = torch.zeros((B, 3, G, G), device=self._dev)

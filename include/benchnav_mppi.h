@@ -1093,6 +1093,35 @@ int bn_segtrain_adam_async(int32_t device_id, void *stream, float *params_device
                            int64_t n, int64_t step, double lr, double beta1, double beta2, double eps, double weight_decay);
 const char *bn_segtrain_last_error(void);
 
+/* ---- The dataset stage: slip observations and the regressor trainer's per-class gather -------------------------
+ * No handle: device pointers, the caller's stream, the caller's workspace; nothing synchronises.  Errors: bn_dataset_last_error().
+ *
+ * The observation stream: map m (its global index in the split, below 2^32) has Philox blocks j = 0 ..
+ * ceil(cells / 4) - 1; block j is Philox4x32-10 of the counter {j, m, epoch, 'OBSV' = 0x4F425356} under the key (lo(seed), hi(seed));
+ * Box-Muller of the words (x, y) gives z of cells 4j and 4j + 1, of (z, w) cells 4j + 2 and 4j + 3; a ragged last block drops the
+ * rest.  slip = z * std + mean as a rounded product and a rounded sum (Normal.sample).
+ *
+ * sample_slips: mean, std and slips are (num_maps, cells) float32; row r is map first_map + r, so a split drawn in chunks equals
+ * the split drawn at once.  z_device (num_maps, cells), unless NULL, replaces the stream (parity tests). */
+int bn_dataset_sample_slips_async(int32_t device_id, void *stream, const float *mean_device, const float *std_device, const float *z_device,
+                                  int64_t num_maps, int64_t cells, int64_t first_map, uint64_t seed, uint32_t epoch, float *slips_device);
+/* Bytes of device workspace one gather over num_maps maps and num_classes classes needs; 0 for arguments out of range. */
+size_t bn_dataset_gather_workspace_bytes(int64_t num_maps, int32_t num_classes);
+/* RegressorTrainer.load_data (regressor_trainer.py:90-126).  slopes, slips, mean, std: (num_maps, cells) float32; classes:
+ * (num_maps, cells) int32; order_device: (num_maps) int64, the maps in visiting order (NULL: 0, 1, ...; an entry outside
+ * [0, num_maps) names no map).  Row k of x and y, (num_classes, cap) float32, receives slopes[m][classes[m] == k] and
+ * slips[m][classes[m] == k] for m in visiting order, row-major inside a map, cut at cap; what lies beyond counts[k] is not written.
+ * counts (num_classes) int32 = min(totals, cap); totals (num_classes) int64.  A class value outside [0, num_classes) selects nothing
+ * (the reference's -1 "unassigned").  slips_device == NULL: the kept cells' observations are drawn in the kernel from mean and std
+ * with (seed, epoch) and the map's index as m -- bit for bit the gather over bn_dataset_sample_slips_async's output (first_map 0).
+ * Three launches (count, scan, scatter), integer ranks, no atomics on the outputs: the result does not depend on the launch
+ * geometry and two runs give the same bits.  num_classes <= 64, cap >= 1, num_maps < 2^32, cells < 2^31. */
+int bn_dataset_gather_async(int32_t device_id, void *stream, const float *slopes_device, const float *slips_device, const float *mean_device,
+                            const float *std_device, const int32_t *classes_device, const int64_t *order_device, int64_t num_maps, int64_t cells,
+                            int32_t num_classes, int32_t cap, uint64_t seed, uint32_t epoch, float *x_device, float *y_device,
+                            int32_t *counts_device, int64_t *totals_device, void *workspace_device, size_t workspace_bytes);
+const char *bn_dataset_last_error(void);
+
 /* Test hook: the library's device arithmetic (DESIGN.md "Arithmetic spec") applied elementwise to n device floats:
  * fn 0 = correctly rounded sqrt, 1 / 2 = sin / cos of the spec, 3 = heading wrap (theta + pi) % 2pi - pi with
  * torch.remainder semantics (robot_model.py:90), 4 = its in-loop form, 5 = the sqrt for zero / normal finite arguments.  Lets the tests compare the kernels' building
