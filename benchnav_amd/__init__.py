@@ -15,6 +15,7 @@
     from benchnav_amd import TrainableTerrainClassifier, ClassifierTrainer, init_state_dict   # ... and its training (unet_train.py)
     from benchnav_amd import DatasetGenerator, TerrainDataset   # the dataset stage: splits on the device, the reference's files (dataset.py)
     from benchnav_amd import TerrainClassificationDataset, SlipRegressionDataset, TraversabilityPredictionDataset   # ... and its three views
+    from benchnav_amd import Benchmark, score_episodes   # the benchmark stage: risk maps, chunked episodes, scores, a report (benchmark.py)
 """
 from .native import NativeMPPI  # noqa: F401
 
@@ -59,4 +60,7 @@ def __getattr__(name):
     if name in ("DatasetGenerator", "TerrainDataset", "TerrainClassificationDataset", "SlipRegressionDataset", "TraversabilityPredictionDataset"):
         from . import dataset
         return getattr(dataset, name)
+    if name in ("Benchmark", "score_episodes"):
+        from . import benchmark
+        return getattr(benchmark, name)
     raise AttributeError(name)

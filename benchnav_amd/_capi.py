@@ -31,6 +31,8 @@ BN_FLAG_HOST_PACED = 8192
 BN_FLAG_UNORDERED_OUTPUTS = 16384
 BN_BUF_STATES_ALT, BN_BUF_CONTROLS_ALT = 10, 11
 BN_RISK_EXPECTED, BN_RISK_VAR, BN_RISK_CVAR = 0, 1, 2
+BN_RISK_MAX_SETTINGS = 16
+BN_OUTCOME_GOAL, BN_OUTCOME_TIME_LIMIT, BN_OUTCOME_STOPPED, BN_OUTCOME_INVALID = 0, 1, 2, 3   # bn_episode_outcome
 BN_AD_OK, BN_AD_OUT_OF_BOUNDS, BN_AD_GOAL_COLLISION, BN_AD_FIELD_ERROR = 0, 1, 2, 3   # bn_astar_dwa_status
 BN_RRT_FLAG_GLOBAL_NODES, BN_RRT_FLAG_ONE_WAVE, BN_RRT_FLAG_FOUR_WAVES = 1, 2, 4
 (BN_RRT_BUF_NODES, BN_RRT_BUF_EDGES, BN_RRT_BUF_COSTS, BN_RRT_BUF_COUNTS, BN_RRT_BUF_SAMPLES, BN_RRT_BUF_SAMPLE_FLAGS,
@@ -144,6 +146,14 @@ SYMBOLS = {
     "bn_risk_map_infer": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int32, C.c_int, C.c_float,
                                     C.c_int32, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_int]),
     "bn_risk_last_error": (C.c_char_p, []),
+    "bn_risk_maps_infer": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int), _FP, C.c_int32,
+                                     C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bn_episode_score": (C.c_int, [C.c_int32] + [C.c_void_p] * 8 + [C.c_int32, C.c_int32, C.c_float, C.c_double] + [C.c_void_p] * 8),
+    "bn_score_last_error": (C.c_char_p, []),
+    "bn_mppi_episode_buffers": (C.c_int, [_H, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int32),
+                                          C.POINTER(C.c_int32)]),
+    "bn_astar_dwa_episode_buffers": (C.c_int, [_H, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                               C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "bn_astar_create": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_H)]),
     "bn_astar_destroy": (None, [_H]),
     "bn_astar_set_map": (C.c_int, [_H, C.c_int32, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_double]),

@@ -27,7 +27,7 @@ import numpy as np
 import torch
 
 from . import _capi
-from ._device import Handle, stream_ptr
+from ._device import Handle, _DevArray, stream_ptr
 
 _MESSAGES = {
     _capi.BN_AD_OUT_OF_BOUNDS: "Start or goal position is out of bounds.",       # astar.py:88-92
@@ -119,11 +119,13 @@ class AStarDWALoop(Handle):
         self.status = np.zeros(self.B, np.int32)
         self.status_step = np.full(self.B, -1, np.int32)
 
-    def run(self, n_steps: int, z: Optional[torch.Tensor] = None):
+    def run(self, n_steps: int, z: Optional[torch.Tensor] = None, log: bool = True):
         """n_steps control steps from the environment's current states.  z: (n_steps, B) injected slip draws; None draws them
         like env.step does (Philox keyed by the env seed and the step index).  Returns numpy arrays (states (n+1, B, 3),
         rewards (n, B), actions (n, B, 2), sub_goals (n, B, 2), done_step (B), status (B)); a frozen instance's rows hold its
-        state and NaN elsewhere.  done_step and status steps count from the last reset."""
+        state and NaN elsewhere.  done_step and status steps count from the last reset.  log=False only enqueues and
+        returns None: the log, done_step and status stay on the device (episode_buffers()), `status` / `status_step` here are
+        not refreshed and the walks' error word is not read."""
         env = self.env
         env._check_stream()
         if env._steps != self._steps:
@@ -145,6 +147,13 @@ class AStarDWALoop(Handle):
             C.c_void_p(None if zp is None else zp.data_ptr())))
         self._keep = (state, zp)
         B = self.B
+        if not log:
+            ptr = self.episode_buffers()[0]
+            env._robot_state = torch.as_tensor(_DevArray(ptr, (n + 1, B, 3)), device=self._dev)[-1].clone()
+            env._steps += n
+            env._elapsed_time += n * env._delta_t
+            self._steps += n
+            return None
         states = np.empty((n + 1, B, 3), np.float32)
         rewards = np.empty((n, B), np.float32)
         actions = np.empty((n, B, 2), np.float32)
@@ -163,6 +172,13 @@ class AStarDWALoop(Handle):
             self.status, self.status_step = status, status_step
         _capi.check(rc)
         return states, rewards, actions, sub_goals, done, status
+
+    def episode_buffers(self):
+        """Device pointers (states (n+1,B,3), rewards (n,B), done_step (B), status (B), both int32) of the latest run's log, its n
+        and the row capacity the log is laid out for.  Nothing is copied."""
+        s, r, d, st, n, cap = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int32(), C.c_int32()
+        _capi.check(self._lib.bn_astar_dwa_episode_buffers(self._h, C.byref(s), C.byref(r), C.byref(d), C.byref(st), C.byref(n), C.byref(cap)))
+        return s.value, r.value, d.value, st.value, n.value, cap.value
 
     def set_root(self, instance: int, cell):
         """Instance `instance`'s root cell (ix, iy), or None to forget it: the start of the previous path DWA keeps where the

@@ -175,6 +175,21 @@ int bn_mppi_episode_log(bn_mppi_t *h, float *states_host, float *rewards_host, f
     return BN_OK;
 }
 
+int bn_mppi_episode_buffers(bn_mppi_t *h, const float **states_device, const float **rewards_device, const int32_t **done_step_device,
+                            int32_t *n_steps, int32_t *row_capacity)
+{
+    if (!h) return fail(BN_ERR_INVALID, "null handle");
+    if (!h->d_ep_states || h->ep_len < 1) return fail(BN_ERR_STATE, "no episode has been run");
+    BN_BIND(h);
+    if (int rc = settle_point(h)) return rc;              // from here on the episode is ordered on the handle's stream
+    if (states_device) *states_device = h->d_ep_states;                                        // (n_steps + 1, B, 3)
+    if (rewards_device) *rewards_device = h->d_ep_reward;                                      // (n_steps, B)
+    if (done_step_device) *done_step_device = h->d_ep_done;                                    // (B)
+    if (n_steps) *n_steps = h->ep_len;
+    if (row_capacity) *row_capacity = h->ep_steps;
+    return BN_OK;
+}
+
 int bn_mppi_dwa_solve(bn_mppi_t *h, const float *states_host, const float *actions_host, int32_t num_actions,
                       const float *stage_goal_host, float *best_action_host, float *best_states_host,
                       float *costs_host, float *weights_host, float *states_all_host, int32_t *best_index_host)

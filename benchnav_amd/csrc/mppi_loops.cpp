@@ -164,6 +164,23 @@ int bn_astar_dwa_episode_log(bn_mppi_t *h, float *states, float *rewards, float 
     return BN_OK;
 }
 
+int bn_astar_dwa_episode_buffers(bn_mppi_t *h, const float **states_device, const float **rewards_device,
+                                 const int32_t **done_step_device, const int32_t **status_device, int32_t *n_steps, int32_t *row_capacity)
+{
+    if (!h) return fail(BN_ERR_INVALID, "null handle");
+    if (!h->d_ad_log || h->ad_len < 1) return fail(BN_ERR_STATE, "no A* + DWA episode has been run");
+    BN_BIND(h);
+    if (int rc = settle_point(h)) return rc;
+    const size_t B = h->p.B, cap = (size_t)h->ad_cap;      // the log is laid out by capacity, as bn_astar_dwa_episode_log reads it
+    if (states_device) *states_device = h->d_ad_log;                                           // (row_capacity + 1, B, 3)
+    if (rewards_device) *rewards_device = h->d_ad_log + (cap + 1) * B * 3;                     // (row_capacity, B)
+    if (done_step_device) *done_step_device = h->d_ad_i + 3 * B;                               // (B)
+    if (status_device) *status_device = h->d_ad_i + B;                                         // (B) bn_astar_dwa_status
+    if (n_steps) *n_steps = h->ad_len;
+    if (row_capacity) *row_capacity = h->ad_cap;
+    return BN_OK;
+}
+
 // ---- the CL-RRT plan-follow-replan loop (clrrt_loop.hip) ----
 
 // what bn_clrrt_loop_reset verified once: the CL-RRT handle plans on the environment's grid

@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from . import _capi
+from ._device import _DevArray
 
 
 def env_inputs(env) -> dict:
@@ -52,13 +53,18 @@ class BatchedPlanetaryEnv:
                    goal_threshold=inp["goal_threshold"], seed=inp["seed"], freeze_on_goal=freeze_on_goal)
 
     def __init__(self, planner, latent_mean, latent_std, start_pos, goal_pos, delta_t: float = 0.1, time_limit: float = 100.0,
-                 stuck_threshold: float = 0.1, goal_threshold: float = 1.0, seed: Optional[int] = None, freeze_on_goal: bool = False):
+                 stuck_threshold: float = 0.1, goal_threshold: float = 1.0, seed: Optional[int] = None, freeze_on_goal: bool = False,
+                 check_positions: bool = True):
         """planner: NativeMPPI with B instances (its goals are set from goal_pos), created on torch's current stream of its
         device (`stream=torch.cuda.current_stream().cuda_stream`): the environment kernels run on the planner's stream and
         their inputs / outputs are torch tensors, so both must be ONE stream (checked on every call).
-        latent_mean / latent_std: (G,G) slip model `grid_map.distributions["latent_models"]` (planetary_env.py:80-84 builds
-        the observation-mode dynamics from it).  start_pos, goal_pos: (B,2) or (2,).
-        freeze_on_goal: opt-in; the reference environment keeps moving when a terminated episode is stepped again."""
+        latent_mean / latent_std: the slip model `grid_map.distributions["latent_models"]` (planetary_env.py:80-84 builds
+        the observation-mode dynamics from it): (G,G) for every instance, or (B,G,G), one per instance, for a planner without
+        shared_map.  start_pos, goal_pos: (B,2) or (2,).
+        freeze_on_goal: opt-in; the reference environment keeps moving when a terminated episode is stepped again.
+        check_positions: False skips the reference's "Start or goal position is not traversable." test and its two collision
+        draws, for a caller that checks per instance itself (benchmark.Benchmark keeps such instances as INVALID episodes
+        instead of losing the batch)."""
         self.planner = planner
         self._freeze = bool(freeze_on_goal)
         self._dev = torch.device("cuda", planner.device_id)
@@ -85,6 +91,8 @@ class BatchedPlanetaryEnv:
         self._steps = 0
         self._draws = 0
         self._on_reset = []                        # weak references to the reset() of loops driving this environment (AStarDWALoop)
+        if not check_positions:
+            return
         if bool(self.collision_check(torch.cat([self._start_pos, torch.zeros(self.B, 1, device=dev)], 1).unsqueeze(1)).any()) or \
            bool(self.collision_check(torch.cat([self._goal_pos, torch.zeros(self.B, 1, device=dev)], 1).unsqueeze(1)).any()):
             raise ValueError("Start or goal position is not traversable.")          # planetary_env.py:124-125
@@ -151,9 +159,17 @@ class BatchedPlanetaryEnv:
         self._draws += 1
         return out.bool()
 
-    def run(self, n_steps: int):
+    def run(self, n_steps: int, log: bool = True):
         """The fused loop: n_steps of solve -> step inside the planner's pipelined launches (bn_mppi_episode_async),
-        from the current robot states.  Returns (states (n_steps+1,B,3), rewards (n_steps,B), first_goal_step (B,))."""
+        from the current robot states.  Returns (states (n_steps+1,B,3), rewards (n_steps,B), first_goal_step (B,)).
+        log=False only enqueues and returns None: the log stays on the device (planner.episode_buffers())."""
+        if not log:
+            self.planner.episode(n_steps, self._robot_state.cpu().numpy(), wait=False)
+            ptr = self.planner.episode_buffers()[0]
+            self._robot_state = torch.as_tensor(_DevArray(ptr, (n_steps + 1, self.B, 3)), device=self._dev)[-1].clone()
+            self._steps += n_steps
+            self._elapsed_time += n_steps * self._delta_t
+            return None
         states, rewards, done = self.planner.episode(n_steps, self._robot_state.cpu().numpy())
         self._robot_state = torch.as_tensor(states[-1], device=self._dev).contiguous()
         self._steps += n_steps

@@ -97,6 +97,10 @@ class NativeMPPI:
         r = _f32(risk, (self.G, self.G))
         _capi.check(self._lib.bn_mppi_set_map(self._h, instance, C.c_void_p(r.ctypes.data), _capi.BN_MEM_HOST))
 
+    def set_map_device(self, risk_ptr: int, instance: int = -1):
+        """set_map from a (G, G) float32 map that is already on the handle's device: copied device to device."""
+        _capi.check(self._lib.bn_mppi_set_map(self._h, instance, C.c_void_p(risk_ptr), _capi.BN_MEM_DEVICE))
+
     def set_slip_std(self, std, instance: int = -1):
         """Sampled-slip mode: per-cell slip std; the map given to set_map is then the slip mean."""
         r = _f32(std, (self.G, self.G))
@@ -279,6 +283,13 @@ class NativeMPPI:
                                                   done.ctypes.data_as(C.POINTER(C.c_int32))))
         self.last_actions = actions
         return states, rewards, done
+
+    def episode_buffers(self):
+        """Device pointers (states (n+1,B,3), rewards (n,B), done_step (B) int32) of the latest episode's log, its n and the
+        buffers' row capacity: for a consumer on the handle's stream (benchmark.score_episodes).  Nothing is copied."""
+        s, r, d, n, cap = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int32(), C.c_int32()
+        _capi.check(self._lib.bn_mppi_episode_buffers(self._h, C.byref(s), C.byref(r), C.byref(d), C.byref(n), C.byref(cap)))
+        return s.value, r.value, d.value, n.value, cap.value
 
     def sync(self):
         """Write the pending tail of the latest solve and wait for the stream."""

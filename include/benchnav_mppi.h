@@ -349,6 +349,11 @@ int bn_mppi_episode_async(bn_mppi_t *h, int32_t n_steps, const float *states0, b
                           const float *z_device);
 int bn_mppi_episode_log(bn_mppi_t *h, float *states_host, float *rewards_host, float *actions_host,
                         int32_t *done_step_host);
+/* Device views of the latest episode's log, for a consumer on the handle's stream (bn_episode_score): states (n_steps + 1, B, 3),
+ * rewards (n_steps, B), done_step (B), valid until the next episode; row_capacity is the rows the buffers were allocated for.
+ * Any pointer may be NULL.  Nothing is copied. */
+int bn_mppi_episode_buffers(bn_mppi_t *h, const float **states_device, const float **rewards_device, const int32_t **done_step_device,
+                            int32_t *n_steps, int32_t *row_capacity);
 /*
  * DWA.forward(state), reference src/planners/local_planners/dwa.py:116-153, on the planner handle's map, goal and
  * geometry.  The caller supplies the dynamic-window candidates (dwa.py:168-199: cartesian_prod of two linspaces),
@@ -509,6 +514,46 @@ int bn_risk_map_infer(int32_t device_id, void *stream, const float *mean, const 
                       int32_t grid_size, bn_risk_metric metric, float confidence, int32_t num_samples,
                       const float *z, bn_mem_kind where_z, uint64_t seed, float *out, bn_mem_kind where_out);
 const char *bn_risk_last_error(void);
+/*
+ * The benchmark's form: num_maps maps under num_settings (metric, confidence) pairs in ONE launch on `stream`.  Device pointers
+ * only: mean, std (num_maps, G, G); z (num_maps, num_samples, G, G) or NULL; seeds (num_maps) or NULL (every seed 0); out
+ * (num_settings, num_maps, G, G).  metrics and confidences are host arrays, read before the call returns.  A wave draws its
+ * cell's samples once -- the Philox counters are bn_risk_map_infer's: the cell index within the map, the lane block, the map's
+ * seed -- and evaluates every setting on them, so out[c][m] is bit for bit what bn_risk_map_infer returns for (mean[m], std[m],
+ * metrics[c], confidences[c], num_samples, z[m] or seeds[m]).  num_settings in [1, BN_RISK_MAX_SETTINGS]; num_samples in
+ * [2, 4096] and confidences in [0, 1] wherever a setting samples.  Nothing synchronises.  Errors: bn_risk_last_error().
+ */
+#define BN_RISK_MAX_SETTINGS 16
+int bn_risk_maps_infer(int32_t device_id, void *stream, const float *mean_device, const float *std_device, int32_t num_maps,
+                       int32_t grid_size, const bn_risk_metric *metrics, const float *confidences, int32_t num_settings,
+                       int32_t num_samples, const float *z_device, const uint64_t *seeds_device, float *out_device);
+
+/*
+ * An episode log reduced to its outcome on the device (csrc/score_kernels.hip): what the benchmark reports per episode.  Device
+ * pointers only, one launch on `stream`, nothing synchronises.  Errors: bn_score_last_error().
+ *   states (n_steps + 1, B, 3), rewards (n_steps, B), goals (B, 2)
+ *   end_step (B)   how many leading rows count, clamped to [0, n_steps]; NULL: done_step + 1 where the goal was reached, else n_steps
+ *   done_step (B)  the 0-based index of the step whose resulting state first lay within the goal threshold, or -1: the word
+ *                  bn_mppi_episode_async and bn_astar_dwa_episode_async write (from bn_clrrt_loop_log: done_iter where the
+ *                  status is BN_CL_GOAL, else -1)
+ *   stopped (B) or NULL: non-zero = the planner gave up (a bn_astar_dwa_status, a CL-RRT status that is no goal and no time limit)
+ *   invalid (B) or NULL: non-zero = the start or the goal was not traversable
+ * A row whose reward is NaN is no step (the frozen rows of the A* + DWA log, the replan rows of the CL-RRT log): it adds nothing,
+ * but its state is still the rover's position.  Outputs, (B) each:
+ *   outcome         bn_episode_outcome: invalid wins, then done_step >= 0, then stopped, else the time limit
+ *   steps           counted rows;  time: `steps` successive += delta_t in float64 (PlanetaryEnv._elapsed_time)
+ *   path_length     float64 sum, in step order, of the float64 distances between consecutive positions over the counted rows
+ *   reward_sum      float64;  reward_min float32, NaN when steps == 0
+ *   stuck_steps     counted rows with reward <= stuck_threshold, compared in float32
+ *   final_distance  float64, from the state after the last row inside end_step to the goal
+ */
+typedef enum bn_episode_outcome { BN_OUTCOME_GOAL = 0, BN_OUTCOME_TIME_LIMIT = 1, BN_OUTCOME_STOPPED = 2, BN_OUTCOME_INVALID = 3 } bn_episode_outcome;
+int bn_episode_score(int32_t device_id, void *stream, const float *states_device, const float *rewards_device, const float *goals_device,
+                     const int32_t *end_step_device, const int32_t *done_step_device, const int32_t *stopped_device,
+                     const uint8_t *invalid_device, int32_t n_steps, int32_t num_episodes, float stuck_threshold, double delta_t,
+                     int32_t *outcome_device, int32_t *steps_device, double *time_device, double *path_length_device,
+                     double *reward_sum_device, float *reward_min_device, int32_t *stuck_steps_device, double *final_distance_device);
+const char *bn_score_last_error(void);
 
 /*
  * AStar (src/planners/global_planners/search_based/astar.py), the A* global planner, as one goal-rooted shortest-path solve
@@ -597,6 +642,11 @@ int bn_astar_dwa_episode_async(bn_mppi_t *h, bn_astar_t *a, int32_t n_steps, con
  * episode step at which it was set.  BN_ERR_STATE if a walk broke (the kernel's error word). */
 int bn_astar_dwa_episode_log(bn_mppi_t *h, float *states, float *rewards, float *actions, float *sub_goals,
                              int32_t *done_step, int32_t *status, int32_t *status_step);
+/* Device views of the latest call's log (bn_episode_score): states (n_steps + 1, B, 3) and rewards (n_steps, B) as the leading rows
+ * of buffers laid out for row_capacity steps, done_step (B) and status (B), both counted from the last reset.  Valid until the next
+ * call; any pointer may be NULL.  Nothing is copied, and the error word is not read (bn_astar_dwa_episode_log does that). */
+int bn_astar_dwa_episode_buffers(bn_mppi_t *h, const float **states_device, const float **rewards_device,
+                                 const int32_t **done_step_device, const int32_t **status_device, int32_t *n_steps, int32_t *row_capacity);
 /* Forget the root cells, the statuses and the step count: a new episode, or a new A* solve. */
 int bn_astar_dwa_reset(bn_mppi_t *h);
 /* Set instance b's root cell (ix, iy), or forget it with ix < 0: starts a teacher-forced step from a given previous path. */
