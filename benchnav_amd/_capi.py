@@ -60,6 +60,18 @@ class Config(C.Structure):
     ]
 
 
+class PlanInfo(C.Structure):
+    """bn_mppi_plan_info: what bn_mppi_create would decide (bn_mppi_debug_plan)."""
+    _fields_ = ([("struct_size", C.c_uint32), ("n_cus", C.c_int32)]
+                + [(n, C.c_int32) for n in ("nblk", "Kp", "pow2", "reach", "WN", "lds_park", "ref_order", "wrap_near", "regen_steps",
+                                            "park_steps", "xs", "map_stride", "slip_on")]
+                + [("inv_lambda", C.c_float)]
+                + [(n, C.c_int32) for n in ("n_maps", "slow_path", "want_wave", "pipelined", "wave_kernel", "lat_kernel", "role_overlap",
+                                            "ticket_det", "ticket_overlap", "ticket_mode", "may_overlap", "n_streams", "has_X", "has_U",
+                                            "has_granules", "has_alt", "has_ticket_buffers", "has_slip_std")]
+                + [("snap_cap", C.c_uint64), ("resident_wgs", C.c_uint64), ("buffer_bytes", C.c_uint64 * 12)])
+
+
 class RRTConfig(C.Structure):
     _fields_ = [
         ("struct_size", C.c_uint32), ("device_id", C.c_int32), ("num_instances", C.c_int32), ("max_iterations", C.c_int32),
@@ -123,6 +135,7 @@ SYMBOLS = {
     "bn_mppi_debug_expire_wait": (C.c_int, [_H]),
     "bn_mppi_flush": (C.c_int, [_H]),
     "bn_mppi_debug_host_paced": (C.c_int, [_H, C.c_int32, C.c_int32]),
+    "bn_mppi_debug_plan": (C.c_int, [C.POINTER(Config), C.c_int32, C.POINTER(PlanInfo)]),
     "bn_mppi_get_weights": (C.c_int, [_H, C.c_int32, _FP]),
     "bn_mppi_get_costs": (C.c_int, [_H, C.c_int32, _FP]),
     "bn_mppi_get_states": (C.c_int, [_H, C.c_int32, _FP]),

@@ -1,10 +1,12 @@
-// bn_host.h -- the host toolkit every handle of the library is written with: the device guard, the HIP check that reports through
-// the family's own fail function (each bn_*_last_error() keeps its thread_local string), the zero-filling allocation, and the table
-// of device buffers, pinned blocks and events a handle fills once in its *_create.  Host code only, internal linkage, no kernels.
+// bn_host.h -- the host toolkit every handle of the library is written with, the MPPI planner's included: the device guard, the HIP
+// check that reports through the family's own fail function (each bn_*_last_error() keeps its thread_local string), the
+// zero-filling allocation, and the table of device buffers, pinned blocks and events a handle fills once in its *_create (and one
+// more table per group it builds on first use).  Host code only, internal linkage, no kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -79,7 +81,7 @@ struct DeviceBuffers {
     template <typename P>
     void add_later(P **slot) { list.push_back(Entry{(void **)slot, 0, -1, kLater, 0}); }
     template <typename P>
-    void add_pinned(P **slot, size_t bytes) { list.push_back(Entry{(void **)slot, bytes, -1, kPinned, 0}); }
+    void add_pinned(P **slot, size_t bytes, unsigned flags = hipHostMallocDefault) { list.push_back(Entry{(void **)slot, bytes, -1, kPinned, flags}); }
     void add_event(hipEvent_t *ev, unsigned flags = 0) { list.push_back(Entry{(void **)ev, 0, -1, kEvent, flags}); }
 
     // Everything or nothing: a failure releases what the earlier entries got.  All are allocated, in the order listed, before any is
@@ -139,7 +141,7 @@ private:
     static int alloc_one(const Entry &e, Fail fail)
     {
         if (e.kind == kDevice) BN_HIP_OR(fail, hipMalloc(e.slot, e.bytes ? e.bytes : 4));
-        if (e.kind == kPinned) BN_HIP_OR(fail, hipHostMalloc(e.slot, e.bytes ? e.bytes : 4, hipHostMallocDefault));
+        if (e.kind == kPinned) BN_HIP_OR(fail, hipHostMalloc(e.slot, e.bytes ? e.bytes : 4, e.flags));
         if (e.kind == kEvent) BN_HIP_OR(fail, hipEventCreateWithFlags((hipEvent_t *)e.slot, e.flags));
         return BN_OK;
     }
@@ -148,6 +150,7 @@ private:
     static int zero_one(const Entry &e, Fail fail)
     {
         if (e.kind == kDevice) BN_HIP_OR(fail, hipMemset(*e.slot, 0, e.bytes ? e.bytes : 4));
+        if (e.kind == kPinned) std::memset(*e.slot, 0, e.bytes ? e.bytes : 4);
         return BN_OK;
     }
 };

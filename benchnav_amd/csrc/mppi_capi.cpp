@@ -4,11 +4,11 @@
 // a solve (mppi_kernels.hip) on the handle's HIP stream.  No torch types, no CPU
 // fallback: creation fails without a gfx950 device.
 //
-// Here: the error string, the kernel choice, the per-device overlap ownership, the journal and the recovery of expired waits,
-// create / destroy / setters, and everything a solve executes (solve_impl, bn_mppi_solve_n_async).  The other concerns have a
+// Here: the error string, the per-device overlap ownership, the journal and the recovery of expired waits,
+// create (from the plan of mppi_plan.cpp: register the buffers, allocate, probe) / destroy / setters, and everything a solve executes (solve_impl, bn_mppi_solve_n_async).  The other concerns have a
 // file each: mppi_paced.cpp (host-paced loop, forward), mppi_shard.cpp (K-shard exchange), mppi_env.cpp (closed-loop
 // environment, DWA), mppi_loops.cpp (A*+DWA and CL-RRT loops), mppi_query.cpp (getters, profiling, lab hooks).
-#include "mppi_handle.h"
+#include "mppi_plan.h"
 
 #include <algorithm>
 #include <atomic>
@@ -31,23 +31,6 @@
 namespace bn {
 namespace host {
 
-// Role kernel or one-wave throughput kernel for a many-instance launch?  Both give bit-identical results; which one is faster
-// depends on the horizon (the role kernel's skeleton -- prologue, barriers, epilogue -- is a fixed cost per workgroup, the one-wave
-// kernel pays per step), on the workgroups per instance (both re-merge nblk rows per workgroup) and on how full the chip gets.
-// A two-term estimate of either kernel's time per launch, fitted to tools/auto_sweep.py (K 128..2048, T 10..100, 16..300
-// instances, overlapped launches): it picks the faster kernel or one within 10 % of it in 51 of 52 cells (worst: 28 %), where a
-// fixed workgroup-count threshold lost 14-60 % in seven.  K=1024, T=50: crossover between 64 and 128 instances as measured.
-static bool wave_kernel_is_faster(const bn::SolveParams &p, size_t resident_role_wgs, int n_cus)
-{
-    const double W = (double)p.B * (p.nblk + 1), R = (double)std::max<size_t>(resident_role_wgs, 1), rows = std::max(0, p.nblk - 16);
-    const double role = (4.5 + 0.19 * p.T + 0.3 * rows) * (1.0 + 0.175 * std::min(W, R) / std::max(n_cus, 1)) * std::max(1.0, W / R);
-    // (round 5: x 0.93 -- the one-wave kernel lost a quarter of its instructions; re-checked against tools/auto_sweep.py, which had
-    // flagged K=1024 T=50 at 80 instances and K=512 T=20 at 128 where the role kernel spills into a second residency round)
-    // (not for short horizons or more than 16 workgroups per instance, where the sweep has the role kernel ahead at the old crossover)
-    const double gain = (rows == 0 && p.T >= 20) ? 0.93 : 1.0;
-    const double wave = gain * (3.3 + 0.44 * p.T + 0.37 * rows) * (1.0 + 1.5 * W / (24.0 * std::max(n_cus, 1)));
-    return wave < role;
-}
 static thread_local std::string g_last_error;
 
 int fail(int code, const char *fmt, ...)
@@ -59,12 +42,6 @@ int fail(int code, const char *fmt, ...)
     va_end(ap);
     g_last_error = buf;
     return code;
-}
-
-static bool is_pow2_float(float v)
-{
-    int ex;
-    return v > 0.0f && std::isfinite(v) && std::frexp(v, &ex) == 0.5f;
 }
 
 // One overlapped batch per device at a time.  Workgroups of an overlapped launch hold their slots while they wait for their
@@ -107,35 +84,13 @@ static bool own_device_for_big_overlap(int device)
     return true;
 }
 
-size_t buffer_bytes(const bn_mppi *h, bn_buffer_id id)
-{
-    const size_t B = h->p.B, K = h->p.K, T = h->p.T, G = h->p.G;
-    switch (id) {
-    case BN_BUF_STATES: return B * (T + 1) * 3 * (size_t)h->p.Kp * 4;
-    case BN_BUF_STATES_ALT: return h->d_Xalt[0] ? B * (T + 1) * 3 * (size_t)h->p.Kp * 4 : 0;
-    case BN_BUF_CONTROLS_ALT: return h->d_Ualt[0] ? B * T * 2 * (size_t)h->p.Kp * 4 : 0;
-    case BN_BUF_WEIGHTS: return B * K * 4;
-    case BN_BUF_COSTS: return B * K * 4;
-    case BN_BUF_CONTROLS: return h->d_U ? B * T * 2 * (size_t)h->p.Kp * 4 : 0;
-    case BN_BUF_USTAR: return B * T * 2 * 4;
-    case BN_BUF_XSTAR: return B * (T + 1) * 3 * 4;
-    case BN_BUF_MEAN: return B * T * 2 * 4;
-    case BN_BUF_MAP: return (size_t)h->n_maps * G * G * 4;
-    case BN_BUF_GOAL: return B * 2 * 4;
-    case BN_BUF_USTAR_XSTAR: return (B * T * 2 + B * (T + 1) * 3) * 4;
-    default: return 0;
-    }
-}
-
 int ensure_scratch(bn_mppi *h, size_t bytes)
 {
     if (bytes <= h->scratch_bytes) return BN_OK;
-    if (h->d_scratch) BN_HIP(hipFree(h->d_scratch));
-    h->d_scratch = nullptr;
     h->scratch_bytes = 0;
-    BN_HIP(hipMalloc(&h->d_scratch, bytes));
+    if (int rc = h->bufs.resize(&h->d_scratch, bytes, table_fail)) return rc;
     h->scratch_bytes = bytes;
-    return BN_OK;
+    return fills_done();
 }
 
 // Write the tail (U*, next mean, X*, weights, cost copy) of the latest solve if it is still pending.
@@ -389,43 +344,145 @@ void bn_mppi_config_init(bn_mppi_config *c)
     c->seed = 42;
 }
 
+// Everything bn_mppi_create allocates, entered into the handle's table from the plan: in the order, and under the conditions, the
+// handle has always allocated it.  The sizes of the buffers bn_mppi_device_buffer hands out are the plan's.
+static void register_buffers(bn_mppi *h, const MppiPlan &m)
+{
+    const bn::SolveParams &p = h->p;
+    const size_t B = p.B, K = p.K, T = p.T;
+    const uint64_t *pub = m.buffer_bytes;
+    bn::DeviceBuffers &t = h->bufs;
+    t.add(&h->d_map, pub[BN_BUF_MAP], BN_BUF_MAP);
+    t.add(&h->d_state, B * 3 * 4);
+    t.add(&h->d_goal, pub[BN_BUF_GOAL], BN_BUF_GOAL);
+    t.add(&h->d_mean, pub[BN_BUF_MEAN], BN_BUF_MEAN);
+    if (m.has_X) t.add(&h->d_X, pub[BN_BUF_STATES], BN_BUF_STATES);
+    t.add(&h->d_mean_used, B * T * 2 * 4);
+    if (m.has_U) t.add(&h->d_U, pub[BN_BUF_CONTROLS], BN_BUF_CONTROLS);
+    for (int q = 0; q < kSlots; ++q) {
+        t.add(&h->d_cost[q], B * K * 4);
+        t.add(&h->d_part[q], B * (size_t)p.nblk * (2 + 2 * T) * 4);
+        t.add(&h->d_state_copy[q], B * 3 * 4);
+    }
+    t.add(&h->d_cost_out, pub[BN_BUF_COSTS], BN_BUF_COSTS);
+    t.add(&h->d_w, pub[BN_BUF_WEIGHTS], BN_BUF_WEIGHTS);
+    t.add(&h->d_ustar, pub[BN_BUF_USTAR_XSTAR], BN_BUF_USTAR_XSTAR);   // U* then X* in ONE block: a caller copies both at once
+    t.add(&h->d_stats, B * 2 * 4);
+    t.add_pinned(&h->h_pinned, B * 3 * 4);
+    t.add(&h->d_flags, ((kSlots + 1) * B + 3) * bn::kFlagStride * sizeof(unsigned long long));      // [kSlots][B] + [B] counters, a spare slot, the device error word
+    t.add(&h->d_mean_snap, B * T * 2 * 4);
+    t.add_pinned(&h->h_err, 64, hipHostMallocMapped);
+    t.add_pinned(&h->h_mail, B * 2 * sizeof(unsigned long long), hipHostMallocMapped);
+    if (m.has_granules)
+        for (int q = 0; q < kSlots; ++q) t.add(&h->d_gran[q], (B * (size_t)p.nblk * (2 + 2 * T) + 4 * B) * sizeof(unsigned long long));   // rows, then 4 per instance for the state
+    if (m.has_alt) {
+        for (int q = 0; q + 1 < m.n_streams; ++q) {
+            if (m.has_X) t.add(&h->d_Xalt[q], pub[BN_BUF_STATES], q ? -1 : BN_BUF_STATES_ALT);
+            if (m.has_U) t.add(&h->d_Ualt[q], pub[BN_BUF_CONTROLS], q ? -1 : BN_BUF_CONTROLS_ALT);
+        }
+        t.add(&h->d_state_snaps, m.snap_cap * B * 3 * 4);      // the journal's state snapshots: only a handle that can overlap ever journals
+        t.add_event(&h->ev_fork, hipEventDisableTiming);
+        for (int q = 0; q < m.n_streams; ++q) t.add_event(&h->ev_guard[q], hipEventDisableTiming);
+        for (int q = 0; q + 1 < m.n_streams; ++q) t.add_event(&h->ev_join[q], hipEventDisableTiming);
+    }
+    if (m.has_slip_std) t.add(&h->d_slip_std, pub[BN_BUF_MAP]);
+    if (m.has_ticket_buffers) {
+        for (int q = 0; q < kSlots; ++q) {
+            t.add(&h->d_ustar2[q], B * T * 2 * 4);
+            t.add(&h->d_stats2[q], B * 2 * 4);
+        }
+        t.add(&h->d_ticket, B * 65 * 4);
+        t.add(&h->d_gpart, B * 64 * (2 + 2 * T) * 4);
+    }
+    t.add_later(&h->d_scratch);
+    t.add_later(&h->d_eps);
+    t.add_later(&h->d_idx);
+}
+
+// The handle's stream (the caller's, or a private one) and the extra streams of overlapped launches.
+static int open_streams(bn_mppi *h)
+{
+    if (!(h->cfg.flags & BN_FLAG_PRIVATE_STREAM)) h->stream = (hipStream_t)h->cfg.stream;          // may be the null stream
+    else if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) == hipSuccess) h->own_stream = true;
+    else return fail(BN_ERR_HIP, "hipStreamCreate failed");
+    for (int q = 0; q + 1 < h->n_streams; ++q)
+        if (hipStreamCreateWithFlags(&h->xstream[q], hipStreamNonBlocking) != hipSuccess)
+            return fail(BN_ERR_HIP, "stream / event creation for overlapped launches failed");
+    return BN_OK;
+}
+
+// General resolution: the in-loop lookups divide with the three-instruction quotient (quotient_general); check it over every
+// float they can see -- ~1e9 values, a millisecond -- before anything relies on it.
+static int check_quotient(bn_mppi *h)
+{
+    bn::SolveParams &p = h->p;
+    if (p.pow2) return BN_OK;
+    int rc = BN_OK;
+    unsigned long long *bad = h->d_flags + ((kSlots + 1) * (size_t)p.B + 1) * bn::kFlagStride;      // the spare counter slot, zero
+    const float d_max = std::max(p.x_hi - p.x0, p.y_hi - p.y0);
+    unsigned long long n_bad = 1;
+    if (!(std::isfinite(d_max) && d_max >= 0.0f) || bn::launch_quotient_check(p.res, p.inv_res, d_max, bad, nullptr) != hipSuccess ||
+        hipMemcpy(&n_bad, bad, sizeof n_bad, hipMemcpyDeviceToHost) != hipSuccess) {
+        (void)hipGetLastError();
+        rc = fail(BN_ERR_HIP, "checking the cell-index quotient for resolution %g failed", (double)p.res);
+    } else if (n_bad != 0) {
+        rc = fail(BN_ERR_INVALID, "resolution %.9g: the correctly rounded three-instruction quotient disagrees with the division for %llu "
+                                  "positions in [0, %g] (no such resolution was known: please report it); use a neighbouring value",
+                  (double)p.res, n_bad, (double)d_max);
+    } else {
+        p.fast_div = 1;
+    }
+    (void)hipMemset(bad, 0, sizeof n_bad);
+    return rc;
+}
+
+// Overlapped launches need an extra stream that DISPATCHES concurrently with the handle's stream.  HIP deals its streams onto a
+// handful of hardware queues in creation order, so which queue a fresh stream lands on depends on how many streams the process
+// has created before: a process that brought up RCCL first got the handle's own queue (15.2 instead of 9.6 us per solve: no
+// overlap at all).  Ask the hardware (launch_queue_probe: can the candidate dispatch while a grid larger than the chip is still
+// being placed on the handle's stream?); a candidate that fails is parked and a fresh stream takes its place.
+static int probe_overlap_streams(bn_mppi *h)
+{
+    if (h->n_streams < 2) return BN_OK;                // (a handle that never overlaps)
+    int rc = BN_OK;
+    int *probe = reinterpret_cast<int *>(h->d_flags + ((kSlots + 1) * (size_t)h->p.B + 1) * bn::kFlagStride);      // the spare counter slot
+    for (int q = 0; rc == BN_OK && q + 1 < h->n_streams; ++q) {
+        bool found = false;
+        for (int attempt = 0; attempt < 8; ++attempt) {
+            int seen = 0;
+            if (hipMemset(probe, 0, 2 * sizeof(int)) != hipSuccess || bn::launch_queue_probe(probe, h->stream, h->xstream[q], h->n_cus) != hipSuccess ||
+                hipStreamSynchronize(h->stream) != hipSuccess || hipStreamSynchronize(h->xstream[q]) != hipSuccess ||
+                hipMemcpy(&seen, probe + 1, sizeof seen, hipMemcpyDeviceToHost) != hipSuccess) {
+                (void)hipGetLastError();
+                rc = fail(BN_ERR_HIP, "probing the streams of overlapped launches failed");
+                break;
+            }
+            if (seen) { found = true; break; }
+            if (attempt == 7) break;                   // (the stream in hand has been probed and failed: do not swap it for an unprobed one)
+            hipStream_t fresh = nullptr;
+            if (hipStreamCreateWithFlags(&fresh, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); break; }
+            h->parked.push_back(h->xstream[q]);        // kept alive until destroy: destroying it would hand its queue slot to the next one
+            h->xstream[q] = fresh;
+        }
+        if (exp_env("BN_DEBUG_CREATE")) std::fprintf(stderr, "[bn_mppi_create] extra stream %d: %s after %zu replacement(s)\n", q, found ? "dispatches concurrently" : "NO concurrent queue found", h->parked.size());
+        // No stream that dispatches concurrently with the handle's: launches of a batch would not overlap, and workgroups waiting
+        // on the device for a predecessor the queue has not started yet would only burn their bounded waits.  One stream then.
+        if (!found && rc == BN_OK) h->overlap_off = true;
+    }
+    (void)hipMemset(probe, 0, 2 * sizeof(int));
+    return rc;
+}
+
+// Plan (mppi_plan.h: every check and decision, no device), open the device, allocate what the plan lists, then the two questions
+// only the device answers: the quotient check and the queue probe.
 int bn_mppi_create(const bn_mppi_config *cfg, bn_mppi_t **out)
 {
     if (!cfg || !out) return fail(BN_ERR_INVALID, "null argument");
     *out = nullptr;
-    if (cfg->struct_size != sizeof(bn_mppi_config))
-        return fail(BN_ERR_INVALID, "bn_mppi_config.struct_size %u != %zu (ABI mismatch)", cfg->struct_size,
-                    sizeof(bn_mppi_config));
-    if (cfg->horizon < 1 || cfg->num_samples < 1 || cfg->num_instances < 1 || cfg->grid_size < 1)
-        return fail(BN_ERR_INVALID, "horizon, num_samples, num_instances and grid_size must be >= 1");
-    if (cfg->num_instances > 32768) return fail(BN_ERR_INVALID, "num_instances must be <= 32768");
-    if ((cfg->flags & BN_FLAG_LEAN) && (cfg->flags & BN_FLAG_SAMPLED_SLIP))
-        return fail(BN_ERR_INVALID, "BN_FLAG_LEAN is not available in sampled-slip mode");
-    if (!(cfg->resolution > 0.0f) || !(cfg->lambda_ > 0.0f) || !(cfg->dt > 0.0f))
-        return fail(BN_ERR_INVALID, "resolution, lambda_ and dt must be positive");
-    for (int d = 0; d < 2; ++d)
-        if (!(cfg->u_min[d] <= cfg->u_max[d]) || !(cfg->sigma[d] >= 0.0f))
-            return fail(BN_ERR_INVALID, "need u_min <= u_max and sigma >= 0");
-    // The default arithmetic carries the heading vector by a small-angle rotation per step (rotate_spec, bn_device_math.h): its
-    // degree-6 polynomials are good to 1e-7 up to 0.5 rad per step (the reference's dt = 0.1, |omega| <= 1 give 0.1), and the
-    // branch-free near form of the heading wrap needs less than pi.  The reference itself has no such bound (transit takes any
-    // delta_t, robot_model.py:60): beyond it the handle takes the reference-order arithmetic -- sincos_spec of every step's heading,
-    // general wrap -- exactly as if BN_FLAG_REFERENCE_ORDER had been given (bn_mppi_arithmetic() tells).
-    const bool big_step = !((double)cfg->dt * std::max(std::fabs((double)cfg->u_min[1]), std::fabs((double)cfg->u_max[1])) <= 0.5);
-    if (big_step && !std::isfinite((double)cfg->dt * ((double)cfg->u_max[1] - (double)cfg->u_min[1])))
-        return fail(BN_ERR_INVALID, "dt and the angular-velocity bounds must be finite");
-    // The kernels share one gather between stage cost t and transit t+1; that needs the upper clamp
-    // to land in the last cell, as it does for every reference GridMap (grid_map.py:42-50).
-    const float span_x = (cfg->x_limits[1] - cfg->x_limits[0]) / cfg->resolution;
-    const float span_y = (cfg->y_limits[1] - cfg->y_limits[0]) / cfg->resolution;
-    if (!(span_x >= (float)(cfg->grid_size - 1)) || !(span_y >= (float)(cfg->grid_size - 1)))
-        return fail(BN_ERR_INVALID, "x/y_limits must span at least grid_size-1 cells of `resolution`");
-
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(BN_ERR_NO_DEVICE, "no HIP device visible: the MPPI planner has no CPU fallback");
-    if (cfg->device_id < 0 || cfg->device_id >= ndev)
-        return fail(BN_ERR_INVALID, "device_id %d out of range (%d devices)", cfg->device_id, ndev);
+    // (the CU count enters the plan; a configuration the plan refuses is refused before the device is looked at, as ever)
+    MppiPlan plan{};
+    if (int rc = plan_mppi(*cfg, 256, &plan)) return rc;
+    if (int rc = bn::open_device(cfg->device_id, table_fail)) return rc;
     DeviceGuard guard(cfg->device_id);
     if (!guard.ok) return fail(BN_ERR_HIP, "hipSetDevice(%d) failed", cfg->device_id);
     hipDeviceProp_t prop;
@@ -433,289 +490,38 @@ int bn_mppi_create(const bn_mppi_config *cfg, bn_mppi_t **out)
     if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
         return fail(BN_ERR_NO_DEVICE, "device %d is %s; this library is built for gfx950 only", cfg->device_id,
                     prop.gcnArchName);
+    if (int rc = plan_mppi(*cfg, prop.multiProcessorCount, &plan)) return rc;
 
     bn_mppi *h = new bn_mppi();
     h->cfg = *cfg;
-    bn::SolveParams &p = h->p;
-    p.K = cfg->num_samples; p.T = cfg->horizon; p.G = cfg->grid_size; p.B = cfg->num_instances;
-    p.nblk = (p.K + bn::kRolloutsPerBlock - 1) / bn::kRolloutsPerBlock;
-    p.Kp = p.nblk * bn::kRolloutsPerBlock;
-    p.res = cfg->resolution; p.inv_res = 1.0f / cfg->resolution;
-    p.pow2 = is_pow2_float(cfg->resolution) ? 1 : 0;
-    p.x0 = cfg->x_limits[0]; p.y0 = cfg->y_limits[0];
-    p.x_hi = cfg->x_limits[1]; p.y_hi = cfg->y_limits[1];
-    p.dt = cfg->dt; p.thr = cfg->stuck_threshold; p.lambda_ = cfg->lambda_;
-    {
-        int e = 0;
-        const float m = std::frexp(cfg->lambda_, &e);                  // lambda_ = m * 2^e, m in [0.5, 1)
-        p.inv_lambda = (m == 0.5f && e > -120 && e < 120) ? std::ldexp(1.0f, 1 - e) : 0.0f;
-    }
-    p.sigma0 = cfg->sigma[0]; p.sigma1 = cfg->sigma[1];
-    p.iv0 = cfg->inv_var[0]; p.iv1 = cfg->inv_var[1];
-    p.umin0 = cfg->u_min[0]; p.umax0 = cfg->u_max[0];
-    p.umin1 = cfg->u_min[1]; p.umax1 = cfg->u_max[1];
-    p.seed = cfg->seed;
-    p.store_u = (cfg->flags & BN_FLAG_STORE_CONTROLS) ? 1 : 0;
-    p.lean = (cfg->flags & BN_FLAG_LEAN) ? 1 : 0;
-    // One-wave kernel, library noise: how much of the horizon the epilogue draws again instead of reading the controls back (see
-    // rollout_wave.inc).  Everything with the trajectory dump (its stores already load the memory system), nothing in lean mode.
-    p.regen_steps = p.T;
-    p.park_steps = bn::kWaveParkSteps;
-    if (const char *e = exp_env("BN_REGEN_STEPS")) p.regen_steps = std::max(0, atoi(e));      // experiments: tools/wave_ab.py
-    if (const char *e = exp_env("BN_PARK_STEPS")) p.park_steps = std::min(std::max(0, atoi(e)), bn::kWaveParkSteps);
-    p.lds_park = 0;                                    // decided below, when the window is known
-    p.ref_order = ((cfg->flags & BN_FLAG_REFERENCE_ORDER) || big_step) ? 1 : 0;
-    p.wrap_near = ((double)cfg->dt * std::max(std::fabs((double)cfg->u_min[1]), std::fabs((double)cfg->u_max[1])) < 3.0) ? 1 : 0;
-    // Workgroup i of a launch runs on XCD i % 8 (observed, used for speed only).  xs = 3 interleaves 8 instances along grid x
-    // so that the workgroups of one instance share an XCD's L2 (rollout_grid); measured SLOWER (64 instances: 29.2 vs 28.1 us,
-    // 60: 28.5 vs 24.9): the dispatcher then fills the CUs unevenly (3 to 5 workgroups per CU instead of 4, tools/block_trace.py)
-    // and a few workgroups wait for a second round.  Default: instance per grid row, workgroups of an instance spread over the XCDs.
-    p.xs = 0;
-    if (const char *e = exp_env("BN_XCD_PACK")) p.xs = (e[0] == '1') ? 3 : 0;      // experiments (tools/r2_measure.py)
-
-    h->n_maps = (cfg->flags & BN_FLAG_SHARED_MAP) ? 1 : p.B;
-    p.map_stride = (h->n_maps == 1) ? 0 : p.G * p.G;
-
-    // Reachable window: |dx| per step <= trav*|v|*dt <= vmax*dt (robot_model.py:82,86-87).
-    const double vmax = std::max(std::fabs((double)cfg->u_min[0]), std::fabs((double)cfg->u_max[0]));
-    const double reach_cells = std::ceil((double)p.T * vmax * (double)cfg->dt / (double)cfg->resolution) + 1.0;
-    p.reach = (int)std::min(reach_cells, (double)p.G);
-    // reach either side of the start cell (reach has a cell to spare), up to the whole map plus the guard row / column at index G
-    // (window_origin_wide).  An odd pitch on purpose: with 2 reach + 2 vertically adjacent cells collided in the LDS banks more
-    // often (K=16384 T=100: 27.4 -> 28.5 us per solve).
-    p.WN = std::min(p.G + 1, 2 * p.reach + 1);
-    const size_t lds_budget = 160 * 1024;
-    // The clamp-free window gather (trav_window) relies on the raw cell of an in-limits position being <= G, the guard row / column:
-    // true for every reference GridMap (limits span exactly G cells, grid_map.py:42-50).  Limits that span MORE cells than the grid
-    // has put raw cells beyond the guard for positions clamped to the upper limit; such a geometry takes the clamped gather from
-    // global memory (the reference's index clamp, grid_map.py:209), like BN_FLAG_NO_LDS_WINDOW.
-    const bool wide_limits = span_x > (float)cfg->grid_size * (1.0f + 1e-6f) || span_y > (float)cfg->grid_size * (1.0f + 1e-6f);
-    if ((cfg->flags & BN_FLAG_NO_LDS_WINDOW) || wide_limits) p.WN = 0;
-    // Slow path: a horizon whose control tile does not fit the role kernels' LDS (MPPI.__init__ takes any horizon, mppi.py:25), or
-    // the reference-order arithmetic in sampled-slip mode (its fused kernel has no such variant).  The one-wave kernel keeps its
-    // controls in HBM and has no tile: rollouts + stand-alone tail, two launches per solve, one stream.  (The reference order by
-    // itself runs on every kernel: rollout_role_ref_*.hip, rollout_wave_ref.hip.)
-    h->slow_path = p.ref_order != 0 && (cfg->flags & BN_FLAG_SAMPLED_SLIP) != 0;
-    if (!h->slow_path) {
-        if (bn::rollout_lds_bytes(p) > lds_budget) p.WN = 0;
-        if (bn::rollout_lds_bytes(p) > lds_budget) { h->slow_path = true; p.WN = wide_limits || (cfg->flags & BN_FLAG_NO_LDS_WINDOW) ? 0 : std::min(p.G + 1, 2 * p.reach + 1); }
-    }
-    // Sampled slip: the tail's optimal rollout stages a (mean, std) window on top of the plain one -- three windows' worth of LDS.  A
-    // reach that fits the rollout kernels (which fall back to the global gather by themselves, sampled_fused) can still be too much
-    // for the tail; then everything gathers from global memory.  (Round 4: tools/fuzz_sweep.py, seed 2327 -- T = 63, 0.1 m cells,
-    // 1 m/s: a 129 x 129 window, 200 KB in the tail, and the launch failed with "invalid argument".)
-    if ((cfg->flags & BN_FLAG_SAMPLED_SLIP) && !h->slow_path && bn::finish_lds_bytes_for(p, true) > lds_budget) p.WN = 0;
-    if (h->slow_path) {
-        const bool sampled = (cfg->flags & BN_FLAG_SAMPLED_SLIP) != 0;
-        if (bn::wave_lds_bytes(p) > lds_budget || (sampled && bn::finish_lds_bytes_for(p, true) > lds_budget)) p.WN = 0;
-        const size_t need = sampled ? sizeof(float) * (4 * (size_t)p.T + 2 * (size_t)p.T * bn::kUPad + 64) : bn::wave_lds_bytes(p);
-        if (need > lds_budget || bn::finish_lds_bytes_for(p, sampled) > lds_budget) {
-            delete h;
-            return fail(BN_ERR_INVALID, "horizon %d needs %zu B of LDS even on the slow path (> 160 KiB)", p.T, std::max(need, bn::finish_lds_bytes_for(p, sampled)));
-        }
-    }
-
-    {
-        const size_t by_lds = lds_budget / std::max<size_t>(bn::rollout_lds_bytes(p), 1);
-        const size_t by_waves = 32 / (bn::kRolloutThreads / 64);
-        h->resident_wgs = std::max<size_t>(1, std::min(by_lds, by_waves)) * (size_t)std::max(prop.multiProcessorCount, 1);
-        h->n_cus = std::max(prop.multiProcessorCount, 1);
-    }
-    int rc = BN_OK;
-    auto alloc = [&](auto **ptr, size_t bytes) {
-        if (rc != BN_OK) return;
-        hipError_t e = hipMalloc((void **)ptr, bytes);
-        if (e == hipSuccess) e = hipMemset(*ptr, 0, bytes);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();       // reported through rc: the sticky error must not surface in the caller's next torch call
-            rc = fail(BN_ERR_HIP, "hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
-        }
-    };
-    const size_t B = p.B, K = p.K, T = p.T, G = p.G;
-    alloc(&h->d_map, (size_t)h->n_maps * G * G * 4);
-    alloc(&h->d_state, B * 3 * 4);
-    alloc(&h->d_goal, B * 2 * 4);
-    alloc(&h->d_mean, B * T * 2 * 4);
-    if (!p.lean) alloc(&h->d_X, B * (T + 1) * 3 * (size_t)p.Kp * 4);      // lean mode never materialises _state_seq_batch
-    alloc(&h->d_mean_used, B * T * 2 * 4);
-    // the throughput kernel keeps its controls in this buffer instead of an LDS tile, requested or not
-    const bool want_wave = !h->slow_path && !(cfg->flags & (BN_FLAG_NO_PIPELINE | BN_FLAG_ROLE_KERNEL | BN_FLAG_SAMPLED_SLIP)) && p.nblk <= 32 &&
-                           ((cfg->flags & BN_FLAG_WAVE_KERNEL) ||
-                            (((size_t)p.B + 1) * (p.nblk + 1) > (size_t)h->n_cus && wave_kernel_is_faster(p, h->resident_wgs, h->n_cus)));
-    if (p.store_u || want_wave || h->slow_path) alloc(&h->d_U, B * T * 2 * (size_t)p.Kp * 4);
-    // one-wave kernel: a second control tile in LDS for the chunk behind the register block, if 16 workgroups per CU still fit
-    if (want_wave && p.park_steps > 0 && p.regen_steps > 0 && p.WN > 0 && !exp_env("BN_NO_LDS_PARK")) {
-        p.lds_park = 1;
-        if (bn::wave_lds_bytes(p) > (size_t)160 * 1024 / 16) p.lds_park = 0;
-    }
-    for (int q = 0; q < kSlots; ++q) {
-        alloc(&h->d_cost[q], B * K * 4);
-        alloc(&h->d_part[q], B * (size_t)p.nblk * (2 + 2 * T) * 4);
-        alloc(&h->d_state_copy[q], B * 3 * 4);
-    }
-    alloc(&h->d_cost_out, B * K * 4);
-    alloc(&h->d_w, B * K * 4);
-    alloc(&h->d_ustar, (B * T * 2 + B * (T + 1) * 3) * 4);   // U* then X* in ONE block (BN_BUF_USTAR_XSTAR): a caller copies both at once
-    if (h->d_ustar) h->d_xstar = h->d_ustar + B * T * 2;
-    alloc(&h->d_stats, B * 2 * 4);
-    if (rc == BN_OK && hipHostMalloc((void **)&h->h_pinned, B * 3 * 4, hipHostMallocDefault) != hipSuccess)
-        rc = fail(BN_ERR_HIP, "hipHostMalloc failed");
+    h->p = plan.p;
+    h->n_cus = plan.n_cus; h->n_maps = plan.n_maps; h->resident_wgs = plan.resident_wgs;
+    h->slow_path = plan.slow_path; h->pipelined = plan.pipelined; h->wave_kernel = plan.wave_kernel; h->lat_kernel = plan.lat_kernel;
+    h->role_overlap = plan.role_overlap; h->ticket_overlap = plan.ticket_overlap; h->ticket_mode = plan.ticket_mode;
+    h->n_streams = plan.n_streams; h->snap_cap = plan.snap_cap;
+    std::copy(plan.buffer_bytes, plan.buffer_bytes + BN_BUF_COUNT_, h->plan_bytes);
+    register_buffers(h, plan);
+    int rc = h->bufs.alloc_all(table_fail);
+    if (rc == BN_OK && (hipHostGetDevicePointer((void **)&h->d_err, h->h_err, 0) != hipSuccess ||
+                        hipHostGetDevicePointer((void **)&h->d_mail, h->h_mail, 0) != hipSuccess))
+        rc = table_fail(BN_ERR_HIP, "hipHostGetDevicePointer failed");
+    if (rc == BN_OK) rc = open_streams(h);
     if (rc == BN_OK) {
-        if (!(cfg->flags & BN_FLAG_PRIVATE_STREAM)) {
-            h->stream = (hipStream_t)cfg->stream;          // may be the null stream
-        } else if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) == hipSuccess) {
-            h->own_stream = true;
-        } else {
-            rc = fail(BN_ERR_HIP, "hipStreamCreate failed");
-        }
-    }
-    if (rc != BN_OK) {
-        bn_mppi_destroy(h);
-        return rc;
-    }
-    p.map = h->d_map; p.state = h->d_state; p.goal = h->d_goal; p.mean = h->d_mean; p.eps = nullptr;
-    p.X = h->d_X; p.U = h->d_U; p.cost = h->d_cost[0]; p.part = h->d_part[0]; p.w = h->d_w;
-    p.state_copy = h->d_state_copy[0]; p.cost_out = h->d_cost_out;
-    p.ustar = h->d_ustar; p.xstar = h->d_xstar; p.stats = h->d_stats; p.mean_used = h->d_mean_used;
-    // every rollout workgroup re-merges the previous solve's nblk partials: only worth it while they are few
-    p.slip_on = (cfg->flags & BN_FLAG_SAMPLED_SLIP) ? 1 : 0;
-    // (the fused sampled-slip kernel has its own, larger LDS layout: what an overlapped batch may count on being resident -- the
-    // residency rules of bn_mppi_solve_n_async -- is that kernel's figure, not the role kernel's)
-    if (p.slip_on && bn::sampled_fused(p)) h->resident_wgs = bn::sampled_resident_per_cu(p) * (size_t)h->n_cus;
-    h->pipelined = !h->slow_path && !(cfg->flags & BN_FLAG_NO_PIPELINE) && p.nblk <= kPipelinedMaxBlocks && !p.slip_on;
-    // throughput kernel: launches with more workgroups than the role kernel keeps resident in one round (4 per CU)
-    h->wave_kernel = h->pipelined && want_wave;
-    // latency variant: every workgroup (rollouts + aux) alone on a CU -- with room left for one instance of an overlapped successor
-    // (15 instances of K=1024 fill 255 of 256 CUs: 15.3 us per launch against the role kernel's 13.9; 14 instances 13.1 against
-    // 13.9) --, its LDS layout must fit, not forced elsewhere
-    h->lat_kernel = h->pipelined && !h->wave_kernel && !(cfg->flags & BN_FLAG_ROLE_KERNEL) && bn::lat_lds_bytes(p) > 0 &&
-                    ((cfg->flags & BN_FLAG_LAT_KERNEL) || ((size_t)p.B + 1) * (p.nblk + 1) <= (size_t)std::max(prop.multiProcessorCount, 1));
-    if (const char *e = exp_env("BN_LAT_KERNEL")) h->lat_kernel = h->lat_kernel && e[0] != '0';      // experiments
-    alloc(&h->d_flags, ((kSlots + 1) * B + 3) * bn::kFlagStride * sizeof(unsigned long long));      // [kSlots][B] + [B] counters, a spare slot, the device error word
-    alloc(&h->d_mean_snap, B * T * 2 * 4);
-    // (the journal's state snapshots, d_state_snaps, are allocated below, and only for a handle that can overlap at all)
-    if (rc == BN_OK) {
-        if (hipHostMalloc((void **)&h->h_err, 64, hipHostMallocMapped) != hipSuccess) rc = fail(BN_ERR_HIP, "hipHostMalloc (error word) failed");
-        else if (hipHostGetDevicePointer((void **)&h->d_err, h->h_err, 0) != hipSuccess) rc = fail(BN_ERR_HIP, "hipHostGetDevicePointer failed");
-        else *h->h_err = 0;
-    }
-    if (rc == BN_OK) {
-        if (hipHostMalloc((void **)&h->h_mail, B * 2 * sizeof(unsigned long long), hipHostMallocMapped) != hipSuccess ||
-            hipHostGetDevicePointer((void **)&h->d_mail, h->h_mail, 0) != hipSuccess) rc = fail(BN_ERR_HIP, "hipHostMalloc (first-action mailbox) failed");
-        else std::memset(h->h_mail, 0, B * 2 * sizeof(unsigned long long));
-    }
-    p.mail = h->d_mail;
-    if (h->lat_kernel && p.nblk <= 16 && 2 * p.T <= bn::kRolloutThreads && !exp_env("BN_NO_GRANULES"))
-        for (int q = 0; q < kSlots; ++q) alloc(&h->d_gran[q], (B * (size_t)p.nblk * (2 + 2 * T) + 4 * B) * sizeof(unsigned long long));   // rows, then 4 per instance for the state
-    // the role kernel (launches that do not leave every workgroup a CU of its own) overlaps its launches as well: a workgroup of
-    // the next solve takes the slot a finished one frees and waits there for ITS instance's previous solve only
-    h->role_overlap = h->pipelined && !h->lat_kernel && !(cfg->flags & BN_FLAG_NO_OVERLAP);
-    if (const char *e = exp_env("BN_ROLE_OVERLAP")) h->role_overlap = h->role_overlap && e[0] != '0';   // experiments
-    // the deterministic kernel's ticket path (K > 4096: one launch per solve, merge by the last workgroup) overlaps its launches as well
-    const bool ticket_det = !h->slow_path && !p.slip_on && !h->pipelined && !(cfg->flags & BN_FLAG_NO_PIPELINE) && p.nblk <= 1024 &&
-                            bn::finish_lds_bytes(p) + 256 <= bn::rollout_lds_bytes(p);
-    h->ticket_overlap = (ticket_det || (!(cfg->flags & BN_FLAG_NO_PIPELINE) && bn::sampled_fused(p))) && !(cfg->flags & BN_FLAG_NO_OVERLAP) &&
-                        !exp_env("BN_NO_TICKET_OVERLAP");
-    const bool may_overlap = (h->lat_kernel || h->role_overlap || h->ticket_overlap) && !(cfg->flags & BN_FLAG_NO_OVERLAP);
-    if (may_overlap) {
-        // Two launches in flight.  Measured with three (role kernel, 64 instances): 23.3 instead of 22.6 us per launch; with
-        // four the launches starve each other of slots (waits expire).  The slot / buffer arithmetic below holds for up to kMaxStreams.
-        h->n_streams = 2;
-        if (const char *e = exp_env("BN_OVERLAP_STREAMS")) h->n_streams = std::min(std::max(std::atoi(e), 2), kMaxStreams);   // experiments
-        for (int q = 0; q + 1 < h->n_streams; ++q) {
-            if (h->d_X) alloc(&h->d_Xalt[q], B * (T + 1) * 3 * (size_t)p.Kp * 4);
-            if (h->d_U) alloc(&h->d_Ualt[q], B * T * 2 * (size_t)p.Kp * 4);
-        }
-        // the journal's state snapshots: only a handle that can overlap ever journals (up to 16 MB per handle otherwise,
-        // times the planners of a K-sharded or per-instance set-up).  At most 16 MB; B <= 341 get the journal's own 4096 entries.
-        h->snap_cap = std::max<size_t>(64, std::min<size_t>(4096, ((size_t)16 << 20) / ((size_t)B * 12)));
-        alloc(&h->d_state_snaps, h->snap_cap * B * 3 * 4);
-    }
-    if (rc == BN_OK && may_overlap) {
-        bool ok = hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) == hipSuccess;
-        for (int q = 0; ok && q < h->n_streams; ++q) ok = hipEventCreateWithFlags(&h->ev_guard[q], hipEventDisableTiming) == hipSuccess;
-        for (int q = 0; ok && q + 1 < h->n_streams; ++q)
-            ok = hipStreamCreateWithFlags(&h->xstream[q], hipStreamNonBlocking) == hipSuccess &&
-                 hipEventCreateWithFlags(&h->ev_join[q], hipEventDisableTiming) == hipSuccess;
-        if (!ok) rc = fail(BN_ERR_HIP, "stream / event creation for overlapped launches failed");
-    }
-    // (late allocations also go through `alloc`: a failure anywhere destroys the handle and everything it owns)
-    if (p.slip_on) {
-        alloc(&h->d_slip_std, (size_t)h->n_maps * p.G * p.G * 4);
-        p.slip_std = h->d_slip_std;
-        for (int q = 0; q < kSlots; ++q) {
-            alloc(&h->d_ustar2[q], (size_t)p.B * p.T * 2 * 4);
-            alloc(&h->d_stats2[q], (size_t)p.B * 2 * 4);
-        }
-        alloc(&h->d_ticket, (size_t)p.B * 65 * 4);
-        alloc(&h->d_gpart, (size_t)p.B * 64 * (2 + 2 * p.T) * 4);
-        p.ticket = h->d_ticket; p.gpart = h->d_gpart;
-        h->ticket_mode = !h->slow_path && !(cfg->flags & BN_FLAG_NO_PIPELINE) && bn::sampled_fused(p);
-    } else if (ticket_det) {
-        // K > 4096: too many partials for every workgroup to re-merge; the last workgroup of a launch merges them
-        for (int q = 0; q < kSlots; ++q) {
-            alloc(&h->d_ustar2[q], (size_t)p.B * p.T * 2 * 4);
-            alloc(&h->d_stats2[q], (size_t)p.B * 2 * 4);
-        }
-        alloc(&h->d_ticket, (size_t)p.B * 65 * 4);
-        alloc(&h->d_gpart, (size_t)p.B * 64 * (2 + 2 * p.T) * 4);
-        p.gpart = h->d_gpart;
-        h->ticket_mode = true;             // p.ticket stays null in h->p: only the one-launch path selects the ticket kernel
-    }
-    if (rc == BN_OK && !p.pow2) {
-        // general resolution: the in-loop lookups divide with the three-instruction quotient (quotient_general); check it over every
-        // float they can see -- ~1e9 values, a millisecond -- before anything relies on it
-        unsigned long long *bad = h->d_flags + ((kSlots + 1) * B + 1) * bn::kFlagStride;      // the spare counter slot, zero
-        const float d_max = std::max(p.x_hi - p.x0, p.y_hi - p.y0);
-        unsigned long long n_bad = 1;
-        if (!(std::isfinite(d_max) && d_max >= 0.0f) || bn::launch_quotient_check(p.res, p.inv_res, d_max, bad, nullptr) != hipSuccess ||
-            hipMemcpy(&n_bad, bad, sizeof n_bad, hipMemcpyDeviceToHost) != hipSuccess) {
-            (void)hipGetLastError();
-            rc = fail(BN_ERR_HIP, "checking the cell-index quotient for resolution %g failed", (double)p.res);
-        } else if (n_bad != 0) {
-            rc = fail(BN_ERR_INVALID, "resolution %.9g: the correctly rounded three-instruction quotient disagrees with the division for %llu "
-                                      "positions in [0, %g] (no such resolution was known: please report it); use a neighbouring value",
-                      (double)p.res, n_bad, (double)d_max);
-        } else {
-            p.fast_div = 1;
-        }
-        (void)hipMemset(bad, 0, sizeof n_bad);
+        bn::SolveParams &p = h->p;
+        h->d_xstar = h->d_ustar + (size_t)p.B * p.T * 2;
+        p.map = h->d_map; p.state = h->d_state; p.goal = h->d_goal; p.mean = h->d_mean; p.eps = nullptr;
+        p.X = h->d_X; p.U = h->d_U; p.cost = h->d_cost[0]; p.part = h->d_part[0]; p.w = h->d_w;
+        p.state_copy = h->d_state_copy[0]; p.cost_out = h->d_cost_out;
+        p.ustar = h->d_ustar; p.xstar = h->d_xstar; p.stats = h->d_stats; p.mean_used = h->d_mean_used;
+        p.mail = h->d_mail;
+        p.slip_std = h->d_slip_std; p.gpart = h->d_gpart;
+        if (p.slip_on) p.ticket = h->d_ticket;         // (p.ticket stays null in the deterministic kernel's h->p: only the one-launch path selects the ticket kernel)
+        rc = check_quotient(h);
     }
     if (rc == BN_OK && hipDeviceSynchronize() != hipSuccess) rc = fail(BN_ERR_HIP, "hipDeviceSynchronize failed after allocation");
-    // Overlapped launches need an extra stream that DISPATCHES concurrently with the handle's stream.  HIP deals its streams onto a
-    // handful of hardware queues in creation order, so which queue a fresh stream lands on depends on how many streams the process
-    // has created before: a process that brought up RCCL first got the handle's own queue (15.2 instead of 9.6 us per solve: no
-    // overlap at all).  Ask the hardware (launch_queue_probe: can the candidate dispatch while a grid larger than the chip is still
-    // being placed on the handle's stream?); a candidate that fails is parked and a fresh stream takes its place.
-    if (rc == BN_OK && may_overlap) {
-        int *probe = reinterpret_cast<int *>(h->d_flags + ((kSlots + 1) * B + 1) * bn::kFlagStride);      // the spare counter slot
-        for (int q = 0; rc == BN_OK && q + 1 < h->n_streams; ++q) {
-            bool found = false;
-            for (int attempt = 0; attempt < 8; ++attempt) {
-                int seen = 0;
-                if (hipMemset(probe, 0, 2 * sizeof(int)) != hipSuccess || bn::launch_queue_probe(probe, h->stream, h->xstream[q], h->n_cus) != hipSuccess ||
-                    hipStreamSynchronize(h->stream) != hipSuccess || hipStreamSynchronize(h->xstream[q]) != hipSuccess ||
-                    hipMemcpy(&seen, probe + 1, sizeof seen, hipMemcpyDeviceToHost) != hipSuccess) {
-                    (void)hipGetLastError();
-                    rc = fail(BN_ERR_HIP, "probing the streams of overlapped launches failed");
-                    break;
-                }
-                if (seen) { found = true; break; }
-                if (attempt == 7) break;                   // (the stream in hand has been probed and failed: do not swap it for an unprobed one)
-                hipStream_t fresh = nullptr;
-                if (hipStreamCreateWithFlags(&fresh, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); break; }
-                h->parked.push_back(h->xstream[q]);        // kept alive until destroy: destroying it would hand its queue slot to the next one
-                h->xstream[q] = fresh;
-            }
-            if (exp_env("BN_DEBUG_CREATE")) std::fprintf(stderr, "[bn_mppi_create] extra stream %d: %s after %zu replacement(s)\n", q, found ? "dispatches concurrently" : "NO concurrent queue found", h->parked.size());
-            // No stream that dispatches concurrently with the handle's: launches of a batch would not overlap, and workgroups waiting
-            // on the device for a predecessor the queue has not started yet would only burn their bounded waits.  One stream then.
-            if (!found && rc == BN_OK) h->overlap_off = true;
-        }
-        (void)hipMemset(probe, 0, 2 * sizeof(int));
-    }
+    if (rc == BN_OK) rc = probe_overlap_streams(h);
     // Host-paced loop (BN_FLAG_HOST_PACED): a second private stream that dispatches concurrently with the first, the request words, events
-    if (rc == BN_OK) rc = paced_setup(h, may_overlap);
+    if (rc == BN_OK) rc = paced_setup(h, plan.may_overlap);
     if (rc != BN_OK) {
         bn_mppi_destroy(h);
         return rc;
@@ -746,39 +552,15 @@ void bn_mppi_destroy(bn_mppi_t *h)
     if (h->shard_comm || h->shard_prepared) shard_comm_release(h);
     env_release(h);
     loops_release(h);
-    // what bn_mppi_create and the solve path allocate
-    void *bufs[] = {h->d_map, h->d_state, h->d_goal, h->d_mean, h->d_eps, h->d_X, h->d_U, h->d_cost_out,
-                    h->d_w, h->d_ustar /* d_xstar lives in the same block */, h->d_stats, h->d_scratch, h->d_idx, h->d_slip_std,
-                    h->d_ticket, h->d_gpart, h->d_mean_used};
-    for (void *b : bufs)
-        if (b) (void)hipFree(b);
-    if (h->d_flags) (void)hipFree(h->d_flags);
-    for (int q = 0; q < kSlots; ++q) {
-        if (h->d_ustar2[q]) (void)hipFree(h->d_ustar2[q]);
-        if (h->d_stats2[q]) (void)hipFree(h->d_stats2[q]);
-        if (h->d_gran[q]) (void)hipFree(h->d_gran[q]);
-        if (h->d_cost[q]) (void)hipFree(h->d_cost[q]);
-        if (h->d_part[q]) (void)hipFree(h->d_part[q]);
-        if (h->d_state_copy[q]) (void)hipFree(h->d_state_copy[q]);
-    }
-    for (int q = 0; q < kMaxStreams - 1; ++q) {
-        if (h->d_Xalt[q]) (void)hipFree(h->d_Xalt[q]);
-        if (h->d_Ualt[q]) (void)hipFree(h->d_Ualt[q]);
-        if (h->xstream[q]) { (void)hipStreamSynchronize(h->xstream[q]); (void)hipStreamDestroy(h->xstream[q]); }
-        if (h->ev_join[q]) (void)hipEventDestroy(h->ev_join[q]);
-    }
-    for (hipStream_t ps : h->parked) (void)hipStreamDestroy(ps);
-    if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
-    for (hipEvent_t e : h->ev_guard) if (e) (void)hipEventDestroy(e);
-    if (h->h_pinned) (void)hipHostFree(h->h_pinned);
-    if (h->h_err) (void)hipHostFree(h->h_err);
-    if (h->h_mail) (void)hipHostFree(h->h_mail);
     paced_release(h);
-    if (h->d_mean_snap) (void)hipFree(h->d_mean_snap);
-    if (h->d_state_snaps) (void)hipFree(h->d_state_snaps);
+    h->bufs.free_all();                                // what bn_mppi_create and the solve path allocated
+    for (hipStream_t &xs : h->xstream)
+        if (xs) { (void)hipStreamSynchronize(xs); (void)hipStreamDestroy(xs); }
+    for (hipStream_t ps : h->parked) (void)hipStreamDestroy(ps);
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
 }
+
 
 int bn_mppi_set_map(bn_mppi_t *h, int32_t instance, const float *risk, bn_mem_kind where)
 {
@@ -937,9 +719,9 @@ int solve_impl(bn_mppi_t *h, const float *states, bn_mem_kind states_where, cons
     case BN_NOISE_HOST_KT2: {
         const size_t bytes = B * K * T * 2 * 4;
         if (bytes > h->eps_bytes) {
-            if (h->d_eps) BN_HIP(hipFree(h->d_eps));
-            h->d_eps = nullptr; h->eps_bytes = 0;
-            BN_HIP(hipMalloc((void **)&h->d_eps, bytes));
+            h->eps_bytes = 0;
+            if (int rc = h->bufs.resize(&h->d_eps, bytes, table_fail)) return rc;
+            if (int rc = fills_done()) return rc;
             h->eps_bytes = bytes;
         }
         BN_HIP(hipMemcpyAsync(h->d_eps, eps, bytes, hipMemcpyHostToDevice, h->stream));

@@ -37,9 +37,8 @@ namespace host {
 
 void env_release(bn_mppi *h)
 {
-    void *bufs[] = {h->d_lat_mean, h->d_lat_std, h->d_ep_states, h->d_ep_reward, h->d_env_state, h->d_ep_done, h->d_ep_action};
-    for (void *b : bufs)
-        if (b) (void)hipFree(b);
+    h->env_bufs.free_all();
+    h->ep_bufs.free_all();
 }
 
 }  // namespace host
@@ -57,11 +56,18 @@ int bn_mppi_env_attach(bn_mppi_t *h, const float *latent_mean, const float *late
     if (int rc = flush_tail(h)) return rc;
     BN_HIP(hipStreamSynchronize(h->stream));
     const size_t bytes = (size_t)h->n_maps * h->p.G * h->p.G * 4;
-    if (!h->d_lat_mean) {
-        BN_HIP(hipMalloc((void **)&h->d_lat_mean, bytes));
-        BN_HIP(hipMalloc((void **)&h->d_lat_std, bytes));
-        BN_HIP(hipMalloc((void **)&h->d_env_state, (size_t)h->p.B * 3 * 4));
-        BN_HIP(hipMalloc((void **)&h->d_ep_done, (size_t)h->p.B * sizeof(int)));
+    if (h->env_bufs.list.empty()) {                    // the environment's group, built by the first attach; the episode log grows on demand
+        h->env_bufs.add(&h->d_lat_mean, bytes);
+        h->env_bufs.add(&h->d_lat_std, bytes);
+        h->env_bufs.add(&h->d_env_state, (size_t)h->p.B * 3 * 4);
+        h->env_bufs.add(&h->d_ep_done, (size_t)h->p.B * sizeof(int));
+        h->ep_bufs.add_later(&h->d_ep_states);
+        h->ep_bufs.add_later(&h->d_ep_reward);
+        h->ep_bufs.add_later(&h->d_ep_action);
+    }
+    if (!h->env_bufs.live) {
+        if (int rc = h->env_bufs.ensure(table_fail)) return rc;
+        if (int rc = fills_done()) return rc;
     }
     const hipMemcpyKind kind = where == BN_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     BN_HIP(hipMemcpy(h->d_lat_mean, latent_mean, bytes, kind));
@@ -131,13 +137,11 @@ int bn_mppi_episode_async(bn_mppi_t *h, int32_t n_steps, const float *states0, b
     const size_t B = h->p.B;
     if (n_steps > h->ep_steps) {
         BN_HIP(hipStreamSynchronize(h->stream));
-        if (h->d_ep_states) BN_HIP(hipFree(h->d_ep_states));
-        if (h->d_ep_reward) BN_HIP(hipFree(h->d_ep_reward));
-        if (h->d_ep_action) BN_HIP(hipFree(h->d_ep_action));
-        h->d_ep_states = h->d_ep_reward = h->d_ep_action = nullptr;
-        BN_HIP(hipMalloc((void **)&h->d_ep_states, (size_t)(n_steps + 1) * B * 3 * 4));
-        BN_HIP(hipMalloc((void **)&h->d_ep_reward, (size_t)n_steps * B * 4));
-        BN_HIP(hipMalloc((void **)&h->d_ep_action, (size_t)n_steps * B * 2 * 4));
+        h->ep_steps = 0;
+        if (int rc = h->ep_bufs.resize(&h->d_ep_states, (size_t)(n_steps + 1) * B * 3 * 4, table_fail)) return rc;
+        if (int rc = h->ep_bufs.resize(&h->d_ep_reward, (size_t)n_steps * B * 4, table_fail)) return rc;
+        if (int rc = h->ep_bufs.resize(&h->d_ep_action, (size_t)n_steps * B * 2 * 4, table_fail)) return rc;
+        if (int rc = fills_done()) return rc;
         h->ep_steps = n_steps;
     }
     h->p.ep_states = h->d_ep_states; h->p.ep_reward = h->d_ep_reward; h->p.ep_action = h->d_ep_action;

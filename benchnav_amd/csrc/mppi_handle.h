@@ -1,5 +1,7 @@
-// mppi_handle.h -- the planner handle behind bn_mppi_t and what the host files of the C ABI share (mppi_capi.cpp, mppi_paced.cpp,
-// mppi_shard.cpp, mppi_env.cpp, mppi_loops.cpp, mppi_query.cpp).  Private, host only, not installed.
+// mppi_handle.h -- the planner handle behind bn_mppi_t and what the host files of the C ABI share (mppi_capi.cpp, mppi_plan.cpp,
+// mppi_paced.cpp, mppi_shard.cpp, mppi_env.cpp, mppi_loops.cpp, mppi_query.cpp): the constants of the launch policy, the handle with
+// its buffer tables (bn_host.h), the functions more than one file calls, the HIP check and the tables' fail adapter, the device
+// binding of an entry point, and the request words of the host-paced loop.  Private, host only, not installed.
 #pragma once
 #include "../../include/benchnav_mppi.h"
 #include "mppi_kernels.h"
@@ -198,6 +200,11 @@ struct bn_mppi {
     bn_clrrt_t *cl_planner = nullptr;       // ... with this CL-RRT handle: the episode's goals, streams and paths live in it
     size_t scratch_bytes = 0, eps_bytes = 0, idx_count = 0;
     float *h_pinned = nullptr;   // pinned staging for (B,3) states
+    // Who owns all of the above (bn_host.h): `bufs` is what bn_mppi_create allocates from its plan, plus d_scratch, d_eps and d_idx,
+    // which grow on demand; the others are the groups a concern builds on first use and its *_release frees.  Streams are not in
+    // any table.
+    bn::DeviceBuffers bufs, env_bufs, ep_bufs, ad_bufs, cl_bufs, shard_bufs, paced_bufs;
+    size_t plan_bytes[BN_BUF_COUNT_] = {};   // MppiPlan::buffer_bytes: what bn_mppi_device_buffer reports for a buffer this handle does not have
     // profiling
     std::vector<hipEvent_t> ev;  // two-launch mode: 3 events per solve (start, after rollout, after finish);
     size_t ev_used = 0;          // pipelined mode: one event at the start of every group of kProfGroup launches
@@ -212,7 +219,6 @@ namespace host __attribute__((visibility("hidden"))) {
 extern std::mutex g_overlap_mu;
 extern std::map<int, std::vector<bn_mppi *>> g_handles;
 int fail(int code, const char *fmt, ...);
-size_t buffer_bytes(const bn_mppi *h, bn_buffer_id id);
 int ensure_scratch(bn_mppi *h, size_t bytes);
 int flush_tail(bn_mppi *h, float *out_copy = nullptr);
 int check_instance(const bn_mppi *h, int32_t instance, bool allow_all);
@@ -245,6 +251,21 @@ void loops_release(bn_mppi *h);                     // mppi_loops.cpp
     } while (0)
 
 namespace {
+
+// What the buffer tables report through (bn_host.h).  The sticky HIP error is taken here: reported through the return code, it must
+// not surface in the caller's next torch call.
+static inline int table_fail(int code, const std::string &msg)
+{
+    if (code == BN_ERR_HIP) (void)hipGetLastError();
+    return bn::host::fail(code, "%s", msg.c_str());
+}
+
+// After a group was built or a buffer grew outside bn_mppi_create: the tables' zero fills run on the null stream, and a private
+// handle stream is not ordered behind that one (seen: a fill landing on top of what the handle's stream had just written).
+static inline int fills_done()
+{
+    return hipStreamSynchronize(nullptr) == hipSuccess ? BN_OK : table_fail(BN_ERR_HIP, "hipStreamSynchronize failed behind an allocation");
+}
 
 // Every entry point works on the handle's device and leaves the calling thread's current device as it found it
 // (one process may drive several GPUs; torch tracks its own notion of the current device).

@@ -15,12 +15,8 @@ namespace host {
 
 void loops_release(bn_mppi *h)
 {
-    void *bufs[] = {h->d_ad_i, h->d_ad_state, h->d_ad_log, h->d_cl_rover, h->d_cl_flags, h->d_cl_goal, h->d_cl_log};
-    for (void *b : bufs)
-        if (b) (void)hipFree(b);
-    if (h->h_cl_pending) (void)hipHostFree(h->h_cl_pending);
-    for (hipEvent_t e : h->cl_ev)
-        if (e) (void)hipEventDestroy(e);
+    h->ad_bufs.free_all();
+    h->cl_bufs.free_all();
 }
 
 }  // namespace host
@@ -34,9 +30,14 @@ extern "C" {
 static int astar_dwa_clear(bn_mppi *h)
 {
     const size_t B = h->p.B;
-    if (!h->d_ad_i) {
-        BN_HIP(hipMalloc((void **)&h->d_ad_i, (4 * B + 1) * sizeof(int32_t)));
-        BN_HIP(hipMalloc((void **)&h->d_ad_state, B * 3 * sizeof(float)));
+    if (h->ad_bufs.list.empty()) {
+        h->ad_bufs.add(&h->d_ad_i, (4 * B + 1) * sizeof(int32_t));
+        h->ad_bufs.add(&h->d_ad_state, B * 3 * sizeof(float));
+        h->ad_bufs.add_later(&h->d_ad_log);            // grows with the longest episode (ad_cap)
+    }
+    if (!h->ad_bufs.live) {
+        if (int rc = h->ad_bufs.ensure(table_fail)) return rc;
+        if (int rc = fills_done()) return rc;
     }
     BN_HIP(hipMemsetAsync(h->d_ad_i, 0xff, B * sizeof(int32_t), h->stream));
     BN_HIP(hipMemsetAsync(h->d_ad_i + B, 0, B * sizeof(int32_t), h->stream));
@@ -104,9 +105,9 @@ int bn_astar_dwa_episode_async(bn_mppi_t *h, bn_astar_t *a, int32_t n_steps, con
         if (int rc = astar_dwa_clear(h)) return rc;
     if (n_steps > h->ad_cap) {
         BN_HIP(hipStreamSynchronize(h->stream));       // the log of the previous call may still be written
-        if (h->d_ad_log) BN_HIP(hipFree(h->d_ad_log));
-        h->d_ad_log = nullptr;
-        BN_HIP(hipMalloc((void **)&h->d_ad_log, ((n + 1) * 3 + n * 5) * B * sizeof(float)));
+        h->ad_cap = 0;
+        if (int rc = h->ad_bufs.resize(&h->d_ad_log, ((n + 1) * 3 + n * 5) * B * sizeof(float), table_fail)) return rc;
+        if (int rc = fills_done()) return rc;
         h->ad_cap = n_steps;
     }
     const hipMemcpyKind kind = where == BN_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
@@ -212,14 +213,16 @@ int bn_clrrt_loop_reset(bn_mppi_t *h, bn_clrrt_t *c, const float *goal_nodes, co
     if (int rc = settle_point(h)) return rc;
     if (int rc = flush_tail(h)) return rc;
     const size_t B = h->p.B;
-    if (!h->d_cl_rover) {
-        BN_HIP(hipMalloc((void **)&h->d_cl_rover, B * sizeof(bn::ClrrtRover)));
-        BN_HIP(hipMalloc((void **)&h->d_cl_flags, (B + 1) * sizeof(int32_t)));
-        BN_HIP(hipMalloc((void **)&h->d_cl_goal, B * 3 * sizeof(float)));
-        BN_HIP(hipHostMalloc((void **)&h->h_cl_pending, sizeof(int32_t), hipHostMallocDefault));
-        BN_HIP(hipEventCreate(&h->cl_ev[0]));
-        BN_HIP(hipEventCreate(&h->cl_ev[1]));
+    if (h->cl_bufs.list.empty()) {
+        h->cl_bufs.add(&h->d_cl_rover, B * sizeof(bn::ClrrtRover));
+        h->cl_bufs.add(&h->d_cl_flags, (B + 1) * sizeof(int32_t));
+        h->cl_bufs.add(&h->d_cl_goal, B * 3 * sizeof(float));
+        h->cl_bufs.add_pinned(&h->h_cl_pending, sizeof(int32_t));
+        h->cl_bufs.add_event(&h->cl_ev[0]);
+        h->cl_bufs.add_event(&h->cl_ev[1]);
+        h->cl_bufs.add_later(&h->d_cl_log);            // grows with the longest run (cl_cap)
     }
+    if (int rc = h->cl_bufs.ensure(table_fail)) return rc;
     BN_HIP(hipStreamSynchronize(h->stream));                               // a previous episode's launches are done with the words below
     std::vector<bn::ClrrtRover> r0(B, bn::ClrrtRover{0, BN_CL_RUNNING, 1, 0, 0, 0, 0, -1});
     BN_HIP(hipMemcpy(h->d_cl_rover, r0.data(), B * sizeof(bn::ClrrtRover), hipMemcpyHostToDevice));
@@ -262,9 +265,9 @@ int bn_clrrt_loop_run(bn_mppi_t *h, bn_clrrt_t *c, int32_t n, float *states_devi
     const size_t B = h->p.B, N = (size_t)n;
     if (n > h->cl_cap) {
         BN_HIP(hipStreamSynchronize(h->stream));
-        if (h->d_cl_log) BN_HIP(hipFree(h->d_cl_log));
-        h->d_cl_log = nullptr;
-        BN_HIP(hipMalloc((void **)&h->d_cl_log, ((N + 1) * 3 + N * 6) * B * sizeof(float)));
+        h->cl_cap = 0;
+        if (int rc = h->cl_bufs.resize(&h->d_cl_log, ((N + 1) * 3 + N * 6) * B * sizeof(float), table_fail)) return rc;
+        if (int rc = fills_done()) return rc;
         h->cl_cap = n;
     }
     const size_t cap = (size_t)h->cl_cap;

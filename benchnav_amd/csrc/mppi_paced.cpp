@@ -149,20 +149,12 @@ int paced_setup(bn_mppi *h, bool may_overlap)
         (void)hipMemset(probe, 0, 2 * sizeof(int));
         if (ok && found) {
             const size_t words = (size_t)kSlots * 8 + 16;      // request slots | [0] spare, [1..4] acknowledgements, [7] create's echo | [8..11] "gave up" per slot
-            ok = hipHostMalloc((void **)&h->h_req, words * sizeof(unsigned long long), hipHostMallocMapped) == hipSuccess &&
-                 hipHostGetDevicePointer((void **)&h->d_req, h->h_req, 0) == hipSuccess;
-            if (ok) std::memset(h->h_req, 0, words * sizeof(unsigned long long));
-            {
-                const size_t bytes = (size_t)kSlots * 8 * sizeof(unsigned long long);
-                hipError_t e = hipMalloc((void **)&h->d_req_dev, bytes);
-                if (e == hipSuccess) e = hipMemset(h->d_req_dev, 0, bytes);
-                if (e != hipSuccess) {
-                    (void)hipGetLastError();
-                    rc = fail(BN_ERR_HIP, "hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
-                }
-            }
-            for (int q = 0; ok && q < 2; ++q) ok = hipEventCreateWithFlags(&h->hp_ev[q], hipEventDisableTiming) == hipSuccess;
-            if (ok && rc == BN_OK) {
+            h->paced_bufs.add_pinned(&h->h_req, words * sizeof(unsigned long long), hipHostMallocMapped);
+            h->paced_bufs.add(&h->d_req_dev, (size_t)kSlots * 8 * sizeof(unsigned long long));
+            for (int q = 0; q < 2; ++q) h->paced_bufs.add_event(&h->hp_ev[q], hipEventDisableTiming);
+            rc = h->paced_bufs.alloc_all(table_fail);
+            ok = rc == BN_OK && fills_done() == BN_OK && hipHostGetDevicePointer((void **)&h->d_req, h->h_req, 0) == hipSuccess;
+            if (ok) {
                 h->hp_stream[0] = h->xstream[0]; h->hp_stream[1] = h->xstream[1];
                 h->hp_enabled = true;
                 // request words in device memory the host can write (see bar_alloc) -- taken only if a kernel reads back what the CPU wrote
@@ -192,10 +184,8 @@ int paced_setup(bn_mppi *h, bool may_overlap)
 
 void paced_release(bn_mppi *h)
 {
-    if (h->h_req) (void)hipHostFree(h->h_req);
+    h->paced_bufs.free_all();
     if (h->req_bar) bar_free(h->req_bar);
-    if (h->d_req_dev) (void)hipFree(h->d_req_dev);
-    for (hipEvent_t e : h->hp_ev) if (e) (void)hipEventDestroy(e);
 }
 
 }  // namespace host

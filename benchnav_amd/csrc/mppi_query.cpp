@@ -162,9 +162,9 @@ int bn_mppi_get_top_samples(bn_mppi_t *h, int32_t instance, int32_t n, float *st
     std::partial_sort(idx.begin(), idx.begin() + n, idx.end(),
                       [&](int a, int b) { return w[a] > w[b] || (w[a] == w[b] && a < b); });
     if ((size_t)n > h->idx_count) {
-        if (h->d_idx) BN_HIP(hipFree(h->d_idx));
-        h->d_idx = nullptr; h->idx_count = 0;
-        BN_HIP(hipMalloc((void **)&h->d_idx, (size_t)n * sizeof(int)));
+        h->idx_count = 0;
+        if (int rc = h->bufs.resize(&h->d_idx, (size_t)n * sizeof(int), table_fail)) return rc;
+        if (int rc = fills_done()) return rc;
         h->idx_count = n;
     }
     if (int rc = ensure_scratch(h, (size_t)n * T1 * 3 * 4)) return rc;
@@ -187,12 +187,16 @@ int bn_mppi_device_buffer(bn_mppi_t *h, bn_buffer_id id, void **device_ptr, size
         BN_BIND(h);
         if (int rc = flush_tail(h)) return rc;
     }
-    void *ptrs[BN_BUF_COUNT_] = {h->d_X, h->d_w, h->d_cost_out, h->d_U, h->d_ustar, h->d_xstar, h->d_mean, h->d_map, h->d_goal, h->d_ustar,
-                                 h->d_Xalt[0], h->d_Ualt[0]};
     if ((int)id < 0 || id >= BN_BUF_COUNT_) return fail(BN_ERR_INVALID, "unknown buffer id %d", (int)id);
-    *device_ptr = ptrs[id];
-    if (bytes) *bytes = buffer_bytes(h, id);
-    if (!ptrs[id]) return fail(BN_ERR_STATE, "buffer %d is not allocated in this configuration", (int)id);
+    // The handle's table answers by id; U* and X* are the two halves of the one BN_BUF_USTAR_XSTAR block.  The size is the plan's,
+    // which the table was filled from -- also for a buffer this configuration does not have.
+    void *ptr = nullptr;
+    size_t block = 0;
+    h->bufs.find(id == BN_BUF_USTAR || id == BN_BUF_XSTAR ? BN_BUF_USTAR_XSTAR : id, &ptr, &block);
+    if (ptr && id == BN_BUF_XSTAR) ptr = h->d_xstar;
+    *device_ptr = ptr;
+    if (bytes) *bytes = h->plan_bytes[id];
+    if (!ptr) return fail(BN_ERR_STATE, "buffer %d is not allocated in this configuration", (int)id);
     return BN_OK;
 }
 

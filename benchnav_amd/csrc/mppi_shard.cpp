@@ -104,12 +104,8 @@ void shard_comm_release(bn_mppi *h)
     if (h->shard_comm) { if (const RcclApi *r = rccl_api()) (void)r->comm_destroy(static_cast<ncclComm_t>(h->shard_comm)); }
     h->shard_comm = nullptr;
     h->shard_prepared = false;
-    if (h->d_gathered) (void)hipFree(h->d_gathered);
-    if (h->d_shard_merged) (void)hipFree(h->d_shard_merged);
-    h->d_gathered = h->d_shard_merged = nullptr;
-    if (h->ev_shard_merge) (void)hipEventDestroy(h->ev_shard_merge);
-    for (hipEvent_t &e : h->ev_shard_tail) { if (e) (void)hipEventDestroy(e); e = nullptr; }
-    h->ev_shard_merge = nullptr;
+    h->shard_bufs.free_all();
+    h->shard_bufs.list.clear();                        // (the next prepare may be for another world size)
     if (h->shard_side_own && h->shard_side) (void)hipStreamDestroy(h->shard_side);
     h->shard_side = nullptr;
 }
@@ -151,21 +147,17 @@ int bn_mppi_shard_comm_prepare(bn_mppi_t *h, int32_t world_size, int32_t rank)
     if (!r) return fail(BN_ERR_HIP, "librccl.so could not be opened: %s", dlerror());
     BN_BIND(h);
     if (int rc = settle_point(h)) return rc;
-    const size_t bytes = (size_t)world_size * h->p.nblk * (2 + 2 * (size_t)h->p.T) * sizeof(float);
-    if (hipMalloc((void **)&h->d_gathered, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        h->d_gathered = nullptr;
-        return fail(BN_ERR_HIP, "hipMalloc of %zu B for the gathered partials failed", bytes);
-    }
+    // [ kSlots merged rows | 64 group rows | ticket ]
+    const size_t merged_floats = kSlots * (2 * (size_t)h->p.T + 2) + 64 * (2 + 2 * (size_t)h->p.T) + 4;
+    h->shard_bufs.add(&h->d_gathered, (size_t)world_size * h->p.nblk * (2 + 2 * (size_t)h->p.T) * sizeof(float));
+    h->shard_bufs.add(&h->d_shard_merged, merged_floats * sizeof(float));
+    h->shard_bufs.add_event(&h->ev_shard_merge, hipEventDisableTiming);
+    for (int q = 0; q < kSlots; ++q) h->shard_bufs.add_event(&h->ev_shard_tail[q], hipEventDisableTiming);
+    if (int rc = h->shard_bufs.alloc_all(table_fail)) { h->shard_bufs.list.clear(); return rc; }
     h->shard_world = world_size;
     h->shard_rank = rank;
     // the side stream of the tail: the handle's second stream if it has one (overlapped batches), else one of its own
-    // [ kSlots merged rows | 64 group rows | ticket ]
-    const size_t merged_floats = kSlots * (2 * (size_t)h->p.T + 2) + 64 * (2 + 2 * (size_t)h->p.T) + 4;
-    bool ok = hipMalloc((void **)&h->d_shard_merged, merged_floats * sizeof(float)) == hipSuccess &&
-              hipMemset(h->d_shard_merged, 0, merged_floats * sizeof(float)) == hipSuccess &&
-              hipEventCreateWithFlags(&h->ev_shard_merge, hipEventDisableTiming) == hipSuccess;
-    for (int q = 0; ok && q < kSlots; ++q) ok = hipEventCreateWithFlags(&h->ev_shard_tail[q], hipEventDisableTiming) == hipSuccess;
+    bool ok = fills_done() == BN_OK;
     if (ok && h->n_streams > 1 && h->xstream[0]) h->shard_side = h->xstream[0];
     else if (ok) { ok = hipStreamCreateWithFlags(&h->shard_side, hipStreamNonBlocking) == hipSuccess; h->shard_side_own = ok; }
     if (!ok) { (void)hipGetLastError(); shard_comm_release(h); return fail(BN_ERR_HIP, "stream / event / buffer creation for the sharded solve failed"); }

@@ -411,6 +411,25 @@ int bn_mppi_debug_expire_wait(bn_mppi_t *h);
 /* Test hook (BN_FLAG_HOST_PACED): how many looks of ~2 us a prelaunched solve waits for its state before it gives up (default 25000), and
  * whether bn_mppi_forward_state_async posts the state without checking that the launch is still waiting. */
 int bn_mppi_debug_host_paced(bn_mppi_t *h, int32_t polls, int32_t post_unchecked);
+/* Test hook: what bn_mppi_create would decide for `cfg` on a device of `n_cus` compute units -- the derived kernel parameters, the
+ * launch policy, which conditional buffer groups exist, and what bn_mppi_device_buffer would report per bn_buffer_id -- without
+ * touching a device.  Set out->struct_size first.  Returns what bn_mppi_create returns for a configuration it refuses. */
+typedef struct bn_mppi_plan_info {
+    uint32_t struct_size;
+    int32_t n_cus;
+    int32_t nblk, Kp, pow2, reach, WN, lds_park, ref_order, wrap_near, regen_steps, park_steps, xs, map_stride, slip_on;
+    float inv_lambda;
+    int32_t n_maps, slow_path, want_wave, pipelined, wave_kernel, lat_kernel, role_overlap, ticket_det, ticket_overlap, ticket_mode,
+        may_overlap, n_streams;
+    /* the conditional buffer groups: the trajectory batch (not in lean mode) | the control batch (requested, or where the one-wave
+     * kernel keeps its controls) | granule copies of the partial rows (latency kernel, K <= 1024) | second trajectory / control
+     * buffers, the journal's snapshots and the events of handles that may overlap | ticket-merge outputs, counters, group rows */
+    int32_t has_X, has_U, has_granules, has_alt, has_ticket_buffers, has_slip_std;
+    uint64_t snap_cap, resident_wgs;
+    uint64_t buffer_bytes[12];   /* by bn_buffer_id; 0: CONTROLS and the *_ALT buffers where this configuration has none (STATES keeps
+                                    its size in lean mode: what the batch would take) */
+} bn_mppi_plan_info;
+int bn_mppi_debug_plan(const bn_mppi_config *cfg, int32_t n_cus, bn_mppi_plan_info *out);
 /* Enqueue the pending tail (if any) without waiting.  An expiry that has already been flagged is repaired here (that does wait). */
 int bn_mppi_flush(bn_mppi_t *h);
 
