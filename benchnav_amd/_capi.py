@@ -72,6 +72,15 @@ class PlanInfo(C.Structure):
                 + [("snap_cap", C.c_uint64), ("resident_wgs", C.c_uint64), ("buffer_bytes", C.c_uint64 * 12)])
 
 
+class LaunchRecord(C.Structure):
+    """bn_mppi_launch_record: one launch of the solve path as it was decided (bn_mppi_debug_launch_log)."""
+    _fields_ = ([(n, C.c_int32) for n in ("call", "entry", "family", "eps_mode", "stream", "have_prev", "mean_from_part", "self_tail", "overlap",
+                                          "cur_slot", "prev_slot", "wave_kernel", "lat_kernel", "aux_prio", "tail_merged", "closed_loop", "env_on",
+                                          "ep_index", "state_inline", "host_paced", "x_buf", "u_buf", "flag_part", "flag_tail", "gran", "gran_prev",
+                                          "mean_snap", "state_snap", "err", "err_dev", "out_copy_self", "env_z", "part_gathered")]
+                + [(n, C.c_uint64) for n in ("solve", "tail_solve", "wait_part", "wait_tail", "wait_part_self", "wait_tail_self")])
+
+
 class RRTConfig(C.Structure):
     _fields_ = [
         ("struct_size", C.c_uint32), ("device_id", C.c_int32), ("num_instances", C.c_int32), ("max_iterations", C.c_int32),
@@ -136,6 +145,7 @@ SYMBOLS = {
     "bn_mppi_flush": (C.c_int, [_H]),
     "bn_mppi_debug_host_paced": (C.c_int, [_H, C.c_int32, C.c_int32]),
     "bn_mppi_debug_plan": (C.c_int, [C.POINTER(Config), C.c_int32, C.POINTER(PlanInfo)]),
+    "bn_mppi_debug_launch_log": (C.c_int, [_H, C.POINTER(LaunchRecord), C.c_int32]),
     "bn_mppi_get_weights": (C.c_int, [_H, C.c_int32, _FP]),
     "bn_mppi_get_costs": (C.c_int, [_H, C.c_int32, _FP]),
     "bn_mppi_get_states": (C.c_int, [_H, C.c_int32, _FP]),

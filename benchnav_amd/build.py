@@ -11,7 +11,7 @@ LIB_DIR = os.path.join(_PKG, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libbenchnav_mppi.so")
 # the host side of the MPPI C ABI, one file per concern behind csrc/mppi_handle.h.  tools/build_variant*.py rebuild ALL of them with
 # their flags: the experiment switches (exp_env) are compiled into every one
-HOST_SOURCES = ["mppi_capi.cpp", "mppi_plan.cpp", "mppi_paced.cpp", "mppi_shard.cpp", "mppi_env.cpp", "mppi_loops.cpp", "mppi_query.cpp"]
+HOST_SOURCES = ["mppi_capi.cpp", "mppi_plan.cpp", "mppi_solve.cpp", "mppi_paced.cpp", "mppi_shard.cpp", "mppi_env.cpp", "mppi_loops.cpp", "mppi_query.cpp"]
 # one translation unit per kernel family: they compile in parallel (the role kernel alone is 72 template instances)
 SOURCES = ["rollout_role_philox.hip", "rollout_role_kt2.hip", "rollout_role_t2k.hip", "rollout_role_ref_philox.hip", "rollout_role_ref_kt2.hip", "rollout_role_ref_t2k.hip", "rollout_wave.hip", "rollout_wave_ref.hip", "rollout_sampled.hip",
            "rollout_lat_host.hip", "rollout_lat_host_ref.hip",

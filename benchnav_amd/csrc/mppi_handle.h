@@ -1,5 +1,5 @@
 // mppi_handle.h -- the planner handle behind bn_mppi_t and what the host files of the C ABI share (mppi_capi.cpp, mppi_plan.cpp,
-// mppi_paced.cpp, mppi_shard.cpp, mppi_env.cpp, mppi_loops.cpp, mppi_query.cpp): the constants of the launch policy, the handle with
+// mppi_solve.cpp, mppi_paced.cpp, mppi_shard.cpp, mppi_env.cpp, mppi_loops.cpp, mppi_query.cpp): the constants of the launch policy, the handle with
 // its buffer tables (bn_host.h), the functions more than one file calls, the HIP check and the tables' fail adapter, the device
 // binding of an entry point, and the request words of the host-paced loop.  Private, host only, not installed.
 #pragma once
@@ -7,6 +7,7 @@
 #include "mppi_kernels.h"
 #include "bn_host.h"
 
+#include <atomic>
 #include <chrono>
 #include <cstdint>
 #include <cstdlib>
@@ -36,6 +37,7 @@ constexpr int kEagerTailMinBatch = 16;    // overlapped batches of at least this
 constexpr int kMaxStreams = 3;            // launches of one overlapped batch in flight at most
 constexpr int kSlots = kMaxStreams + 1;   // per-solve buffer slots (see bn_mppi::d_cost)
 constexpr size_t kJournalCap = 4096;
+constexpr size_t kLaunchLogCap = 256;     // bn_mppi_debug_launch_log keeps the latest this many launches
 
 }  // namespace
 
@@ -82,7 +84,7 @@ struct bn_mppi {
     std::vector<hipStream_t> parked;            // streams that turned out to share the handle's hardware queue (see bn_mppi_create)
     hipEvent_t ev_fork = nullptr, ev_join[kMaxStreams - 1] = {};
     hipEvent_t ev_guard[kMaxStreams] = {};      // recorded on this handle's streams BY another handle that must run behind this one's overlapped batch
-    unsigned long long *d_flags = nullptr;      // [kSlots][B] flag_part per slot and instance, [B] flag_tail per instance, then int err
+    unsigned long long *d_flags = nullptr;      // [kSlots][B] flag_part per slot and instance, [B] flag_tail per instance, then int err (accessors: mppi_launch.h)
     bool role_overlap = false;                  // the role kernel's launches of a batch may overlap too (see bn_mppi_solve_n_async)
     unsigned long long *d_gran[kSlots] = {};   // granule copies of the partial rows per slot (K <= 1024, 2T <= 320)
     // Second trajectory / control buffers for overlapped batches.  Two launches in flight must not write the same addresses: whose
@@ -205,6 +207,10 @@ struct bn_mppi {
     // any table.
     bn::DeviceBuffers bufs, env_bufs, ep_bufs, ad_bufs, cl_bufs, shard_bufs, paced_bufs;
     size_t plan_bytes[BN_BUF_COUNT_] = {};   // MppiPlan::buffer_bytes: what bn_mppi_device_buffer reports for a buffer this handle does not have
+    // launch log (bn_mppi_debug_launch_log): a ring of kLaunchLogCap records, allocated when recording is turned on
+    bool log_on = false;
+    std::vector<bn_mppi_launch_record> launch_log;
+    uint64_t log_head = 0, log_read = 0;        // records made / handed out so far
     // profiling
     std::vector<hipEvent_t> ev;  // two-launch mode: 3 events per solve (start, after rollout, after finish);
     size_t ev_used = 0;          // pipelined mode: one event at the start of every group of kProfGroup launches
@@ -218,6 +224,8 @@ namespace host __attribute__((visibility("hidden"))) {
 // mppi_capi.cpp
 extern std::mutex g_overlap_mu;
 extern std::map<int, std::vector<bn_mppi *>> g_handles;
+extern std::map<int, bn_mppi *> g_overlap_owner;
+extern std::atomic<int> g_overlap_owners;
 int fail(int code, const char *fmt, ...);
 int ensure_scratch(bn_mppi *h, size_t bytes);
 int flush_tail(bn_mppi *h, float *out_copy = nullptr);
@@ -227,9 +235,10 @@ void journal_push(bn_mppi *h, bn_mppi::BatchRec r, bool replayable);
 int self_check(bn_mppi *h);
 int settle_point(bn_mppi *h);
 void tune_record(bn_mppi *h, int mode, double us);
+// mppi_solve.cpp.  solve_impl: `q` = the stream (and trajectory buffer) of a member of an overlapped batch, 0 = the handle's
 int guard_foreign_overlap(bn_mppi *h);
 int solve_impl(bn_mppi_t *h, const float *states, bn_mem_kind states_where, const float *eps, bn_noise_kind noise,
-               bool shard_rollout, bool overlap = false, hipStream_t on_stream = nullptr, int alt_buffers = 0, bool self_tail = false);
+               bool shard_rollout, bool overlap = false, int q = 0, bool self_tail = false);
 // each concern frees what it allocates (bn_mppi_destroy calls them); paced_setup is bn_mppi_create's host-paced part
 int paced_setup(bn_mppi *h, bool may_overlap);      // mppi_paced.cpp
 void paced_release(bn_mppi *h);
@@ -308,7 +317,9 @@ static inline bool hp_gave_up(const bn_mppi *h, uint32_t tag)
 }
 
 // A launch that still waits for its state is told to leave -- it has touched nothing but its own LDS -- and the host's bookkeeping
-// goes back to where it was before the prelaunch.  No synchronisation: the launch ends by itself within a poll.
+// goes back to where it was before the prelaunch: exactly what hp_prelaunch (mppi_paced.cpp) advanced through advance_mirrors
+// (mppi_launch.h) -- nblk published into the solve's slot, one tail -- and the solve counter.  No synchronisation: the launch ends by
+// itself within a poll.
 static inline void hp_cancel(bn_mppi *h)
 {
     if (!h->hp_armed) return;

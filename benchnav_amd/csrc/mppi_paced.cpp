@@ -1,7 +1,8 @@
 // mppi_paced.cpp -- the host-paced loop of the C ABI (BN_FLAG_HOST_PACED) and MPPI.forward as one call: the request words the host
 // writes into device memory (HSA-runtime loader, PCIe-BAR allocator), prelaunch / post / redo, bn_mppi_forward_async,
-// bn_mppi_forward_state_async, bn_mppi_first_action and the loop's test hooks.  The solve itself is solve_impl (mppi_capi.cpp).
-#include "mppi_handle.h"
+// bn_mppi_forward_state_async, bn_mppi_first_action and the loop's test hooks.  The solve itself is solve_impl (mppi_solve.cpp); the
+// prelaunch is decided and applied like every launch of the solve path (mppi_launch.h).
+#include "mppi_launch.h"
 
 #include <chrono>
 #include <cstdio>
@@ -121,7 +122,6 @@ int paced_setup(bn_mppi *h, bool may_overlap)
 {
     const bn_mppi_config *cfg = &h->cfg;
     bn::SolveParams &p = h->p;
-    const size_t B = p.B;
     int rc = BN_OK;
     if ((cfg->flags & BN_FLAG_HOST_PACED) && p.B == 1 && h->lat_kernel && h->d_gran[0] && may_overlap && !h->overlap_off &&
         h->n_streams > 1 && h->xstream[0] && !p.slip_on && !(cfg->flags & (BN_FLAG_NO_PIPELINE | BN_FLAG_PROFILE))) {
@@ -130,7 +130,7 @@ int paced_setup(bn_mppi *h, bool may_overlap)
             q.spec_extra = h->hp_extra;
             if (bn::lat_lds_bytes(q) == 0) h->hp_extra = 0;        // no room for the wider window: every state but the previous one stages again
         }
-        int *probe = reinterpret_cast<int *>(h->d_flags + ((kSlots + 1) * B + 1) * bn::kFlagStride);      // the spare counter slot
+        int *probe = reinterpret_cast<int *>(spare_counter(h));
         bool found = false, ok = hipStreamCreateWithFlags(&h->xstream[1], hipStreamNonBlocking) == hipSuccess;
         for (int attempt = 0; ok && attempt < 8 && !found; ++attempt) {
             int seen = 0;
@@ -209,6 +209,60 @@ extern "C" void bn_mppi_debug_hp_clock(void)
 #define BN_HP_TICK(i) do { } while (0)
 #endif
 
+// Not beside another handle's launches (the latency kernel is sized for a device it has to itself: see g_handles).
+static bool other_handles_idle(bn_mppi *h)
+{
+    std::lock_guard<std::mutex> lock(g_overlap_mu);
+    for (bn_mppi *o : g_handles[h->cfg.device_id]) {
+        if (o == h) continue;
+        for (int q = 0; q < kMaxStreams; ++q) {
+            const hipStream_t os = q ? o->xstream[q - 1] : o->stream;
+            if ((q && !os) || os == h->stream) continue;
+            if (hipStreamQuery(os) != hipSuccess) { (void)hipGetLastError(); return false; }
+        }
+    }
+    (void)hipGetLastError();
+    return true;
+}
+
+// The slot's previous user -- the launch four tags back -- must have taken (or given up on) its request before the words are
+// written again: its tail workgroup says so.  In a loop paced by bn_mppi_first_action that was three solves ago; a caller that
+// fires forwards back to back is held to the device's pace here (bounded: a launch gives up by itself after ~50 ms).
+static bool hp_slot_released(const bn_mppi *h, uint32_t tag, int slot)
+{
+    if (tag <= (uint32_t)kSlots) return true;
+    const unsigned long long *ack = h->h_req + (size_t)kSlots * 8 + 1 + slot;
+    const auto t0 = std::chrono::steady_clock::now();
+    for (long it = 0; __atomic_load_n(ack, __ATOMIC_ACQUIRE) != (unsigned long long)(tag - kSlots); ++it)
+        if ((it & 0x3ff) == 0x3ff && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) return false;
+    return true;
+}
+
+// The prelaunch: the latency kernel as the only member of a batch that always waits -- for its predecessor's rows and for the host --
+// with its own tail in the launch, on the other trajectory buffer and the next private stream.
+static LaunchDecision decide_prelaunch(const bn_mppi *h, LaunchDecision d)
+{
+    bn_mppi_launch_record &r = d.r;
+    r.call = kCallPrelaunch;
+    r.tail_solve = r.solve;
+    r.mean_from_part = 1;                              // (have_prev = 0) the mean IS the merge of the previous solve's rows (its tail writes the same values)
+    r.lat_kernel = 1;
+    r.flag_tail = r.flag_part = r.err = r.err_dev = 1;
+    r.cur_slot = d.cur; r.prev_slot = d.prev;
+    r.wait_part = h->pub[d.prev];
+    r.gran = h->d_gran[d.cur] ? 1 : 0; r.gran_prev = h->d_gran[d.prev] ? 1 : 0;
+    r.overlap = 1;
+    d.publish = (unsigned long long)h->p.nblk;
+    carry_own_tail(h, d);
+    const int xi = 1 - h->x_idx;                       // the other trajectory / control buffer: two launches in flight never write the same addresses
+    r.x_buf = (xi && h->d_Xalt[0]) ? 1 : 0;
+    r.u_buf = !h->p.store_u ? -1 : ((xi && h->d_Ualt[0]) ? 1 : (h->p.U ? 0 : -1));
+    r.host_paced = 1;
+    r.stream = 1 + h->hp_next_q;
+    r.entry = h->p.ref_order ? kRolloutLatHostRef : kRolloutLatHost;
+    return d;
+}
+
 // Host-paced loop: enqueue the launch of the solve AFTER the latest one, on a private stream; it waits on the device for its state.
 // Best effort: returns false (and leaves nothing behind) when the handle's state does not allow it.
 static bool hp_prelaunch(bn_mppi *h)
@@ -217,56 +271,19 @@ static bool hp_prelaunch(bn_mppi *h)
         !h->map_set || !h->goal_set || h->solves == 0)
         return false;
     std::chrono::steady_clock::time_point bn_t_pre = std::chrono::steady_clock::now(); (void)bn_t_pre;
-    {   // not beside another handle's launches (the latency kernel is sized for a device it has to itself: see g_handles)
-        std::lock_guard<std::mutex> lock(g_overlap_mu);
-        for (bn_mppi *o : g_handles[h->cfg.device_id]) {
-            if (o == h) continue;
-            for (int q = 0; q < kMaxStreams; ++q) {
-                const hipStream_t os = q ? o->xstream[q - 1] : o->stream;
-                if ((q && !os) || os == h->stream) continue;
-                if (hipStreamQuery(os) != hipSuccess) { (void)hipGetLastError(); return false; }
-            }
-        }
-        (void)hipGetLastError();
-    }
+    if (!other_handles_idle(h)) return false;
     bn::SolveParams p = h->p;
-    const size_t B = 1;
-    const int cur3 = (int)(h->solves % kSlots), prev3 = (int)((h->solves + kSlots - 1) % kSlots);
-    p.solve = h->solves; p.tail_solve = p.solve;
-    p.part = h->d_part[cur3]; p.cost = h->d_cost[cur3]; p.state_copy = h->d_state_copy[cur3];
-    p.part_prev = h->d_part[prev3]; p.cost_prev = h->d_cost[prev3]; p.state_prev = h->d_state_copy[prev3];
-    p.have_prev = 0; p.mean_from_part = 1;             // the mean IS the merge of the previous solve's rows (its tail writes the same values)
-    p.lat_kernel = 1; p.wave_kernel = 0;
-    p.flag_tail = h->d_flags + kSlots * B * bn::kFlagStride;
-    p.flag_part = h->d_flags;
-    p.err = h->d_err; p.err_dev = reinterpret_cast<int *>(h->d_flags + ((kSlots + 1) * B + 2) * bn::kFlagStride);
-    p.cur_slot = cur3; p.prev_slot = prev3;
-    p.wait_part = h->pub[prev3];
-    p.gran = h->d_gran[cur3]; p.gran_prev = h->d_gran[prev3];
-    p.overlap = 1;
-    p.self_tail = 1;
-    p.wait_part_self = h->pub[cur3] + (unsigned long long)p.nblk;
-    p.wait_tail_self = h->tails;
-    const int xi = 1 - h->x_idx;                       // the other trajectory / control buffer: two launches in flight never write the same addresses
-    if (xi && h->d_Xalt[0]) p.X = h->d_Xalt[0];
-    if (!p.store_u) p.U = nullptr;
-    else if (xi && h->d_Ualt[0]) p.U = h->d_Ualt[0];
-    p.host_paced = 1;
+    LaunchDecision d;
+    rotate_slots(h, p, d);
+    d = decide_prelaunch(h, d);
+    fill_params(h, p, d);
     if (exp_env("BN_NO_EARLY_MAIL")) p.no_early_mail = 1;      // (experiment builds)
     p.sv0 = h->hp_prev_state[0]; p.sv1 = h->hp_prev_state[1]; p.sv2 = h->hp_prev_state[2];
     p.spec_extra = h->hp_extra;
     const uint32_t tag = h->hp_seq + 1;
     const int slot = (int)(tag % kSlots);
     static_assert(kSlots == 4, "the kernels acknowledge a request in word 1 + (tag & 3)");
-    if (tag > (uint32_t)kSlots) {
-        // The slot's previous user -- the launch four tags back -- must have taken (or given up on) its request before the words are
-        // written again: its tail workgroup says so.  In a loop paced by bn_mppi_first_action that was three solves ago; a caller that
-        // fires forwards back to back is held to the device's pace here (bounded: a launch gives up by itself after ~50 ms).
-        const unsigned long long *ack = h->h_req + (size_t)kSlots * 8 + 1 + slot;
-        const auto t0 = std::chrono::steady_clock::now();
-        for (long it = 0; __atomic_load_n(ack, __ATOMIC_ACQUIRE) != (unsigned long long)(tag - kSlots); ++it)
-            if ((it & 0x3ff) == 0x3ff && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) { h->hp_enabled = false; return false; }
-    }
+    if (!hp_slot_released(h, tag, slot)) { h->hp_enabled = false; return false; }
     h->hp_seq = tag;
     p.req_tag = tag;
     p.req_direct = h->req_bar ? 1 : 0;
@@ -281,14 +298,14 @@ static bool hp_prelaunch(bn_mppi *h)
 #ifdef BN_TIMING
     g_hpc[2].ns += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - bn_t_pre).count(); g_hpc[2].n += 1;
 #endif
+    log_launch(h, d.r);
     hipError_t e;
     // (the completion event goes out with the launch: one runtime call)
-    { BN_HP_TICK(3); e = p.ref_order ? bn::launch_rollout_lat_host_ref(p, h->hp_stream[q], h->hp_ev[q]) : bn::launch_rollout_lat_host(p, h->hp_stream[q], h->hp_ev[q]); }
+    { BN_HP_TICK(3); e = d.r.entry == kRolloutLatHostRef ? bn::launch_rollout_lat_host_ref(p, h->hp_stream[q], h->hp_ev[q]) : bn::launch_rollout_lat_host(p, h->hp_stream[q], h->hp_ev[q]); }
     if (e != hipSuccess) { (void)hipGetLastError(); h->hp_enabled = false; return false; }
-    h->pub[cur3] += (unsigned long long)p.nblk;
-    h->tails += 1;
+    advance_mirrors(h, d);                             // (hp_cancel takes these back: nblk published, one tail, one solve)
     h->solves += 1;
-    h->hp_armed = true; h->hp_tag = tag; h->hp_slot = slot; h->hp_q = q; h->hp_xidx = xi;
+    h->hp_armed = true; h->hp_tag = tag; h->hp_slot = slot; h->hp_q = q; h->hp_xidx = 1 - h->x_idx;
     h->hp_armed_at = std::chrono::steady_clock::now();
     h->hp_next_q = 1 - q;
     return true;
@@ -343,7 +360,7 @@ static int forward_impl(bn_mppi_t *h, const float *states_device, const float *s
         (hp_gave_up(h, h->hp_tag) || std::chrono::steady_clock::now() - h->hp_armed_at > std::chrono::milliseconds(20))) hp_cancel(h);
     if (paced && h->hp_armed) {                        // the loop's steady state: the launch is there and waits for exactly this
         BN_BIND_Q(h);
-        if (int rc = self_check(h)) return rc;
+        if (int rc = self_check(h)) return rc;         // (ADVICE: resets pub[] / tails while the armed launch's advance_mirrors still stands; settle_point cancels first)
         const int q_posted = h->hp_q;
         if (int rc = hp_post(h, state_host, out_device)) return rc;
         (void)hp_prelaunch(h);                         // ... and the next one goes out while this one runs
@@ -361,7 +378,7 @@ static int forward_impl(bn_mppi_t *h, const float *states_device, const float *s
     const bool by_value = state_host && h->p.B == 1 && h->lat_kernel && !h->self_off && !h->tail_pending && !(h->cfg.flags & BN_FLAG_NO_PIPELINE);
     h->inline_state = by_value ? state_host : nullptr;
     const float *st = by_value ? h->d_state : (state_host ? state_host : states_device);
-    const int rc0 = solve_impl(h, st, (state_host && !by_value) ? BN_MEM_HOST : BN_MEM_DEVICE, eps_device, noise, false, false, nullptr, 0, true);
+    const int rc0 = solve_impl(h, st, (state_host && !by_value) ? BN_MEM_HOST : BN_MEM_DEVICE, eps_device, noise, false, false, 0, true);
     h->self_out_copy = nullptr;
     h->inline_state = nullptr;
     if (rc0) return rc0;

@@ -430,6 +430,29 @@ typedef struct bn_mppi_plan_info {
                                     its size in lean mode: what the batch would take) */
 } bn_mppi_plan_info;
 int bn_mppi_debug_plan(const bn_mppi_config *cfg, int32_t n_cus, bn_mppi_plan_info *out);
+/* Test hook: what the solve path decided for every kernel launch it made -- the launch decision of csrc/mppi_launch.h as plain
+ * numbers, buffers by identity, never an address and nothing that is the machine's answer and not the policy's.  A call with
+ * out == NULL turns recording on and clears the log; every later call copies out, oldest first, the records made since the previous
+ * call (at most `cap`) and returns how many.  The log is a ring of 256 records: the oldest are overwritten.  While recording is off
+ * (every handle starts that way) a launch pays one predictable branch. */
+typedef struct bn_mppi_launch_record {
+    int32_t call;        /* who launched: 0 a solve (bn_mppi_solve*, forward), 1 a member of an overlapped batch, 2 a stand-alone tail
+                            (flush), 3 a host-paced prelaunch, 4 the rollouts of a K-sharded solve */
+    int32_t entry;       /* 0 launch_rollout  1 launch_rollout_lat_self  2 launch_rollout_lat_host  3 launch_rollout_lat_host_ref
+                            4 launch_rollout_sampled  5 launch_finish */
+    int32_t family;      /* entry 0: 0 role kernel, 1 one-wave kernel, 2 latency kernel; else 0 */
+    int32_t eps_mode;    /* 0 Philox, 1 (K,T,2), 2 (T,2,K) */
+    int32_t stream;      /* 0 the handle's stream, 1 / 2 its extra (host-paced: private) streams */
+    int32_t have_prev, mean_from_part, self_tail, overlap, cur_slot, prev_slot;
+    int32_t wave_kernel, lat_kernel, aux_prio, tail_merged, closed_loop, env_on, ep_index, state_inline, host_paced;
+    int32_t x_buf;       /* trajectories: 0 the exposed buffer (or none: lean mode), 1 / 2 the alternates */
+    int32_t u_buf;       /* controls: -1 none, 0 the exposed buffer, 1 / 2 the alternates */
+    int32_t flag_part, flag_tail, gran, gran_prev, mean_snap, state_snap, err, err_dev, out_copy_self, env_z;   /* the pointer is set */
+    int32_t part_gathered;   /* the partial rows go straight into the gathered rows of a K-sharded solve */
+    uint64_t solve, tail_solve, wait_part, wait_tail, wait_part_self, wait_tail_self;   /* as in the kernel arguments; solve is 0 in the
+                                                                                           record of a stand-alone tail */
+} bn_mppi_launch_record;
+int bn_mppi_debug_launch_log(bn_mppi_t *h, bn_mppi_launch_record *out, int32_t cap);
 /* Enqueue the pending tail (if any) without waiting.  An expiry that has already been flagged is repaired here (that does wait). */
 int bn_mppi_flush(bn_mppi_t *h);
 

@@ -2,7 +2,7 @@
 three timed batches of NB.  Prints the per-launch time and bn_mppi_recovery_count() of every handle.  With even NW / NB the first solve
 of a batch used to land on the handle's internal stream, whose queue wakes up later than the handle's own: solve 1 overtook solve 0, its
 waiting workgroups crowded solve 0 out and the bounded waits expired -- 3-7 recoveries per 18 handles (round 3 and early round 4), none
-with odd lengths.  Since the fix (big launches always start on the handle's own stream, mppi_capi.cpp) none either way.
+with odd lengths.  Since the fix (big launches always start on the handle's own stream, mppi_solve.cpp) none either way.
     NW=30 NB=400 python tools/handle_sequence.py"""
 import os, sys, time
 sys.path.insert(0, os.getcwd())
