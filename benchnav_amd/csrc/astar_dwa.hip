@@ -11,7 +11,7 @@
 //                   instance's root cell (the last start whose walk reached the goal).  No root yet: the stage cost runs against the
 //                   goal (dwa.py:243-247).
 //   3. window + sub-goal, 4. rollouts + argmin: DWA.forward (dwa.py:116-153) with dwa_device.h, the code of the stand-alone kernels.
-//   5. env step     PlanetaryEnv.step (planetary_env.py:189-219): env_advance of mppi_device.h with the argmin action.
+//   5. env step     PlanetaryEnv.step (planetary_env.py:189-219): env_advance of mppi_env_step.h with the argmin action.
 // The path is never materialised: one lane chases `next` (staged in LDS when it fits) a segment of nthreads nodes at a time and
 // the workgroup evaluates the segment's distances.  With the A* handle's jump tables (walk mode 1, JUMP) every lane fetches its
 // own node of the segment instead, by pointer doubling: the same nodes in the same order, so the outputs are bit-identical.
@@ -20,6 +20,8 @@
 #include "../../include/benchnav_mppi.h"
 #include "astar_dwa.h"
 #include "dwa_device.h"
+#include "mppi_env_step.h"
+#include "rollout_launch.h"
 
 namespace bn {
 

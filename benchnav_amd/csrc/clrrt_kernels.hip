@@ -62,7 +62,7 @@ __device__ __forceinline__ float norm32(float dx, float dy) { return sqrtf(__fad
 __device__ __forceinline__ float sign32(float v) { return v > 0.0f ? 1.0f : (v < 0.0f ? -1.0f : 0.0f); }
 
 // What the steer needs beside the states: geometry, map and bounds travel in the library's SolveParams, so that the transit and
-// the lookups are the library's own (mppi_device.h).
+// the lookups are the library's own (mppi_geometry.h, mppi_chain.h).
 struct ClrrtCommon {
     SolveParams p;
     int max_seqs;

@@ -9,7 +9,7 @@
 //   deviation   t > 0: min over ALL L + 1 planned states of rrt_norm(plan_xy - state_xy), float32 (torch.norm(..., dim=2) then
 //               torch.min); > 1.0 flags a replan and the iteration takes no step.
 //   action      plan_actions[action_index++]; action_index == L is the reference's IndexError: PLAN_EXHAUSTED.
-//   env step    env_advance of mppi_device.h: observation-mode transit with the slip draw of iteration t (z row t of the call, or
+//   env step    env_advance of mppi_env_step.h: observation-mode transit with the slip draw of iteration t (z row t of the call, or
 //               Philox keyed by (env seed, t)), then the goal test, then the time limit on the rover's own step count.
 // The steps of a rover depend on one another, so one iteration is one scan of the plan, ONE barrier and one env_advance: the
 // threads stride over the planned (x, y) -- staged in LDS as float2 at launch when L + 1 <= kClrrtFollowLdsStates, else read from
@@ -21,6 +21,8 @@
 #include "../../include/benchnav_mppi.h"
 #include "clrrt_view.h"
 #include "dwa_device.h"
+#include "mppi_env_step.h"
+#include "rollout_launch.h"
 #include "rrt_device.h"
 
 namespace bn {

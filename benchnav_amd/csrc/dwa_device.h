@@ -1,8 +1,11 @@
 // dwa_device.h -- the DWA step's device code (reference src/planners/local_planners/dwa.py:116-285), shared by the stand-alone
 // kernels of DWA.forward (mppi_kernels.hip: dwa_window_kernel, dwa_kernel) and the fused A* + DWA episode (astar_dwa.hip).  One
-// definition of every operation, so the two paths agree bit for bit by construction.  Internal linkage like mppi_device.h.
+// definition of every operation, so the two paths agree bit for bit by construction.  Internal linkage like the MPPI kernels'
+// headers, of which it takes the lookups (mppi_geometry.h), the transit step (mppi_chain.h) and the wave reductions (mppi_sync.h).
 #pragma once
-#include "mppi_device.h"
+#include "mppi_geometry.h"
+#include "mppi_chain.h"
+#include "mppi_sync.h"
 
 namespace bn {
 

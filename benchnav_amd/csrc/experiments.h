@@ -1,4 +1,4 @@
-// experiments.h -- the measurement builds' hooks into the kernels; included by mppi_device.h under -DBN_EXPERIMENTS only
+// experiments.h -- the measurement builds' hooks into the kernels; included by mppi_stamps.h under -DBN_EXPERIMENTS only
 // (tools/build_variant*.py).  The shipped library (benchnav_amd/build.py) never sees this file.
 //   BN_TIMING          in-kernel cycle / wall-clock stamps of workgroup 0 (tools/stamps*.py) and per-workgroup traces
 //                      (tools/block_trace*.py): SolveParams::stamps must point at a device buffer (bn_mppi_debug_set_stamps)

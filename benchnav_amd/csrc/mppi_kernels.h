@@ -28,7 +28,7 @@ struct SolveParams {
     int map_stride;      // G*G if every instance has its own map, 0 if shared
     int pow2;            // resolution is a power of two
     int fast_div;        // general resolution: the in-loop quotient (p - origin) / res (Markstein's three-instruction form, quotient_general
-                         // in mppi_device.h) passed the exhaustive check at create
+                         // in mppi_geometry.h) passed the exhaustive check at create
     int store_u;
     int wave_kernel;     // launch the one-wave-per-64-rollouts throughput variant (many workgroups per launch)
     int lat_kernel;      // launch the barrier-free latency variant of the role kernel (every workgroup has a CU to itself)

@@ -18,7 +18,8 @@
 #include "mppi_kernels.h"
 // This translation unit holds the tail kernel, DWA, the environment mirror and the small helpers; the rollout kernels
 // live in rollout_role_*.hip (five-wave role split, one file per noise source), rollout_wave.hip (throughput
-// variant) and rollout_sampled.hip (config 3); the device code they share is mppi_device.h.
+// variant) and rollout_sampled.hip (config 3); the device code they share is one header per concern (mppi_*.h), mppi_device.h
+// includes all of them.
 #include "mppi_device.h"
 #include "dwa_device.h"
 #include <cstring>
@@ -54,7 +55,7 @@ __global__ __launch_bounds__(kShardMergeThreads) void shard_merge_kernel(const S
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int T = p.T, tid = threadIdx.x, PS = 2 + 2 * p.T;
     float *us = smem, *sc = us + 2 * T, *red = sc + 64;
-    int *flag = reinterpret_cast<int *>(red + 32);
+    int *flag = reinterpret_cast<int *>(red + kRedFloats);
     float m, S;
     if (p.nblk > 64) {
         const int g = blockIdx.x, ng = gridDim.x;
@@ -384,9 +385,7 @@ size_t rollout_lds_bytes(const SolveParams &p)
 
 size_t finish_lds_bytes(const SolveParams &p)
 {
-    const size_t slip = p.slip_on ? 2 * (size_t)p.WN * p.WN + (size_t)p.T + 16 : 0;    // (mean, std) window + the draws of X*
-    const size_t groups = (p.nblk > 64 && p.nblk <= 64 * 16) ? (size_t)((p.nblk + 15) / 16) * (2 + 2 * (size_t)p.T) : 0;   // two-level merge rows
-    return sizeof(float) * ((size_t)p.WN * p.WN + 2 * (size_t)p.T + 3 * ((size_t)p.T + 1) + (size_t)p.nblk + 32 + groups + slip);
+    return sizeof(float) * tail_lds_floats(p.WN, p.T, p.nblk, p.slip_on != 0);      // (mppi_tail.h: term by term what finish_body's pointer chain adds up)
 }
 
 size_t finish_lds_bytes_for(SolveParams p, bool sampled)

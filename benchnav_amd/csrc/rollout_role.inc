@@ -9,9 +9,6 @@
 #ifndef BN_ROLE_REF
 #define BN_ROLE_REF false
 #endif
-#ifndef BN_ROLE_FRESH
-#define BN_ROLE_FRESH false      /* experiment: -DBN_ROLE_FRESH=true (tools/build_variant_fast.py) */
-#endif
 
 namespace bn {
 
@@ -162,7 +159,7 @@ __global__ __launch_bounds__(kRolloutThreads) void rollout_kernel(const SolvePar
 #pragma unroll
         for (int q = 0; q < TU / 4; ++q) {
             const int t = wid * (TU / 2) + 2 * q;
-            if (t < T) produce_pair<EPS, STORE_U, BN_ROLE_FRESH>(p, eps, b, kk, t, solve, ml, Ul, Ub, Kp, lane);
+            if (t < T) produce_pair<EPS, STORE_U>(p, eps, b, kk, t, solve, ml, Ul, Ub, Kp, lane);
         }
     }
     BN_BAR();
@@ -254,7 +251,7 @@ __global__ __launch_bounds__(kRolloutThreads) void rollout_kernel(const SolvePar
         } else {                                                                                               \
             _Pragma("unroll") for (int q = 0; q < TU / 4; ++q) {                                               \
                 const int t = ((cc) + 2) * TU + (wv == 1 ? 0 : TU / 2) + 2 * q;                                \
-                if (t < T) produce_pair<EPS, STORE_U, BN_ROLE_FRESH>(p, eps, b, kk, t, solve, ml, Ul, Ub, Kp, lane);          \
+                if (t < T) produce_pair<EPS, STORE_U>(p, eps, b, kk, t, solve, ml, Ul, Ub, Kp, lane);          \
             }                                                                                                  \
         }                                                                                                      \
     } while (0)

@@ -6,7 +6,7 @@
 // The sums are float64 and sequential, exactly the order of tests/benchmark_spec.py: the device's double square root is the
 // only operation whose rounding may differ from the host's.
 //
-// done_step's convention is the one the loops write (mppi_device.h `p.ep_done[b] = p.ep_index`, astar_dwa.hip `done = (int)ep`):
+// done_step's convention is the one the loops write (mppi_tail.h `p.ep_done[b] = p.ep_index`, astar_dwa.hip `done = (int)ep`):
 // the 0-BASED INDEX OF THE STEP whose resulting state first lay within the goal threshold -- reward row done_step, state row
 // done_step + 1 -- or -1.  An episode that reached its goal at step k therefore counts k + 1 rows.
 #include "../../include/benchnav_mppi.h"

@@ -148,7 +148,7 @@ def test_parked_register_block_is_touched_by_its_two_statements_only(tmp_path):
 @pytest.mark.skipif(not (os.path.exists(f"{LLVM}/llvm-objdump") and os.path.exists(f"{LLVM}/clang-offload-bundler")), reason="ROCm LLVM tools not installed")
 def test_latency_kernel_scratch_registers_belong_to_its_two_asm_blocks(tmp_path):
     """The latency kernel's chain wave runs its gather address and its heading rotation as one asm block each, with v124-v127 as
-    fixed scratch registers (csrc/mppi_device.h trav_window<.., 2>, csrc/bn_device_math.h rotate_spec<true>).
+    fixed scratch registers (csrc/mppi_geometry.h trav_window<.., 2>, csrc/bn_device_math.h rotate_spec<true>).
     In the SHIPPED code objects every instruction that names one of the four is an instruction of those blocks -- by opcode, and in
     the blocks' proportions (one gather block = 1 v_pk_fma + 2 v_cvt_flr + 1 v_mad_u32_u24 + 1 v_lshl_add; one rotation block =
     2 v_mul + 4 v_pk_fma + 1 v_pk_mul) -- and the two kinds come in pairs (one of each per unrolled step; rotation blocks alone
