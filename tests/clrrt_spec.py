@@ -31,7 +31,54 @@ TRANSIT_DT = f32(0.1)               # UnicycleModel.transit's default delta_t: C
 # a steer whose discrete decisions change when the points move by this much is "marginal" and may be left out of a comparison.
 EPS_POINT = 2.0e-6
 
-M32 = SimpleNamespace(cos=np.cos, sin=np.sin, arctan2=np.arctan2, arccos=np.arccos, arcsin=np.arcsin, sqrt=np.sqrt)
+# mid_height: h = sqrt(4 - (inter / 2)^2) of the middle circle, which the reference writes with the scalars' own power operator
+M32 = SimpleNamespace(cos=np.cos, sin=np.sin, arctan2=np.arctan2, arccos=np.arccos, arcsin=np.arcsin, sqrt=np.sqrt,
+                      mid_height=lambda inter: f32((f32(4) - (inter / f32(2)) ** 2) ** 0.5))
+
+
+def _rounded(fn):
+    """The float64 function (Python's math) rounded once to float32: what the device takes a float32 transcendental to be."""
+    return lambda *a: f32(fn(*(float(v) for v in a)))
+
+
+def _mid_height_sqrt(inter):
+    hi = f32(f32(inter) * f32(0.5))
+    return f32(np.sqrt(f32(f32(4) - f32(hi * hi))))
+
+
+# The device's own float32 math (csrc/clrrt_kernels.hip sincos32, atan2_32, acos, asin): with it the float32 half of a steer has no
+# freedom left.  sqrt is IEEE on both sides; the middle circle's height is a float32 sqrt in the kernel.
+M64R = SimpleNamespace(cos=_rounded(math.cos), sin=_rounded(math.sin), arctan2=_rounded(math.atan2), arccos=_rounded(math.acos),
+                       arcsin=_rounded(math.asin), sqrt=np.sqrt, mid_height=_mid_height_sqrt)
+DOUBLE_ROUNDING_BAND = 2.0 ** -44
+
+
+def rounding_margin(r: float) -> float:
+    """Relative distance of the float64 r from the nearest float32 rounding boundary (the midpoint of two neighbouring float32
+    values); inf where r is 0 or not finite."""
+    r = float(r)
+    if r == 0.0 or not math.isfinite(r):
+        return math.inf
+    v = f32(r)
+    lo, hi = float(np.nextafter(v, f32(-np.inf))), float(np.nextafter(v, f32(np.inf)))
+    return min(abs(r - (float(v) + lo) / 2), abs(r - (float(v) + hi) / 2)) / abs(r)
+
+
+def instrumented_m64r():
+    """(namespace, margins): M64R whose every transcendental call appends rounding_margin of its float64 result to `margins`.  A
+    steer "sits in the double-rounding band" if one of them is below DOUBLE_ROUNDING_BAND: there a 1-ulp difference between two
+    float64 libraries could flip the float32 value."""
+    margins = []
+
+    def wrap(fn):
+        def call(*a):
+            r = fn(*(float(v) for v in a))
+            margins.append(rounding_margin(r))
+            return f32(r)
+        return call
+    ns = SimpleNamespace(cos=wrap(math.cos), sin=wrap(math.sin), arctan2=wrap(math.atan2), arccos=wrap(math.acos), arcsin=wrap(math.asin),
+                         sqrt=np.sqrt, mid_height=_mid_height_sqrt)
+    return ns, margins
 
 
 def pymod(a, b):
@@ -177,7 +224,7 @@ def dubins_points(start, end, m=M32, limit: Optional[int] = None):
         inter = norm2_32(c0[0] - c2[0], c0[1] - c2[1])
         u = (c2 - c0) / inter
         orth = np.array([-u[1], u[0]], np.float32)
-        h = f32((f32(4) - (inter / f32(2)) ** 2) ** 0.5)              # the scalars' own power operator, as the reference writes it
+        h = m.mid_height(inter)
         c1 = ((c0 + c2) / f32(2) + (np.sign(path[0]) * orth) * h).astype(np.float32)
         psi0 = f32(f32(m.arctan2(f32(c1[1] - c0[1]), f32(c1[0] - c0[0]))) - PI32)
     count = int(math.ceil(float(total) / SPACING))               # len(np.arange(0, total, 0.25)), computed in float64
@@ -306,27 +353,34 @@ class Steer:
     length: int
     ctrl: np.ndarray                 # (4,) float64: previous error and integral of the linear, then the angular controller
     integrals: np.ndarray            # (2,) float32: the integrals, what the parent's stored row receives
+    wrap_arg: float = 0.0            # the last step's (bearing - heading) + pi, the largest intermediate of its angular error
 
 
-def follow(cfg: Config, from_state, ctrl, path, word=-1) -> Steer:
-    """_simulate_path_following on a given (truncated) path."""
+def follow(cfg: Config, from_state, ctrl, path, word=-1, nudge=None) -> Steer:
+    """_simulate_path_following on a given (truncated) path.  nudge=(a, b): the linear error is multiplied by 1 + a and b is added
+    to every bearing atan2(dy, dx), the lanes' validity test and the target's errors alike, before anything is cast or compared:
+    the freedom another float64 atan2 / sqrt / fmod has once the points are given.  None leaves the arithmetic as it is."""
     x, y, th = (f32(v) for v in np.asarray(from_state, np.float32))
     lin_i, ang_i = f32(ctrl[1]), f32(ctrl[3])
     e_lin, e_ang = f64(ctrl[0]), f64(ctrl[2])
     px, py = path[:, 0], path[:, 1]
     dt = float(cfg.delta_t)
     targets, actions, states, cells = [], [], [], []
-    cost, feasible = f32(0), False
+    cost, feasible, wrap_arg = f32(0), False, 0.0
     umin, umax = np.float32(cfg.u_min), np.float32(cfg.u_max)
     for t in range(cfg.max_seqs):
         # pure pursuit in float64
         dx, dy = px - f64(x), py - f64(y)
-        ang = np.arctan2(dy, dx) - f64(th)
+        ang = np.arctan2(dy, dx) - f64(th) if nudge is None else (np.arctan2(dy, dx) + f64(nudge[1])) - f64(th)
         valid = (np.abs(ang) < PI / 2) & ((dx * dx + dy * dy) > LOOKAHEAD2)
         k = int(np.argmax(valid)) if valid.any() else len(px) - 1
         tx, ty = float(dx[k]), float(dy[k])
         e_lin = f64(math.sqrt(tx * tx + ty * ty))
-        e_ang = f64(pymod(float(math.atan2(ty, tx) - float(th)) + PI, TWO_PI) - PI)
+        bearing = math.atan2(ty, tx)
+        if nudge is not None:
+            e_lin, bearing = f64(e_lin * (1.0 + nudge[0])), bearing + nudge[1]
+        wrap_arg = float(bearing - float(th)) + PI
+        e_ang = f64(pymod(wrap_arg, TWO_PI) - PI)
         lin_i = f32(f64(lin_i) + e_lin * dt)
         ang_i = f32(f64(ang_i) + e_ang * dt)
         v, om = f32(e_lin), f32(e_ang)
@@ -356,7 +410,7 @@ def follow(cfg: Config, from_state, ctrl, path, word=-1) -> Steer:
     cells.append(c2)
     states.append((x, y, th))
     return Steer(path, word, np.asarray(targets, np.int32), np.asarray(actions, np.float32).reshape(-1, 2), np.asarray(states, np.float32),
-                 cells, cost, feasible, len(actions), np.array([e_lin, lin_i, e_ang, ang_i], np.float64), np.array([lin_i, ang_i], np.float32))
+                 cells, cost, feasible, len(actions), np.array([e_lin, lin_i, e_ang, ang_i], np.float64), np.array([lin_i, ang_i], np.float32), wrap_arg)
 
 
 def steer(cfg: Config, from_state, ctrl, target, m=M32) -> Steer:
@@ -364,15 +418,15 @@ def steer(cfg: Config, from_state, ctrl, target, m=M32) -> Steer:
     return follow(cfg, from_state, ctrl, path, w)
 
 
-def steer_is_marginal(cfg: Config, from_state, ctrl, target, eps: float = EPS_POINT) -> bool:
+def steer_is_marginal(cfg: Config, from_state, ctrl, target, eps: float = EPS_POINT, m=M32) -> bool:
     """A discrete decision of this steer hangs on less than the device's measured point difference: the two shortest words are
     within 8 float32 ulps of each other, the point count hangs on the last bits of the total, or the follow loop on the points
     moved by +-eps changes a target index, the termination step, feasibility or a traversability cell."""
-    opts = all_options(from_state, target)
+    opts = all_options(from_state, target, m)
     lens = sorted(float(o[0]) for o in opts)
     if lens[1] - lens[0] <= 8 * float(np.spacing(f32(lens[0]))):
         return True
-    path, w = reference_path(from_state, target, cfg.delta)
+    path, w = reference_path(from_state, target, cfg.delta, m)
     q = lens[0] / SPACING
     if len(path) - 1 >= math.floor(q) and min(q - math.floor(q), math.ceil(q) - q) < 1e-5:
         return True
