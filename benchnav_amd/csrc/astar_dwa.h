@@ -1,6 +1,7 @@
 // astar_dwa.h -- launch interface of the fused A* + DWA episode (astar_dwa.hip) for the C ABI (mppi_loops.cpp).
 #pragma once
 #include "astar_view.h"
+#include "episode_rows.h"
 #include "mppi_kernels.h"
 
 namespace bn {
@@ -22,10 +23,8 @@ struct AstarDwaArgs {
     float *prev;                  // (B, 2) in/out: the window centre (the previous argmin action, dwa.py:147)
     int32_t *root;                // (B) in/out: iy * W + ix of the last start cell whose walk reached the goal, or -1
     int32_t *status, *status_step, *done;   // (B) in/out: bn_astar_dwa_status, the step it was set at, first goal step or -1
-    float *log_states;            // (n + 1, B, 3) this call's states, [0] = the call's start
-    float *log_reward;            // (n, B)
-    float *log_action;            // (n, B, 2)
-    float *log_subgoal;           // (n, B, 2) the stage-cost target of each step
+    EpisodeRows log;              // this call's states, rewards and actions
+    float *log_subgoal;           // (cap, B, 2) the stage-cost target of each step
     const float *z;               // (n, B) injected slip draws, or nullptr: Philox keyed by (env seed, step0 + step)
     int32_t *err;                 // device error word of the handle: bit 0 = a next-hop walk exceeded H*W nodes or hit an unreachable cell
     float alim0, alim1, dwa_dt, lookahead;

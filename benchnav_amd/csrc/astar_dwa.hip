@@ -90,11 +90,7 @@ __device__ __forceinline__ WalkSeg jump_segment(const int32_t *jump, int cells, 
 __device__ __forceinline__ void log_step(const AstarDwaArgs &a, int gs, int b, float x, float y, float th, float reward, float u0, float u1,
                                          float hx, float hy)
 {
-    const size_t B = gridDim.x, r = (size_t)gs * B + b;
-    float *ls = a.log_states + (r + B) * 3;
-    ls[0] = x; ls[1] = y; ls[2] = th;
-    a.log_reward[r] = reward;
-    a.log_action[r * 2 + 0] = u0; a.log_action[r * 2 + 1] = u1;
+    const size_t r = a.log.write(gs, b, x, y, th, reward, u0, u1);
     a.log_subgoal[r * 2 + 0] = hx; a.log_subgoal[r * 2 + 1] = hy;
 }
 
@@ -143,7 +139,7 @@ __global__ void astar_dwa_kernel(const SolveParams p, const AstarDwaArgs a)
     else if (gi.gx < 0) goal_code = BN_AD_OUT_OF_BOUNDS;
     else if (a.arisk[(size_t)b * cells + (size_t)gi.gy * W + gi.gx] <= gi.thr) goal_code = BN_AD_GOAL_COLLISION;
     const size_t B = p.B;
-    if (a.s0 == 0 && tid == 0) { a.log_states[b * 3 + 0] = sx; a.log_states[b * 3 + 1] = sy; a.log_states[b * 3 + 2] = sth; }
+    if (a.s0 == 0 && tid == 0) { a.log.states[b * 3 + 0] = sx; a.log.states[b * 3 + 1] = sy; a.log.states[b * 3 + 2] = sth; }
 
     for (int i = 0; i < a.ns; ++i) {
         const int gs = a.s0 + i;                           // step of this call

@@ -33,11 +33,7 @@ namespace {
 __device__ __forceinline__ void follow_log(const ClrrtFollowArgs &a, int row, int b, float x, float y, float th, float reward, float u0, float u1,
                                            float dev, int plan, int event)
 {
-    const size_t B = gridDim.x, r = (size_t)row * B + b;
-    float *ls = a.log_states + (r + B) * 3;
-    ls[0] = x; ls[1] = y; ls[2] = th;
-    a.log_reward[r] = reward;
-    a.log_action[r * 2 + 0] = u0; a.log_action[r * 2 + 1] = u1;
+    const size_t r = a.log.write(row, b, x, y, th, reward, u0, u1);
     a.log_dev[r] = dev;
     a.log_plan[r] = plan;
     a.log_event[r] = event;
@@ -55,7 +51,7 @@ __global__ __launch_bounds__(kClrrtFollowThreads) void clrrt_follow_kernel(const
     const float *pa = a.path_actions + (size_t)b * a.path_cap * 2;
     const float *ps = a.path_states + (size_t)b * ((size_t)a.path_cap + 1) * 3;
     int it = min(max(r.iter, a.iter0), end);
-    if (it == a.iter0 && tid == 0) { a.log_states[b * 3 + 0] = sx; a.log_states[b * 3 + 1] = sy; a.log_states[b * 3 + 2] = sth; }
+    if (it == a.iter0 && tid == 0) { a.log.states[b * 3 + 0] = sx; a.log.states[b * 3 + 1] = sy; a.log.states[b * 3 + 2] = sth; }
     // the plan the previous round asked for: CLRRT.forward's return, in its order (None, then _raise_unless_path)
     if (r.status == BN_CL_RUNNING && r.need == 2) {
         const int32_t *res = a.results + (size_t)b * kClrrtResultWords;

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "../../include/benchnav_mppi.h"
+#include "episode_rows.h"
 #include "mppi_kernels.h"
 
 struct bn_clrrt;
@@ -61,9 +62,7 @@ struct ClrrtFollowArgs {
     float *psamples;              // (B, iters, 3) the planner's sample rows
     const float *inj;             // (P, B, iters, 3) injected sample tables, or nullptr
     int P, iters, path_cap;
-    float *log_states;            // (cap + 1, B, 3): row i + 1 = the state after iteration i of the call
-    float *log_reward;            // (cap, B)
-    float *log_action;            // (cap, B, 2)
+    EpisodeRows log;              // rows by iteration of the call
     float *log_dev;               // (cap, B)
     int32_t *log_plan;            // (cap, B)
     int32_t *log_event;           // (cap, B)

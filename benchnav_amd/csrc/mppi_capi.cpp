@@ -86,8 +86,8 @@ int flush_tail(bn_mppi *h, float *out_copy)
     p.tail_solve = h->solves - 1;
     if (h->in_episode) {
         p.env_on = 1;
-        p.ep_index = h->ep_len - 1;
-        p.env_z = h->ep_z ? h->ep_z + (size_t)(h->ep_len - 1) * p.B : nullptr;
+        p.ep_index = h->ep_log.len - 1;
+        p.env_z = h->ep_z ? h->ep_z + (size_t)(h->ep_log.len - 1) * p.B : nullptr;
     }
     p.flag_tail = flag_tail(h);                        // every tail counts itself in (stream-ordered here: nothing to wait for)
     h->tails += 1;

@@ -38,7 +38,6 @@ namespace host {
 void env_release(bn_mppi *h)
 {
     h->env_bufs.free_all();
-    h->ep_bufs.free_all();
 }
 
 }  // namespace host
@@ -61,9 +60,7 @@ int bn_mppi_env_attach(bn_mppi_t *h, const float *latent_mean, const float *late
         h->env_bufs.add(&h->d_lat_std, bytes);
         h->env_bufs.add(&h->d_env_state, (size_t)h->p.B * 3 * 4);
         h->env_bufs.add(&h->d_ep_done, (size_t)h->p.B * sizeof(int));
-        h->ep_bufs.add_later(&h->d_ep_states);
-        h->ep_bufs.add_later(&h->d_ep_reward);
-        h->ep_bufs.add_later(&h->d_ep_action);
+        h->ep_log.attach(h->env_bufs, h->p.B, 0);
     }
     if (!h->env_bufs.live) {
         if (int rc = h->env_bufs.ensure(table_fail)) return rc;
@@ -135,16 +132,9 @@ int bn_mppi_episode_async(bn_mppi_t *h, int32_t n_steps, const float *states0, b
     BN_BIND(h);
     if (int rc = flush_tail(h)) return rc;            // anything pending belongs to the pre-episode state
     const size_t B = h->p.B;
-    if (n_steps > h->ep_steps) {
-        BN_HIP(hipStreamSynchronize(h->stream));
-        h->ep_steps = 0;
-        if (int rc = h->ep_bufs.resize(&h->d_ep_states, (size_t)(n_steps + 1) * B * 3 * 4, table_fail)) return rc;
-        if (int rc = h->ep_bufs.resize(&h->d_ep_reward, (size_t)n_steps * B * 4, table_fail)) return rc;
-        if (int rc = h->ep_bufs.resize(&h->d_ep_action, (size_t)n_steps * B * 2 * 4, table_fail)) return rc;
-        if (int rc = fills_done()) return rc;
-        h->ep_steps = n_steps;
-    }
-    h->p.ep_states = h->d_ep_states; h->p.ep_reward = h->d_ep_reward; h->p.ep_action = h->d_ep_action;
+    bn::EpisodeLog &lg = h->ep_log;
+    if (int rc = lg.reserve(h->env_bufs, h->stream, n_steps, table_fail)) return rc;
+    h->p.ep_states = lg.states(); h->p.ep_reward = lg.reward(); h->p.ep_action = lg.action();
     BN_HIP(hipMemsetAsync(h->d_ep_done, 0xff, B * sizeof(int), h->stream));        // -1: goal not reached
     if (!states0) return fail(BN_ERR_INVALID, "states0 is null");
     if (states_where == BN_MEM_HOST) {                 // one upload; the loop below must not touch the host again
@@ -155,7 +145,7 @@ int bn_mppi_episode_async(bn_mppi_t *h, int32_t n_steps, const float *states0, b
     }
     journal_arm_states(h);                            // the first step's launch keeps states0 for a re-run
     h->in_episode = true;
-    h->ep_len = 0;
+    lg.len = 0;                                       // every enqueued solve counts itself in (mppi_solve.cpp)
     h->ep_z = z_device;
     int rc = bn_mppi_solve_n_async(h, n_steps, states0, states_where, eps, noise, eps_ring, eps_stride);
     if (rc == BN_OK) rc = flush_tail(h);              // the last solve's tail and the last environment step
@@ -167,15 +157,12 @@ int bn_mppi_episode_async(bn_mppi_t *h, int32_t n_steps, const float *states0, b
 int bn_mppi_episode_log(bn_mppi_t *h, float *states_host, float *rewards_host, float *actions_host, int32_t *done_step_host)
 {
     if (!h) return fail(BN_ERR_INVALID, "null handle");
-    if (!h->d_ep_states || h->ep_len < 1) return fail(BN_ERR_STATE, "no episode has been run");
+    if (h->ep_log.empty()) return fail(BN_ERR_STATE, "no episode has been run");
     BN_BIND(h);
     if (int rc = settle_point(h)) return rc;
     BN_HIP(hipStreamSynchronize(h->stream));
-    const size_t B = h->p.B, n = (size_t)h->ep_len;
-    if (states_host) BN_HIP(hipMemcpy(states_host, h->d_ep_states, (n + 1) * B * 3 * 4, hipMemcpyDeviceToHost));
-    if (rewards_host) BN_HIP(hipMemcpy(rewards_host, h->d_ep_reward, n * B * 4, hipMemcpyDeviceToHost));
-    if (actions_host) BN_HIP(hipMemcpy(actions_host, h->d_ep_action, n * B * 2 * 4, hipMemcpyDeviceToHost));
-    if (done_step_host) BN_HIP(hipMemcpy(done_step_host, h->d_ep_done, B * sizeof(int), hipMemcpyDeviceToHost));
+    if (int rc = h->ep_log.copy_out(states_host, rewards_host, actions_host, table_fail)) return rc;
+    if (done_step_host) BN_HIP(hipMemcpy(done_step_host, h->d_ep_done, (size_t)h->p.B * sizeof(int), hipMemcpyDeviceToHost));
     return BN_OK;
 }
 
@@ -183,14 +170,15 @@ int bn_mppi_episode_buffers(bn_mppi_t *h, const float **states_device, const flo
                             int32_t *n_steps, int32_t *row_capacity)
 {
     if (!h) return fail(BN_ERR_INVALID, "null handle");
-    if (!h->d_ep_states || h->ep_len < 1) return fail(BN_ERR_STATE, "no episode has been run");
+    const bn::EpisodeLog &lg = h->ep_log;
+    if (lg.empty()) return fail(BN_ERR_STATE, "no episode has been run");
     BN_BIND(h);
     if (int rc = settle_point(h)) return rc;              // from here on the episode is ordered on the handle's stream
-    if (states_device) *states_device = h->d_ep_states;                                        // (n_steps + 1, B, 3)
-    if (rewards_device) *rewards_device = h->d_ep_reward;                                      // (n_steps, B)
+    if (states_device) *states_device = lg.states();                                           // (row_capacity + 1, B, 3)
+    if (rewards_device) *rewards_device = lg.reward();                                         // (row_capacity, B)
     if (done_step_device) *done_step_device = h->d_ep_done;                                    // (B)
-    if (n_steps) *n_steps = h->ep_len;
-    if (row_capacity) *row_capacity = h->ep_steps;
+    if (n_steps) *n_steps = lg.len;
+    if (row_capacity) *row_capacity = lg.cap;
     return BN_OK;
 }
 

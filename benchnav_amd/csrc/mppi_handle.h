@@ -6,6 +6,7 @@
 #include "../../include/benchnav_mppi.h"
 #include "mppi_kernels.h"
 #include "bn_host.h"
+#include "episode_log.h"
 
 #include <atomic>
 #include <chrono>
@@ -173,30 +174,26 @@ struct bn_mppi {
     bool ticket_mode = false;        // one launch per solve: ticket merge by the last workgroup + the previous tail as aux
                                      // workgroup (sampled-slip kernel; deterministic kernel at K > 2048)
     bool slip_std_set = false;
-    // device-side closed loop (bn_mppi_env_attach / bn_mppi_episode_async)
-    float *d_lat_mean = nullptr, *d_lat_std = nullptr, *d_ep_states = nullptr, *d_ep_reward = nullptr, *d_env_state = nullptr;
-    float *d_ep_action = nullptr;
+    // device-side closed loop (bn_mppi_env_attach / bn_mppi_episode_async).  The three loops' logs: episode_log.h
+    float *d_lat_mean = nullptr, *d_lat_std = nullptr, *d_env_state = nullptr;
     int *d_ep_done = nullptr;
     bool env_attached = false;
-    int ep_steps = 0;            // capacity of the episode log
-    int ep_len = 0;              // steps enqueued in the current episode
+    bn::EpisodeLog ep_log;       // len: steps enqueued in the current episode
     const float *ep_z = nullptr; // (n_steps, B) device slip draws of the current episode, or nullptr
     bool in_episode = false;
     // fused A* + DWA episode (bn_astar_dwa_episode_async)
-    int32_t *d_ad_i = nullptr;   // (B) root cell | (B) status | (B) status step | (B) done step | error word
+    int32_t *d_ad_i = nullptr;   // the loop's integer words (AdWords, mppi_loops.cpp)
     float *d_ad_state = nullptr; // (B, 3) the environment states the episode advances
-    float *d_ad_log = nullptr;   // (n+1, B, 3) states | (n, B) rewards | (n, B, 2) actions | (n, B, 2) sub-goals
-    int ad_cap = 0, ad_len = 0;  // steps the log holds / the latest call ran
+    bn::EpisodeLog ad_log;       // + the sub-goals
     uint64_t ad_step = 0;        // episode steps since bn_astar_dwa_reset
     int ad_walk = 0;             // bn_astar_dwa_set_walk: 0 the serial next-hop walk, 1 the A* handle's jump tables
     // CL-RRT plan-follow-replan loop (bn_clrrt_loop_run)
     bn::ClrrtRover *d_cl_rover = nullptr;   // (B)
-    int32_t *d_cl_flags = nullptr;          // (B) the replan mask | the pending counter
+    int32_t *d_cl_flags = nullptr;          // the replan mask and the pending counter (ClFlags, mppi_loops.cpp)
     float *d_cl_goal = nullptr;             // (B, 3) goal nodes
-    float *d_cl_log = nullptr;              // (cap+1, B, 3) states | (cap, B) rewards | (cap, B, 2) actions | (cap, B) deviations | plan index | events
+    bn::EpisodeLog cl_log;                  // + deviation, plan index, event
     int32_t *h_cl_pending = nullptr;        // pinned: the pending counter of the latest round
     hipEvent_t cl_ev[2] = {};               // around a follow launch (follow_ms)
-    int cl_cap = 0, cl_len = 0;             // iterations the log holds / the latest call ran
     int32_t cl_iter = 0, cl_limit_steps = 0;   // iterations since the reset; the step count at which elapsed > time_limit
     bool cl_ready = false;                  // bn_clrrt_loop_reset has run
     bn_clrrt_t *cl_planner = nullptr;       // ... with this CL-RRT handle: the episode's goals, streams and paths live in it
@@ -205,7 +202,7 @@ struct bn_mppi {
     // Who owns all of the above (bn_host.h): `bufs` is what bn_mppi_create allocates from its plan, plus d_scratch, d_eps and d_idx,
     // which grow on demand; the others are the groups a concern builds on first use and its *_release frees.  Streams are not in
     // any table.
-    bn::DeviceBuffers bufs, env_bufs, ep_bufs, ad_bufs, cl_bufs, shard_bufs, paced_bufs;
+    bn::DeviceBuffers bufs, env_bufs, ad_bufs, cl_bufs, shard_bufs, paced_bufs;
     size_t plan_bytes[BN_BUF_COUNT_] = {};   // MppiPlan::buffer_bytes: what bn_mppi_device_buffer reports for a buffer this handle does not have
     // launch log (bn_mppi_debug_launch_log): a ring of kLaunchLogCap records, allocated when recording is turned on
     bool log_on = false;

@@ -10,6 +10,33 @@
 
 using namespace bn::host;
 
+namespace {
+
+// The integer words of the A* + DWA loop (d_ad_i): root cell | status | status step | done step, (B) each, then the error word.
+struct AdWords {
+    int32_t *w;
+    size_t B;
+    static size_t count(size_t B) { return 4 * B + 1; }
+    int32_t *root() const { return w; }
+    int32_t *status() const { return w + B; }              // bn_astar_dwa_status
+    int32_t *status_step() const { return status() + B; }
+    int32_t *done() const { return status_step() + B; }
+    int32_t *err() const { return done() + B; }
+};
+AdWords ad_words(const bn_mppi *h) { return AdWords{h->d_ad_i, (size_t)h->p.B}; }
+
+// The flag words of the CL-RRT loop (d_cl_flags): (B) the replan mask, then the pending counter.
+struct ClFlags {
+    int32_t *w;
+    size_t B;
+    static size_t count(size_t B) { return B + 1; }
+    int32_t *active() const { return w; }
+    int32_t *pending() const { return w + B; }
+};
+ClFlags cl_flags(const bn_mppi *h) { return ClFlags{h->d_cl_flags, (size_t)h->p.B}; }
+
+}  // namespace
+
 namespace bn {
 namespace host {
 
@@ -31,18 +58,19 @@ static int astar_dwa_clear(bn_mppi *h)
 {
     const size_t B = h->p.B;
     if (h->ad_bufs.list.empty()) {
-        h->ad_bufs.add(&h->d_ad_i, (4 * B + 1) * sizeof(int32_t));
+        h->ad_bufs.add(&h->d_ad_i, AdWords::count(B) * sizeof(int32_t));
         h->ad_bufs.add(&h->d_ad_state, B * 3 * sizeof(float));
-        h->ad_bufs.add_later(&h->d_ad_log);            // grows with the longest episode (ad_cap)
+        h->ad_log.attach(h->ad_bufs, B, 2);            // + the sub-goals (x, y); grows with the longest episode
     }
     if (!h->ad_bufs.live) {
         if (int rc = h->ad_bufs.ensure(table_fail)) return rc;
         if (int rc = fills_done()) return rc;
     }
-    BN_HIP(hipMemsetAsync(h->d_ad_i, 0xff, B * sizeof(int32_t), h->stream));
-    BN_HIP(hipMemsetAsync(h->d_ad_i + B, 0, B * sizeof(int32_t), h->stream));
-    BN_HIP(hipMemsetAsync(h->d_ad_i + 2 * B, 0xff, 2 * B * sizeof(int32_t), h->stream));
-    BN_HIP(hipMemsetAsync(h->d_ad_i + 4 * B, 0, sizeof(int32_t), h->stream));
+    const AdWords w = ad_words(h);
+    BN_HIP(hipMemsetAsync(w.root(), 0xff, B * sizeof(int32_t), h->stream));
+    BN_HIP(hipMemsetAsync(w.status(), 0, B * sizeof(int32_t), h->stream));
+    BN_HIP(hipMemsetAsync(w.status_step(), 0xff, 2 * B * sizeof(int32_t), h->stream));       // ... and the done steps behind them
+    BN_HIP(hipMemsetAsync(w.err(), 0, sizeof(int32_t), h->stream));
     h->ad_step = 0;
     return BN_OK;
 }
@@ -66,7 +94,7 @@ int bn_astar_dwa_set_root(bn_mppi_t *h, int32_t instance, int32_t ix, int32_t iy
         if (int rc = astar_dwa_clear(h)) return rc;
     const int32_t cell = ix < 0 ? -1 : iy * h->p.G + ix;
     BN_HIP(hipStreamSynchronize(h->stream));
-    BN_HIP(hipMemcpy(h->d_ad_i + instance, &cell, sizeof(int32_t), hipMemcpyHostToDevice));
+    BN_HIP(hipMemcpy(ad_words(h).root() + instance, &cell, sizeof(int32_t), hipMemcpyHostToDevice));
     return BN_OK;
 }
 
@@ -100,29 +128,23 @@ int bn_astar_dwa_episode_async(bn_mppi_t *h, bn_astar_t *a, int32_t n_steps, con
     if (int rc = settle_point(h)) return rc;
     if (int rc = flush_tail(h)) return rc;
     if (int rc = guard_foreign_overlap(h)) return rc;
-    const size_t B = h->p.B, n = (size_t)n_steps;
+    const size_t B = h->p.B;
     if (!h->d_ad_i)
         if (int rc = astar_dwa_clear(h)) return rc;
-    if (n_steps > h->ad_cap) {
-        BN_HIP(hipStreamSynchronize(h->stream));       // the log of the previous call may still be written
-        h->ad_cap = 0;
-        if (int rc = h->ad_bufs.resize(&h->d_ad_log, ((n + 1) * 3 + n * 5) * B * sizeof(float), table_fail)) return rc;
-        if (int rc = fills_done()) return rc;
-        h->ad_cap = n_steps;
-    }
+    bn::EpisodeLog &lg = h->ad_log;
+    if (int rc = lg.reserve(h->ad_bufs, h->stream, n_steps, table_fail)) return rc;
     const hipMemcpyKind kind = where == BN_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     BN_HIP(hipMemcpyAsync(h->d_ad_state, states0, B * 3 * sizeof(float), kind, h->stream));
     if (where == BN_MEM_HOST) BN_HIP(hipStreamSynchronize(h->stream));   // (pageable source: one upload, before the loop)
     BN_HIP(hipStreamWaitEvent(h->stream, v.solved, 0));                 // behind a's latest solve, without the host
     if (h->ad_walk == 1) BN_HIP(hipStreamWaitEvent(h->stream, v.jump_built, 0));   // ... and its table build
-    float *lg = h->d_ad_log;
-    const size_t cap = (size_t)h->ad_cap;                                 // the log's layout is by capacity (bn_astar_dwa_episode_log)
+    const AdWords w = ad_words(h);
     bn::AstarDwaArgs x{};
     x.next = v.next; x.arisk = v.risk; x.ainst = v.inst; x.aerr = v.err; x.H = v.H; x.W = v.W;
     if (h->ad_walk == 1) { x.hops = v.hops; x.jump = v.jump; x.jerr = v.jerr; x.levels = v.levels; }
     x.state = h->d_ad_state; x.prev = prev_action_device;
-    x.root = h->d_ad_i; x.status = h->d_ad_i + B; x.status_step = h->d_ad_i + 2 * B; x.done = h->d_ad_i + 3 * B; x.err = h->d_ad_i + 4 * B;
-    x.log_states = lg; x.log_reward = lg + (cap + 1) * B * 3; x.log_action = x.log_reward + cap * B; x.log_subgoal = x.log_action + cap * B * 2;
+    x.root = w.root(); x.status = w.status(); x.status_step = w.status_step(); x.done = w.done(); x.err = w.err();
+    x.log = lg.columns(); x.log_subgoal = lg.extra(0);
     x.z = z_device;
     x.alim0 = a_lim[0]; x.alim1 = a_lim[1]; x.dwa_dt = dwa_delta_t; x.lookahead = lookahead;
     x.nv = num_lin_vel; x.nw = num_ang_vel;
@@ -137,8 +159,8 @@ int bn_astar_dwa_episode_async(bn_mppi_t *h, bn_astar_t *a, int32_t n_steps, con
         BN_HIP(bn::launch_astar_dwa(h->p, x, h->stream));
     }
     if (bn::astar_add_reader(a, h->stream) != BN_OK) return fail(BN_ERR_HIP, "%s", bn_astar_last_error());
-    h->ad_step += n;
-    h->ad_len = n_steps;
+    h->ad_step += (uint64_t)n_steps;
+    lg.len = n_steps;
     return BN_OK;
 }
 
@@ -146,21 +168,20 @@ int bn_astar_dwa_episode_log(bn_mppi_t *h, float *states, float *rewards, float 
                              int32_t *done_step, int32_t *status, int32_t *status_step)
 {
     if (!h) return fail(BN_ERR_INVALID, "null handle");
-    if (!h->d_ad_log || h->ad_len < 1) return fail(BN_ERR_STATE, "no A* + DWA episode has been run");
+    const bn::EpisodeLog &lg = h->ad_log;
+    if (lg.empty()) return fail(BN_ERR_STATE, "no A* + DWA episode has been run");
     BN_BIND(h);
     if (int rc = settle_point(h)) return rc;
     BN_HIP(hipStreamSynchronize(h->stream));
-    const size_t B = h->p.B, n = (size_t)h->ad_len, cap = (size_t)h->ad_cap;
-    const float *lg = h->d_ad_log, *rw = lg + (cap + 1) * B * 3, *ac = rw + cap * B, *sg = ac + cap * B * 2;
-    if (states) BN_HIP(hipMemcpy(states, lg, (n + 1) * B * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    if (rewards) BN_HIP(hipMemcpy(rewards, rw, n * B * sizeof(float), hipMemcpyDeviceToHost));
-    if (actions) BN_HIP(hipMemcpy(actions, ac, n * B * 2 * sizeof(float), hipMemcpyDeviceToHost));
-    if (sub_goals) BN_HIP(hipMemcpy(sub_goals, sg, n * B * 2 * sizeof(float), hipMemcpyDeviceToHost));
-    if (status) BN_HIP(hipMemcpy(status, h->d_ad_i + B, B * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (status_step) BN_HIP(hipMemcpy(status_step, h->d_ad_i + 2 * B, B * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (done_step) BN_HIP(hipMemcpy(done_step, h->d_ad_i + 3 * B, B * sizeof(int32_t), hipMemcpyDeviceToHost));
+    const size_t B = h->p.B;
+    const AdWords w = ad_words(h);
+    if (int rc = lg.copy_out(states, rewards, actions, table_fail)) return rc;
+    if (sub_goals) BN_HIP(hipMemcpy(sub_goals, lg.extra(0), lg.rows() * 2 * sizeof(float), hipMemcpyDeviceToHost));
+    if (status) BN_HIP(hipMemcpy(status, w.status(), B * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (status_step) BN_HIP(hipMemcpy(status_step, w.status_step(), B * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (done_step) BN_HIP(hipMemcpy(done_step, w.done(), B * sizeof(int32_t), hipMemcpyDeviceToHost));
     int32_t err = 0;
-    BN_HIP(hipMemcpy(&err, h->d_ad_i + 4 * B, sizeof(int32_t), hipMemcpyDeviceToHost));
+    BN_HIP(hipMemcpy(&err, w.err(), sizeof(int32_t), hipMemcpyDeviceToHost));
     if (err) return fail(BN_ERR_STATE, "a next-hop walk broke (more than H*W nodes, or onto an unreachable cell): the A* field is not a valid solve");
     return BN_OK;
 }
@@ -169,16 +190,16 @@ int bn_astar_dwa_episode_buffers(bn_mppi_t *h, const float **states_device, cons
                                  const int32_t **done_step_device, const int32_t **status_device, int32_t *n_steps, int32_t *row_capacity)
 {
     if (!h) return fail(BN_ERR_INVALID, "null handle");
-    if (!h->d_ad_log || h->ad_len < 1) return fail(BN_ERR_STATE, "no A* + DWA episode has been run");
+    const bn::EpisodeLog &lg = h->ad_log;
+    if (lg.empty()) return fail(BN_ERR_STATE, "no A* + DWA episode has been run");
     BN_BIND(h);
     if (int rc = settle_point(h)) return rc;
-    const size_t B = h->p.B, cap = (size_t)h->ad_cap;      // the log is laid out by capacity, as bn_astar_dwa_episode_log reads it
-    if (states_device) *states_device = h->d_ad_log;                                           // (row_capacity + 1, B, 3)
-    if (rewards_device) *rewards_device = h->d_ad_log + (cap + 1) * B * 3;                     // (row_capacity, B)
-    if (done_step_device) *done_step_device = h->d_ad_i + 3 * B;                               // (B)
-    if (status_device) *status_device = h->d_ad_i + B;                                         // (B) bn_astar_dwa_status
-    if (n_steps) *n_steps = h->ad_len;
-    if (row_capacity) *row_capacity = h->ad_cap;
+    if (states_device) *states_device = lg.states();                                           // (row_capacity + 1, B, 3)
+    if (rewards_device) *rewards_device = lg.reward();                                         // (row_capacity, B)
+    if (done_step_device) *done_step_device = ad_words(h).done();                              // (B)
+    if (status_device) *status_device = ad_words(h).status();                                  // (B) bn_astar_dwa_status
+    if (n_steps) *n_steps = lg.len;
+    if (row_capacity) *row_capacity = lg.cap;
     return BN_OK;
 }
 
@@ -215,18 +236,18 @@ int bn_clrrt_loop_reset(bn_mppi_t *h, bn_clrrt_t *c, const float *goal_nodes, co
     const size_t B = h->p.B;
     if (h->cl_bufs.list.empty()) {
         h->cl_bufs.add(&h->d_cl_rover, B * sizeof(bn::ClrrtRover));
-        h->cl_bufs.add(&h->d_cl_flags, (B + 1) * sizeof(int32_t));
+        h->cl_bufs.add(&h->d_cl_flags, ClFlags::count(B) * sizeof(int32_t));
         h->cl_bufs.add(&h->d_cl_goal, B * 3 * sizeof(float));
         h->cl_bufs.add_pinned(&h->h_cl_pending, sizeof(int32_t));
         h->cl_bufs.add_event(&h->cl_ev[0]);
         h->cl_bufs.add_event(&h->cl_ev[1]);
-        h->cl_bufs.add_later(&h->d_cl_log);            // grows with the longest run (cl_cap)
+        h->cl_log.attach(h->cl_bufs, B, 3);            // + deviation, plan index, event; grows with the longest run
     }
     if (int rc = h->cl_bufs.ensure(table_fail)) return rc;
     BN_HIP(hipStreamSynchronize(h->stream));                               // a previous episode's launches are done with the words below
     std::vector<bn::ClrrtRover> r0(B, bn::ClrrtRover{0, BN_CL_RUNNING, 1, 0, 0, 0, 0, -1});
     BN_HIP(hipMemcpy(h->d_cl_rover, r0.data(), B * sizeof(bn::ClrrtRover), hipMemcpyHostToDevice));
-    BN_HIP(hipMemset(h->d_cl_flags, 0, (B + 1) * sizeof(int32_t)));
+    BN_HIP(hipMemset(h->d_cl_flags, 0, ClFlags::count(B) * sizeof(int32_t)));
     BN_HIP(hipMemcpy(h->d_cl_goal, goal_nodes, B * 3 * sizeof(float), hipMemcpyHostToDevice));
     if (bn::clrrt_loop_reset(c, h->stream, goal_nodes, seeds) != BN_OK) return fail(BN_ERR_INVALID, "%s", bn_clrrt_last_error());
     // PlanetaryEnv: elapsed += delta_t in float64, elapsed > time_limit after the step: the first step count at which that holds
@@ -240,7 +261,7 @@ int bn_clrrt_loop_reset(bn_mppi_t *h, bn_clrrt_t *c, const float *goal_nodes, co
     }
     h->cl_limit_steps = k;
     h->cl_iter = 0;
-    h->cl_len = 0;
+    h->cl_log.len = 0;
     h->cl_ready = true;
     h->cl_planner = c;
     return BN_OK;
@@ -262,23 +283,16 @@ int bn_clrrt_loop_run(bn_mppi_t *h, bn_clrrt_t *c, int32_t n, float *states_devi
     if (int rc = settle_point(h)) return rc;
     if (int rc = flush_tail(h)) return rc;
     if (int rc = guard_foreign_overlap(h)) return rc;
-    const size_t B = h->p.B, N = (size_t)n;
-    if (n > h->cl_cap) {
-        BN_HIP(hipStreamSynchronize(h->stream));
-        h->cl_cap = 0;
-        if (int rc = h->cl_bufs.resize(&h->d_cl_log, ((N + 1) * 3 + N * 6) * B * sizeof(float), table_fail)) return rc;
-        if (int rc = fills_done()) return rc;
-        h->cl_cap = n;
-    }
-    const size_t cap = (size_t)h->cl_cap;
+    bn::EpisodeLog &lg = h->cl_log;
+    if (int rc = lg.reserve(h->cl_bufs, h->stream, n, table_fail)) return rc;
+    const ClFlags f = cl_flags(h);
     bn::ClrrtFollowArgs x{};
     x.rover = h->d_cl_rover; x.state = states_device; x.starts = v.starts; x.goal_nodes = h->d_cl_goal;
     x.path_actions = v.path_actions; x.path_states = v.path_states; x.results = v.results;
-    x.active = h->d_cl_flags; x.pending = h->d_cl_flags + B; x.psamples = v.samples;
+    x.active = f.active(); x.pending = f.pending(); x.psamples = v.samples;
     x.inj = samples_device; x.P = samples_device ? num_tables : 0; x.iters = v.iters; x.path_cap = v.path_cap;
-    float *lg = h->d_cl_log;
-    x.log_states = lg; x.log_reward = lg + (cap + 1) * B * 3; x.log_action = x.log_reward + cap * B; x.log_dev = x.log_action + cap * B * 2;
-    x.log_plan = reinterpret_cast<int32_t *>(x.log_dev + cap * B); x.log_event = x.log_plan + cap * B;
+    x.log = lg.columns(); x.log_dev = lg.extra(0);
+    x.log_plan = reinterpret_cast<int32_t *>(lg.extra(1)); x.log_event = reinterpret_cast<int32_t *>(lg.extra(2));
     x.z = z_device; x.iter0 = h->cl_iter; x.n = n; x.limit_steps = h->cl_limit_steps; x.use_lds = (flags & 1u) ? 0 : 1;
     x.xlo = v.cfg.x_limits[0]; x.xhi = v.cfg.x_limits[1]; x.ylo = v.cfg.y_limits[0]; x.yhi = v.cfg.y_limits[1];
     float ms_total = 0.0f;
@@ -288,7 +302,7 @@ int bn_clrrt_loop_run(bn_mppi_t *h, bn_clrrt_t *c, int32_t n, float *states_devi
         if (follow_ms) BN_HIP(hipEventRecord(h->cl_ev[0], h->stream));
         BN_HIP(bn::launch_clrrt_follow(h->p, x, h->stream));
         if (follow_ms) BN_HIP(hipEventRecord(h->cl_ev[1], h->stream));
-        BN_HIP(hipMemcpyAsync(h->h_cl_pending, h->d_cl_flags + B, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+        BN_HIP(hipMemcpyAsync(h->h_cl_pending, f.pending(), sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
         BN_HIP(hipStreamSynchronize(h->stream));
         if (follow_ms) {
             float ms = 0.0f;
@@ -296,12 +310,12 @@ int bn_clrrt_loop_run(bn_mppi_t *h, bn_clrrt_t *c, int32_t n, float *states_devi
             ms_total += ms;
         }
         if (*h->h_cl_pending == 0) break;
-        if (bn::clrrt_plan_masked(c, h->stream, h->d_cl_flags, samples_device ? 0 : 1) != BN_OK) return fail(BN_ERR_HIP, "%s", bn_clrrt_last_error());
-        BN_HIP(hipMemsetAsync(h->d_cl_flags + B, 0, sizeof(int32_t), h->stream));     // (the follow kernel clears the mask words it takes)
+        if (bn::clrrt_plan_masked(c, h->stream, f.active(), samples_device ? 0 : 1) != BN_OK) return fail(BN_ERR_HIP, "%s", bn_clrrt_last_error());
+        BN_HIP(hipMemsetAsync(f.pending(), 0, sizeof(int32_t), h->stream));     // (the follow kernel clears the mask words it takes)
     }
     if (follow_ms) *follow_ms = ms_total;
     h->cl_iter += n;
-    h->cl_len = n;
+    lg.len = n;
     return BN_OK;
 }
 
@@ -309,18 +323,16 @@ int bn_clrrt_loop_log(bn_mppi_t *h, float *states, float *rewards, float *action
                       int32_t *events, int32_t *done_iter, int32_t *status, int32_t *plans, int32_t *steps)
 {
     if (!h) return fail(BN_ERR_INVALID, "null handle");
-    if (!h->d_cl_log || h->cl_len < 1) return fail(BN_ERR_STATE, "no CL-RRT loop has been run");
+    const bn::EpisodeLog &lg = h->cl_log;
+    if (lg.empty()) return fail(BN_ERR_STATE, "no CL-RRT loop has been run");
     BN_BIND(h);
     if (int rc = settle_point(h)) return rc;
     BN_HIP(hipStreamSynchronize(h->stream));
-    const size_t B = h->p.B, n = (size_t)h->cl_len, cap = (size_t)h->cl_cap;
-    const float *lg = h->d_cl_log, *rw = lg + (cap + 1) * B * 3, *ac = rw + cap * B, *dv = ac + cap * B * 2, *pl = dv + cap * B, *ev = pl + cap * B;
-    if (states) BN_HIP(hipMemcpy(states, lg, (n + 1) * B * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    if (rewards) BN_HIP(hipMemcpy(rewards, rw, n * B * sizeof(float), hipMemcpyDeviceToHost));
-    if (actions) BN_HIP(hipMemcpy(actions, ac, n * B * 2 * sizeof(float), hipMemcpyDeviceToHost));
-    if (deviations) BN_HIP(hipMemcpy(deviations, dv, n * B * sizeof(float), hipMemcpyDeviceToHost));
-    if (plan_index) BN_HIP(hipMemcpy(plan_index, pl, n * B * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (events) BN_HIP(hipMemcpy(events, ev, n * B * sizeof(int32_t), hipMemcpyDeviceToHost));
+    const size_t B = h->p.B;
+    if (int rc = lg.copy_out(states, rewards, actions, table_fail)) return rc;
+    if (deviations) BN_HIP(hipMemcpy(deviations, lg.extra(0), lg.rows() * sizeof(float), hipMemcpyDeviceToHost));
+    if (plan_index) BN_HIP(hipMemcpy(plan_index, lg.extra(1), lg.rows() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (events) BN_HIP(hipMemcpy(events, lg.extra(2), lg.rows() * sizeof(int32_t), hipMemcpyDeviceToHost));
     std::vector<bn::ClrrtRover> r(B);
     BN_HIP(hipMemcpy(r.data(), h->d_cl_rover, B * sizeof(bn::ClrrtRover), hipMemcpyDeviceToHost));
     for (size_t b = 0; b < B; ++b) {
@@ -356,7 +368,7 @@ int bn_clrrt_loop_set_plans(bn_mppi_t *h, bn_clrrt_t *c, const float *actions, c
         if (iteration >= 0) r[b].iter = iteration;
     }
     BN_HIP(hipMemcpy(h->d_cl_rover, r.data(), B * sizeof(bn::ClrrtRover), hipMemcpyHostToDevice));
-    BN_HIP(hipMemset(h->d_cl_flags, 0, (B + 1) * sizeof(int32_t)));
+    BN_HIP(hipMemset(h->d_cl_flags, 0, ClFlags::count(B) * sizeof(int32_t)));
     if (iteration >= 0) h->cl_iter = iteration;
     return BN_OK;
 }

@@ -503,11 +503,7 @@ int bn_mppi_debug_expire_wait(bn_mppi_t *h)
     BN_HIP(hipMemset(h->d_cost_out, 0xff, B * K * 4));
     if (h->d_X) BN_HIP(hipMemset(h->d_X, 0xff, B * (T + 1) * 3 * (size_t)h->p.Kp * 4));
     if (h->d_ticket) BN_HIP(hipMemset(h->d_ticket, 0x01, B * 65 * 4));      // what two launches drawing tickets at once leave behind (recover_overlap)
-    if (h->d_ep_states && h->ep_len > 0) {
-        BN_HIP(hipMemset(h->d_ep_states, 0xff, (size_t)(h->ep_len + 1) * B * 3 * 4));
-        BN_HIP(hipMemset(h->d_ep_reward, 0xff, (size_t)h->ep_len * B * 4));
-        BN_HIP(hipMemset(h->d_ep_action, 0xff, (size_t)h->ep_len * B * 2 * 4));
-    }
+    if (!h->ep_log.empty()) BN_HIP(hipMemset(h->ep_log.block, 0xff, h->ep_log.floats(h->ep_log.cap) * 4));    // the episode's rows and the unused ones behind them
     *h->h_err = 1;
     h->overlap_used = true;
     return BN_OK;

@@ -198,9 +198,9 @@ LaunchDecision decide_pipelined(const bn_mppi *h, const SolveCall &c, LaunchDeci
     if (h->in_episode) {
         // closed loop: from the second step on, the rollout workgroups advance the state themselves
         r.env_on = 1;
-        r.closed_loop = (h->ep_len > 0 && h->tail_pending) ? 1 : 0;
-        r.ep_index = h->ep_len - 1;                                    // the env step applied / logged by this launch
-        r.env_z = (h->ep_z && h->ep_len > 0) ? 1 : 0;
+        r.closed_loop = (h->ep_log.len > 0 && h->tail_pending) ? 1 : 0;
+        r.ep_index = h->ep_log.len - 1;                                    // the env step applied / logged by this launch
+        r.env_z = (h->ep_z && h->ep_log.len > 0) ? 1 : 0;
     }
     r.wave_kernel = (h->wave_kernel && !h->in_episode) ? 1 : 0;
     r.lat_kernel = h->lat_kernel ? 1 : 0;
@@ -276,7 +276,7 @@ LaunchDecision decide_two_launches(const bn_mppi *h, const SolveCall &c, LaunchD
 int solve_pipelined(bn_mppi *h, bn::SolveParams &p, const SolveCall &c, const LaunchDecision &d0, const Prof &prof)
 {
     const LaunchDecision d = decide_pipelined(h, c, d0);
-    if (h->in_episode) h->ep_len += 1;
+    if (h->in_episode) h->ep_log.len += 1;
     h->self_tail_launched = d.lone_self;
     if (d.lone_self) {
         h->self_used = true;

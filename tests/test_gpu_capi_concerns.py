@@ -4,7 +4,9 @@
 1. Handles that use EVERY concern -- host-paced forward, closed-loop episode, DWA, the A* + DWA loop, the CL-RRT loop, the local
    half of the K-shard exchange -- leave the device's free memory where it was.
 2. The four DWA entry points share one scratch layout (DwaScratch, mppi_env.cpp): the views bn_mppi_dwa_buffers and
-   bn_mppi_dwa_candidates hand out point at what bn_mppi_dwa_solve wrote."""
+   bn_mppi_dwa_candidates hand out point at what bn_mppi_dwa_solve wrote.
+3. The three closed loops share one log layout (EpisodeLog, csrc/episode_log.h), laid out by the rows the log holds: the copies
+   and the device views of a call shorter than the log agree with a fresh handle's."""
 import ctypes as C
 import os
 
@@ -187,3 +189,85 @@ def test_dwa_views_point_at_what_dwa_solve_wrote():
         assert np.isfinite(out["costs"]).all() and len(np.unique(out["costs"])) > NB     # distinct rollouts: a shifted view would not match
         with pytest.raises(_capi.BenchnavError, match="no bn_mppi_dwa_solve with this num_actions has run"):
             pl.dwa_buffers(NA + 1)
+
+
+N_LONG, N_SHORT, NB = 7, 3, 2                  # a call that sizes the logs, then a shorter one on the same handle; two rovers
+
+
+def _bits(a):
+    a = np.ascontiguousarray(a)
+    return a.view(np.uint32) if a.dtype == np.float32 else a
+
+
+def _short_calls(fx, z, eps, long_first):
+    """The N_SHORT-row call of each closed loop on one planner handle -- behind an N_LONG-row call of the same loop from the same
+    start when `long_first` -- as its copies, its device views and (rows of the call, rows the log holds)."""
+    from benchnav_amd import CLRRT, AStarDWALoop, CLRRTLoop, NativeMPPI, _capi
+    from benchnav_amd.astar import _DevArray
+    from benchnav_amd.env import BatchedPlanetaryEnv
+    from helpers import FakeDynamics, FakeGridMap, FakeObjectives
+    risk = np.clip(fx["mean"], 0.0, 0.7).astype(np.float32)
+    dt = float(fx["delta_t"])
+    pl = NativeMPPI(horizon=T, num_samples=K, grid_size=G, resolution=RES, num_instances=NB, stuck_threshold=THR, stream=0)
+    env = BatchedPlanetaryEnv(pl, risk, np.full((G, G), float(fx["std"]), np.float32), fx["start"], fx["goal"], delta_t=dt,
+                              time_limit=float(fx["time_limit"]), stuck_threshold=THR, goal_threshold=float(fx["goal_threshold"]), seed=1,
+                              check_positions=False)                                      # the rovers differ by their slip draws
+    ad = AStarDWALoop(env, np.zeros((G, G), np.float32), risk, THR, (0.5, 0.5), dt, 3, 3, 1.0)
+    gm = FakeGridMap(G, RES)
+    iters, max_seqs, seed, _ = (int(v) for v in fx["params"])
+    cl = CLRRTLoop(env, CLRRT(3, 2, FakeDynamics(risk, gm), FakeObjectives(torch.as_tensor(fx["goal"].copy()), THR), gm, delta_t=dt,
+                              max_iterations=iters, max_seqs=max_seqs, seed=seed))
+    view = lambda p, shape, t="<f4": torch.as_tensor(_DevArray(p, shape, t), device="cuda").cpu().numpy().copy()
+    calls = (N_LONG, N_SHORT) if long_first else (N_SHORT,)
+    state0 = env.reset().cpu().numpy()
+    out = {}
+    for n in calls:                             # injected noise and a zero warm start: a call depends on nothing before it
+        pl.set_mean(None)
+        s, r, d = pl.episode(n, state0, z_device_ptr=z.data_ptr(), eps_ptr=eps.data_ptr(), kind=_capi.BN_NOISE_DEVICE_KT2,
+                             eps_ring=N_SHORT, eps_stride=eps[0].numel())
+    out["mppi"] = dict(states=s, rewards=r, actions=pl.last_actions, done_step=d)
+    ps, pr, pd, n, cap = pl.episode_buffers()
+    out["mppi_views"] = dict(states=view(ps, (n + 1, NB, 3)), rewards=view(pr, (n, NB)), done_step=view(pd, (NB,), "<i4"))
+    out["mppi_rows"] = (n, cap)
+    for n in calls:
+        env.reset()
+        log = ad.run(n, z=z[:n])
+    out["astar_dwa"] = dict(zip(("states", "rewards", "actions", "sub_goals", "done_step", "status"), log))
+    ps, pr, pd, pst, n, cap = ad.episode_buffers()
+    out["astar_dwa_views"] = dict(states=view(ps, (n + 1, NB, 3)), rewards=view(pr, (n, NB)), done_step=view(pd, (NB,), "<i4"),
+                                  status=view(pst, (NB,), "<i4"))
+    out["astar_dwa_rows"] = (n, cap)
+    for n in calls:
+        env.reset()
+        out["clrrt"] = cl.run(n, z=z[:n])
+    cl.close()
+    return out
+
+
+def test_episode_views_and_copies_agree_when_the_log_holds_more_rows_than_the_call_ran():
+    """A reader of a log that takes the call's rows for the log's rows (or the other way round) reads the wrong rows as soon as
+    the two differ: N_LONG rows, then N_SHORT on the same handle.  Every comparison is bit for bit."""
+    fx = np.load(os.path.join(HERE, "golden", "clrrt_loop.npz"))
+    rng = np.random.default_rng(11)
+    z = torch.from_numpy(rng.standard_normal((N_LONG, NB)).astype(np.float32)).cuda()
+    eps = torch.from_numpy(rng.standard_normal((N_SHORT, NB, K, T, 2)).astype(np.float32)).cuda()
+    torch.cuda.synchronize()
+    reused, fresh = _short_calls(fx, z, eps, True), _short_calls(fx, z, eps, False)
+    assert reused["mppi_rows"] == reused["astar_dwa_rows"] == (N_SHORT, N_LONG)
+    assert fresh["mppi_rows"] == fresh["astar_dwa_rows"] == (N_SHORT, N_SHORT)
+    for loop in ("mppi", "astar_dwa", "clrrt"):
+        assert reused[loop].keys() == fresh[loop].keys() and len(reused["clrrt"]) == 10
+        for k in fresh[loop]:
+            assert np.array_equal(_bits(reused[loop][k]), _bits(fresh[loop][k])), (loop, k)
+    for got in (reused, fresh):
+        for loop in ("mppi", "astar_dwa"):
+            for k, v in got[loop + "_views"].items():
+                assert v.shape == got[loop][k].shape and np.array_equal(_bits(v), _bits(got[loop][k])), (loop, k)
+    # the runs say something: the rovers move, the two differ, and the sub-goals are points of the path, not the goal (a shifted
+    # column would not match)
+    for loop in ("mppi", "astar_dwa", "clrrt"):
+        s = fresh[loop]["states"]
+        assert np.isfinite(s).all() and not np.array_equal(s[1:, 0], s[1:, 1]) and not np.array_equal(s[0], s[-1]), loop
+    assert (fresh["astar_dwa"]["status"] == 0).all() and np.isfinite(fresh["astar_dwa"]["rewards"]).all()        # BN_AD_OK
+    assert (fresh["astar_dwa"]["sub_goals"] != fx["goal"].astype(np.float32)).any(axis=-1).all()
+    assert (fresh["clrrt"]["plans"] >= 1).all() and (fresh["clrrt"]["steps"] >= 1).all()
