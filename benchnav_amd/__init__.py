@@ -21,7 +21,7 @@ from .native import NativeMPPI  # noqa: F401
 
 
 def __getattr__(name):
-    if name == "MPPI":          # torch is imported only when the torch-facing classes are used
+    if name == "MPPI":          # every class but NativeMPPI is imported when it is first used
         from .mppi import MPPI
         return MPPI
     if name == "DWA":

@@ -4,6 +4,7 @@ checks, the reference Tree's capacity rule, and the plumbing of the two tree pla
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import Optional
 
 import numpy as np
@@ -46,10 +47,11 @@ def tree_capacity(n: int) -> int:
     return cap
 
 
-def check(lib, family: str, code: int):
-    """Raise the family's last error for a negative code (some entry points return a count)."""
-    if code < 0:
-        raise _capi.BenchnavError(code, getattr(lib, f"bn_{family}_last_error")().decode("utf-8", "replace"))
+def check(lib, family: str, code: int, last_error: Optional[str] = None, nonzero: bool = False):
+    """Raise the family's last error (`last_error`, default bn_<family>_last_error) for a negative code -- some entry points
+    return a count -- or, with `nonzero`, for any code but 0."""
+    if code < 0 or (nonzero and code):
+        raise _capi.BenchnavError(code, getattr(lib, last_error or f"bn_{family}_last_error")().decode("utf-8", "replace"))
 
 
 def resolve_device(device, who: str, lenient: bool = False) -> torch.device:
@@ -67,18 +69,29 @@ def resolve_device(device, who: str, lenient: bool = False) -> torch.device:
 
 
 class Handle:
-    """One handle of the library's `family` (bn_<family>_destroy / _last_error).  The owner sets `_lib` and, from the family's
-    create call, `_handle` (a c_void_p); it is destroyed once -- by close(), by leaving a `with` block, or when the object goes."""
-    family = ""
-    _lib = None
-    _handle = None
+    """One handle of the library's `family` (bn_<family>_destroy / _last_error / _device_buffer).  The owner sets `_lib` and, from
+    the family's create call, `_handle` (a c_void_p); it is destroyed once -- by close(), by leaving a `with` block, or when the
+    object goes (also during interpreter shutdown, with module globals gone: __del__ swallows what that raises).  `last_error`
+    names the call that holds the family's error text if not bn_<family>_last_error; `nonzero_is_error`: not only negative codes raise."""
+    family, last_error, nonzero_is_error = "", None, False
+    _lib = _handle = dev = None              # dev: the torch device of the handle's memory, what buffer() and view() wrap for
+
+    def _create(self, lib, cfg) -> None:
+        """bn_<family>_create(&cfg, &handle), for a family created from a config struct: sets `_lib`, `_handle` and `dev`."""
+        self._lib, self.dev = lib, torch.device("cuda", cfg.device_id)
+        h = C.c_void_p()
+        self._check(getattr(lib, f"bn_{self.family}_create")(C.byref(cfg), C.byref(h)))
+        self._handle = h
 
     def _check(self, code: int) -> None:
-        check(self._lib, self.family, code)
+        if code:
+            check(self._lib, self.family, code, self.last_error, self.nonzero_is_error)
 
     def close(self) -> None:
-        if self._handle:
-            getattr(self._lib, f"bn_{self.family}_destroy")(self._handle)
+        h = self._handle
+        if h:
+            getattr(self._lib, f"bn_{self.family}_destroy")(h)
+            h.value = None                   # an alias the owner bound once (NativeMPPI._h) reads as closed too
         self._handle = None
 
     def __enter__(self):
@@ -93,6 +106,22 @@ class Handle:
         except Exception:
             pass
 
+    def device_buffer(self, which: int):
+        """(device pointer, bytes) of the family's buffer `which`."""
+        ptr, nbytes = C.c_void_p(), C.c_size_t()
+        self._check(getattr(self._lib, f"bn_{self.family}_device_buffer")(self._handle, which, C.byref(ptr), C.byref(nbytes)))
+        return ptr.value, nbytes.value
+
+    def view(self, ptr: int, shape, typestr="<f4") -> torch.Tensor:
+        """Library memory on `dev` as a tensor: for a pointer the library hands back without a buffer id."""
+        return torch.as_tensor(_DevArray(ptr, shape, typestr), device=self.dev)
+
+    def buffer(self, which: int, shape, typestr="<f4") -> torch.Tensor:
+        """The family's buffer `which` as a tensor of `shape`, which must account for every byte of it."""
+        ptr, nbytes = self.device_buffer(which)
+        assert math.prod(shape) * int(typestr[2:]) == nbytes, (which, tuple(shape), typestr, nbytes)
+        return self.view(ptr, shape, typestr)
+
 
 class _PlannerHandle(Handle):
     """One handle of a tree planner's `family` ("rrt", "clrrt": bn_<family>_create / _device_buffer): B instances of one
@@ -100,16 +129,8 @@ class _PlannerHandle(Handle):
     h = property(lambda self: self._handle)
 
     def __init__(self, lib, dev: torch.device, B: int, cfg):
-        self._lib, self.dev, self.B = lib, dev, B
-        self.used = False                    # a plan has run: its streams are seeded
-        h = C.c_void_p()
-        self._check(getattr(lib, f"bn_{self.family}_create")(C.byref(cfg), C.byref(h)))
-        self._handle = h
-
-    def buffer(self, which: int, shape, typestr="<f4") -> torch.Tensor:
-        ptr, nbytes = C.c_void_p(), C.c_size_t()
-        self._check(getattr(self._lib, f"bn_{self.family}_device_buffer")(self._handle, which, C.byref(ptr), C.byref(nbytes)))
-        return torch.as_tensor(_DevArray(ptr.value, shape, typestr), device=self.dev)
+        self._create(lib, cfg)
+        self.B, self.used = B, False         # used: a plan has run, its streams are seeded
 
 
 class _TreePlanner:

@@ -43,7 +43,7 @@ class CLRRTLoop:
         rovers' planner streams, reseeded at every reset (default: the planner's seed for each)."""
         self.env, self.planner = env, planner
         self.B = env.B
-        self._lib, self._h, self._dev = env._lib, env._h, env._dev
+        self._lib, self._h, self._dev = env.planner._lib, env.planner._h, env._dev
         if planner._dev != self._dev:
             raise ValueError(f"the planner is on {planner._dev}, the environment on {self._dev}")
         env._check_stream()

@@ -18,9 +18,8 @@ import torch.nn as nn
 
 import ctypes as C
 
-from . import _capi
-from ._device import resolve_device
-from .mppi import MPPI as _MPPI, _DevArray, _planner_inputs
+from ._device import Handle, resolve_device
+from .mppi import MPPI as _MPPI, _planner_inputs
 from .native import NativeMPPI
 
 
@@ -64,6 +63,12 @@ class DWA(nn.Module):
         self._solved = False
         self.reference_path: Optional[torch.Tensor] = None
         self._path_dev: Optional[torch.Tensor] = None
+
+    def close(self) -> None:
+        """Release the planner's library handle now (leaving a `with` block does; otherwise it goes with the object)."""
+        self._native.close()
+
+    __enter__, __exit__ = Handle.__enter__, Handle.__exit__        # (return self; close())
 
     # -- host geometry (tiny; torch-CPU like the reference so the numbers are the reference's) -----------------
     def _generate_actions(self) -> torch.Tensor:
@@ -130,10 +135,10 @@ class DWA(nn.Module):
             with torch.cuda.stream(self._stream):
                 if prev is not self._prev_seen[0] or prev._version != self._prev_seen[1]:      # assigned or modified by the caller (or the
                     self._prev_buf.copy_(prev[:1].to(self._device, self._dtype))               # initial zeros): mirror its first row
-                _capi.check(self._native._lib.bn_mppi_dwa_forward_async(
-                    self._native._h, state.data_ptr(), self._prev_buf.data_ptr(), self._a_lim_c, self._delta_t, self._num_lin_vel,
+                self._native.dwa_forward_async_device(
+                    state.data_ptr(), self._prev_buf.data_ptr(), self._a_lim_c, self._delta_t, self._num_lin_vel,
                     self._num_ang_vel, None if path is None else path.data_ptr(), 0 if path is None else path.shape[0],
-                    self._lookahead_distance, x_opt.data_ptr()))
+                    self._lookahead_distance, x_opt.data_ptr())
                 optimal_action_seq = self._prev_buf.clone()             # (1,2): the argmin action, written by the kernel
         self._keep = state
         self._previous_action_seq = optimal_action_seq                  # dwa.py:147
@@ -146,8 +151,8 @@ class DWA(nn.Module):
         Internal; the public attributes below hand out copies like the reference's fresh tensors (dwa.py:148-149)."""
         n = self._num_lin_vel * self._num_ang_vel
         xp, cp, wp = self._native.dwa_buffers(n)
-        return (torch.as_tensor(_DevArray(xp, (n, self._horizon + 1, 3)), device=self._device),
-                torch.as_tensor(_DevArray(cp, (n,)), device=self._device), torch.as_tensor(_DevArray(wp, (n,)), device=self._device))
+        view = self._native.view
+        return view(xp, (n, self._horizon + 1, 3)), view(cp, (n,)), view(wp, (n,))
 
     @property
     def _state_seq_batch(self) -> torch.Tensor:
@@ -172,11 +177,9 @@ class DWA(nn.Module):
     def last_candidates(self) -> Tuple[torch.Tensor, torch.Tensor]:
         """(actions (n,2), sub_goal (2,)) the latest forward() used, as computed on the device."""
         n = self._num_lin_vel * self._num_ang_vel
-        a, g = C.c_void_p(), C.c_void_p()
-        _capi.check(self._native._lib.bn_mppi_dwa_candidates(self._native._h, n, C.byref(a), C.byref(g)))
+        a, g = self._native.dwa_candidates(n)
         with _MPPI._Fence(self), torch.cuda.stream(self._stream):
-            return (torch.as_tensor(_DevArray(a.value, (n, 2)), device=self._device).clone(),
-                    torch.as_tensor(_DevArray(g.value, (2,)), device=self._device).clone())
+            return self._native.view(a, (n, 2)).clone(), self._native.view(g, (2,)).clone()
 
     def get_top_samples(self) -> Tuple[torch.Tensor, torch.Tensor]:
         """All candidates sorted by weight, best first (dwa.py:287-299)."""

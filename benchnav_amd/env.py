@@ -17,14 +17,10 @@ scope.  All tensors live on the planner's GPU; nothing returns to the host per c
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Optional, Tuple
 
 import numpy as np
 import torch
-
-from . import _capi
-from ._device import _DevArray
 
 
 def env_inputs(env) -> dict:
@@ -69,8 +65,6 @@ class BatchedPlanetaryEnv:
         self._freeze = bool(freeze_on_goal)
         self._dev = torch.device("cuda", planner.device_id)
         self.B = planner.B
-        self._lib = planner._lib
-        self._h = planner._h
         self._delta_t, self._time_limit = float(delta_t), float(time_limit)
         self.stuck_threshold = float(stuck_threshold)
         self._goal_threshold = float(goal_threshold)
@@ -136,9 +130,8 @@ class BatchedPlanetaryEnv:
         assert a.shape == (self.B, 2)
         zp = None if z is None else z.to(self._dev, torch.float32).contiguous()
         state = self._robot_state.clone()                          # the reference returns a new tensor every step
-        _capi.check(self._lib.bn_mppi_env_step(self._h, C.c_void_p(a.data_ptr()), C.c_void_p(state.data_ptr()),
-                                               C.c_void_p(self._reward.data_ptr()), C.c_void_p(self._terminated.data_ptr()),
-                                               C.c_void_p(None if zp is None else zp.data_ptr()), self._steps))
+        self.planner.env_step_device(a.data_ptr(), state.data_ptr(), self._reward.data_ptr(), self._terminated.data_ptr(),
+                                     None if zp is None else zp.data_ptr(), self._steps)
         self._keep = (a, zp)
         self._robot_state = state
         self._steps += 1
@@ -152,9 +145,8 @@ class BatchedPlanetaryEnv:
         assert s.dim() == 3 and s.shape[0] == self.B and s.shape[2] == 3
         out = torch.empty(self.B, s.shape[1], dtype=torch.uint8, device=self._dev)
         zp = None if z is None else z.to(self._dev, torch.float32).contiguous()
-        _capi.check(self._lib.bn_mppi_env_collision_check(self._h, C.c_void_p(s.data_ptr()), s.shape[1], self.stuck_threshold,
-                                                          C.c_void_p(None if zp is None else zp.data_ptr()), self._draws,
-                                                          C.c_void_p(out.data_ptr())))
+        self.planner.env_collision_check_device(s.data_ptr(), s.shape[1], self.stuck_threshold, None if zp is None else zp.data_ptr(),
+                                                self._draws, out.data_ptr())
         self._keep_c = (s, zp)
         self._draws += 1
         return out.bool()
@@ -166,7 +158,7 @@ class BatchedPlanetaryEnv:
         if not log:
             self.planner.episode(n_steps, self._robot_state.cpu().numpy(), wait=False)
             ptr = self.planner.episode_buffers()[0]
-            self._robot_state = torch.as_tensor(_DevArray(ptr, (n_steps + 1, self.B, 3)), device=self._dev)[-1].clone()
+            self._robot_state = self.planner.view(ptr, (n_steps + 1, self.B, 3))[-1].clone()
             self._steps += n_steps
             self._elapsed_time += n_steps * self._delta_t
             return None

@@ -19,6 +19,7 @@ import torch.nn as nn
 
 from . import _capi
 from ._device import _DevArray, resolve_device  # noqa: F401  (tests and tools import _DevArray from here)
+from ._mppi_handle import MPPIHandle, mppi_config
 
 
 def _raw_stream(dev_index: int) -> int:
@@ -80,8 +81,9 @@ def _planner_inputs(dynamics, objectives, sampled_slip=False):
                 goal=objectives._goal_pos, stuck_threshold=float(objectives._stuck_threshold))
 
 
-class MPPI(nn.Module):
-    """Model Predictive Path Integral control on one MI355X.
+class MPPI(MPPIHandle, nn.Module):
+    """Model Predictive Path Integral control on one MI355X.  Owns one library handle: `close()`, or a `with` block, releases
+    it before the object goes.
 
     Extra keyword arguments (not in the reference):
       noise  "torch_device"  (default) draw eps with torch's generator on the planner's device, as the
@@ -161,32 +163,20 @@ class MPPI(nn.Module):
 
         inp = _planner_inputs(dynamics, objectives, sampled_slip)
         lib = _capi.load()
-        cfg = _capi.Config()
-        lib.bn_mppi_config_init(C.byref(cfg))
-        cfg.device_id = dev.index
-        cfg.horizon, cfg.num_samples, cfg.num_instances = horizon, num_samples, 1
-        cfg.grid_size, cfg.resolution = inp["grid_size"], inp["resolution"]
         s_cpu = sigmas.detach().cpu().to(dtype)
-        umin, umax = dynamics.min_action.detach().cpu().to(dtype), dynamics.max_action.detach().cpu().to(dtype)
-        for i in range(2):
-            cfg.x_limits[i], cfg.y_limits[i] = inp["x_limits"][i], inp["y_limits"][i]
-            cfg.sigma[i], cfg.inv_var[i] = float(s_cpu[i]), float(inv_cov[i, i])
-            cfg.u_min[i], cfg.u_max[i] = float(umin[i]), float(umax[i])
-        cfg.lambda_, cfg.dt, cfg.stuck_threshold = lambda_, delta_t, inp["stuck_threshold"]
-        cfg.seed = seed
-        cfg.flags = ((_capi.BN_FLAG_STORE_CONTROLS if store_controls else 0) | (_capi.BN_FLAG_PROFILE if profile else 0)
-                     | (_capi.BN_FLAG_SAMPLED_SLIP if sampled_slip else 0) | (_capi.BN_FLAG_LEAN if lean else 0)
-                     | (_capi.BN_FLAG_REFERENCE_ORDER if reference_order else 0)
-                     | (_capi.BN_FLAG_HOST_PACED if (host_loop and noise == "philox") else 0)
-                     | (_capi.BN_FLAG_UNORDERED_OUTPUTS if (host_loop == "actions" and noise == "philox") else 0))
         self._lean = bool(lean)
         with torch.cuda.device(dev):
             self._stream = torch.cuda.current_stream(dev)
-            cfg.stream = self._stream.cuda_stream
             self._stream_id, self._dev_index = self._stream.cuda_stream, dev.index
-            self._handle = C.c_void_p()
-            _capi.check(lib.bn_mppi_create(C.byref(cfg), C.byref(self._handle)))
-        self._lib = lib
+            # the switches the reference-shaped planner has; the rest (shared_map, lds_window, pipeline, overlap, kernel) keep the library's defaults
+            self._create(lib, mppi_config(
+                lib, horizon=horizon, num_samples=num_samples, num_instances=1, grid_size=inp["grid_size"], resolution=inp["resolution"],
+                x_limits=inp["x_limits"], y_limits=inp["y_limits"], sigma=s_cpu.tolist(), inv_var=inv_cov.diagonal().tolist(),
+                lambda_=lambda_, u_min=dynamics.min_action.detach().cpu().to(dtype).tolist(),
+                u_max=dynamics.max_action.detach().cpu().to(dtype).tolist(), dt=delta_t, stuck_threshold=inp["stuck_threshold"], seed=seed,
+                device_id=dev.index, stream=self._stream_id, store_controls=store_controls, profile=profile, sampled_slip=sampled_slip,
+                lean=lean, reference_order=reference_order, host_paced=host_loop and noise == "philox",
+                unordered_outputs=host_loop == "actions" and noise == "philox"))
         risks = inp["risks"].detach().to(torch.float32).contiguous()
         assert risks.shape == (inp["grid_size"], inp["grid_size"])
         self.set_risk_map(risks)
@@ -194,21 +184,21 @@ class MPPI(nn.Module):
             std = inp["slip_std"].detach().to(torch.float32).contiguous()
             assert std.shape == risks.shape
             self._slip_std = std.to(dev)
-            _capi.check(lib.bn_mppi_set_slip_std(self._handle, 0, C.c_void_p(self._slip_std.data_ptr()), _capi.BN_MEM_DEVICE))
+            self._check(lib.bn_mppi_set_slip_std(self._handle, 0, C.c_void_p(self._slip_std.data_ptr()), _capi.BN_MEM_DEVICE))
         self.set_goal(inp["goal"])
 
         K, T = num_samples, horizon
         Kp = int(lib.bn_mppi_row_pitch(self._handle))        # rows are pitched to 64*ceil(K/64) floats
-        self._buf_X = None if lean else self._wrap(_capi.BN_BUF_STATES, (T + 1, 3, Kp))[:, :, :K]
+        self._buf_X = None if lean else self.buffer(_capi.BN_BUF_STATES, (T + 1, 3, Kp))[:, :, :K]
         self._host_loop = int(lib.bn_mppi_host_paced(self._handle)) >= 1
         self._unordered = self._host_loop and host_loop == "actions"
         # host-paced solves alternate between two trajectory / control buffers (two launches in flight): bn_mppi_states_buffer_index
-        self.__dict__["_buf_X_alt"] = self._wrap(_capi.BN_BUF_STATES_ALT, (T + 1, 3, Kp))[:, :, :K] if (self._host_loop and not lean) else None
-        self._buf_w = self._wrap(_capi.BN_BUF_WEIGHTS, (K,))
-        self._buf_cost = self._wrap(_capi.BN_BUF_COSTS, (K,))
-        self._buf_U = self._wrap(_capi.BN_BUF_CONTROLS, (T, 2, Kp))[:, :, :K] if store_controls else None
-        self.__dict__["_buf_U_alt"] = self._wrap(_capi.BN_BUF_CONTROLS_ALT, (T, 2, Kp))[:, :, :K] if (self._host_loop and store_controls) else None
-        self._buf_out = self._wrap(_capi.BN_BUF_USTAR_XSTAR, (T * 2 + (T + 1) * 3,))     # U* | X*, one block
+        self.__dict__["_buf_X_alt"] = self.buffer(_capi.BN_BUF_STATES_ALT, (T + 1, 3, Kp))[:, :, :K] if (self._host_loop and not lean) else None
+        self._buf_w = self.buffer(_capi.BN_BUF_WEIGHTS, (K,))
+        self._buf_cost = self.buffer(_capi.BN_BUF_COSTS, (K,))
+        self._buf_U = self.buffer(_capi.BN_BUF_CONTROLS, (T, 2, Kp))[:, :, :K] if store_controls else None
+        self.__dict__["_buf_U_alt"] = self.buffer(_capi.BN_BUF_CONTROLS_ALT, (T, 2, Kp))[:, :, :K] if (self._host_loop and store_controls) else None
+        self._buf_out = self.buffer(_capi.BN_BUF_USTAR_XSTAR, (T * 2 + (T + 1) * 3,))     # U* | X*, one block
         self._buf_ustar = self._buf_out[:T * 2].view(T, 2)
         self._buf_xstar = self._buf_out[T * 2:].view(1, T + 1, 3)
         self._n_out = T * 2 + (T + 1) * 3
@@ -216,7 +206,7 @@ class MPPI(nn.Module):
         self._fwd_state = lib.bn_mppi_forward_state_async       # ... for a state that lives on the host (test_mppi.py:174-181)
         self._h = self._handle.value
 
-        self._buf_mean = self._wrap(_capi.BN_BUF_MEAN, (T, 2))
+        self._buf_mean = self.buffer(_capi.BN_BUF_MEAN, (T, 2))
         self._cs = _CallState()
         self._n_out4 = self._n_out * 4
         self._fast_ok = noise == "philox" and bool(copy_outputs) and dtype == torch.float32        # forward()'s short path (a CPU state handed over by value)
@@ -230,28 +220,11 @@ class MPPI(nn.Module):
             self._cs.noise_cache = torch.randn(K, T, 2, device=dev) * self._sigmas
 
     # -- plumbing ------------------------------------------------------------------
-    def _wrap(self, buf_id, shape):
-        ptr, nbytes = C.c_void_p(), C.c_size_t()
-        _capi.check(self._lib.bn_mppi_device_buffer(self._handle, buf_id, C.byref(ptr), C.byref(nbytes)))
-        n = 1
-        for s in shape:
-            n *= s
-        assert n * 4 == nbytes.value, (shape, nbytes.value)
-        return torch.as_tensor(_DevArray(ptr.value, shape), device=self._device)
+    def close(self) -> None:
+        self.__dict__["_h"] = None             # forward() after close() hands the library NULL -- its "null handle" error -- not a freed handle
+        super().close()
 
-    def __del__(self):
-        try:                                   # also runs during interpreter shutdown, when module globals are gone
-            h = self.__dict__.get("_handle")
-            if h is not None and h.value:
-                self._lib.bn_mppi_destroy(h)
-                h.value = None
-        except Exception:
-            pass
-
-    @property
-    def arithmetic(self) -> str:
-        """'spec' (default: carried heading vector, fused transit) or 'reference_order' (robot_model.py:86-88 as written)."""
-        return "reference_order" if self._lib.bn_mppi_arithmetic(self._handle) == 1 else "spec"
+    arithmetic = property(MPPIHandle.arithmetic, doc=MPPIHandle.arithmetic.__doc__)       # an attribute here, like the reference's
 
     def set_risk_map(self, risks: torch.Tensor) -> None:
         """Replace the risk map (dynamics._traversability_model._risks, (G,G) [iy,ix])."""
@@ -259,12 +232,12 @@ class MPPI(nn.Module):
         where = _capi.BN_MEM_DEVICE if r.is_cuda else _capi.BN_MEM_HOST
         if r.is_cuda:
             torch.cuda.current_stream(r.device).synchronize()
-        _capi.check(self._lib.bn_mppi_set_map(self._handle, 0, C.c_void_p(r.data_ptr()), where))
+        self._check(self._lib.bn_mppi_set_map(self._handle, 0, C.c_void_p(r.data_ptr()), where))
 
     def set_goal(self, goal_pos) -> None:
         g = torch.as_tensor(goal_pos).detach().to("cpu", torch.float32).contiguous()   # int64 goals promote (test_mppi.py:133)
         assert g.shape == (2,)
-        _capi.check(self._lib.bn_mppi_set_goal(self._handle, 0, C.cast(g.data_ptr(), C.POINTER(C.c_float))))
+        self._check(self._lib.bn_mppi_set_goal(self._handle, 0, C.cast(g.data_ptr(), C.POINTER(C.c_float))))
 
     # -- reference attributes --------------------------------------------------------
     @property
@@ -274,7 +247,7 @@ class MPPI(nn.Module):
 
     @_previous_action_seq.setter
     def _previous_action_seq(self, value: torch.Tensor) -> None:
-        _capi.check(self._lib.bn_mppi_flush(self._handle))            # the mean buffer is authoritative after a flush
+        self._check(self._lib.bn_mppi_flush(self._handle))            # the mean buffer is authoritative after a flush
         self._buf_mean.copy_(torch.as_tensor(value).to(self._device, self._dtype))
 
     @property
@@ -296,22 +269,22 @@ class MPPI(nn.Module):
         paced by the host's store, not by the stream, so reads still queued there would see the next solve's values.  It is cancelled
         here (bn_mppi_flush, which also orders the stream behind the latest solve): the next forward() enqueues its solve on the stream,
         behind those reads, and prelaunches the one after it again.  Same results; forward() + first_action() alone keep their pace."""
-        _capi.check(self._lib.bn_mppi_flush(self._handle))
+        self._check(self._lib.bn_mppi_flush(self._handle))
 
     def order_outputs(self) -> None:
         """host_loop="actions": order torch's stream behind the latest solve -- before torch work that consumes the tensors forward()
         returned.  A no-op otherwise; the loop keeps its pace (the launch that waits for the next state is left alone)."""
-        _capi.check(self._lib.bn_mppi_order_outputs(self._handle))
+        self._check(self._lib.bn_mppi_order_outputs(self._handle))
 
     def release(self) -> None:
         """End a `host_loop` loop: cancels the launch that waits on the device for the next state (a word in pinned memory, no
         synchronisation) and enqueues anything pending.  Every other method of the planner but forward() / first_action() does the same."""
-        _capi.check(self._lib.bn_mppi_flush(self._handle))
+        self._check(self._lib.bn_mppi_flush(self._handle))
 
     def _reroll(self, idx: Optional[torch.Tensor], n: int) -> torch.Tensor:
         out = torch.empty(n, self._horizon + 1, 3, device=self._device, dtype=self._dtype)
         with self._on_planner_stream():
-            _capi.check(self._lib.bn_mppi_reroll_async(self._handle, 0, None if idx is None else idx.data_ptr(), n, out.data_ptr()))
+            self._check(self._lib.bn_mppi_reroll_async(self._handle, 0, None if idx is None else idx.data_ptr(), n, out.data_ptr()))
         return out
 
     @property
@@ -484,7 +457,7 @@ class MPPI(nn.Module):
         cs.eps = eps.detach().to(self._device, self._dtype).contiguous()
         cs.noise_cache, cs.rolled, cs.state = None, None, st
         with self._on_planner_stream():
-            _capi.check(self._fwd(self._h, st.data_ptr(), cs.eps.data_ptr(), _capi.BN_NOISE_DEVICE_KT2, None))
+            self._check(self._fwd(self._h, st.data_ptr(), cs.eps.data_ptr(), _capi.BN_NOISE_DEVICE_KT2, None))
         return self._buf_ustar.clone(), self._buf_xstar.clone()
 
     def get_top_samples(self, num_samples: int) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -500,11 +473,6 @@ class MPPI(nn.Module):
         return top_samples[order], top_weights[order]
 
     # -- measurement helpers -------------------------------------------------------------
-    def kernel_ms(self):
-        r, f, n = C.c_float(), C.c_float(), C.c_int32()
-        _capi.check(self._lib.bn_mppi_kernel_ms(self._handle, C.byref(r), C.byref(f), C.byref(n)))
-        return r.value, f.value, n.value
-
-    def algorithmic_bytes(self) -> int:
-        kind = _capi.BN_NOISE_PHILOX if self._noise_mode == "philox" else _capi.BN_NOISE_DEVICE_KT2
-        return int(self._lib.bn_mppi_algorithmic_bytes(self._handle, kind))
+    def algorithmic_bytes(self, injected_noise: Optional[bool] = None, window: bool = False) -> int:
+        """MPPIHandle.algorithmic_bytes, by default for the noise this planner runs with."""
+        return super().algorithmic_bytes(self._noise_mode != "philox" if injected_noise is None else injected_noise, window)

@@ -170,15 +170,11 @@ class ShardedMPPI:
         self._dist.all_reduce(t, op=self._dist.ReduceOp.MIN, group=group)
         return bool(int(t.item()))
 
-    def _view(self, ptr, shape):
-        from .mppi import _DevArray
-        return torch.as_tensor(_DevArray(ptr, shape), device=self.device)
-
     def _partials_tensor(self):
         ptr, n, ps = self.planner.shard_partials()
         v = self._views.get(ptr)
         if v is None:
-            v = self._views[ptr] = self._view(ptr, (n, ps))
+            v = self._views[ptr] = self.planner.view(ptr, (n, ps))
         return v
 
     def solve(self, state_dev: torch.Tensor, eps_dev: Optional[torch.Tensor] = None, kind: Optional[int] = None):
@@ -216,8 +212,8 @@ class ShardedMPPI:
         """(U* (T,2), X* (T+1,3)) of the latest solve as device tensors (views of planner memory, stream-ordered)."""
         from . import _capi
         self.planner.flush()                             # (library-enqueued exchange: joins the side-stream tail; enqueue only)
-        us = self._view(self.planner.device_buffer(_capi.BN_BUF_USTAR)[0], (self.T, 2))
-        xs = self._view(self.planner.device_buffer(_capi.BN_BUF_XSTAR)[0], (self.T + 1, 3))
+        us = self.planner.view(self.planner.device_buffer(_capi.BN_BUF_USTAR)[0], (self.T, 2))
+        xs = self.planner.view(self.planner.device_buffer(_capi.BN_BUF_XSTAR)[0], (self.T + 1, 3))
         return us, xs
 
     def close(self):

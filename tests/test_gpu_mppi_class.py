@@ -172,3 +172,58 @@ def test_first_action_is_the_first_row_of_the_optimal_action_sequence():
             pl.sync()
             for b in range(B):
                 assert np.array_equal(firsts[b], pl.get_mean(b)[0]), (n, b)
+
+
+# ---- the handle the classes own: K = 64, T = 4, G = 16, the smallest shapes the kernels accept ---------------------------------
+def _small_problem():
+    from helpers import FakeDynamics, FakeGridMap, FakeObjectives
+    G = 16
+    iy, ix = np.mgrid[0:G, 0:G]
+    risk = (((ix * 7 + iy * 3) % 11) / 16.0).astype(np.float32)          # inline risk map, no two neighbours alike
+    risk[6:9, 9:12] = 1.0
+    gm = FakeGridMap(G, 0.5)
+    return risk, FakeDynamics(risk, gm), FakeObjectives(torch.tensor([6.5, 6.0]), 0.3), torch.tensor([1.25, 1.5, 0.3])
+
+
+def test_drop_in_class_and_numpy_level_planner_agree_bit_for_bit():
+    """One config function behind both constructors: with sigma = (0.5, 0.5) the inverted covariance and float32 1/(s*s) are the
+    same 4.0, so MPPI(noise="philox") and NativeMPPI with the same seed, on the same stream, solve identically, warm starts included."""
+    from benchnav_amd import MPPI, NativeMPPI
+    K, T, seed = 64, 4, 11
+    risk, dyn, obj, state = _small_problem()
+    with MPPI(T, K, 3, 2, dyn, obj, torch.tensor([0.5, 0.5]), 0.5, seed=seed, noise="philox") as solver, \
+            NativeMPPI(horizon=T, num_samples=K, grid_size=16, resolution=0.5, seed=seed,
+                       stream=torch.cuda.current_stream().cuda_stream) as pl:
+        assert solver._inv_covariance.diagonal().tolist() == [4.0, 4.0]
+        pl.set_map(risk); pl.set_goal([6.5, 6.0])
+        for i in range(3):
+            st = state + torch.tensor([0.05 * i, 0.04 * i, 0.01 * i])
+            U, X = solver.forward(st)
+            us, xs = pl.solve(st.numpy())
+            assert np.array_equal(U.cpu().numpy(), us[0]) and np.array_equal(X[0].cpu().numpy(), xs[0]), i
+        assert np.abs(us[0]).max() > 0 and not np.array_equal(xs[0][0], xs[0][-1])
+
+
+def test_with_block_releases_the_handle_of_every_owner():
+    from benchnav_amd import MPPI, NativeMPPI
+    from benchnav_amd.dwa import DWA
+    risk, dyn, obj, state = _small_problem()
+    with MPPI(4, 64, 3, 2, dyn, obj, torch.tensor([0.5, 0.5]), 0.5, noise="philox") as p:
+        U, _ = p.forward(state)
+        assert torch.isfinite(U).all() and bool(p._handle)
+    assert not p._handle
+    with pytest.raises(RuntimeError, match="null handle"):               # a closed planner refuses, it does not touch freed memory
+        p.forward(state)
+    del p
+    with DWA(4, 3, 2, dyn, obj, torch.tensor([0.5, 1.0]), 0.1) as d:
+        u, x = d.forward(state.cuda())
+        assert u.shape == (1, 2) and torch.isfinite(x).all() and bool(d._native._h)
+    assert not d._native._h and not d._native._handle
+    del d
+    with NativeMPPI(horizon=4, num_samples=64, grid_size=16, resolution=0.5) as pl:
+        pl.set_map(risk); pl.set_goal([6.5, 6.0])
+        us, _ = pl.solve(state.numpy())
+        assert np.isfinite(us).all() and bool(pl._h)
+    assert not pl._h and not pl._handle
+    pl.close()                                                           # once more: nothing left to destroy
+    del pl
