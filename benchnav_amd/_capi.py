@@ -232,6 +232,7 @@ SYMBOLS = {
     "bn_clrrt_create": (C.c_int, [C.POINTER(CLRRTConfig), C.POINTER(_H)]),
     "bn_clrrt_destroy": (None, [_H]),
     "bn_clrrt_set_map": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_double]),
+    "bn_clrrt_set_instance_maps": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.c_double]),
     "bn_clrrt_plan_async": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bn_clrrt_grow_from_samples_async": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "bn_clrrt_steer_async": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -242,6 +243,9 @@ SYMBOLS = {
     "bn_clrrt_loop_reset": (C.c_int, [_H, _H, C.c_void_p, C.c_void_p, C.c_double, C.c_double]),
     "bn_clrrt_loop_run": (C.c_int, [_H, _H, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, _FP]),
     "bn_clrrt_loop_log": (C.c_int, [_H] + [C.c_void_p] * 10),
+    "bn_clrrt_loop_episode_buffers": (C.c_int, [_H, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                                C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "bn_clrrt_loop_rover_buffers": (C.c_int, [_H, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "bn_clrrt_loop_set_plans": (C.c_int, [_H, _H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),
     "bn_gp_max_points": (C.c_int32, []),
     "bn_gp_create": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double,

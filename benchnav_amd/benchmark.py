@@ -11,11 +11,17 @@ freeze_on_goal, and `score_episodes` reduces the log to per-episode figures on t
 reaches the host; the score arrays are collected once, at the end of the run.
 
 Episode e = m * trials + r (map m, trial r) is instance e % chunk of chunk e // chunk.  Chunk j's environment seed is
-(seed + j) mod 2^64 and map m's risk seed (seed + m) mod 2^64, so a report is a function of (seed, chunk, trials), which it stores.
+(seed + j) mod 2^64, map m's risk seed (seed + m) mod 2^64 and episode e's CL-RRT stream seed (seed + e) mod 2^32, so a report is a
+function of (seed, chunk, trials), which it stores.
 An episode whose start or goal is not traversable (one collision draw each, as PlanetaryEnv.__init__ makes them) is INVALID: it is
 kept, counted, and left out of every rate and mean.
 
-The module's arithmetic rules (`max_steps`, `episode_slot`, the seed rules, `parse_setting`) need no device.
+A "cl_rrt" run drives `CLRRTLoop` on per-rover risk maps: its log has a row per loop ITERATION, of which a flagged replan takes
+one without a step, so it runs `clrrt_iterations(max_steps)` rows; a rover the planner fails (no plan, no sequence, a plan run out,
+a path too long, out of bounds) is STOPPED, alone.
+
+The module's arithmetic rules (`max_steps`, `clrrt_iterations`, `episode_slot`, the seed rules, `clrrt_outcome_words`,
+`parse_setting`) need no device.
 """
 from __future__ import annotations
 
@@ -33,11 +39,12 @@ from ._device import check, resolve_device, stream_ptr
 GOAL, TIME_LIMIT, STOPPED, INVALID = (_capi.BN_OUTCOME_GOAL, _capi.BN_OUTCOME_TIME_LIMIT, _capi.BN_OUTCOME_STOPPED,
                                       _capi.BN_OUTCOME_INVALID)
 OUTCOMES = ("GOAL", "TIME_LIMIT", "STOPPED", "INVALID")          # indexed by the outcome code
-PLANNERS = ("mppi", "astar_dwa")
+PLANNERS = ("mppi", "astar_dwa", "cl_rrt")
 # the per-episode arrays of score_episodes and of a Report, with their dtypes
 FIELDS = (("outcome", torch.int32), ("steps", torch.int32), ("time", torch.float64), ("path_length", torch.float64),
           ("reward_sum", torch.float64), ("reward_min", torch.float32), ("stuck_steps", torch.int32), ("final_distance", torch.float64))
 _MASK64 = (1 << 64) - 1
+_MASK32 = (1 << 32) - 1
 
 
 # ---- the rules that need no device ---------------------------------------------------------------------------------------------
@@ -55,6 +62,15 @@ def max_steps(time_limit: float, delta_t: float) -> int:
     return k
 
 
+def clrrt_iterations(max_steps: int) -> int:
+    """Loop iterations that end every CL-RRT rover: 2 * max_steps.  An iteration takes a step, flags a replan or finds the rover
+    stopped.  The iteration behind a plan never flags one -- the plan's first stored state lies within two transit steps, at most
+    0.2 m with the reference's action bounds, of the state it was planned from, and the flag needs a deviation above 1 m
+     -- so of two successive iterations of a running rover at least one steps, and the max_steps-th step is the
+    time limit.  A campaign does not lean on it: it raises if a rover is still running."""
+    return 2 * int(max_steps)
+
+
 def episode_slot(episode: int, chunk: int) -> Tuple[int, int]:
     """(chunk index, instance within the chunk) of episode e = m * trials + r."""
     return int(episode) // int(chunk), int(episode) % int(chunk)
@@ -68,6 +84,20 @@ def chunk_seed(seed: int, chunk_index: int) -> int:
 def risk_seed(seed: int, map_index: int) -> int:
     """The Philox seed of map m's risk samples."""
     return (int(seed) + int(map_index)) & _MASK64
+
+
+def planner_seed(seed: int, episode: int) -> int:
+    """The seed of episode e's CL-RRT sample stream (MT19937 takes 32 bits)."""
+    return (int(seed) + int(episode)) & _MASK32
+
+
+def clrrt_outcome_words(status, done_iter) -> Tuple[np.ndarray, np.ndarray]:
+    """A CLRRTLoop's per-rover words as score_episodes takes them: (done_step, stopped), int32.  done_step is done_iter where the
+    status is BN_CL_GOAL, else -1; stopped is the status where it is neither RUNNING, GOAL nor TIME_LIMIT, else 0.  The rule the
+    loop's device words follow (CLRRTLoop.episode_buffers)."""
+    status, done_iter = np.asarray(status, np.int32), np.asarray(done_iter, np.int32)
+    regular = (status == _capi.BN_CL_RUNNING) | (status == _capi.BN_CL_GOAL) | (status == _capi.BN_CL_TIME_LIMIT)
+    return (np.where(status == _capi.BN_CL_GOAL, done_iter, -1).astype(np.int32), np.where(regular, 0, status).astype(np.int32))
 
 
 def parse_setting(setting) -> Tuple[str, Optional[float]]:
@@ -146,7 +176,8 @@ def score_episodes(states, rewards, goals, end_step, done_step, stopped=None, in
 # ---- the report ----------------------------------------------------------------------------------------------------------------------
 class Report:
     """Per-episode arrays shaped (C, M, trials) -- outcome, steps, time, path_length, reward_sum, reward_min, stuck_steps,
-    final_distance -- for the C settings of one run, with what the run was a function of: seed, chunk, trials."""
+    final_distance -- for the C settings of one run, with what the run was a function of: seed, chunk, trials.  A "cl_rrt" run
+    also has `plans` (C, M, trials) int32, the planner's forward calls per episode; for the other planners it is None."""
 
     def __init__(self, planner: str, settings: Sequence[Tuple[str, Optional[float]]], arrays: Dict[str, np.ndarray], seed: int, chunk: int,
                  trials: int, max_steps: int, delta_t: float, time_limit: float) -> None:
@@ -155,6 +186,7 @@ class Report:
         self.delta_t, self.time_limit = float(delta_t), float(time_limit)
         for name, _ in FIELDS:
             setattr(self, name, arrays[name])
+        self.plans = arrays.get("plans")
 
     def summary(self) -> List[dict]:
         """Per setting: the counts of the four outcomes, their rates over the non-INVALID episodes, mean and median time to goal
@@ -189,9 +221,12 @@ class Report:
 
     def to_dict(self) -> dict:
         listed = lambda a: [[[None if isinstance(v, float) and v != v else v for v in row] for row in m] for m in a.tolist()]
-        return {"planner": self.planner, "settings": [setting_name(s) for s in self.settings], "seed": self.seed, "chunk": self.chunk,
-                "trials": self.trials, "max_steps": self.max_steps, "delta_t": self.delta_t, "time_limit": self.time_limit,
-                "outcomes": list(OUTCOMES), "summary": self.summary(), "episodes": {name: listed(getattr(self, name)) for name, _ in FIELDS}}
+        doc = {"planner": self.planner, "settings": [setting_name(s) for s in self.settings], "seed": self.seed, "chunk": self.chunk,
+               "trials": self.trials, "max_steps": self.max_steps, "delta_t": self.delta_t, "time_limit": self.time_limit,
+               "outcomes": list(OUTCOMES), "summary": self.summary(), "episodes": {name: listed(getattr(self, name)) for name, _ in FIELDS}}
+        if self.plans is not None:
+            doc["episodes"]["plans"] = self.plans.tolist()
+        return doc
 
     def to_json(self, path: str) -> None:
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
@@ -250,6 +285,8 @@ class Benchmark:
         kw = dict(kw)
         if kind == "astar_dwa":
             kw = {"horizon": kw.get("horizon", 10), "num_samples": 64}       # the DWA rolls its candidates out on this handle's kernels
+        elif kind == "cl_rrt":
+            kw = {"horizon": 8, "num_samples": 64}                           # the handle carries the environment; nothing solves on it
         else:
             kw.setdefault("horizon", 50)
             kw.setdefault("num_samples", 1024)
@@ -259,17 +296,22 @@ class Benchmark:
     def run(self, planner: str, settings, **planner_kwargs) -> Report:
         """Every episode of the split under every setting.  planner "mppi": planner_kwargs go to NativeMPPI (horizon, num_samples,
         sigmas, lambda_, seed, ...).  "astar_dwa": horizon (10), a_lim ((0.5, 0.5)), dwa_delta_t (delta_t), num_lin_vel (10),
-        num_ang_vel (10), lookahead_distance (1.0), walk ("serial"); the A* planner reads the split's heights."""
+        num_ang_vel (10), lookahead_distance (1.0), walk ("serial"); the A* planner reads the split's heights.  "cl_rrt": the
+        reference CLRRT's max_iterations (500), max_seqs (250), delta_distance (5), goal_sample_rate (0.25) and path_cap (None);
+        a rover still running after clrrt_iterations(max_steps) iterations raises."""
         from .env import BatchedPlanetaryEnv
         if planner not in PLANNERS:
-            raise ValueError(f"planner must be one of {PLANNERS} (a CL-RRT campaign needs per-rover risk maps in its kernels: DESIGN.md 8)")
+            raise ValueError(f"planner must be one of {PLANNERS}")
         settings = [parse_setting(s) for s in settings]
         ds, dev, n = self.dataset, self.dev, self.max_steps
+        rows = clrrt_iterations(n) if planner == "cl_rrt" else n       # rows of an episode's log
         E, Cn = self.M * self.trials, len(settings)
         with torch.cuda.device(dev):
             risk = self.risk_maps(settings)
             total = {name: torch.empty(Cn, E, device=dev, dtype=dt) for name, dt in FIELDS}
+            words = {name: torch.empty(Cn, E, device=dev, dtype=torch.int32) for name in ("status", "plans")} if planner == "cl_rrt" else {}
             handles: Dict[int, object] = {}
+            rrts: Dict[int, object] = {}
             try:
                 for j in range((E + self.chunk - 1) // self.chunk):
                     e0 = j * self.chunk
@@ -288,14 +330,20 @@ class Benchmark:
                     bad_goal = env.collision_check(at(env._goal_pos))[:, 0]
                     invalid = (bad_start | bad_goal).to(torch.uint8).contiguous()
                     loops = []
+                    if planner == "cl_rrt":                            # one loop per chunk: its rovers' maps change with the setting
+                        if B not in rrts:
+                            rrts[B] = self._clrrt(pl, planner_kwargs)
+                        loops.append(self._clrrt_loop(env, rrts[B], e0))
                     for c in range(Cn):
                         chunk_risk = risk[c, idx].contiguous()
                         if planner == "mppi":
                             for b in range(B):
                                 pl.set_map_device(chunk_risk[b].data_ptr(), b)
+                        elif planner == "cl_rrt":
+                            loops[0].set_risk_maps(chunk_risk)
                         else:                                          # (the loop sets the planner's maps and solves A* on them)
                             loops.append(self._astar_dwa(env, ds.heights[idx], chunk_risk, planner_kwargs))
-                        env.reset(seed=chunk_seed(self.seed, j))
+                        env.reset(seed=chunk_seed(self.seed, j))       # (resets the chunk's loop too)
                         pl.set_mean(None)
                         out = {name: t[c, e0:e0 + B] for name, t in total.items()}
                         if planner == "mppi":
@@ -303,18 +351,42 @@ class Benchmark:
                             states, rewards, done, _, _ = pl.episode_buffers()
                             stopped = None
                         else:
-                            loops[-1].run(n, log=False)
+                            loops[-1].run(rows, log=False)
                             states, rewards, done, stopped, _, _ = loops[-1].episode_buffers()
-                        _score_pointers(dev, n, B, states, rewards, env._goal_pos.data_ptr(), None, done, stopped, invalid.data_ptr(),
+                        _score_pointers(dev, rows, B, states, rewards, env._goal_pos.data_ptr(), None, done, stopped, invalid.data_ptr(),
                                         self.stuck_threshold, self.delta_t, out)
+                        if planner == "cl_rrt":
+                            for name, view in zip(("status", "plans"), loops[0].rover_buffers()):
+                                words[name][c, e0:e0 + B].copy_(view)
                     torch.cuda.current_stream(dev).synchronize()       # the chunk's scores are written: its loops and maps may go
                     for loop in loops:
                         loop.close()
                 arrays = {name: t.cpu().numpy().reshape(Cn, self.M, self.trials) for name, t in total.items()}
+                if planner == "cl_rrt":
+                    running = np.argwhere(words["status"].cpu().numpy() == _capi.BN_CL_RUNNING)
+                    if running.size:
+                        c, e = (int(v) for v in running[0])
+                        raise RuntimeError(f"episode {e} under setting {setting_name(settings[c])} is still running after {rows} loop iterations "
+                                           f"({len(running)} such episodes): clrrt_iterations' bound does not hold")
+                    arrays["plans"] = words["plans"].cpu().numpy().reshape(Cn, self.M, self.trials)
             finally:
                 for pl in handles.values():
                     pl.close()
         return Report(planner, settings, arrays, self.seed, self.chunk, self.trials, n, self.delta_t, self.time_limit)
+
+    def _clrrt(self, pl, kw: dict):
+        """The chunk size's CLRRT, on the grid, limits and action bounds of the environment's handle."""
+        from .clrrt import CLRRT
+        unknown = set(kw) - {"max_iterations", "max_seqs", "delta_distance", "goal_sample_rate", "path_cap"}
+        if unknown:
+            raise TypeError(f"unknown cl_rrt keywords: {sorted(unknown)}")
+        return CLRRT.from_parameters(self.G, self.resolution, pl.x_limits, pl.y_limits, stuck_threshold=self.stuck_threshold,
+                                     delta_t=self.delta_t, goal_threshold=self.goal_threshold, device=str(self.dev), seed=self.seed & _MASK32,
+                                     **kw)
+
+    def _clrrt_loop(self, env, rrt, e0: int):
+        from .clrrt_loop import CLRRTLoop
+        return CLRRTLoop(env, rrt, seeds=[planner_seed(self.seed, e0 + i) for i in range(env.B)])
 
     def _astar_dwa(self, env, heights, risks, kw: dict):
         from .astar_dwa import AStarDWALoop

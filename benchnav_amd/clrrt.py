@@ -14,6 +14,8 @@ the device, seeded like the reference's and continued across forward() calls.
     planner = CLRRT(3, 2, dynamics, objectives, grid_map, delta_t=0.1, max_iterations=500, seed=42)
     action_seq, state_seq = planner(state)               # (L, 2), (1, L + 1, 3) or (None, None), as the reference
     actions, states, lengths, found = planner.plan_batch(states, goals, seeds)       # B planners per launch
+    ... = planner.plan_batch(states, goals, seeds, risk_maps=maps)                   # ... each on its own (G, G) risk map
+    planner = CLRRT.from_parameters(64, 0.5, delta_t=0.1, stuck_threshold=0.1)       # without reference-shaped objects
 """
 from __future__ import annotations
 
@@ -25,7 +27,7 @@ import torch
 import torch.nn as nn
 
 from . import _capi
-from ._device import _PlannerHandle, _TreePlanner, _check_seed, check, resolve_device, seed_array, tree_capacity
+from ._device import _PlannerHandle, _TreePlanner, _check_seed, check, resolve_device, seed_array, stream_ptr, tree_capacity
 
 WORDS = ("LSL", "RSR", "RSL", "LSR", "RLR", "LRL")
 _POINTS = 64
@@ -62,7 +64,7 @@ def _check(lib, code: int):
 
 
 class _Handle(_PlannerHandle):
-    """One bn_clrrt handle: B instances of one parameter set on one map."""
+    """One bn_clrrt handle: B instances of one parameter set, on the owner's map or (set_maps) on one map each."""
     family = "clrrt"
 
     def __init__(self, lib, dev: torch.device, B: int, owner: "CLRRT"):
@@ -81,8 +83,33 @@ class _Handle(_PlannerHandle):
         self.iters, self.S = owner._max_iterations, owner._max_seqs
         super().__init__(lib, dev, B, cfg)
         self.path_cap = int(lib.bn_clrrt_path_cap(self.h))
-        goal = np.ascontiguousarray(owner._goal_host.numpy()[:2], np.float32)
-        self._check(lib.bn_clrrt_set_map(self.h, owner._risk.ctypes.data, goal.ctypes.data, float(owner._stuck_threshold)))
+        self.G, self.per_instance = owner._grid_size, False
+        self._shared = (owner._risk, np.ascontiguousarray(owner._goal_host.numpy()[:2], np.float32), float(owner._stuck_threshold))
+        self._set_shared()
+
+    def _set_shared(self):
+        risk, goal, thr = self._shared
+        self._check(self._lib.bn_clrrt_set_map(self.h, risk.ctypes.data, goal.ctypes.data, thr))
+        self.per_instance = False
+
+    def set_maps(self, risk_maps=None):
+        """risk_maps (B, G, G) float32 -- a torch tensor on the host or the device (copied device to device on torch's current
+        stream), or a NumPy array -- become the instances' own maps; None returns the handle to the owner's shared map."""
+        if risk_maps is None:
+            if self.per_instance:
+                self._set_shared()
+            return
+        if isinstance(risk_maps, torch.Tensor) and risk_maps.is_cuda:
+            keep = risk_maps.detach().to(self.dev, torch.float32).contiguous()
+            where, ptr = _capi.BN_MEM_DEVICE, keep.data_ptr()
+        else:
+            host = risk_maps.detach().numpy() if isinstance(risk_maps, torch.Tensor) else risk_maps
+            keep = np.ascontiguousarray(host, np.float32)
+            where, ptr = _capi.BN_MEM_HOST, keep.ctypes.data
+        if tuple(keep.shape) != (self.B, self.G, self.G):
+            raise ValueError(f"risk_maps must be ({self.B}, {self.G}, {self.G}), got {tuple(keep.shape)}")
+        self._check(self._lib.bn_clrrt_set_instance_maps(self.h, stream_ptr(self.dev), C.c_void_p(ptr), where, self._shared[2]))
+        self.per_instance = True
 
 
 class CLRRT(_TreePlanner, nn.Module):
@@ -107,25 +134,54 @@ class CLRRT(_TreePlanner, nn.Module):
         except TypeError as e:
             raise TypeError("CLRRT needs dynamics in 'inference' mode: the device transit reads the predicted risk map, and the "
                             "reference's own CLRRT fails on observation mode's (state, traversability) tuple") from e
+        self._dim_state, self._dim_control, self._dtype = dim_state, dim_control, dtype
+        self._configure(inp["grid_size"], float(grid_map.resolution), grid_map.x_limits, grid_map.y_limits,
+                        dynamics.min_action.detach().to("cpu", torch.float32).tolist(), dynamics.max_action.detach().to("cpu", torch.float32).tolist(),
+                        inp["stuck_threshold"], inp["risks"], inp["goal"], delta_t, max_iterations, delta_distance, goal_sample_rate, max_seqs,
+                        goal_threshold, device, seed, path_cap)
+
+    @classmethod
+    def from_parameters(cls, grid_size: int, resolution: float, x_limits=None, y_limits=None, u_min=(0.0, -1.0), u_max=(1.0, 1.0),
+                        stuck_threshold: float = 0.1, delta_t: float = 0.1, max_iterations: int = 500, delta_distance: float = 5,
+                        goal_sample_rate: float = 0.25, max_seqs: int = 250, goal_threshold: float = 1.0, risk_map=None, goal=None,
+                        device: Optional[str] = None, seed: int = 42, path_cap: Optional[int] = None) -> "CLRRT":
+        """A planner from the numbers the constructor reads off `dynamics`, `objectives` and `grid_map`: the grid (x_limits and
+        y_limits default to (0, grid_size * resolution)), the action bounds, the stuck threshold and the planner's parameters.
+        risk_map: the shared (G, G) map (default zeros: a caller that plans on per-instance maps gives them to plan_batch or
+        CLRRTLoop); goal: (2,) the default goal of forward and plan_batch and the goal steer_batch's costs run against (default
+        the limits' lower corner)."""
+        self = cls.__new__(cls)
+        nn.Module.__init__(self)
+        G = int(grid_size)
+        x_limits = (0.0, G * float(resolution)) if x_limits is None else x_limits
+        y_limits = x_limits if y_limits is None else y_limits
+        self._dim_state, self._dim_control, self._dtype = 3, 2, torch.float32
+        self._configure(G, float(resolution), torch.as_tensor(x_limits, dtype=torch.float32), torch.as_tensor(y_limits, dtype=torch.float32),
+                        [float(v) for v in u_min], [float(v) for v in u_max], float(stuck_threshold),
+                        torch.zeros(G, G) if risk_map is None else torch.as_tensor(risk_map),
+                        torch.tensor([float(x_limits[0]), float(y_limits[0])]) if goal is None else goal, delta_t, max_iterations,
+                        delta_distance, goal_sample_rate, max_seqs, goal_threshold, device, seed, path_cap)
+        return self
+
+    def _configure(self, grid_size, resolution, x_limits, y_limits, u_min, u_max, stuck_threshold, risks, goal, delta_t, max_iterations,
+                   delta_distance, goal_sample_rate, max_seqs, goal_threshold, device, seed, path_cap) -> None:
         self._seed = _check_seed(seed)
-        self.resolution = float(grid_map.resolution)
-        self.x_limits, self.y_limits = grid_map.x_limits, grid_map.y_limits
+        self.resolution = resolution
+        self.x_limits, self.y_limits = x_limits, y_limits
         self.device = device if device is not None else "cuda" if torch.cuda.is_available() else "cpu"
         self._max_iterations, self._max_seqs = int(max_iterations), int(max_seqs)
         if self._max_iterations < 1 or self._max_seqs < 1:
             raise ValueError("max_iterations and max_seqs must be >= 1")
         self._delta_distance, self._goal_sample_rate, self._goal_threshold = delta_distance, goal_sample_rate, goal_threshold
         self._delta_t = float(delta_t)
-        self._dim_state, self._dim_control, self._dtype = dim_state, dim_control, dtype
         self._path_cap = 0 if path_cap is None else int(path_cap)
-        self._grid_size = inp["grid_size"]
-        self._stuck_threshold = inp["stuck_threshold"]
-        self._risk = np.ascontiguousarray(inp["risks"].detach().to("cpu", torch.float32).numpy())
+        self._grid_size = grid_size
+        self._stuck_threshold = stuck_threshold
+        self._risk = np.ascontiguousarray(torch.as_tensor(risks).detach().to("cpu", torch.float32).numpy())
         if self._risk.shape != (self._grid_size, self._grid_size):
             raise ValueError(f"the risk map must be ({self._grid_size}, {self._grid_size}), got {self._risk.shape}")
-        self._u_min = dynamics.min_action.detach().to("cpu", torch.float32).tolist()
-        self._u_max = dynamics.max_action.detach().to("cpu", torch.float32).tolist()
-        self._goal_host = torch.as_tensor(inp["goal"]).detach().to("cpu", torch.float32)[:2].contiguous()
+        self._u_min, self._u_max = u_min, u_max
+        self._goal_host = torch.as_tensor(goal).detach().to("cpu", torch.float32)[:2].contiguous()
         self.tree = None
         self._planner_name = "cl_rrt"
         self._start_node = None
@@ -148,6 +204,7 @@ class CLRRT(_TreePlanner, nn.Module):
         if not self._is_within_bounds(start) or not self._is_within_bounds(self._goal_node):        # before any launch
             raise ValueError("Start or goal position is out of bounds.")
         h = self._handle(1)
+        h.set_maps(None)
         seeds = None if h.used else np.array([self._seed], np.uint64)
         self._launch(h, start.numpy()[None], self._goal_node[:3].numpy()[None], seeds)
         res = h.buffer(_capi.BN_CLRRT_BUF_RESULTS, (1, 6), "<i4").cpu().numpy()[0]
@@ -186,34 +243,38 @@ class CLRRT(_TreePlanner, nn.Module):
                 raise ValueError("Start or goal position is out of bounds.")
         return B, np.ascontiguousarray(states.numpy()), np.ascontiguousarray(g.numpy())
 
-    def plan_batch(self, states, goals=None, seeds=None):
+    def plan_batch(self, states, goals=None, seeds=None, risk_maps=None):
         """forward() of B planners that share this one's map and parameters, in one launch.  states: (B, 3); goals: (B, 2) -- the
         goal heading is then each instance's own atan2(goal - start), a fresh planner's -- or (B, 3) goal nodes, default this
         planner's goal; seeds: B integers in 0 ... 2^32 - 1, each reseeding its planner's stream as constructing it does; None
         continues the B streams of the last plan_batch of this batch size.  The costs of instance b run against ITS goal.
+        risk_maps: (B, G, G) float32, a torch tensor on the host or the device or a NumPy array: instance b plans on map b, as a
+        planner constructed on that map does; None plans on this planner's map, also after a call with maps.
         Returns (actions (B, Lmax, 2), states (B, Lmax + 1, 3), lengths (B,) int32, found (B,) bool) on the device, NaN beyond a
         path; `batch_tree(b)` and `last_batch` hold the rest."""
         B, sn, gn = self._batch_inputs(states, goals)
         sd = None if seeds is None else seed_array(seeds, B)
         h = self._handle(B)
+        h.set_maps(risk_maps)
         if sd is None and not h.used:
             sd = np.full(B, self._seed, np.uint64)
         self._launch(h, sn, gn, sd)
         return self._batch_result(h)
 
-    def grow_from_samples(self, states, samples, goals=None):
+    def grow_from_samples(self, states, samples, goals=None, risk_maps=None):
         """plan_batch on the caller's samples in place of the stream's: samples (B, max_iterations, 3) float32, host or device."""
         B, sn, gn = self._batch_inputs(states, goals)
         samples = torch.as_tensor(samples).detach().to(torch.float32).contiguous()
         if tuple(samples.shape) != (B, self._max_iterations, 3):
             raise ValueError(f"samples must be ({B}, {self._max_iterations}, 3), got {tuple(samples.shape)}")
         h = self._handle(B)
+        h.set_maps(risk_maps)
         self._grow(h, sn, gn, samples)
         return self._batch_result(h)
 
-    def steer_batch(self, from_states, controller_states, targets):
+    def steer_batch(self, from_states, controller_states, targets, risk_maps=None):
         """One _steer per instance with no tree: from_states (B, 3), controller_states (B, 4) (previous error and integral of the
-        linear, then the angular controller), targets (B, 3).  The costs run against this planner's goal.  Returns a dict of
+        linear, then the angular controller), targets (B, 3).  The costs run against this planner's goal; risk_maps as plan_batch's.  Returns a dict of
         device tensors: `path` (B, 64, 2) float64 truncated reference paths (NaN beyond), `points` (B,), `word` (B,) index into
         WORDS, `targets` (B, max_seqs) target index per step, `actions` (B, max_seqs, 2), `states` (B, max_seqs + 1, 3),
         `feasible`, `length`, `cost`, `controllers` (B, 4) float64."""
@@ -224,6 +285,7 @@ class CLRRT(_TreePlanner, nn.Module):
         if f.shape != (B, 3) or c.shape != (B, 4) or t.shape != (B, 3):
             raise ValueError("from_states (B, 3), controller_states (B, 4), targets (B, 3)")
         h = self._handle(B)
+        h.set_maps(risk_maps)
         _check(self._lib, self._lib.bn_clrrt_steer_async(h.h, self._stream(), f.ctypes.data, c.ctypes.data, t.ctypes.data))
         torch.cuda.current_stream(self._dev).synchronize()
         res = h.buffer(_capi.BN_CLRRT_BUF_STEER_RESULTS, (B, 4), "<i4").clone()

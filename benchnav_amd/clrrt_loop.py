@@ -9,6 +9,7 @@ replan, the others keep every byte.  The host looks at one counter per ROUND of 
     env = BatchedPlanetaryEnv(mppi, latent_mean, latent_std, start_pos, goal_pos, time_limit=100.0)
     planner = CLRRT(3, 2, dynamics, objectives, grid_map, delta_t=0.1)
     loop = CLRRTLoop(env, planner)                      # all rovers plan on the planner's one risk map, each to ITS goal
+    loop = CLRRTLoop(env, planner, risk_maps=maps)      # ... or rover b on maps[b]; loop.set_risk_maps(maps) between episodes
     env.reset(seed=0)                                   # also resets the loop
     log = loop.run(1000)                                # dict of numpy arrays, rows by loop iteration
     loop.raise_for_status()                             # what the reference raised, for the first rover that stopped
@@ -37,10 +38,11 @@ EVENT_NAMES = ("STEP", "REPLAN", "FROZEN")
 
 
 class CLRRTLoop:
-    def __init__(self, env, planner, seeds=None):
+    def __init__(self, env, planner, seeds=None, risk_maps=None):
         """env: a BatchedPlanetaryEnv (its goals are the rovers' goals, its time limit the loop's); planner: a CLRRT on the same
         grid (its risk map, limits, action bounds and parameters serve every rover); seeds: B integers in 0 ... 2^32 - 1 for the
-        rovers' planner streams, reseeded at every reset (default: the planner's seed for each)."""
+        rovers' planner streams, reseeded at every reset (default: the planner's seed for each); risk_maps: (B, G, G), rover b
+        plans on map b (set_risk_maps)."""
         self.env, self.planner = env, planner
         self.B = env.B
         self._lib, self._h, self._dev = env.planner._lib, env.planner._h, env._dev
@@ -52,6 +54,8 @@ class CLRRTLoop:
             raise ValueError("one seed per rover")
         self._seeds = np.array([_check_seed(s) for s in sd], np.uint64)
         self._handle = _Handle(self._lib, self._dev, self.B, planner)       # the loop's own: plan_batch and forward keep theirs
+        if risk_maps is not None:
+            self._handle.set_maps(risk_maps)
         self._iters = 0
         self._zero()
         self.reset()
@@ -88,14 +92,24 @@ class CLRRTLoop:
         self._iters = 0
         self._zero()
 
-    def run(self, n_iterations: int, z: Optional[torch.Tensor] = None, samples: Optional[torch.Tensor] = None, stage_in_lds: bool = True):
+    def set_risk_maps(self, risk_maps):
+        """The rovers' own risk maps from the next plan on: (B, G, G) float32, a torch tensor on the host or the device (copied
+        device to device on torch's current stream) or a NumPy array; None returns every rover to the planner's map.  Between
+        episodes: the rovers' current plans stay as they were grown."""
+        self.env._check_stream()
+        self._handle.set_maps(risk_maps)
+
+    def run(self, n_iterations: int, z: Optional[torch.Tensor] = None, samples: Optional[torch.Tensor] = None, stage_in_lds: bool = True,
+            log: bool = True):
         """n loop iterations from the environment's current states; calling it again continues the episode.  z: (n, B) injected
         slip draws (row t: iteration t of this call); None draws them like env.step (Philox keyed by the env seed and the episode's
         iteration index).  samples: (P, B, max_iterations, 3) sample tables (teacher forcing).  stage_in_lds=False is a test knob:
         the follow kernel reads every plan from global memory; the logs are bit-identical.
         Returns a dict of numpy arrays, rows by iteration of this call: states (n+1, B, 3), rewards (n, B), actions (n, B, 2),
         deviations (n, B), plan_index (n, B), events (n, B); and per rover done_iter, status, plans, steps (since the reset).  A
-        row without a step holds the rover's state and NaN elsewhere (a flagged replan keeps its deviation)."""
+        row without a step holds the rover's state and NaN elsewhere (a flagged replan keeps its deviation).
+        log=False downloads nothing and returns None: the log and the rovers' words stay on the device (episode_buffers(),
+        rover_buffers()); `status`, `done_iter`, `plans`, `steps` and `elapsed` here are not refreshed."""
         env = self.env
         env._check_stream()
         if env._steps != self._iters:
@@ -123,6 +137,13 @@ class CLRRTLoop:
                                          C.c_void_p(None if sp is None else sp.data_ptr()), P, 0 if stage_in_lds else 1, C.byref(ms))
         _capi.check(rc)
         self.follow_ms = float(ms.value)
+        self._keep = (zp, sp)
+        if not log:
+            env._robot_state = state
+            env._steps += n
+            env._draws += n
+            self._iters += n
+            return None
         out = {"states": np.empty((n + 1, B, 3), np.float32), "rewards": np.empty((n, B), np.float32), "actions": np.empty((n, B, 2), np.float32),
                "deviations": np.empty((n, B), np.float32), "plan_index": np.empty((n, B), np.int32), "events": np.empty((n, B), np.int32),
                "done_iter": np.empty(B, np.int32), "status": np.empty(B, np.int32), "plans": np.empty(B, np.int32), "steps": np.empty(B, np.int32)}
@@ -137,6 +158,21 @@ class CLRRTLoop:
         self.status, self.done_iter, self.plans, self.steps = out["status"], out["done_iter"], out["plans"], out["steps"]
         env._elapsed_time = float(self.elapsed.max())
         return out
+
+    def episode_buffers(self):
+        """Device pointers (states (cap + 1, B, 3), rewards (cap, B), done_step (B), stopped (B), both int32) of the latest run's
+        log, its n and the row capacity `cap` the log is laid out for: what bn_episode_score reads.  done_step is done_iter where
+        the rover reached its goal, else -1; stopped the status where it is neither RUNNING, GOAL nor TIME_LIMIT, else 0
+        (benchmark.clrrt_outcome_words states the rule on NumPy).  Nothing is copied."""
+        s, r, d, st, n, cap = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int32(), C.c_int32()
+        _capi.check(self._lib.bn_clrrt_loop_episode_buffers(self._h, C.byref(s), C.byref(r), C.byref(d), C.byref(st), C.byref(n), C.byref(cap)))
+        return s.value, r.value, d.value, st.value, n.value, cap.value
+
+    def rover_buffers(self):
+        """(status (B,), plans (B,)) int32 device tensors: views of the words the latest run left, valid until the next run."""
+        st, pl = C.c_void_p(), C.c_void_p()
+        _capi.check(self._lib.bn_clrrt_loop_rover_buffers(self._h, C.byref(st), C.byref(pl)))
+        return self._handle.view(st.value, (self.B,), "<i4"), self._handle.view(pl.value, (self.B,), "<i4")
 
     def set_plans(self, actions, states, lengths=None, iteration: Optional[int] = None):
         """Teacher forcing: actions (B, L, 2), states (B, L + 1, 3) and lengths (B,) (default L for every rover) become the rovers'

@@ -15,6 +15,8 @@
 // segment lengths for the truncation, then the serial follow loop: validity mask on the lanes, first set lane, PID in float64, the
 // float32 cast of the action, the library's reference-order transit (chain_step<..., REF>) and costs in float32.
 // Every loop is bounded (iterations, max_seqs, 64 points, the parent walk by the node count); no workgroup waits for another.
+// The map: one for all instances (bn_clrrt_set_map: SolveParams.map_stride 0) or one per instance (bn_clrrt_set_instance_maps:
+// stride G * G over a buffer of B maps); clrrt_steer is the only reader, instance b at p.map + b * p.map_stride.
 // The host side is written with bn_host.h (guard, HIP check, buffer table) and shares its plan steps with RRT (rrt_host.h).
 #include <hip/hip_runtime.h>
 
@@ -512,7 +514,9 @@ struct bn_clrrt {
     bool seeded = false, ev_recorded = false, have_map = false;
     size_t lds_bytes = 0;
     bn::DeviceBuffers bufs;                  // every device pointer below, filled by bn_clrrt_create
+    bn::DeviceBuffers late;                  // ... but inst_maps: built by the first bn_clrrt_set_instance_maps
     float *map = nullptr, *goal = nullptr;
+    float *inst_maps = nullptr;              // (B, G, G) one risk map per instance; c.p.map points here while c.p.map_stride == G * G
     float *nodes = nullptr, *costs = nullptr, *ctrl = nullptr, *aseq = nullptr, *sseq = nullptr, *samples = nullptr, *starts = nullptr, *goals = nullptr;
     float *path_actions = nullptr, *path_states = nullptr;
     int32_t *edges = nullptr, *lens = nullptr, *counts = nullptr, *flags = nullptr, *results = nullptr, *pos = nullptr, *near = nullptr, *feasible = nullptr;
@@ -731,6 +735,7 @@ void bn_clrrt_destroy(bn_clrrt_t *h)
     bn::DeviceGuard guard(h->cfg.device_id);
     if (h->ev_recorded && h->ev_done) (void)hipEventSynchronize(h->ev_done);
     h->bufs.free_all();
+    h->late.free_all();
     delete h;
 }
 
@@ -742,6 +747,34 @@ int bn_clrrt_set_map(bn_clrrt_t *h, const float *risk, const float *goal, double
     if (h->ev_recorded) CLRRT_HIP(hipEventSynchronize(h->ev_done));
     CLRRT_HIP(hipMemcpy(h->map, risk, (size_t)h->c.p.G * h->c.p.G * 4, hipMemcpyHostToDevice));
     CLRRT_HIP(hipMemcpy(h->goal, goal, 8, hipMemcpyHostToDevice));
+    h->c.p.map = h->map; h->c.p.map_stride = 0;                     // back from per-instance maps, if they were set
+    h->c.p.thr = (float)stuck_threshold;
+    h->have_map = true;
+    return BN_OK;
+}
+
+int bn_clrrt_set_instance_maps(bn_clrrt_t *h, void *stream, const void *risks, int where, double stuck_threshold)
+{
+    if (!h || !risks) return clrrt_fail(BN_ERR_INVALID, "null argument");
+    if (where != BN_MEM_HOST && where != BN_MEM_DEVICE) return clrrt_fail(BN_ERR_INVALID, "where must be BN_MEM_HOST or BN_MEM_DEVICE");
+    if (!std::isfinite(stuck_threshold)) return clrrt_fail(BN_ERR_INVALID, "stuck threshold must be finite");
+    BN_ON_DEVICE(clrrt_fail, h->cfg.device_id);
+    hipStream_t s = (hipStream_t)stream;
+    if (h->ev_recorded) CLRRT_HIP(hipEventSynchronize(h->ev_done));                    // no launch of the handle reads a map any more
+    const size_t bytes = (size_t)h->B * h->c.p.G * h->c.p.G * 4;
+    if (h->late.list.empty()) h->late.add(&h->inst_maps, bytes);
+    if (!h->late.live) {
+        if (int rc = h->late.ensure(clrrt_fail)) return rc;
+        CLRRT_HIP(hipStreamSynchronize(nullptr));                                       // the zero fill ran on the null stream
+    }
+    if (where == BN_MEM_HOST) {
+        CLRRT_HIP(hipMemcpyAsync(h->inst_maps, risks, bytes, hipMemcpyHostToDevice, s));
+        CLRRT_HIP(hipStreamSynchronize(s));                                             // the caller's array is consumed before this returns
+    } else {
+        CLRRT_HIP(hipMemcpyAsync(h->inst_maps, risks, bytes, hipMemcpyDeviceToDevice, s));
+    }
+    // the pointer and the stride change together, and only with the B maps behind them: a non-zero stride over h->map reads out of bounds
+    h->c.p.map = h->inst_maps; h->c.p.map_stride = h->c.p.G * h->c.p.G;
     h->c.p.thr = (float)stuck_threshold;
     h->have_map = true;
     return BN_OK;

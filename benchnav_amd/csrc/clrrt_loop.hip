@@ -18,6 +18,9 @@
 // passed), and the latent cell's two loads (env_fetch) are issued before the scan so that they are back behind the barrier.
 // Every lane evaluates the step itself (same inputs, same operations); lane 0 logs.  min() is exact, so the LDS and the global
 // path give the same bits.  Every loop is bounded by the call's iteration count; no workgroup waits for another.
+//
+// clrrt_outcome_kernel: behind a run, the rovers' words as bn_episode_score takes them (done_step, stopped) and as a campaign
+// reads them (status, plans), one thread per rover.
 #include "../../include/benchnav_mppi.h"
 #include "clrrt_view.h"
 #include "dwa_device.h"
@@ -143,6 +146,19 @@ __global__ __launch_bounds__(kClrrtFollowThreads) void clrrt_follow_kernel(const
     }
 }
 
+// The rovers' words as the episode scores read them (ClrrtOutcome, clrrt_view.h): one thread per rover, behind a run's last launch.
+__global__ void clrrt_outcome_kernel(const ClrrtRover *__restrict__ rover, ClrrtOutcome out)
+{
+    const size_t b = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= out.B) return;
+    const ClrrtRover r = rover[b];
+    const bool regular = r.status == BN_CL_RUNNING || r.status == BN_CL_GOAL || r.status == BN_CL_TIME_LIMIT;
+    out.done_step()[b] = r.status == BN_CL_GOAL ? r.done_iter : -1;
+    out.stopped()[b] = regular ? 0 : r.status;
+    out.status()[b] = r.status;
+    out.plans()[b] = r.plans;
+}
+
 template <int GEO>
 hipError_t launch_g(const SolveParams &p, const ClrrtFollowArgs &a, hipStream_t s)
 {
@@ -162,6 +178,12 @@ hipError_t launch_clrrt_follow(const SolveParams &p, const ClrrtFollowArgs &a, h
     case kGeoPow2: return launch_g<kGeoPow2>(p, a, s);
     default: return launch_g<kGeoGeneral>(p, a, s);
     }
+}
+
+hipError_t launch_clrrt_outcome(const ClrrtRover *rover, const ClrrtOutcome &out, hipStream_t s)
+{
+    clrrt_outcome_kernel<<<dim3((unsigned)((out.B + 63) / 64)), dim3(64), 0, s>>>(rover, out);
+    return hipGetLastError();
 }
 
 }  // namespace bn

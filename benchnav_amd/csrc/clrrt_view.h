@@ -75,4 +75,19 @@ struct ClrrtFollowArgs {
 
 hipError_t launch_clrrt_follow(const SolveParams &p, const ClrrtFollowArgs &a, hipStream_t s);
 
+// What a run leaves of the rovers' words for readers on the device, (B) int32 each, one column behind the other:
+//   done_step  done_iter where the status is BN_CL_GOAL, else -1           (bn_episode_score's done_step)
+//   stopped    the status where it is neither RUNNING, GOAL nor TIME_LIMIT, else 0      (... and its stopped)
+//   status, plans  the rover's own words
+struct ClrrtOutcome {
+    int32_t *w;
+    size_t B;
+    static size_t count(size_t B) { return 4 * B; }
+    __host__ __device__ int32_t *done_step() const { return w; }
+    __host__ __device__ int32_t *stopped() const { return w + B; }
+    __host__ __device__ int32_t *status() const { return w + 2 * B; }
+    __host__ __device__ int32_t *plans() const { return w + 3 * B; }
+};
+hipError_t launch_clrrt_outcome(const ClrrtRover *rover, const ClrrtOutcome &out, hipStream_t s);
+
 }  // namespace bn

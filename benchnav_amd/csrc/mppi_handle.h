@@ -191,6 +191,7 @@ struct bn_mppi {
     bn::ClrrtRover *d_cl_rover = nullptr;   // (B)
     int32_t *d_cl_flags = nullptr;          // the replan mask and the pending counter (ClFlags, mppi_loops.cpp)
     float *d_cl_goal = nullptr;             // (B, 3) goal nodes
+    int32_t *d_cl_words = nullptr;          // what the latest run left of the rovers, by column (ClrrtOutcome, clrrt_view.h)
     bn::EpisodeLog cl_log;                  // + deviation, plan index, event
     int32_t *h_cl_pending = nullptr;        // pinned: the pending counter of the latest round
     hipEvent_t cl_ev[2] = {};               // around a follow launch (follow_ms)

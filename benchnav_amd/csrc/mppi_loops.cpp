@@ -238,6 +238,7 @@ int bn_clrrt_loop_reset(bn_mppi_t *h, bn_clrrt_t *c, const float *goal_nodes, co
         h->cl_bufs.add(&h->d_cl_rover, B * sizeof(bn::ClrrtRover));
         h->cl_bufs.add(&h->d_cl_flags, ClFlags::count(B) * sizeof(int32_t));
         h->cl_bufs.add(&h->d_cl_goal, B * 3 * sizeof(float));
+        h->cl_bufs.add(&h->d_cl_words, bn::ClrrtOutcome::count(B) * sizeof(int32_t));
         h->cl_bufs.add_pinned(&h->h_cl_pending, sizeof(int32_t));
         h->cl_bufs.add_event(&h->cl_ev[0]);
         h->cl_bufs.add_event(&h->cl_ev[1]);
@@ -313,6 +314,7 @@ int bn_clrrt_loop_run(bn_mppi_t *h, bn_clrrt_t *c, int32_t n, float *states_devi
         if (bn::clrrt_plan_masked(c, h->stream, f.active(), samples_device ? 0 : 1) != BN_OK) return fail(BN_ERR_HIP, "%s", bn_clrrt_last_error());
         BN_HIP(hipMemsetAsync(f.pending(), 0, sizeof(int32_t), h->stream));     // (the follow kernel clears the mask words it takes)
     }
+    BN_HIP(bn::launch_clrrt_outcome(h->d_cl_rover, bn::ClrrtOutcome{h->d_cl_words, (size_t)h->p.B}, h->stream));
     if (follow_ms) *follow_ms = ms_total;
     h->cl_iter += n;
     lg.len = n;
@@ -341,6 +343,34 @@ int bn_clrrt_loop_log(bn_mppi_t *h, float *states, float *rewards, float *action
         if (plans) plans[b] = r[b].plans;
         if (steps) steps[b] = r[b].steps;
     }
+    return BN_OK;
+}
+
+int bn_clrrt_loop_episode_buffers(bn_mppi_t *h, const float **states_device, const float **rewards_device,
+                                  const int32_t **done_step_device, const int32_t **stopped_device, int32_t *n_iterations, int32_t *row_capacity)
+{
+    if (!h) return fail(BN_ERR_INVALID, "null handle");
+    const bn::EpisodeLog &lg = h->cl_log;
+    if (lg.empty()) return fail(BN_ERR_STATE, "no CL-RRT loop has been run");
+    BN_BIND(h);
+    if (int rc = settle_point(h)) return rc;
+    const bn::ClrrtOutcome w{h->d_cl_words, (size_t)h->p.B};
+    if (states_device) *states_device = lg.states();                                           // (row_capacity + 1, B, 3)
+    if (rewards_device) *rewards_device = lg.reward();                                         // (row_capacity, B)
+    if (done_step_device) *done_step_device = w.done_step();                                   // (B)
+    if (stopped_device) *stopped_device = w.stopped();                                         // (B)
+    if (n_iterations) *n_iterations = lg.len;
+    if (row_capacity) *row_capacity = lg.cap;
+    return BN_OK;
+}
+
+int bn_clrrt_loop_rover_buffers(bn_mppi_t *h, const int32_t **status_device, const int32_t **plans_device)
+{
+    if (!h) return fail(BN_ERR_INVALID, "null handle");
+    if (h->cl_log.empty()) return fail(BN_ERR_STATE, "no CL-RRT loop has been run");
+    const bn::ClrrtOutcome w{h->d_cl_words, (size_t)h->p.B};
+    if (status_device) *status_device = w.status();
+    if (plans_device) *plans_device = w.plans();
     return BN_OK;
 }
 

@@ -835,7 +835,8 @@ const char *bn_rrt_last_error(void);
 
 /* ------------------------------------------------------------------------------------------------------------------------------
  * The closed-loop RRT planner (csrc/clrrt_kernels.hip): `CLRRT` of src/planners/global_planners/sampling_based/cl_rrt.py for B
- * planners that share the map, limits and parameters, one wave each: the MT19937 stream of each instance parsed
+ * planners that share the limits and parameters and plan on one risk map (bn_clrrt_set_map) or on one map each
+ * (bn_clrrt_set_instance_maps), one wave each: the MT19937 stream of each instance parsed
  * into (x, y, theta) samples, the tree grown by nearest neighbour + Dubins path + pure-pursuit closed-loop simulation on the
  * library's float32 transit and costs, then the goal test, the pick and the concatenated action / state sequences.
  * Errors: the clrrt error string below.
@@ -894,8 +895,14 @@ void bn_clrrt_config_init(bn_clrrt_config *cfg);
 int bn_clrrt_create(const bn_clrrt_config *cfg, bn_clrrt_t **out);
 void bn_clrrt_destroy(bn_clrrt_t *h);
 /* The risk map the dynamics reads, HOST (G, G) float32 (traversability = 1 - clamp(risk, 0, 1)), shared by the instances; the
- * goal (2) the costs of bn_clrrt_steer_async run against; the stuck threshold.  Synchronous. */
+ * goal (2) the costs of bn_clrrt_steer_async run against; the stuck threshold.  Synchronous.  Ends bn_clrrt_set_instance_maps. */
 int bn_clrrt_set_map(bn_clrrt_t *h, const float *risk, const float *goal, double stuck_threshold);
+/* One risk map per instance: risks (B, G, G) float32, `where` a bn_mem_kind; a device source is copied device to device on
+ * `stream`, a host source is consumed before the call returns.  From here on instance b's plans and steers read map b, until
+ * bn_clrrt_set_map returns the handle to its shared map; the goal of bn_clrrt_steer_async stays bn_clrrt_set_map's (zeros before
+ * it).  Waits for the handle's latest launch.  The B maps are allocated by the first call: a handle that never makes it holds
+ * the shared map only. */
+int bn_clrrt_set_instance_maps(bn_clrrt_t *h, void *stream, const void *risks, int where, double stuck_threshold);
 /* One forward() of every instance on `stream`: starts HOST (B, 3) float32 states, goals HOST (B, 3) float32 goal nodes (x, y,
  * heading; the costs run against (x, y)), consumed before the call returns; a position out of the limits is BN_ERR_INVALID and
  * nothing is launched.  seeds as bn_rrt_plan_async. */
@@ -957,6 +964,15 @@ int bn_clrrt_loop_run(bn_mppi_t *h, bn_clrrt_t *c, int32_t n, float *states_devi
  * (the iteration its status was set at, or -1), status, plans (forward calls), steps (environment steps) since the reset. */
 int bn_clrrt_loop_log(bn_mppi_t *h, float *states, float *rewards, float *actions, float *deviations, int32_t *plan_index,
                       int32_t *events, int32_t *done_iter, int32_t *status, int32_t *plans, int32_t *steps);
+/* The latest run's log where it lies, for readers on the device (bn_episode_score): states (row_capacity + 1, B, 3) and rewards
+ * (row_capacity, B), laid out by the rows the log holds, of which the first n_iterations (+ 1) are the run's; done_step (B) int32:
+ * done_iter where the status is BN_CL_GOAL, else -1; stopped (B) int32: the status where it is neither RUNNING, GOAL nor
+ * TIME_LIMIT, else 0.  The two words are written on h's stream behind the run (done_iter counts from the reset: they index the
+ * log of a run that started there).  Any pointer may be NULL; nothing is copied or synchronised. */
+int bn_clrrt_loop_episode_buffers(bn_mppi_t *h, const float **states_device, const float **rewards_device,
+                                  const int32_t **done_step_device, const int32_t **stopped_device, int32_t *n_iterations, int32_t *row_capacity);
+/* ... and the rovers' status (bn_clrrt_loop_status) and plans (forward calls since the reset), (B) int32 each, as that run left them. */
+int bn_clrrt_loop_rover_buffers(bn_mppi_t *h, const int32_t **status_device, const int32_t **plans_device);
 /* Teacher forcing: actions HOST (B, Lmax, 2), states HOST (B, Lmax + 1, 3) and lengths HOST (B) int32 (1 <= L <= min(Lmax,
  * path_cap)) become the rovers' current plans, action_index 0, no replan pending; iteration >= 0 also sets every rover's
  * iteration counter.  The follow kernel can be driven with this alone. */

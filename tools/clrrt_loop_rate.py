@@ -8,9 +8,11 @@ their own planner seeds and Philox slip draws.  Per B, median of --reps runs aft
   plan_share                1 - follow time / wall: the masked plans and the host's look at the pending counter, once per round
 and, at B = 1, the HOST-COMPOSED loop from the parts that exist without this class, in alternating runs with the fused one:
 CLRRT.forward, then per control step the torch deviation (torch.norm + torch.min + the comparison's host read) and
-BatchedPlanetaryEnv.step.  Every repeat goes to the JSON.
+BatchedPlanetaryEnv.step.  Behind the shared-map cases, B = 64 / 256 with one risk map per rover (CLRRTLoop(..., risk_maps=...): the
+fixture's map times a factor in [0.8, 1.3] that cycles over eleven values); --shared-only leaves those out, for runs against a
+commit that has no such maps.  Every repeat goes to the JSON.
 
-    python tools/clrrt_loop_rate.py [--reps 5] [--out profiles/clrrt_loop_rates.json]
+    python tools/clrrt_loop_rate.py [--reps 5] [--shared-only] [--out profiles/clrrt_loop_rates.json]
 """
 from __future__ import annotations
 
@@ -29,7 +31,12 @@ import torch  # noqa: E402
 N, SCALE, G, RES, THR = 1000, 1.4, 64, 0.5, 0.2
 
 
-def make(fx, B):
+def rover_maps(fx, B):
+    """(B, G, G): rover b's risk map, the fixture's times 0.8 + 0.05 (b mod 11)."""
+    return np.stack([np.clip(fx["mean"] * np.float32(0.8 + 0.05 * (b % 11)), 0.0, 0.95) for b in range(B)]).astype(np.float32)
+
+
+def make(fx, B, per_rover=False):
     from benchnav_amd import CLRRT, CLRRTLoop, NativeMPPI
     from benchnav_amd.env import BatchedPlanetaryEnv
     from helpers import FakeDynamics, FakeGridMap, FakeObjectives
@@ -42,7 +49,8 @@ def make(fx, B):
     gm = FakeGridMap(G, RES)
     planner = CLRRT(3, 2, FakeDynamics(mean, gm), FakeObjectives(torch.as_tensor(fx["goal"].copy()), THR), gm, delta_t=0.1, max_iterations=60,
                     max_seqs=250, seed=42)
-    loop = CLRRTLoop(env, planner, seeds=[42 + b for b in range(B)])
+    kw = {"risk_maps": torch.from_numpy(rover_maps(fx, B)).cuda()} if per_rover else {}
+    loop = CLRRTLoop(env, planner, seeds=[42 + b for b in range(B)], **kw)
     return env, planner, loop
 
 
@@ -95,12 +103,14 @@ def composed_run(env, planner):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--shared-only", action="store_true", help="only the cases in which every rover plans on the planner's one map")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "clrrt_loop_rates.json"))
     args = ap.parse_args()
     fx = np.load(os.path.join(ROOT, "tests", "golden", "clrrt_loop.npz"))
     rows = []
-    for B in (1, 64, 256):
-        env, planner, loop = make(fx, B)
+    cases = [(1, False), (64, False), (256, False)] + ([] if args.shared_only else [(64, True), (256, True)])
+    for B, per_rover in cases:
+        env, planner, loop = make(fx, B, per_rover)
         fused_run(env, loop)                                            # warm-up
         if B == 1:
             composed_run(env, planner)
@@ -113,7 +123,7 @@ def main():
                 comp.append(composed_run(env, planner))
         steps = int(log["steps"].max())
         wall, follow = float(np.median(walls)), float(np.median(follows))
-        row = {"B": B, "iterations": N, "steps_max": steps, "plans_mean": round(float(log["plans"].mean()), 2), "plans_max": int(log["plans"].max()),
+        row = {"B": B, "maps": "per_rover" if per_rover else "shared", "iterations": N, "steps_max": steps, "plans_mean": round(float(log["plans"].mean()), 2), "plans_max": int(log["plans"].max()),
                "status_counts": np.bincount(log["status"], minlength=8).tolist(),
                "wall_us_per_iteration": round(1e6 * wall / N, 3), "wall_us_per_rover_iteration": round(1e6 * wall / N / B, 4),
                "follow_us_per_step": round(1e3 * follow / max(steps, 1), 3), "plan_share": round(1.0 - 1e-3 * follow / wall, 4),

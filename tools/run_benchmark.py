@@ -2,8 +2,9 @@
 """The benchmark stage end to end on the device: a test split, its predictions, risk maps under three risk settings, a planner
 driving every map, and the summary table -- what the reference spreads over its test_*.py drivers, one map at a time.
 
-    python tools/run_benchmark.py [--planner mppi|astar_dwa] [--data-directory DIR | --grid-size 64 --environments 10 --test-instances 1]
+    python tools/run_benchmark.py [--planner mppi|astar_dwa|cl_rrt] [--data-directory DIR | --grid-size 64 --environments 10 --test-instances 1]
                                   [--models DIR] [--trials 1] [--chunk 64] [--seed 0] [--out report.json]
+                                  [--max-iterations 500] [--max-seqs 250]                                    # cl_rrt
     python tools/run_benchmark.py --rates [--baseline-lib libbenchnav_mppi.so]      # -> profiles/benchmark_rates.json
 
 The split is test subset 1: read from --data-directory (the reference's files), or generated in memory with the seeds
@@ -148,7 +149,7 @@ def score_rates():
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--planner", default="mppi", choices=["mppi", "astar_dwa"])
+    ap.add_argument("--planner", default="mppi", choices=["mppi", "astar_dwa", "cl_rrt"])
     ap.add_argument("--data-directory", default=None, help="read test/subsetNN from the reference's files here")
     ap.add_argument("--subset", type=int, default=1)
     ap.add_argument("--models", default=None, help="the --out directory of tools/make_models.py; default: the latent model predicts")
@@ -169,6 +170,8 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--horizon", type=int, default=None)
     ap.add_argument("--num-samples", type=int, default=None, help="MPPI rollouts per solve")
+    ap.add_argument("--max-iterations", type=int, default=None, help="cl_rrt: samples per plan (the reference's 500)")
+    ap.add_argument("--max-seqs", type=int, default=None, help="cl_rrt: closed-loop steps per steer (the reference's 250)")
     ap.add_argument("--out", default=None, help="write the report (per-episode arrays and summary) as JSON")
     ap.add_argument("--rates", action="store_true", help="measure the risk-map and scoring kernels instead -> profiles/benchmark_rates.json")
     ap.add_argument("--baseline-lib", default=None, help="--rates: time the single-map calls through this library (another commit's build)")
@@ -196,6 +199,8 @@ def main():
     kw = {k: v for k, v in (("horizon", args.horizon), ("num_samples", args.num_samples)) if v is not None}
     if args.planner == "astar_dwa":
         kw.pop("num_samples", None)
+    if args.planner == "cl_rrt":
+        kw = {k: v for k, v in (("max_iterations", args.max_iterations), ("max_seqs", args.max_seqs)) if v is not None}
     t0 = time.perf_counter()
     report = bench.run(args.planner, SETTINGS, **kw)
     seconds = time.perf_counter() - t0
