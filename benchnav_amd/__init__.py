@@ -16,6 +16,7 @@
     from benchnav_amd import DatasetGenerator, TerrainDataset   # the dataset stage: splits on the device, the reference's files (dataset.py)
     from benchnav_amd import TerrainClassificationDataset, SlipRegressionDataset, TraversabilityPredictionDataset   # ... and its three views
     from benchnav_amd import Benchmark, score_episodes   # the benchmark stage: risk maps, chunked episodes, scores, a report (benchmark.py)
+    from benchnav_amd import Evaluator, EvaluationReport, confusion_matrix, slip_metrics, risk_calibration   # how good the models are (evaluate.py)
 """
 from .native import NativeMPPI  # noqa: F401
 
@@ -63,4 +64,7 @@ def __getattr__(name):
     if name in ("Benchmark", "score_episodes"):
         from . import benchmark
         return getattr(benchmark, name)
+    if name in ("Evaluator", "EvaluationReport", "confusion_matrix", "slip_metrics", "risk_calibration"):
+        from . import evaluate
+        return getattr(evaluate, name)
     raise AttributeError(name)

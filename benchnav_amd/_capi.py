@@ -32,6 +32,7 @@ BN_FLAG_UNORDERED_OUTPUTS = 16384
 BN_BUF_STATES_ALT, BN_BUF_CONTROLS_ALT = 10, 11
 BN_RISK_EXPECTED, BN_RISK_VAR, BN_RISK_CVAR = 0, 1, 2
 BN_RISK_MAX_SETTINGS = 16
+BN_EVAL_MAX_CLASSES, BN_EVAL_MAX_BINS, BN_EVAL_MAX_GROUPS, BN_EVAL_SLAB_CELLS, BN_EVAL_SLIP_SUMS, BN_EVAL_RISK_COUNTS = 64, 64, 512, 4096, 8, 5
 BN_OUTCOME_GOAL, BN_OUTCOME_TIME_LIMIT, BN_OUTCOME_STOPPED, BN_OUTCOME_INVALID = 0, 1, 2, 3   # bn_episode_outcome
 BN_AD_OK, BN_AD_OUT_OF_BOUNDS, BN_AD_GOAL_COLLISION, BN_AD_FIELD_ERROR = 0, 1, 2, 3   # bn_astar_dwa_status
 BN_RRT_FLAG_GLOBAL_NODES, BN_RRT_FLAG_ONE_WAVE, BN_RRT_FLAG_FOUR_WAVES = 1, 2, 4
@@ -173,6 +174,12 @@ SYMBOLS = {
                                      C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bn_episode_score": (C.c_int, [C.c_int32] + [C.c_void_p] * 8 + [C.c_int32, C.c_int32, C.c_float, C.c_double] + [C.c_void_p] * 8),
     "bn_score_last_error": (C.c_char_p, []),
+    "bn_eval_confusion_async": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
+    "bn_eval_slip_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int32, C.c_int32]),
+    "bn_eval_slip_async": (C.c_int, [C.c_int32] + [C.c_void_p] * 8 + [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_double] + [C.c_void_p] * 5
+                           + [C.c_size_t]),
+    "bn_eval_risk_async": (C.c_int, [C.c_int32] + [C.c_void_p] * 4 + [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_float, C.c_void_p, C.c_void_p]),
+    "bn_eval_last_error": (C.c_char_p, []),
     "bn_mppi_episode_buffers": (C.c_int, [_H, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int32),
                                           C.POINTER(C.c_int32)]),
     "bn_astar_dwa_episode_buffers": (C.c_int, [_H, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),

@@ -598,6 +598,62 @@ int bn_episode_score(int32_t device_id, void *stream, const float *states_device
 const char *bn_score_last_error(void);
 
 /*
+ * The model-evaluation stage (csrc/eval_kernels.hip): three reductions over num_maps maps of `cells` cells each,
+ * on arrays that already sit on the device.  Device pointers only, everything is enqueued on `stream`, nothing synchronises, the
+ * outputs are overwritten (only `total` of bn_eval_slip_async is added to).  num_classes in [1, BN_EVAL_MAX_CLASSES].  Every
+ * function refuses a null pointer, num_maps < 1, cells < 1 and a count out of its range with BN_ERR_INVALID before it touches the
+ * device.  Errors: bn_eval_last_error().
+ *
+ * bn_eval_confusion_async: true_classes, pred_classes (num_maps, cells) int32.
+ *   table (num_maps, C, C)   cells with true class t and predicted class p, at [t][p]
+ *   ignored (num_maps)       cells with either class outside [0, C): they are in no table entry
+ *
+ * bn_eval_slip_async: the predicted slip N(mean, std^2) against the latent N(latent_mean, latent_std^2) and, with slips (may be
+ * NULL), against one observation y per cell; all (num_maps, cells) float32, classes int32.  A cell belongs to the group (true
+ * class c, slope bin j), j = min(max(trunc((double)slope * num_bins / max_slope), 0), num_bins - 1) in float64: num_bins equal
+ * bins over [0, max_slope], closed on the left, a slope below 0 in the first and one at or above max_slope in the last.
+ * num_bins in [1, BN_EVAL_MAX_BINS] with C * num_bins <= BN_EVAL_MAX_GROUPS; max_slope > 0.  With d = mean - latent_mean,
+ * e = y - mean, all in float64 on the float32 inputs:
+ *   sums (num_maps, C, num_bins, BN_EVAL_SLIP_SUMS) per map and group, in this order:
+ *       sum d, sum |d|, sum d^2, sum std, sum latent_std,
+ *       sum KL(latent || predicted) = (log(std / latent_std) + (latent_std^2 + d^2) / (2 std^2)) - 0.5,
+ *       sum NLL = 0.5 log(2 pi std^2) + e^2 / (2 std^2), sum (e / std)^2     (both 0 without slips)
+ *   counts (num_maps, C, num_bins, 2)  the group's cells, and those of them with |e| <= 2 std (0 without slips)
+ *   invalid (num_maps)   cells in no sum and no count: a class outside [0, C), a non-finite slope, mean, std, latent_mean,
+ *                        latent_std or y, std <= 0 or latent_std <= 0 (a class without a regressor predicts std = 0)
+ *   total (C, num_bins, BN_EVAL_SLIP_SUMS) or NULL: in/out, the maps' `sums` are added onto it in map order, so that calls over
+ *                        successive runs of maps leave the bits of one call over all of them
+ * The float64 sums are added in a fixed order that depends on the cell index and the map index alone: not on
+ * num_maps, the grid or atomics; a map's entries are bit for bit the same in any batch.  workspace: at least
+ * bn_eval_slip_workspace_bytes(...) bytes (0 for arguments out of range), free again once the stream has passed the call.
+ *
+ * bn_eval_risk_async: risk (num_settings, num_maps, cells) float32, the tensor bn_risk_maps_infer writes; slips y and classes
+ * (num_maps, cells); num_settings in [1, BN_RISK_MAX_SETTINGS].  stuck(v) = 1.0f - clamp(v, 0, 1) <= stuck_threshold in float32,
+ * the environment step's arithmetic.  One launch handles every setting and reads y and the classes once.
+ *   counts (num_maps, num_settings, C, BN_EVAL_RISK_COUNTS) per map, setting k and true class:
+ *       [0] y > risk_k;  [1 + 2 stuck(risk_k) + stuck(y)]: [1] believed safe and safe, [2] BELIEVED SAFE, ACTUALLY STUCK,
+ *       [3] believed stuck, actually safe, [4] believed stuck and stuck
+ *   invalid (num_maps, num_settings)  cells in no count: a class outside [0, C), a non-finite y or a non-finite risk_k
+ */
+#define BN_EVAL_MAX_CLASSES 64
+#define BN_EVAL_MAX_BINS 64
+#define BN_EVAL_MAX_GROUPS 512
+#define BN_EVAL_SLAB_CELLS 4096
+#define BN_EVAL_SLIP_SUMS 8
+#define BN_EVAL_RISK_COUNTS 5
+int bn_eval_confusion_async(int32_t device_id, void *stream, const int32_t *true_classes_device, const int32_t *pred_classes_device,
+                            int32_t num_maps, int64_t cells, int32_t num_classes, int64_t *table_device, int64_t *ignored_device);
+size_t bn_eval_slip_workspace_bytes(int32_t num_maps, int64_t cells, int32_t num_classes, int32_t num_bins);
+int bn_eval_slip_async(int32_t device_id, void *stream, const float *mean_device, const float *std_device, const float *latent_mean_device,
+                       const float *latent_std_device, const float *slopes_device, const int32_t *classes_device, const float *slips_device,
+                       int32_t num_maps, int64_t cells, int32_t num_classes, int32_t num_bins, double max_slope, double *sums_device,
+                       int64_t *counts_device, int64_t *invalid_device, double *total_device, void *workspace_device, size_t workspace_bytes);
+int bn_eval_risk_async(int32_t device_id, void *stream, const float *risk_device, const float *slips_device, const int32_t *classes_device,
+                       int32_t num_settings, int32_t num_maps, int64_t cells, int32_t num_classes, float stuck_threshold,
+                       int64_t *counts_device, int64_t *invalid_device);
+const char *bn_eval_last_error(void);
+
+/*
  * AStar (src/planners/global_planners/search_based/astar.py), the A* global planner, as one goal-rooted shortest-path solve
  * per (map, goal) on the GPU: the cost-to-go field D and a one-byte next-hop map for B instances of one H x W shape, then
  * O(path length) host walks per start (csrc/astar_kernels.hip).  Graph and arithmetic are astar.py's: 8-connected cells

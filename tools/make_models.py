@@ -7,7 +7,8 @@ scripts/generate_terrain_dataset.py, scripts/train_terrain_classifier.py and scr
   3. SlipRegressorTrainer on SlipRegressionDataset(train)              -> <out>/regressors/.../models/NN_class.pth and
                                                                           <out>/slip_observations/NN_class.pth;
   4. load_terrain_classifier + load_slip_regressors read both back;
-  5. TraversabilityPredictor.predict on every map of the test split: a Normal of (G, G) per map, compared with the latent model.
+  5. TraversabilityPredictor.predict: a Normal of (G, G) per map; Evaluator.run on the test split: the classifier's confusion matrix, the
+     regressors' errors against the latent model per class and slope bin, the risk maps' calibration (tools/evaluate_models.py).
 
     python tools/make_models.py --out /tmp/models [--grid-size 64] [--environments 10] [--train-instances 8] [--epochs 2] [--iterations 20]
 
@@ -59,6 +60,7 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("tools/make_models.py needs an MI355X (gfx950) device")
     from benchnav_amd.dataset import DatasetGenerator, SlipRegressionDataset, TerrainClassificationDataset, TraversabilityPredictionDataset
+    from benchnav_amd.evaluate import Evaluator
     from benchnav_amd.gp import SlipRegressorTrainer, TraversabilityPredictor, load_slip_regressors
     from benchnav_amd.terrain import slip_models
     from benchnav_amd.unet import load_terrain_classifier
@@ -109,21 +111,24 @@ def main():
     regressors = load_slip_regressors(T, reg_trainer.model_directory, out, device=dev)
     predictor = TraversabilityPredictor(classifier, regressors, device=dev)
     view = TraversabilityPredictionDataset(test)
-    mean_err, pixel_acc = [], []
-    for m in range(len(view)):
-        colors, slopes, lat_mean, _ = view[m]
-        pred = predictor.predict(colors, slopes)
-        assert isinstance(pred, torch.distributions.Normal) and tuple(pred.mean.shape) == (args.grid_size, args.grid_size)
-        mean_err.append(float((pred.mean - lat_mean).abs().mean()))
-        pixel_acc.append(float((classifier.predict(colors[None])[0] == test.classes(m)).float().mean()))
+    colors, slopes, _, _ = view[0]
+    pred = predictor.predict(colors, slopes)
+    assert isinstance(pred, torch.distributions.Normal) and tuple(pred.mean.shape) == (args.grid_size, args.grid_size)
+    # every map of the test split through the evaluation stage: one pass on the device, one download (benchnav_amd/evaluate.py)
+    evaluation = Evaluator(test, predictor, num_classes=T, seed=args.seed).run(["expected_value", "var@0.9", "cvar@0.9"])
+    pixel_accuracy = evaluation.summary()["classification"]["pixel_accuracy"]
+    rows = [r for r in evaluation.summary()["slip"]["per_class"] if r["count"]]
+    mean_abs_error = sum(r["mae"] * r["count"] for r in rows) / sum(r["count"] for r in rows) if rows else None
     times["predict_s"] = time.perf_counter() - t0
     report = {"out": out, "maps": {"train": len(train), "valid": len(valid), "test": len(test)}, "grid_size": args.grid_size,
               "classifier": {"epochs": args.epochs, "train_loss": clf_trainer.history["train_epoch"], "valid_loss": clf_trainer.history["valid_epoch"],
-                             "test_pixel_accuracy": sum(pixel_acc) / len(pixel_acc)},
+                             "test_pixel_accuracy": pixel_accuracy},
               "regressors": {"iterations": args.iterations, "points": [int(phis[k].numel()) for k in range(T)]},
-              "prediction": {"shape": [args.grid_size, args.grid_size], "mean_abs_error_of_the_slip_mean": sum(mean_err) / len(mean_err)},
+              "prediction": {"shape": [args.grid_size, args.grid_size], "mean_abs_error_of_the_slip_mean": mean_abs_error},
+              "evaluation": evaluation.to_dict(),
               "seconds": {k: round(v, 3) for k, v in times.items()}}
     print(json.dumps(report))
+    print(evaluation.table())
     print(f"predict: Normal(mean, std) of shape ({args.grid_size}, {args.grid_size}) for {len(view)} test maps")
 
 
