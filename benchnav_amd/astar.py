@@ -21,7 +21,7 @@ import torch
 import torch.nn as nn
 
 from . import _capi
-from ._device import Handle, _DevArray, resolve_device, stream_ptr
+from ._device import Handle, _DevArray, resolve_device, stream_ptr  # noqa: F401  (tests import _DevArray from here)
 
 
 class AStar(Handle, nn.Module):
@@ -39,7 +39,7 @@ class AStar(Handle, nn.Module):
         assert risks.shape == heights.shape, "Traversability and height maps must have the same shape."
         self._h, self._w = heights.shape
         self._goal_node = self._pos_to_index(goal_pos)                             # astar.py:71
-        self._dev = resolve_device(self.device, "AStar", lenient=True)
+        self.dev = self._dev = resolve_device(self.device, "AStar", lenient=True)
         heights = heights.to(torch.float32).contiguous()
         risks = risks.to(torch.float32).contiguous()
         # the goal checks of forward() (astar.py:88-94), decided once: the goal never changes
@@ -86,8 +86,8 @@ class AStar(Handle, nn.Module):
         self._check(self._lib.bn_astar_sync(self._handle))
         d, nx = C.c_void_p(), C.c_void_p()
         self._check(self._lib.bn_astar_buffers(self._handle, 0, C.byref(d), C.byref(nx)))
-        D = torch.as_tensor(_DevArray(d.value, (self._h, self._w)), device=self._dev).clone()
-        n = torch.as_tensor(_DevArray(nx.value, (self._h, self._w), typestr="|u1"), device=self._dev).clone()
+        D = self.view(d.value, (self._h, self._w)).clone()
+        n = self.view(nx.value, (self._h, self._w), "|u1").clone()
         return D, n
 
     # ---- jump tables (csrc/astar_kernels.hip): hop counts and batched paths that stay on the device --------------------------
@@ -112,7 +112,7 @@ class AStar(Handle, nn.Module):
         self._check(self._lib.bn_astar_sync(self._handle))
         hp, jp, lv, eb = C.c_void_p(), C.c_void_p(), C.c_int32(), C.c_int32()
         self._check(self._lib.bn_astar_jump_buffers(self._handle, 0, C.byref(hp), C.byref(jp), C.byref(lv), C.byref(eb)))
-        return torch.as_tensor(_DevArray(hp.value, (self._h, self._w), typestr="<i4"), device=self._dev).clone()
+        return self.view(hp.value, (self._h, self._w), "<i4").clone()
 
     def paths(self, states: torch.Tensor, max_len: Optional[int] = None):
         """forward() for N starts at once, on the device.  states: (N, 2) or (N, 3) positions, host or device.  Returns

@@ -20,14 +20,14 @@ Semantics the reference loop fixes ("A* + DWA loop"):
 from __future__ import annotations
 
 import ctypes as C
-import weakref
 from typing import Optional
 
 import numpy as np
 import torch
 
 from . import _capi
-from ._device import Handle, _DevArray, stream_ptr
+from ._device import Handle, stream_ptr
+from ._episodes import EpisodeLoop
 
 _MESSAGES = {
     _capi.BN_AD_OUT_OF_BOUNDS: "Start or goal position is out of bounds.",       # astar.py:88-92
@@ -44,9 +44,10 @@ def _per_instance(a, B: int, G: int, what: str) -> np.ndarray:
     return np.ascontiguousarray(a)
 
 
-class AStarDWALoop(Handle):
+class AStarDWALoop(Handle, EpisodeLoop):       # (Handle first: its close() and `with` are the loop's)
     family = "astar"                         # the handle the loop owns; the planner's (`_h`) is the environment's
     _astar = property(lambda self: self._handle)
+    _noun, _buffers_fn = "steps", "bn_astar_dwa_episode_buffers"
 
     def __init__(self, env, heights, risks, stuck_threshold: float, a_lim, delta_t: float, num_lin_vel: int = 10,
                  num_ang_vel: int = 10, lookahead_distance: float = 1.0, walk: str = "serial"):
@@ -58,11 +59,10 @@ class AStarDWALoop(Handle):
         if walk not in ("serial", "jump"):
             raise ValueError(f"walk must be 'serial' or 'jump', got {walk!r}")
         self.walk = walk
+        EpisodeLoop.__init__(self, env)
         planner = env.planner
-        self.env, self.B, self.G = env, planner.B, planner.G
-        self._lib, self._h = planner._lib, planner._h
-        self._dev = env._dev
-        B, G = self.B, self.G
+        self.dev = self._dev
+        B, G = self.B, self.G = planner.B, planner.G
         self._heights = _per_instance(heights, B, G, "heights")
         self._risks = _per_instance(risks, B, G, "risks")
         if planner._shared_map and B > 1 and not all(np.array_equal(self._risks[0], r) for r in self._risks[1:]):
@@ -97,11 +97,10 @@ class AStarDWALoop(Handle):
         if walk == "jump":
             self._check(self._lib.bn_astar_jump_build_async(self._astar, stream_ptr(self._dev)))
         self._prev = torch.zeros(B, 2, device=self._dev)          # the window centre: DWA's _previous_action_seq[0] (zeros, dwa.py:59)
-        self._steps = 0
         self.status = np.zeros(B, np.int32)
         self.status_step = np.full(B, -1, np.int32)
         _capi.check(self._lib.bn_astar_dwa_reset(self._h))
-        env._on_reset.append(weakref.WeakMethod(self.reset))
+        self._register()
 
     def pos_to_index(self, pos):
         """AStar._pos_to_index (astar.py:215-228): float32 arithmetic, int() truncates toward zero."""
@@ -115,7 +114,7 @@ class AStarDWALoop(Handle):
         self.env._check_stream()
         _capi.check(self._lib.bn_astar_dwa_reset(self._h))
         self._prev.zero_()
-        self._steps = 0
+        self._rows = 0
         self.status = np.zeros(self.B, np.int32)
         self.status_step = np.full(self.B, -1, np.int32)
 
@@ -126,20 +125,9 @@ class AStarDWALoop(Handle):
         state and NaN elsewhere.  done_step and status steps count from the last reset.  log=False only enqueues and
         returns None: the log, done_step and status stay on the device (episode_buffers()), `status` / `status_step` here are
         not refreshed and the walks' error word is not read."""
-        env = self.env
-        env._check_stream()
-        if env._steps != self._steps:
-            raise RuntimeError(f"the environment has taken {env._steps} steps since its reset, this loop {self._steps}: "
-                               "drive an episode either with env.step or with run()")
-        n = int(n_steps)
-        if n < 1:
-            raise ValueError("n_steps must be >= 1")
-        zp = None
-        if z is not None:
-            zp = torch.as_tensor(z).to(self._dev, torch.float32).contiguous()
-            if zp.shape != (n, self.B):
-                raise ValueError(f"z must be (n_steps, B) = {(n, self.B)}, got {tuple(zp.shape)}")
-        state = env._robot_state.contiguous()
+        n = self._guard(n_steps)
+        zp = self._slip_draws(z, n)
+        state = self.env._robot_state.contiguous()
         _capi.check(self._lib.bn_astar_dwa_set_walk(self._h, 1 if self.walk == "jump" else 0))   # (the planner handle may serve other loops)
         _capi.check(self._lib.bn_astar_dwa_episode_async(
             self._h, self._astar, n, C.c_void_p(state.data_ptr()), _capi.BN_MEM_DEVICE, C.c_void_p(self._prev.data_ptr()),
@@ -149,10 +137,7 @@ class AStarDWALoop(Handle):
         B = self.B
         if not log:
             ptr = self.episode_buffers()[0]
-            env._robot_state = torch.as_tensor(_DevArray(ptr, (n + 1, B, 3)), device=self._dev)[-1].clone()
-            env._steps += n
-            env._elapsed_time += n * env._delta_t
-            self._steps += n
+            self._advance(n, self.view(ptr, (n + 1, B, 3))[-1].clone())
             return None
         states = np.empty((n + 1, B, 3), np.float32)
         rewards = np.empty((n, B), np.float32)
@@ -165,20 +150,10 @@ class AStarDWALoop(Handle):
         rc = self._lib.bn_astar_dwa_episode_log(self._h, ptr(states), ptr(rewards), ptr(actions), ptr(sub_goals), ptr(done),
                                                 ptr(status), ptr(status_step))
         if rc == _capi.BN_OK or rc == _capi.BN_ERR_STATE:      # the steps ran (a broken walk only froze its rover): keep in step
-            env._robot_state = torch.as_tensor(states[-1], device=self._dev).contiguous()
-            env._steps += n
-            env._elapsed_time += n * env._delta_t
-            self._steps += n
+            self._advance(n, torch.as_tensor(states[-1], device=self._dev).contiguous())
             self.status, self.status_step = status, status_step
         _capi.check(rc)
         return states, rewards, actions, sub_goals, done, status
-
-    def episode_buffers(self):
-        """Device pointers (states (n+1,B,3), rewards (n,B), done_step (B), status (B), both int32) of the latest run's log, its n
-        and the row capacity the log is laid out for.  Nothing is copied."""
-        s, r, d, st, n, cap = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int32(), C.c_int32()
-        _capi.check(self._lib.bn_astar_dwa_episode_buffers(self._h, C.byref(s), C.byref(r), C.byref(d), C.byref(st), C.byref(n), C.byref(cap)))
-        return s.value, r.value, d.value, st.value, n.value, cap.value
 
     def set_root(self, instance: int, cell):
         """Instance `instance`'s root cell (ix, iy), or None to forget it: the start of the previous path DWA keeps where the

@@ -39,7 +39,6 @@ from ._device import check, resolve_device, stream_ptr
 GOAL, TIME_LIMIT, STOPPED, INVALID = (_capi.BN_OUTCOME_GOAL, _capi.BN_OUTCOME_TIME_LIMIT, _capi.BN_OUTCOME_STOPPED,
                                       _capi.BN_OUTCOME_INVALID)
 OUTCOMES = ("GOAL", "TIME_LIMIT", "STOPPED", "INVALID")          # indexed by the outcome code
-PLANNERS = ("mppi", "astar_dwa", "cl_rrt")
 # the per-episode arrays of score_episodes and of a Report, with their dtypes
 FIELDS = (("outcome", torch.int32), ("steps", torch.int32), ("time", torch.float64), ("path_length", torch.float64),
           ("reward_sum", torch.float64), ("reward_min", torch.float32), ("stuck_steps", torch.int32), ("final_distance", torch.float64))
@@ -235,7 +234,111 @@ class Report:
             f.write("\n")
 
 
-# ---- the driver ------------------------------------------------------------------------------------------------------------------------
+# ---- episode drivers: a planner's side of a run ------------------------------------------------------------------------------------------
+class EpisodeDriver:
+    """What Benchmark.run asks of a planner.  One driver per run; per chunk open(handle, env, first episode, map indices); per
+    setting set_risk_maps((B, G, G) device tensor) and, after env.reset, run(rows), the log=False run; then score_inputs(), the
+    device pointers (states, rewards, done_step, stopped or None) bn_episode_score reads, and words(), the rovers' int32 device
+    words by name (`word_names`); close() once the chunk's scores are written.  handle_kwargs(kw): the keywords of the chunk's
+    NativeMPPI; rows(max_steps): the rows of an episode's log.  This base drives closed loops: `loops[-1]` runs, and the loops of
+    earlier settings live until close()."""
+    word_names: Tuple[str, ...] = ()
+    rows = staticmethod(int)
+
+    def __init__(self, bench: "Benchmark", kw: dict) -> None:
+        self.bench, self.kw, self.loops = bench, dict(kw), []
+
+    def open(self, pl, env, e0: int, idx: torch.Tensor) -> None:
+        self.pl, self.env, self.idx = pl, env, idx
+
+    def run(self, rows: int) -> None:
+        self.loops[-1].run(rows, log=False)
+
+    def score_inputs(self):
+        return self.loops[-1].episode_buffers()[:4]
+
+    def words(self) -> Dict[str, torch.Tensor]:
+        return {}
+
+    def close(self) -> None:
+        while self.loops:
+            self.loops.pop().close()
+
+
+class MPPIDriver(EpisodeDriver):
+    handle_kwargs = classmethod(lambda cls, kw: {"horizon": 50, "num_samples": 1024, **kw})
+
+    def set_risk_maps(self, chunk_risk: torch.Tensor) -> None:
+        for b in range(self.env.B):
+            self.pl.set_map_device(chunk_risk[b].data_ptr(), b)
+
+    def run(self, rows: int) -> None:
+        self.env.run(rows, log=False)
+
+    def score_inputs(self):
+        return self.pl.episode_buffers()[:3] + (None,)
+
+
+class AStarDWADriver(EpisodeDriver):
+    # the DWA rolls its candidates out on this handle's kernels
+    handle_kwargs = classmethod(lambda cls, kw: {"horizon": kw.get("horizon", 10), "num_samples": 64})
+
+    def set_risk_maps(self, chunk_risk: torch.Tensor) -> None:
+        """A fresh loop on the split's heights: it sets the planner's maps and solves A* on them."""
+        from .astar_dwa import AStarDWALoop
+        bn, kw = self.bench, self.kw
+        self.loops.append(AStarDWALoop(self.env, bn.dataset.heights[self.idx], chunk_risk, stuck_threshold=bn.stuck_threshold,
+                                       a_lim=kw.get("a_lim", (0.5, 0.5)), delta_t=kw.get("dwa_delta_t", bn.delta_t),
+                                       num_lin_vel=kw.get("num_lin_vel", 10), num_ang_vel=kw.get("num_ang_vel", 10),
+                                       lookahead_distance=kw.get("lookahead_distance", 1.0), walk=kw.get("walk", "serial")))
+
+
+class CLRRTDriver(EpisodeDriver):
+    word_names = ("status", "plans")
+    rows = staticmethod(clrrt_iterations)
+    # the handle carries the environment; nothing solves on it
+    handle_kwargs = classmethod(lambda cls, kw: {"horizon": 8, "num_samples": 64})
+
+    def __init__(self, bench: "Benchmark", kw: dict) -> None:
+        unknown = set(kw) - {"max_iterations", "max_seqs", "delta_distance", "goal_sample_rate", "path_cap"}
+        if unknown:
+            raise TypeError(f"unknown cl_rrt keywords: {sorted(unknown)}")
+        super().__init__(bench, kw)
+        self.rrts: Dict[int, object] = {}                                    # the chunk size's CLRRT
+
+    def open(self, pl, env, e0: int, idx: torch.Tensor) -> None:
+        """One loop per chunk (its rovers' maps change with the setting), on a CLRRT with the grid, limits and action bounds of
+        the environment's handle."""
+        from .clrrt import CLRRT
+        from .clrrt_loop import CLRRTLoop
+        bn = self.bench
+        if env.B not in self.rrts:
+            self.rrts[env.B] = CLRRT.from_parameters(bn.G, bn.resolution, pl.x_limits, pl.y_limits, stuck_threshold=bn.stuck_threshold,
+                                                     delta_t=bn.delta_t, goal_threshold=bn.goal_threshold, device=str(bn.dev),
+                                                     seed=bn.seed & _MASK32, **self.kw)
+        self.loops = [CLRRTLoop(env, self.rrts[env.B], seeds=[planner_seed(bn.seed, e0 + i) for i in range(env.B)])]
+
+    def set_risk_maps(self, chunk_risk: torch.Tensor) -> None:
+        self.loops[0].set_risk_maps(chunk_risk)
+
+    def words(self) -> Dict[str, torch.Tensor]:
+        return dict(zip(self.word_names, self.loops[0].rover_buffers()))
+
+
+DRIVERS = {"mppi": MPPIDriver, "astar_dwa": AStarDWADriver, "cl_rrt": CLRRTDriver}
+PLANNERS = tuple(DRIVERS)
+
+
+def _raise_if_running(status: Optional[np.ndarray], settings, rows: int) -> None:
+    """status: the (C, ...) status words a driver reported, or None.  A rover still RUNNING breaks clrrt_iterations' bound."""
+    running = np.argwhere(status.reshape(len(settings), -1) == _capi.BN_CL_RUNNING) if status is not None else np.empty((0, 2))
+    if running.size:
+        c, e = (int(v) for v in running[0])
+        raise RuntimeError(f"episode {e} under setting {setting_name(settings[c])} is still running after {rows} loop iterations "
+                           f"({len(running)} such episodes): clrrt_iterations' bound does not hold")
+
+
+# ---- the benchmark -----------------------------------------------------------------------------------------------------------------------
 class Benchmark:
     def __init__(self, dataset, predictor=None, start_pos=(4.0, 4.0), goal_pos=(28.0, 28.0), delta_t: float = 0.1, time_limit: float = 100.0,
                  stuck_threshold: float = 0.1, goal_threshold: float = 1.0, trials: int = 1, chunk: int = 64, seed: int = 0,
@@ -280,18 +383,27 @@ class Benchmark:
                                seeds=[risk_seed(self.seed, m) for m in range(self.M)], device=self.dev)
 
     # -- a run --
-    def _planner(self, B: int, kind: str, kw: dict):
+    def _chunk(self, handles: Dict[int, object], kw: dict, j: int):
+        """Chunk j: (its first episode, the planner handle of its size -- made with `kw` where `handles` has none: a last, shorter
+        chunk gets one of its own --, the environment, every instance's map index (B,) on the device, the INVALID flags (B,) uint8)."""
+        from .env import BatchedPlanetaryEnv
         from .native import NativeMPPI
-        kw = dict(kw)
-        if kind == "astar_dwa":
-            kw = {"horizon": kw.get("horizon", 10), "num_samples": 64}       # the DWA rolls its candidates out on this handle's kernels
-        elif kind == "cl_rrt":
-            kw = {"horizon": 8, "num_samples": 64}                           # the handle carries the environment; nothing solves on it
-        else:
-            kw.setdefault("horizon", 50)
-            kw.setdefault("num_samples", 1024)
-        return NativeMPPI(grid_size=self.G, resolution=self.resolution, num_instances=B, shared_map=False, stuck_threshold=self.stuck_threshold,
-                          stream=torch.cuda.current_stream(self.dev).cuda_stream, device_id=self.dev.index, **kw)
+        ds, dev, e0 = self.dataset, self.dev, j * self.chunk
+        B = min(self.chunk, self.M * self.trials - e0)
+        if B not in handles:
+            handles[B] = NativeMPPI(grid_size=self.G, resolution=self.resolution, num_instances=B, shared_map=False, stuck_threshold=self.stuck_threshold,
+                                    stream=torch.cuda.current_stream(dev).cuda_stream, device_id=dev.index, **kw)
+        pl = handles[B]
+        maps = [(e0 + i) // self.trials for i in range(B)]
+        idx = torch.as_tensor(maps, device=dev)
+        env = BatchedPlanetaryEnv(pl, ds.latent_mean[idx].cpu().numpy(), ds.latent_std[idx].cpu().numpy(), self.start_pos[maps],
+                                  self.goal_pos[maps], delta_t=self.delta_t, time_limit=self.time_limit,
+                                  stuck_threshold=self.stuck_threshold, goal_threshold=self.goal_threshold,
+                                  seed=chunk_seed(self.seed, j), freeze_on_goal=True, check_positions=False)
+        at = lambda pos: torch.cat([pos, torch.zeros(B, 1, device=dev)], 1).unsqueeze(1)
+        bad_start = env.collision_check(at(env._start_pos))[:, 0]          # PlanetaryEnv.__init__'s two draws, kept per instance
+        bad_goal = env.collision_check(at(env._goal_pos))[:, 0]
+        return e0, pl, env, idx, (bad_start | bad_goal).to(torch.uint8).contiguous()
 
     def run(self, planner: str, settings, **planner_kwargs) -> Report:
         """Every episode of the split under every setting.  planner "mppi": planner_kwargs go to NativeMPPI (horizon, num_samples,
@@ -299,98 +411,37 @@ class Benchmark:
         num_ang_vel (10), lookahead_distance (1.0), walk ("serial"); the A* planner reads the split's heights.  "cl_rrt": the
         reference CLRRT's max_iterations (500), max_seqs (250), delta_distance (5), goal_sample_rate (0.25) and path_cap (None);
         a rover still running after clrrt_iterations(max_steps) iterations raises."""
-        from .env import BatchedPlanetaryEnv
         if planner not in PLANNERS:
             raise ValueError(f"planner must be one of {PLANNERS}")
         settings = [parse_setting(s) for s in settings]
-        ds, dev, n = self.dataset, self.dev, self.max_steps
-        rows = clrrt_iterations(n) if planner == "cl_rrt" else n       # rows of an episode's log
-        E, Cn = self.M * self.trials, len(settings)
+        dev, n, E, Cn = self.dev, self.max_steps, self.M * self.trials, len(settings)
+        drv = DRIVERS[planner](self, planner_kwargs)
+        rows = drv.rows(n)                                             # rows of an episode's log
         with torch.cuda.device(dev):
             risk = self.risk_maps(settings)
-            total = {name: torch.empty(Cn, E, device=dev, dtype=dt) for name, dt in FIELDS}
-            words = {name: torch.empty(Cn, E, device=dev, dtype=torch.int32) for name in ("status", "plans")} if planner == "cl_rrt" else {}
+            total = {name: torch.empty(Cn, E, device=dev, dtype=dt) for name, dt in FIELDS + tuple((w, torch.int32) for w in drv.word_names)}
             handles: Dict[int, object] = {}
-            rrts: Dict[int, object] = {}
             try:
                 for j in range((E + self.chunk - 1) // self.chunk):
-                    e0 = j * self.chunk
-                    B = min(self.chunk, E - e0)
-                    maps = [(e0 + i) // self.trials for i in range(B)]
-                    if B not in handles:                               # a last, shorter chunk gets a handle of its own size
-                        handles[B] = self._planner(B, planner, planner_kwargs)
-                    pl = handles[B]
-                    idx = torch.as_tensor(maps, device=dev)
-                    env = BatchedPlanetaryEnv(pl, ds.latent_mean[idx].cpu().numpy(), ds.latent_std[idx].cpu().numpy(), self.start_pos[maps],
-                                              self.goal_pos[maps], delta_t=self.delta_t, time_limit=self.time_limit,
-                                              stuck_threshold=self.stuck_threshold, goal_threshold=self.goal_threshold,
-                                              seed=chunk_seed(self.seed, j), freeze_on_goal=True, check_positions=False)
-                    at = lambda pos: torch.cat([pos, torch.zeros(B, 1, device=dev)], 1).unsqueeze(1)
-                    bad_start = env.collision_check(at(env._start_pos))[:, 0]          # PlanetaryEnv.__init__'s two draws, kept per instance
-                    bad_goal = env.collision_check(at(env._goal_pos))[:, 0]
-                    invalid = (bad_start | bad_goal).to(torch.uint8).contiguous()
-                    loops = []
-                    if planner == "cl_rrt":                            # one loop per chunk: its rovers' maps change with the setting
-                        if B not in rrts:
-                            rrts[B] = self._clrrt(pl, planner_kwargs)
-                        loops.append(self._clrrt_loop(env, rrts[B], e0))
+                    e0, pl, env, idx, invalid = self._chunk(handles, drv.handle_kwargs(planner_kwargs), j)
+                    drv.open(pl, env, e0, idx)
                     for c in range(Cn):
                         chunk_risk = risk[c, idx].contiguous()
-                        if planner == "mppi":
-                            for b in range(B):
-                                pl.set_map_device(chunk_risk[b].data_ptr(), b)
-                        elif planner == "cl_rrt":
-                            loops[0].set_risk_maps(chunk_risk)
-                        else:                                          # (the loop sets the planner's maps and solves A* on them)
-                            loops.append(self._astar_dwa(env, ds.heights[idx], chunk_risk, planner_kwargs))
+                        drv.set_risk_maps(chunk_risk)
                         env.reset(seed=chunk_seed(self.seed, j))       # (resets the chunk's loop too)
                         pl.set_mean(None)
-                        out = {name: t[c, e0:e0 + B] for name, t in total.items()}
-                        if planner == "mppi":
-                            env.run(n, log=False)
-                            states, rewards, done, _, _ = pl.episode_buffers()
-                            stopped = None
-                        else:
-                            loops[-1].run(rows, log=False)
-                            states, rewards, done, stopped, _, _ = loops[-1].episode_buffers()
-                        _score_pointers(dev, rows, B, states, rewards, env._goal_pos.data_ptr(), None, done, stopped, invalid.data_ptr(),
+                        drv.run(rows)
+                        states, rewards, done, stopped = drv.score_inputs()
+                        out = {name: t[c, e0:e0 + env.B] for name, t in total.items()}
+                        _score_pointers(dev, rows, env.B, states, rewards, env._goal_pos.data_ptr(), None, done, stopped, invalid.data_ptr(),
                                         self.stuck_threshold, self.delta_t, out)
-                        if planner == "cl_rrt":
-                            for name, view in zip(("status", "plans"), loops[0].rover_buffers()):
-                                words[name][c, e0:e0 + B].copy_(view)
+                        for name, view in drv.words().items():
+                            out[name].copy_(view)
                     torch.cuda.current_stream(dev).synchronize()       # the chunk's scores are written: its loops and maps may go
-                    for loop in loops:
-                        loop.close()
+                    drv.close()
                 arrays = {name: t.cpu().numpy().reshape(Cn, self.M, self.trials) for name, t in total.items()}
-                if planner == "cl_rrt":
-                    running = np.argwhere(words["status"].cpu().numpy() == _capi.BN_CL_RUNNING)
-                    if running.size:
-                        c, e = (int(v) for v in running[0])
-                        raise RuntimeError(f"episode {e} under setting {setting_name(settings[c])} is still running after {rows} loop iterations "
-                                           f"({len(running)} such episodes): clrrt_iterations' bound does not hold")
-                    arrays["plans"] = words["plans"].cpu().numpy().reshape(Cn, self.M, self.trials)
             finally:
                 for pl in handles.values():
                     pl.close()
+        _raise_if_running(arrays.pop("status", None), settings, rows)
         return Report(planner, settings, arrays, self.seed, self.chunk, self.trials, n, self.delta_t, self.time_limit)
-
-    def _clrrt(self, pl, kw: dict):
-        """The chunk size's CLRRT, on the grid, limits and action bounds of the environment's handle."""
-        from .clrrt import CLRRT
-        unknown = set(kw) - {"max_iterations", "max_seqs", "delta_distance", "goal_sample_rate", "path_cap"}
-        if unknown:
-            raise TypeError(f"unknown cl_rrt keywords: {sorted(unknown)}")
-        return CLRRT.from_parameters(self.G, self.resolution, pl.x_limits, pl.y_limits, stuck_threshold=self.stuck_threshold,
-                                     delta_t=self.delta_t, goal_threshold=self.goal_threshold, device=str(self.dev), seed=self.seed & _MASK32,
-                                     **kw)
-
-    def _clrrt_loop(self, env, rrt, e0: int):
-        from .clrrt_loop import CLRRTLoop
-        return CLRRTLoop(env, rrt, seeds=[planner_seed(self.seed, e0 + i) for i in range(env.B)])
-
-    def _astar_dwa(self, env, heights, risks, kw: dict):
-        from .astar_dwa import AStarDWALoop
-        return AStarDWALoop(env, heights, risks, stuck_threshold=self.stuck_threshold, a_lim=kw.get("a_lim", (0.5, 0.5)),
-                            delta_t=kw.get("dwa_delta_t", self.delta_t), num_lin_vel=kw.get("num_lin_vel", 10),
-                            num_ang_vel=kw.get("num_ang_vel", 10), lookahead_distance=kw.get("lookahead_distance", 1.0),
-                            walk=kw.get("walk", "serial"))

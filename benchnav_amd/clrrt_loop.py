@@ -23,7 +23,6 @@ MT19937 stream, and a rover that needs a plan beyond P stops with NO_PLAN; `set_
 from __future__ import annotations
 
 import ctypes as C
-import weakref
 from typing import Optional
 
 import numpy as np
@@ -32,20 +31,25 @@ import torch
 from . import _capi
 from .clrrt import _Handle
 from ._device import _check_seed
+from ._episodes import EpisodeLoop
 
 STATUS_NAMES = ("RUNNING", "GOAL", "TIME_LIMIT", "NO_PLAN", "NO_SEQUENCE", "PLAN_EXHAUSTED", "PATH_OVERFLOW", "OUT_OF_BOUNDS")
 EVENT_NAMES = ("STEP", "REPLAN", "FROZEN")
 
 
-class CLRRTLoop:
+class CLRRTLoop(EpisodeLoop):
+    _noun, _buffers_fn, _row_draws = "iterations", "bn_clrrt_loop_episode_buffers", True
+    _iters = property(lambda self: self._rows)
+    # episode_buffers(): done_step is done_iter where the rover reached its goal, else -1; stopped the status where it is neither
+    # RUNNING, GOAL nor TIME_LIMIT, else 0 (benchmark.clrrt_outcome_words states the rule on NumPy)
+
     def __init__(self, env, planner, seeds=None, risk_maps=None):
         """env: a BatchedPlanetaryEnv (its goals are the rovers' goals, its time limit the loop's); planner: a CLRRT on the same
         grid (its risk map, limits, action bounds and parameters serve every rover); seeds: B integers in 0 ... 2^32 - 1 for the
         rovers' planner streams, reseeded at every reset (default: the planner's seed for each); risk_maps: (B, G, G), rover b
         plans on map b (set_risk_maps)."""
-        self.env, self.planner = env, planner
-        self.B = env.B
-        self._lib, self._h, self._dev = env.planner._lib, env.planner._h, env._dev
+        super().__init__(env)
+        self.planner = planner
         if planner._dev != self._dev:
             raise ValueError(f"the planner is on {planner._dev}, the environment on {self._dev}")
         env._check_stream()
@@ -56,10 +60,9 @@ class CLRRTLoop:
         self._handle = _Handle(self._lib, self._dev, self.B, planner)       # the loop's own: plan_batch and forward keep theirs
         if risk_maps is not None:
             self._handle.set_maps(risk_maps)
-        self._iters = 0
         self._zero()
         self.reset()
-        env._on_reset.append(weakref.WeakMethod(self.reset))
+        self._register()
 
     def _zero(self):
         self.status = np.zeros(self.B, np.int32)
@@ -89,7 +92,7 @@ class CLRRTLoop:
         self._goal_nodes = np.ascontiguousarray(nodes.numpy(), np.float32)
         _capi.check(self._lib.bn_clrrt_loop_reset(self._h, self._handle.h, self._goal_nodes.ctypes.data, self._seeds.ctypes.data,
                                                   float(env._delta_t), float(env._time_limit)))
-        self._iters = 0
+        self._rows = 0
         self._zero()
 
     def set_risk_maps(self, risk_maps):
@@ -110,19 +113,9 @@ class CLRRTLoop:
         row without a step holds the rover's state and NaN elsewhere (a flagged replan keeps its deviation).
         log=False downloads nothing and returns None: the log and the rovers' words stay on the device (episode_buffers(),
         rover_buffers()); `status`, `done_iter`, `plans`, `steps` and `elapsed` here are not refreshed."""
-        env = self.env
-        env._check_stream()
-        if env._steps != self._iters:
-            raise RuntimeError(f"the environment has taken {env._steps} steps since its reset, this loop {self._iters} iterations: "
-                               "drive an episode either with env.step or with run()")
-        n, B = int(n_iterations), self.B
-        if n < 1:
-            raise ValueError("n_iterations must be >= 1")
-        zp = None
-        if z is not None:
-            zp = torch.as_tensor(z).to(self._dev, torch.float32).contiguous()
-            if tuple(zp.shape) != (n, B):
-                raise ValueError(f"z must be (n_iterations, B) = {(n, B)}, got {tuple(zp.shape)}")
+        env, B = self.env, self.B
+        n = self._guard(n_iterations)
+        zp = self._slip_draws(z, n)
         sp, P = None, 0
         if samples is not None:
             sp = torch.as_tensor(samples).to(self._dev, torch.float32).contiguous()
@@ -139,10 +132,7 @@ class CLRRTLoop:
         self.follow_ms = float(ms.value)
         self._keep = (zp, sp)
         if not log:
-            env._robot_state = state
-            env._steps += n
-            env._draws += n
-            self._iters += n
+            self._advance(n, state, elapsed=env._elapsed_time)
             return None
         out = {"states": np.empty((n + 1, B, 3), np.float32), "rewards": np.empty((n, B), np.float32), "actions": np.empty((n, B, 2), np.float32),
                "deviations": np.empty((n, B), np.float32), "plan_index": np.empty((n, B), np.int32), "events": np.empty((n, B), np.int32),
@@ -151,22 +141,9 @@ class CLRRTLoop:
         _capi.check(self._lib.bn_clrrt_loop_log(self._h, ptr(out["states"]), ptr(out["rewards"]), ptr(out["actions"]), ptr(out["deviations"]),
                                                 ptr(out["plan_index"]), ptr(out["events"]), ptr(out["done_iter"]), ptr(out["status"]),
                                                 ptr(out["plans"]), ptr(out["steps"])))
-        env._robot_state = state
-        env._steps += n
-        env._draws += n
-        self._iters += n
         self.status, self.done_iter, self.plans, self.steps = out["status"], out["done_iter"], out["plans"], out["steps"]
-        env._elapsed_time = float(self.elapsed.max())
+        self._advance(n, state, elapsed=float(self.elapsed.max()))
         return out
-
-    def episode_buffers(self):
-        """Device pointers (states (cap + 1, B, 3), rewards (cap, B), done_step (B), stopped (B), both int32) of the latest run's
-        log, its n and the row capacity `cap` the log is laid out for: what bn_episode_score reads.  done_step is done_iter where
-        the rover reached its goal, else -1; stopped the status where it is neither RUNNING, GOAL nor TIME_LIMIT, else 0
-        (benchmark.clrrt_outcome_words states the rule on NumPy).  Nothing is copied."""
-        s, r, d, st, n, cap = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int32(), C.c_int32()
-        _capi.check(self._lib.bn_clrrt_loop_episode_buffers(self._h, C.byref(s), C.byref(r), C.byref(d), C.byref(st), C.byref(n), C.byref(cap)))
-        return s.value, r.value, d.value, st.value, n.value, cap.value
 
     def rover_buffers(self):
         """(status (B,), plans (B,)) int32 device tensors: views of the words the latest run left, valid until the next run."""
@@ -189,7 +166,7 @@ class CLRRTLoop:
         it = -1 if iteration is None else int(iteration)
         _capi.check(self._lib.bn_clrrt_loop_set_plans(self._h, self._handle.h, a.ctypes.data, s.ctypes.data, ln.ctypes.data, L, it))
         if it >= 0:
-            self._iters = it
+            self._rows = it
             self.env._steps = self.env._draws = it          # run() advances the two together
 
     def buffer(self, which: int, shape, typestr="<f4") -> torch.Tensor:
@@ -212,9 +189,3 @@ class CLRRTLoop:
             if s == _capi.BN_CL_PATH_OVERFLOW:
                 raise RuntimeError(f"rover {b}, iteration {t}: the path does not fit the path buffer: construct CLRRT with a larger path_cap")
             raise RuntimeError(f"rover {b}, iteration {t}: the start node is the cheapest node within the goal threshold: there is no sequence to return")
-
-    def close(self):
-        h = getattr(self, "_handle", None)
-        if h is not None:
-            h.close()
-            self._handle = None                             # (a loop that just goes leaves the closing to its _Handle)

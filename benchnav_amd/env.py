@@ -84,7 +84,7 @@ class BatchedPlanetaryEnv:
         self._elapsed_time = 0.0
         self._steps = 0
         self._draws = 0
-        self._on_reset = []                        # weak references to the reset() of loops driving this environment (AStarDWALoop)
+        self._on_reset = []                        # weak references to the reset() of the loops driving this environment (_episodes.EpisodeLoop)
         if not check_positions:
             return
         if bool(self.collision_check(torch.cat([self._start_pos, torch.zeros(self.B, 1, device=dev)], 1).unsqueeze(1)).any()) or \
@@ -155,15 +155,12 @@ class BatchedPlanetaryEnv:
         """The fused loop: n_steps of solve -> step inside the planner's pipelined launches (bn_mppi_episode_async),
         from the current robot states.  Returns (states (n_steps+1,B,3), rewards (n_steps,B), first_goal_step (B,)).
         log=False only enqueues and returns None: the log stays on the device (planner.episode_buffers())."""
-        if not log:
-            self.planner.episode(n_steps, self._robot_state.cpu().numpy(), wait=False)
+        out = self.planner.episode(n_steps, self._robot_state.cpu().numpy(), wait=log)       # the log, or None
+        if log:
+            self._robot_state = torch.as_tensor(out[0][-1], device=self._dev).contiguous()
+        else:
             ptr = self.planner.episode_buffers()[0]
             self._robot_state = self.planner.view(ptr, (n_steps + 1, self.B, 3))[-1].clone()
-            self._steps += n_steps
-            self._elapsed_time += n_steps * self._delta_t
-            return None
-        states, rewards, done = self.planner.episode(n_steps, self._robot_state.cpu().numpy())
-        self._robot_state = torch.as_tensor(states[-1], device=self._dev).contiguous()
-        self._steps += n_steps
+        self._steps += n_steps                                     # (EpisodeLoop._advance states the loops' rules next to this one)
         self._elapsed_time += n_steps * self._delta_t
-        return states, rewards, done
+        return out

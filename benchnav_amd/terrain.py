@@ -40,7 +40,7 @@ import numpy as np
 import torch
 
 from . import _capi
-from ._device import Handle, _DevArray, resolve_device, stream_ptr
+from ._device import Handle, resolve_device, stream_ptr
 
 # the dataset script's ranges (scripts/generate_terrain_dataset.py:31-34), the defaults of slip_models()
 SLIP_SENSITIVITY_MINMAX = (1.0, 9.0)
@@ -295,7 +295,7 @@ class TerrainGenerator(Handle):
 
     def __init__(self, grid_size: int, resolution: float, batch: int = 1, roughness_exponent: float = 0.75,
                  amplitude_gain: float = 10, device_id: Optional[int] = None) -> None:
-        self._dev = resolve_device(None if device_id is None else torch.device("cuda", device_id), "TerrainGenerator")
+        self.dev = self._dev = resolve_device(None if device_id is None else torch.device("cuda", device_id), "TerrainGenerator")
         self.grid_size, self.resolution, self.batch = int(grid_size), float(resolution), int(batch)
         self.roughness_exponent, self.amplitude_gain = float(roughness_exponent), float(amplitude_gain)
         self._lib = _capi.load()
@@ -543,9 +543,9 @@ class TerrainGenerator(Handle):
         self._check(self._lib.bn_terrain_color_buffers(self._handle, *[C.byref(p) for p in ptrs]))
         B, G = self.batch, self.grid_size
         with torch.cuda.device(self._dev):
-            cls = torch.as_tensor(_DevArray(ptrs[0].value, (B, G, G), "<i4"), device=self._dev).clone()
-            colors = torch.as_tensor(_DevArray(ptrs[1].value, (B, 3, G, G)), device=self._dev).clone()
-            nz = torch.as_tensor(_DevArray(ptrs[2].value, (B, G, G)), device=self._dev).clone()
+            cls = self.view(ptrs[0].value, (B, G, G), "<i4").clone()
+            colors = self.view(ptrs[1].value, (B, 3, G, G)).clone()
+            nz = self.view(ptrs[2].value, (B, G, G)).clone()
         return cls, colors, nz
 
     def colorize(self, heights, t_classes, num_classes: int, light, ambient_intensity: float = 0.1) -> torch.Tensor:
@@ -615,7 +615,7 @@ class TerrainGenerator(Handle):
         self._check(self._lib.bn_terrain_buffers(self._handle, *[C.byref(p) for p in ptrs]))
         shape = (self.batch, self.grid_size, self.grid_size)
         with torch.cuda.device(self._dev):
-            return tuple(torch.as_tensor(_DevArray(p.value, shape), device=self._dev).clone() for p in ptrs)
+            return tuple(self.view(p.value, shape).clone() for p in ptrs)
 
     def spectrum(self, instance: int = 0) -> np.ndarray:
         """Test hook: the scaled fBm spectrum of `instance` that the inverse DFT reads, (G+2, G+2) complex64."""
