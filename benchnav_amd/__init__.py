@@ -17,6 +17,7 @@
     from benchnav_amd import TerrainClassificationDataset, SlipRegressionDataset, TraversabilityPredictionDataset   # ... and its three views
     from benchnav_amd import Benchmark, score_episodes   # the benchmark stage: risk maps, chunked episodes, scores, a report (benchmark.py)
     from benchnav_amd import Evaluator, EvaluationReport, confusion_matrix, slip_metrics, risk_calibration   # how good the models are (evaluate.py)
+    from benchnav_amd import TaskSet, passable_mask, label_components, sample_pairs, optimal_lengths   # solvable start/goal pairs, SPL (tasks.py)
 """
 from .native import NativeMPPI  # noqa: F401
 
@@ -67,4 +68,7 @@ def __getattr__(name):
     if name in ("Evaluator", "EvaluationReport", "confusion_matrix", "slip_metrics", "risk_calibration"):
         from . import evaluate
         return getattr(evaluate, name)
+    if name in ("TaskSet", "passable_mask", "label_components", "sample_pairs", "optimal_lengths"):
+        from . import tasks
+        return getattr(tasks, name)
     raise AttributeError(name)

@@ -33,6 +33,9 @@ BN_BUF_STATES_ALT, BN_BUF_CONTROLS_ALT = 10, 11
 BN_RISK_EXPECTED, BN_RISK_VAR, BN_RISK_CVAR = 0, 1, 2
 BN_RISK_MAX_SETTINGS = 16
 BN_EVAL_MAX_CLASSES, BN_EVAL_MAX_BINS, BN_EVAL_MAX_GROUPS, BN_EVAL_SLAB_CELLS, BN_EVAL_SLIP_SUMS, BN_EVAL_RISK_COUNTS = 64, 64, 512, 4096, 8, 5
+(BN_TASK_TILE, BN_TASK_STATS, BN_TASK_MAX_SIDE, BN_TASK_MAX_CELLS, BN_TASK_MAX_MAPS, BN_TASK_MAX_PAIRS,
+ BN_TASK_MAX_ATTEMPTS) = 32, 8, 4096, 1 << 24, 4096, 65536, 4096
+BN_TASK_ERR_TILE, BN_TASK_ERR_UNITE, BN_TASK_ERR_FLATTEN = 1, 2, 4
 BN_OUTCOME_GOAL, BN_OUTCOME_TIME_LIMIT, BN_OUTCOME_STOPPED, BN_OUTCOME_INVALID = 0, 1, 2, 3   # bn_episode_outcome
 BN_AD_OK, BN_AD_OUT_OF_BOUNDS, BN_AD_GOAL_COLLISION, BN_AD_FIELD_ERROR = 0, 1, 2, 3   # bn_astar_dwa_status
 BN_RRT_FLAG_GLOBAL_NODES, BN_RRT_FLAG_ONE_WAVE, BN_RRT_FLAG_FOUR_WAVES = 1, 2, 4
@@ -180,6 +183,14 @@ SYMBOLS = {
                            + [C.c_size_t]),
     "bn_eval_risk_async": (C.c_int, [C.c_int32] + [C.c_void_p] * 4 + [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_float, C.c_void_p, C.c_void_p]),
     "bn_eval_last_error": (C.c_char_p, []),
+    "bn_task_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "bn_task_mask_async": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_float, C.c_void_p]),
+    "bn_task_label_async": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_size_t]),
+    "bn_task_sample_async": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint64,
+                                       C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_void_p,
+                                       C.c_void_p, C.c_void_p]),
+    "bn_task_last_error": (C.c_char_p, []),
     "bn_mppi_episode_buffers": (C.c_int, [_H, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int32),
                                           C.POINTER(C.c_int32)]),
     "bn_astar_dwa_episode_buffers": (C.c_int, [_H, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),

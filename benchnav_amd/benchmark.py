@@ -14,7 +14,9 @@ Episode e = m * trials + r (map m, trial r) is instance e % chunk of chunk e // 
 (seed + j) mod 2^64, map m's risk seed (seed + m) mod 2^64 and episode e's CL-RRT stream seed (seed + e) mod 2^32, so a report is a
 function of (seed, chunk, trials), which it stores.
 An episode whose start or goal is not traversable (one collision draw each, as PlanetaryEnv.__init__ makes them) is INVALID: it is
-kept, counted, and left out of every rate and mean.
+kept, counted, and left out of every rate and mean.  With `tasks=` (a tasks.TaskSet: start/goal pairs drawn inside one connected
+region of passable ground, each with its shortest grid path length) a task that cannot be solved is INVALID too, and the report
+adds SPL; without it a report is byte for byte what it was.
 
 A "cl_rrt" run drives `CLRRTLoop` on per-rover risk maps: its log has a row per loop ITERATION, of which a flagged replan takes
 one without a step, so it runs `clrrt_iterations(max_steps)` rows; a rover the planner fails (no plan, no sequence, a plan run out,
@@ -179,18 +181,22 @@ class Report:
     also has `plans` (C, M, trials) int32, the planner's forward calls per episode; for the other planners it is None."""
 
     def __init__(self, planner: str, settings: Sequence[Tuple[str, Optional[float]]], arrays: Dict[str, np.ndarray], seed: int, chunk: int,
-                 trials: int, max_steps: int, delta_t: float, time_limit: float) -> None:
+                 trials: int, max_steps: int, delta_t: float, time_limit: float, tasks=None) -> None:
         self.planner, self.settings = planner, [parse_setting(s) for s in settings]
         self.seed, self.chunk, self.trials, self.max_steps = int(seed), int(chunk), int(trials), int(max_steps)
         self.delta_t, self.time_limit = float(delta_t), float(time_limit)
         for name, _ in FIELDS:
             setattr(self, name, arrays[name])
         self.plans = arrays.get("plans")
+        # with a tasks.TaskSet: every episode's L* (M, trials) float64, and the parameters the tasks were a function of
+        self.optimal_length = None if tasks is None else np.asarray(tasks.optimal_length, np.float64)
+        self.task_params = None if tasks is None else dict(tasks.params)
 
     def summary(self) -> List[dict]:
         """Per setting: the counts of the four outcomes, their rates over the non-INVALID episodes, mean and median time to goal
         and mean path length over the GOAL episodes, mean stuck steps and mean reward (per step) over all valid episodes.  A mean
-        over nothing is None."""
+        over nothing is None.  A run on a task set adds `spl`, the mean over the valid episodes of [outcome == GOAL] * L* / max(L, L*),
+        and `path_ratio_mean`, the mean of L / L* over the GOAL episodes (tasks.py states L*'s two biases)."""
         mean = lambda a: float(np.mean(a)) if a.size else None
         rows = []
         for c, setting in enumerate(self.settings):
@@ -207,15 +213,21 @@ class Report:
                          "path_length_mean": mean(self.path_length[c].ravel()[goal]),
                          "stuck_steps_mean": mean(self.stuck_steps[c].ravel()[valid].astype(np.float64)),
                          "reward_mean": mean(rsum[moved] / steps[moved])})
+            if self.optimal_length is not None:
+                from .tasks import spl_figures
+                rows[-1]["spl"], rows[-1]["path_ratio_mean"] = spl_figures(oc, self.path_length[c], self.optimal_length)
         return rows
 
     def table(self) -> str:
         fmt = lambda v, w, p: f"{'-':>{w}}" if v is None else f"{v:>{w}.{p}f}"
-        lines = [f"{'setting':<16}{'valid':>6}{'goal':>8}{'limit':>8}{'stopped':>8}{'t_goal':>9}{'median':>9}{'path':>9}{'stuck':>8}{'reward':>8}"]
+        with_tasks = self.optimal_length is not None
+        lines = [f"{'setting':<16}{'valid':>6}{'goal':>8}{'limit':>8}{'stopped':>8}{'t_goal':>9}{'median':>9}{'path':>9}{'stuck':>8}{'reward':>8}"
+                 + (f"{'spl':>8}" if with_tasks else "")]
         for r in self.summary():
             lines.append(f"{r['setting']:<16}{r['valid']:>6}{fmt(r['rates']['GOAL'], 8, 3)}{fmt(r['rates']['TIME_LIMIT'], 8, 3)}"
                          f"{fmt(r['rates']['STOPPED'], 8, 3)}{fmt(r['time_to_goal_mean'], 9, 2)}{fmt(r['time_to_goal_median'], 9, 2)}"
-                         f"{fmt(r['path_length_mean'], 9, 2)}{fmt(r['stuck_steps_mean'], 8, 1)}{fmt(r['reward_mean'], 8, 3)}")
+                         f"{fmt(r['path_length_mean'], 9, 2)}{fmt(r['stuck_steps_mean'], 8, 1)}{fmt(r['reward_mean'], 8, 3)}"
+                         + (fmt(r["spl"], 8, 3) if with_tasks else ""))
         return "\n".join(lines)
 
     def to_dict(self) -> dict:
@@ -225,6 +237,10 @@ class Report:
                "outcomes": list(OUTCOMES), "summary": self.summary(), "episodes": {name: listed(getattr(self, name)) for name, _ in FIELDS}}
         if self.plans is not None:
             doc["episodes"]["plans"] = self.plans.tolist()
+        if self.optimal_length is not None:
+            number = lambda v: None if v != v else ("inf" if v == float("inf") else v)
+            doc["tasks"] = self.task_params
+            doc["episodes"]["optimal_length"] = [[number(v) for v in row] for row in self.optimal_length.tolist()]
         return doc
 
     def to_json(self, path: str) -> None:
@@ -342,11 +358,14 @@ def _raise_if_running(status: Optional[np.ndarray], settings, rows: int) -> None
 class Benchmark:
     def __init__(self, dataset, predictor=None, start_pos=(4.0, 4.0), goal_pos=(28.0, 28.0), delta_t: float = 0.1, time_limit: float = 100.0,
                  stuck_threshold: float = 0.1, goal_threshold: float = 1.0, trials: int = 1, chunk: int = 64, seed: int = 0,
-                 num_samples: int = 1000, resolution: float = 0.5) -> None:
+                 num_samples: int = 1000, resolution: float = 0.5, tasks=None) -> None:
         """dataset: a dataset.TerrainDataset (the test split).  predictor: a gp.TraversabilityPredictor, asked for `chunk` maps per
         predict_maps call on colours and slopes; None takes the latent model as the prediction, as io.planner_inputs does.
         start_pos, goal_pos: (2,) for every map or (M, 2).  trials: episodes per map (they differ in the environment's slip draws
-        and the planner's noise).  num_samples: samples per cell of the risk maps.  resolution: metres per cell of the maps."""
+        and the planner's noise).  num_samples: samples per cell of the risk maps.  resolution: metres per cell of the maps.
+        tasks: a tasks.TaskSet of (M, trials) pairs instead of start_pos and goal_pos: episode e = m * trials + r starts at
+        tasks.start[m, r] and aims at tasks.goal[m, r], a task that is not valid is INVALID (next to the two collision draws), and
+        the report gains optimal_length, spl and path_ratio_mean."""
         self.dataset, self.predictor = dataset, predictor
         self.M, self.G = len(dataset), dataset.grid_size
         if self.M < 1:
@@ -359,6 +378,9 @@ class Benchmark:
         self.num_samples, self.resolution = int(num_samples), float(resolution)
         per_map = lambda a: np.ascontiguousarray(np.broadcast_to(np.asarray(a, np.float32), (self.M, 2)))
         self.start_pos, self.goal_pos = per_map(start_pos), per_map(goal_pos)
+        self.tasks = tasks
+        if tasks is not None and tuple(tasks.valid.shape) != (self.M, self.trials):
+            raise ValueError(f"tasks must hold ({self.M}, {self.trials}) pairs, got {tuple(tasks.valid.shape)}")
         self.max_steps = max_steps(self.time_limit, self.delta_t)
         self.dev = resolve_device(dataset.device if dataset.device.type == "cuda" else None, "benchmark")
 
@@ -396,14 +418,26 @@ class Benchmark:
         pl = handles[B]
         maps = [(e0 + i) // self.trials for i in range(B)]
         idx = torch.as_tensor(maps, device=dev)
-        env = BatchedPlanetaryEnv(pl, ds.latent_mean[idx].cpu().numpy(), ds.latent_std[idx].cpu().numpy(), self.start_pos[maps],
-                                  self.goal_pos[maps], delta_t=self.delta_t, time_limit=self.time_limit,
+        if self.tasks is None:
+            starts, goals, no_task = self.start_pos[maps], self.goal_pos[maps], None
+        else:
+            flat = lambda a: a.reshape(self.M * self.trials, -1)[e0:e0 + B]
+            no_task = ~flat(self.tasks.valid)[:, 0]
+            starts, goals = flat(self.tasks.start), flat(self.tasks.goal)
+            nowhere = ~(np.isfinite(starts).all(axis=1) & np.isfinite(goals).all(axis=1))   # no pair was found: INVALID wherever it stands
+            starts = np.where(nowhere[:, None], self.start_pos[maps], starts).astype(np.float32)
+            goals = np.where(nowhere[:, None], self.goal_pos[maps], goals).astype(np.float32)
+        env = BatchedPlanetaryEnv(pl, ds.latent_mean[idx].cpu().numpy(), ds.latent_std[idx].cpu().numpy(), starts,
+                                  goals, delta_t=self.delta_t, time_limit=self.time_limit,
                                   stuck_threshold=self.stuck_threshold, goal_threshold=self.goal_threshold,
                                   seed=chunk_seed(self.seed, j), freeze_on_goal=True, check_positions=False)
         at = lambda pos: torch.cat([pos, torch.zeros(B, 1, device=dev)], 1).unsqueeze(1)
         bad_start = env.collision_check(at(env._start_pos))[:, 0]          # PlanetaryEnv.__init__'s two draws, kept per instance
         bad_goal = env.collision_check(at(env._goal_pos))[:, 0]
-        return e0, pl, env, idx, (bad_start | bad_goal).to(torch.uint8).contiguous()
+        bad = bad_start | bad_goal
+        if no_task is not None:
+            bad = bad | torch.as_tensor(no_task, device=dev)
+        return e0, pl, env, idx, bad.to(torch.uint8).contiguous()
 
     def run(self, planner: str, settings, **planner_kwargs) -> Report:
         """Every episode of the split under every setting.  planner "mppi": planner_kwargs go to NativeMPPI (horizon, num_samples,
@@ -444,4 +478,4 @@ class Benchmark:
                 for pl in handles.values():
                     pl.close()
         _raise_if_running(arrays.pop("status", None), settings, rows)
-        return Report(planner, settings, arrays, self.seed, self.chunk, self.trials, n, self.delta_t, self.time_limit)
+        return Report(planner, settings, arrays, self.seed, self.chunk, self.trials, n, self.delta_t, self.time_limit, tasks=self.tasks)

@@ -19,7 +19,7 @@ SOURCES = ["rollout_role_philox.hip", "rollout_role_kt2.hip", "rollout_role_t2k.
            "rollout_lat_self_ref_philox.hip", "rollout_lat_self_ref_kt2.hip", "rollout_lat_self_ref_t2k.hip",
            "mppi_kernels.hip", *HOST_SOURCES, "risk_kernels.hip", "astar_kernels.hip", "astar_dwa.hip", "terrain_kernels.hip", "rrt_kernels.hip", "clrrt_kernels.hip", "clrrt_loop.hip", "gp_kernels.hip", "gp_fit_kernels.hip",
            "unet_kernels.hip", "unet_host.cpp", "segtrain_kernels.hip", "segtrain_host.cpp", "dataset_kernels.hip", "score_kernels.hip",
-           "eval_kernels.hip"]
+           "eval_kernels.hip", "task_kernels.hip"]
 # per-source flags.  rollout_wave_ref.hip: see the note at its top (a register-allocation fault behind the SLP vectoriser)
 EXTRA_FLAGS = {f: ["-fno-slp-vectorize"] for f in ("rollout_wave_ref.hip", "rollout_role_ref_philox.hip", "rollout_role_ref_kt2.hip", "rollout_role_ref_t2k.hip",
                                                       "rollout_lat_host_ref.hip", "rollout_lat_self_ref_philox.hip", "rollout_lat_self_ref_kt2.hip",

@@ -654,6 +654,59 @@ int bn_eval_risk_async(int32_t device_id, void *stream, const float *risk_device
 const char *bn_eval_last_error(void);
 
 /*
+ * The task stage (csrc/task_kernels.hip): the truly passable ground of num_maps maps of H x W cells, its connected
+ * regions, and start/goal pairs drawn inside one region.  Device pointers only, everything is enqueued on `stream`, nothing
+ * synchronises or allocates, the outputs are overwritten.  H, W in [1, BN_TASK_MAX_SIDE] with H * W <= BN_TASK_MAX_CELLS, num_maps
+ * in [1, BN_TASK_MAX_MAPS].  Every function checks every argument before it touches the device (BN_ERR_INVALID).  Every result is
+ * an integer or a fixed function of integers.  Errors: bn_task_last_error().
+ *
+ * bn_task_mask_async: mean, std (num_maps, cells) float32, the latent slip model.  In float32, a rounded product then a rounded sum:
+ *   mask (num_maps, cells) uint8 = isfinite(mean) && isfinite(std) && 1.0f - clamp(mean + kappa * std, 0, 1) > stuck_threshold
+ * the complement of the environment step's stuck rule at the slip mean + kappa std; kappa = 0 reads the mean.
+ *
+ * bn_task_label_async: mask (num_maps, H, W) uint8, non-zero = passable (bn_task_mask_async's, or the caller's own);
+ * connectivity 4 or 8.
+ *   labels (num_maps, H, W) int32   the smallest linear index iy * W + ix of the cell's component, -1 on a blocked cell
+ *   sizes (num_maps, H * W) int32   the component's cell count at such a smallest index, 0 elsewhere
+ *   stats (num_maps, BN_TASK_STATS) int32: passable cells, components, the largest size, the label of the largest (the smallest
+ *          label wins a tie; -1 without a component), error flags (BN_TASK_ERR_*: a loop reached its bound, the map's labels are
+ *          not to be used), three zeros
+ * The labelling is unique: a map's outputs depend neither on the order workgroups run in nor on the batch it is in.  workspace:
+ * at least bn_task_workspace_bytes(num_maps, H, W) bytes (0 for a shape out of range), free once the stream has passed the call.
+ *
+ * bn_task_sample_async: labels and sizes as bn_task_label_async wrote them.  Attempt a of pair p of map m draws
+ *   r = philox4x32_10(counter {a, p, first_map + m, 0x5441534B}, key {lo32(seed), hi32(seed)});
+ * with Win = W - 2 border, Hin = H - 2 border, n = Win Hin the start cell is s = mulhi32(r0, n): (s % Win + border, s / Win + border),
+ * the goal cell likewise from r1.  An attempt is accepted when both cells are labelled >= 0 with one label, sizes[label] >=
+ * min_component_cells and dx^2 + dy^2 >= min_separation_sq in integer cells; a pair takes the lowest accepted a < max_attempts
+ * (a multiple of 64 in [64, BN_TASK_MAX_ATTEMPTS]).  2 * border < min(H, W); num_pairs in [1, BN_TASK_MAX_PAIRS].
+ *   cells (num_maps, num_pairs, 4) int32     (sx, sy, gx, gy), all -1 when no attempt is accepted
+ *   attempt (num_maps, num_pairs) int32      the accepted attempt, -1 when none
+ *   positions (num_maps, num_pairs, 4) float32   the cell centres fl32(x0 + fl32(fl32(i + 0.5) * resolution)), NaN when none
+ */
+#define BN_TASK_TILE 32
+#define BN_TASK_STATS 8
+#define BN_TASK_MAX_SIDE 4096
+#define BN_TASK_MAX_CELLS (1 << 24)
+#define BN_TASK_MAX_MAPS 4096
+#define BN_TASK_MAX_PAIRS 65536
+#define BN_TASK_MAX_ATTEMPTS 4096
+#define BN_TASK_ERR_TILE 1
+#define BN_TASK_ERR_UNITE 2
+#define BN_TASK_ERR_FLATTEN 4
+size_t bn_task_workspace_bytes(int32_t num_maps, int32_t H, int32_t W);
+int bn_task_mask_async(int32_t device_id, void *stream, const float *mean_device, const float *std_device, int32_t num_maps, int64_t cells,
+                       float kappa, float stuck_threshold, uint8_t *mask_device);
+int bn_task_label_async(int32_t device_id, void *stream, const uint8_t *mask_device, int32_t num_maps, int32_t H, int32_t W,
+                        int32_t connectivity, int32_t *labels_device, int32_t *sizes_device, int32_t *stats_device, void *workspace_device,
+                        size_t workspace_bytes);
+int bn_task_sample_async(int32_t device_id, void *stream, const int32_t *labels_device, const int32_t *sizes_device, int32_t num_maps,
+                         int32_t H, int32_t W, int32_t num_pairs, uint64_t seed, int64_t first_map, int32_t border, int64_t min_separation_sq,
+                         int32_t min_component_cells, int32_t max_attempts, float x0, float y0, float resolution, int32_t *cells_device,
+                         int32_t *attempt_device, float *positions_device);
+const char *bn_task_last_error(void);
+
+/*
  * AStar (src/planners/global_planners/search_based/astar.py), the A* global planner, as one goal-rooted shortest-path solve
  * per (map, goal) on the GPU: the cost-to-go field D and a one-byte next-hop map for B instances of one H x W shape, then
  * O(path length) host walks per start (csrc/astar_kernels.hip).  Graph and arithmetic are astar.py's: 8-connected cells

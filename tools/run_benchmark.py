@@ -5,12 +5,14 @@ driving every map, and the summary table -- what the reference spreads over its 
     python tools/run_benchmark.py [--planner mppi|astar_dwa|cl_rrt] [--data-directory DIR | --grid-size 64 --environments 10 --test-instances 1]
                                   [--models DIR] [--trials 1] [--chunk 64] [--seed 0] [--out report.json]
                                   [--max-iterations 500] [--max-seqs 250]                                    # cl_rrt
+                                  [--tasks sampled [--min-separation 10] [--connectivity 4] [--kappa 0] [--task-seed 0]]
     python tools/run_benchmark.py --rates [--baseline-lib libbenchnav_mppi.so]      # -> profiles/benchmark_rates.json
 
 The split is test subset 1: read from --data-directory (the reference's files), or generated in memory with the seeds
 tools/make_models.py's chain reaches (--train-instances / --valid-instances say how far the chain has run).  --models is the --out
 directory of tools/make_models.py (its classifier and slip regressors predict the slip); without it the latent model is the
-predictor.  --rates measures the two new device operations instead (host clock to a device synchronise, medians of 5):
+predictor.  --tasks sampled draws every episode's start and goal inside one connected region of the latent model's passable ground
+(benchnav_amd/tasks.py) instead of --start / --goal, and the table gains an `spl` column.  --rates measures the two new device operations instead (host clock to a device synchronise, medians of 5):
 infer_risk_maps against one infer_risk_map call per map and setting -- through --baseline-lib, a library built from another
 commit, when one is given -- and the scoring of 4096 episodes of 1001 steps from the device views against the log download plus the
 NumPy spec of tests/benchmark_spec.py."""
@@ -172,6 +174,11 @@ def main():
     ap.add_argument("--num-samples", type=int, default=None, help="MPPI rollouts per solve")
     ap.add_argument("--max-iterations", type=int, default=None, help="cl_rrt: samples per plan (the reference's 500)")
     ap.add_argument("--max-seqs", type=int, default=None, help="cl_rrt: closed-loop steps per steer (the reference's 250)")
+    ap.add_argument("--tasks", default="fixed", choices=["fixed", "sampled"], help="fixed: --start / --goal for every map; sampled: a TaskSet")
+    ap.add_argument("--min-separation", type=float, default=None, help="--tasks sampled: metres between start and goal at least (default: 0.3 of the extent)")
+    ap.add_argument("--connectivity", type=int, default=4, choices=[4, 8], help="--tasks sampled: of the regions a pair must share")
+    ap.add_argument("--kappa", type=float, default=0.0, help="--tasks sampled: passable is judged at the latent slip mean + kappa std")
+    ap.add_argument("--task-seed", type=int, default=0, help="--tasks sampled: the seed of the draws")
     ap.add_argument("--out", default=None, help="write the report (per-episode arrays and summary) as JSON")
     ap.add_argument("--rates", action="store_true", help="measure the risk-map and scoring kernels instead -> profiles/benchmark_rates.json")
     ap.add_argument("--baseline-lib", default=None, help="--rates: time the single-map calls through this library (another commit's build)")
@@ -194,8 +201,15 @@ def main():
     extent = split.grid_size * args.resolution
     start = args.start or (0.2 * extent, 0.2 * extent)
     goal = args.goal or (0.8 * extent, 0.8 * extent)
+    tasks = None
+    if args.tasks == "sampled":
+        from benchnav_amd.tasks import TaskSet
+        tasks = TaskSet.sample(split, args.trials, args.task_seed, min_separation=0.3 * extent if args.min_separation is None else args.min_separation,
+                               connectivity=args.connectivity, kappa=args.kappa, resolution=args.resolution, chunk=args.chunk)
+        print(f"tasks: {int(tasks.valid.sum())} of {tasks.valid.size} pairs found, mean optimal length "
+              f"{float(np.mean(tasks.optimal_length[tasks.valid])) if tasks.valid.any() else float('nan'):.2f} m")
     bench = Benchmark(split, predictor, start_pos=start, goal_pos=goal, time_limit=args.time_limit, trials=args.trials, chunk=args.chunk,
-                      seed=args.seed, resolution=args.resolution)
+                      seed=args.seed, resolution=args.resolution, tasks=tasks)
     kw = {k: v for k, v in (("horizon", args.horizon), ("num_samples", args.num_samples)) if v is not None}
     if args.planner == "astar_dwa":
         kw.pop("num_samples", None)
